@@ -6,7 +6,10 @@ buffer pre-filled with 2^18 transitions (episode length 100) and priorities rand
 update pass (SURVEY.md §8d "Synthetic inputs").  One "step" = one `SAC_Base.train()`:
 PER sample of 256 windows + every gradient/optimizer step + Polyak + priority / mu-prob write-back.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak] [--full] [--dump-outputs DIR]
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`); `roofline`, `roofline_hbm`,
+`sweep`, `configs`, `kernels`, `cpu_baseline` and `value_runs_of_4` / `value_lookahead` below are measured only with
+`--full` (null or absent otherwise).  `--dump-outputs DIR`: the learner state the timed steps left, as DIR/<name>.npy.
 N > 1: one rank per GPU over RCCL — under torch.distributed.run, or spawned by this script itself when it is started
 plainly with --gpus N.  Every rank owns a replay shard (capacity 524288/N); gradients are mean all-reduced.
   strong (default) the GLOBAL batch stays the BASELINE's 256, 256/N rows per rank: `value` = global-batch
@@ -459,6 +462,43 @@ def emit(full: dict, mode: str) -> None:
     print(compact_line(full, written or 'not written'), flush=True)
 
 
+DUMP_LIMIT = 64 << 20      # bytes written by --dump-outputs in all
+DUMP_SAMPLE = 1 << 21      # elements kept of a larger array: a fixed, seeded sample of its positions
+
+
+def dump_outputs(agent, out_dir) -> None:
+    """--dump-outputs: what the timed train() calls computed, as float32 / float64 `<out_dir>/<name>.npy` — the learner's
+    parameters and Adam moments per segment, the target networks, the replay priorities (the sum tree) and the step
+    counter.  A segment without parameters (cfg2's representation) has nothing to write and is left out.  The inputs are
+    seeded, so two builds run with the same arguments can be compared output for output."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {'global_step': np.array([agent.get_global_step()], dtype=np.float64)}
+    for name, (s, e) in agent._params.segments.items():
+        if e <= s:
+            continue
+        arrays[f'param_{name}'] = agent._params.flat[s:e]
+        arrays[f'adam_exp_avg_{name}'] = agent._exp_avg[s:e]
+        arrays[f'adam_exp_avg_sq_{name}'] = agent._exp_avg_sq[s:e]
+    for name, (s, e) in agent._target_params.segments.items():
+        if e > s:
+            arrays[f'target_param_{name}'] = agent._target_params.flat[s:e]
+    tree = getattr(agent.replay_buffer, '_tree', None)
+    if tree is not None:
+        arrays['replay_priority_tree'] = tree
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy().ravel() if torch.is_tensor(t) else t
+        assert a.size > 0, name
+        if a.size > DUMP_SAMPLE:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        total += a.nbytes
+        if total > DUMP_LIMIT:
+            raise SystemExit(f'--dump-outputs: more than {DUMP_LIMIT >> 20} MB at {name}')
+        np.save(out / f'{name}.npy', a)
+
+
 def _free_port() -> int:
     import socket
     with socket.socket() as sk:
@@ -484,7 +524,8 @@ def other_configs(names=('cfg2_lookahead', 'cfg2_force_dist', 'cfg3', 'cfg3_h64'
             env.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(_free_port()), RANK='0', WORLD_SIZE='1', LOCAL_RANK='0')
         else:
             cmd = [sys.executable, str(Path(__file__).resolve()), '--config', name, '--steps', str(steps), '--warmup',
-                   str(warmup), '--cpu-budget', '8', '--profile-steps', '12', '--no-extras', '--run-length', '0', '--emit', 'full']
+                   str(warmup), '--full', '--cpu-budget', '8', '--profile-steps', '12', '--no-extras', '--run-length', '0',
+                   '--emit', 'full']
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
             line = [ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1]
@@ -510,11 +551,21 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-budget', type=float, default=24.0, help='seconds of host time for the CPU port leg')
     ap.add_argument('--no-graph', action='store_true')
-    ap.add_argument('--run-length', type=int, default=4,
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: runs of k, the per-kernel HIP-event timing and '
+                         'rooflines, the saturating-size sweep, the side configurations and the CPU baseline.  Without it '
+                         'a run sets up, warms up, times the steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the learner state they left (parameters, Adam moments, target '
+                         'networks, replay priorities, step counter) as DIR/<name>.npy')
+    ap.add_argument('--run-length', type=int, default=None,
                     help='the secondary figure `value_runs_of_<k>`: the same steps issued as SAC_Base.train_steps(k) '
-                         '(one hipGraph replay holds k steps); 0 or 1 = skip it.  `value` is always plain train() calls')
-    ap.add_argument('--no-extras', action='store_true', help='skip the saturating-size sweep and the cfg3-5 side runs')
-    ap.add_argument('--profile-steps', type=int, default=50)
+                         '(one hipGraph replay holds k steps); 0 or 1 = skip it (default: 4 with --full, else 0).  '
+                         '`value` is always plain train() calls')
+    ap.add_argument('--no-extras', action='store_true',
+                    help='with --full: skip the saturating-size sweep and the cfg3-5 side runs')
+    ap.add_argument('--profile-steps', type=int, default=None,
+                    help='eager steps of per-kernel HIP-event timing (default: 50 with --full, else 0)')
     ap.add_argument('--fill', type=int, default=None, help='transitions resident before timing')
     ap.add_argument('--force-dist', action='store_true',
                     help='take the multi-rank code path (process group, RCCL collectives in the step) even with one rank')
@@ -527,6 +578,10 @@ def main():
     CFG.update(CONFIGS[args.config])
     if args.fill is None:
         args.fill = CFG['fill']
+    if args.run_length is None:
+        args.run_length = 4 if args.full else 0
+    if args.profile_steps is None:
+        args.profile_steps = 50 if args.full else 0
 
     # --gpus N started plainly (no launcher): spawn the N ranks ourselves, one per GPU, and hand their line through
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -609,6 +664,8 @@ def main():
         agent.train()
     sync_all()
     dt = max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(agent, args.dump_outputs)
     # ... and, reported beside it, the same number of steps as runs of k (SAC_Base.train_steps: one graph replay per run;
     # the first run of that length captures its graph, so one is done before the clock starts)
     spl, dt_runs = max(1, args.run_length), None
@@ -731,7 +788,7 @@ def main():
                                     'in situ = inside the replayed hipGraph step'}
 
     sweep = configs = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         agent._graph = None
         torch.cuda.empty_cache()
         from tools import kernel_sweep
@@ -739,7 +796,7 @@ def main():
         configs = other_configs()
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if rank == 0 and args.full and not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline(args.cpu_budget, args.fill)
 
     if rank == 0:

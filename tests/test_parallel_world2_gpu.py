@@ -317,7 +317,7 @@ def test_bench_two_ranks_host_path_on_one_gpu(tmp_path):
     env = dict(os.environ, ASAC_BENCH_ONE_DEVICE='1', MASTER_ADDR='127.0.0.1')
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT'):
         env.pop(k, None)
-    cmd = [sys.executable, str(root / 'bench.py'), '--gpus', '2', '--steps', '24', '--warmup', '6', '--no-cpu-baseline',
+    cmd = [sys.executable, str(root / 'bench.py'), '--gpus', '2', '--steps', '24', '--warmup', '6', '--full', '--no-cpu-baseline',
            '--no-extras', '--profile-steps', '4', '--run-length', '0', '--fill', '20000']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=tmp_path)
     assert r.returncode == 0, r.stderr[-2000:]

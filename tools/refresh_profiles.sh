@@ -45,11 +45,11 @@ python $R/tools/step_sequence.py $(find /tmp/prof_la -name "*kernel_trace.csv" |
 python $R/tools/summarize_rocprof.py $(find /tmp/prof_la -name "*kernel_stats.csv" | head -1) 440 40 $O/cfg2_lookahead_kernel_stats.json > $O/cfg2_lookahead_kernel_stats_summary.txt
 for c in cfg2 cfg3 cfg3_h64 cfg4 cfg4_84 cfg5 cfg5_without_prediction cfg_attn_h64; do cp $O/${c}_kernel_stats.json $R/profiles/r06_${c}_kernel_stats.json; [ -f $O/${c}_pmc_traffic.json ] && cp $O/${c}_pmc_traffic.json $R/profiles/r06_${c}_pmc_traffic.json; done
 cd $R
-timeout 1200 python bench.py > $O/cfg2_bench_line.json 2> $O/cfg2_bench.err
+timeout 1200 python bench.py --full > $O/cfg2_bench_line.json 2> $O/cfg2_bench.err
 cp $R/bench_details.json $O/cfg2_bench.json      # (the full record; cfg2_bench_line.json: the < 4 KB line the driver parses)
-timeout 900 python bench.py --no-extras --config cfg3 --cpu-budget 10 --emit full > $O/cfg3_bench.json 2> $O/cfg3_bench.err
-timeout 900 python bench.py --no-extras --config cfg4 --cpu-budget 10 --emit full > $O/cfg4_bench.json 2> $O/cfg4_bench.err
-timeout 900 python bench.py --no-extras --config cfg4_84 --cpu-budget 10 --emit full > $O/cfg4_84_bench.json 2> $O/cfg4_84_bench.err
-timeout 900 python bench.py --no-extras --config cfg5 --steps 500 --cpu-budget 10 --emit full > $O/cfg5_bench.json 2> $O/cfg5_bench.err
+timeout 900 python bench.py --full --no-extras --config cfg3 --cpu-budget 10 --emit full > $O/cfg3_bench.json 2> $O/cfg3_bench.err
+timeout 900 python bench.py --full --no-extras --config cfg4 --cpu-budget 10 --emit full > $O/cfg4_bench.json 2> $O/cfg4_bench.err
+timeout 900 python bench.py --full --no-extras --config cfg4_84 --cpu-budget 10 --emit full > $O/cfg4_84_bench.json 2> $O/cfg4_84_bench.err
+timeout 900 python bench.py --full --no-extras --config cfg5 --steps 500 --cpu-budget 10 --emit full > $O/cfg5_bench.json 2> $O/cfg5_bench.err
 ls -la $O
 tail -c 400 $O/cfg2_bench_line.json

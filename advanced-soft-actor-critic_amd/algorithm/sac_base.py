@@ -18,7 +18,10 @@ captured into one hipGraph (torch.cuda.CUDAGraph) and replayed; `hip_config={'us
 keeps it eager.  Every random draw comes from `self.noise` (device Philox by default; tests inject
 recorded draws to compare against the reference bit-for-bit on index selection).
 
-Not carried over: `use_replay_buffer=False` (BatchBuffer path) — outside the hot path.
+`use_replay_buffer=False` trains from fresh episodes instead (reference BatchBuffer, batch_buffer.py): every
+episode's windows go, shuffled and padded, into an HBM window pool in ONE launch (`asac_batch_put`), and step 1 above
+becomes ONE launch that copies the oldest queued batch into the same static batch (`asac_batch_pop_gather`).  That mode
+has no PER draws, no IS weights and no step 6 (the reference's `train` skips them too); the step is still one hipGraph.
 """
 import contextlib
 import logging
@@ -39,6 +42,7 @@ from .fused_mlp import DeferredPartialSums, StockMLP, describe_policy, describe_
 from .nn_models import *  # noqa: F401,F403
 from .nn_models.layers.seq_layers import step_mask_cache
 from .nn_models.representation import ModelSimpleRep
+from .batch_buffer import BatchBuffer
 from .replay_buffer import PrioritizedReplayBuffer
 from .sac_aux import AuxHeadsMixin
 from .utils import *  # noqa: F401,F403
@@ -284,7 +288,12 @@ class SAC_Base(AuxHeadsMixin):
         self._set_logger()
 
         if not use_replay_buffer:
-            raise NotImplementedError('use_replay_buffer=False (BatchBuffer) is outside the MI355X hot path')
+            if self._dist is not None:
+                raise ValueError('use_replay_buffer=False (the episode batch queue) is single-GPU: a data-parallel '
+                                 "context (hip_config['dist']) is not supported with it")
+            if self._lookahead:
+                self._logger.info("hip_config['lookahead'] does not apply without a replay buffer: forced to 0")
+                self._lookahead = 0
 
         if self.use_n_step_is and c_action_size == 0 and len(d_action_sizes) != 0 and discrete_dqn_like:
             self.use_n_step_is = False
@@ -586,6 +595,15 @@ class SAC_Base(AuxHeadsMixin):
 
     def _init_replay_buffer(self, replay_config: dict | None = None) -> None:
         if not self.train_mode:
+            return
+        if not self.use_replay_buffer:
+            # (reference sac_base.py:640-644; the windows' padding action is the learner's)
+            self.batch_buffer = BatchBuffer(burn_in_step=self.burn_in_step,
+                                            n_step=self.n_step,
+                                            padding_action=self._padding_action,
+                                            batch_size=self.batch_size,
+                                            device=self.device,
+                                            obs_names=self.obs_names)
             return
         self.replay_buffer = PrioritizedReplayBuffer(batch_size=self.batch_size,
                                                      sample_prev_n=self.burn_in_step,
@@ -1748,6 +1766,11 @@ class SAC_Base(AuxHeadsMixin):
             last[:, -1] = True
             last[ep_indexes == -1] = True
             obs_dev = None
+        if not self.use_replay_buffer:
+            # (the reference updates the normalizer only on the replay path: `_fill_replay_buffer`)
+            self.batch_buffer.put_episode(ep_indexes, last, ep_obses_list, ep_actions, ep_rewards, ep_dones, ep_probs,
+                                          ep_pre_seq_hidden_states)
+            return
         rows = {'index': ep_indexes[0], 'last_mask': last[0],
                 **{f'obs_{name}': o[0] for name, o in zip(self.obs_names, ep_obses_list)},
                 'action': ep_actions[0], 'reward': ep_rewards[0], 'done': ep_dones[0],
@@ -1783,6 +1806,14 @@ class SAC_Base(AuxHeadsMixin):
         self._step_policy(w)
         post = _AfterPolicy()
         self._vtrace_sidecars = self._pending_alpha = None
+        if not self.use_replay_buffer:
+            # batch mode (reference train 2536-2539): no TD error, no priorities, no mu-probability / hidden-state
+            # write-back — only the temperature step follows the policy step
+            self._step_temperature_and_aux(w, post)
+            if not self._counter_advanced:
+                self._opt_steps.add_(1)
+            self.batch_buffer.advance_head()     # (every launch that read the head is behind us)
+            return
         self._join_lookahead()       # (everything below may write priorities / replay rows)
         if w.stock and self.use_n_step_is:
             with torch.no_grad():
@@ -1805,13 +1836,19 @@ class SAC_Base(AuxHeadsMixin):
 
     def _step_sample(self):
         """-> the step's window views (`_Window`): [B, L] tensors are `bnx_*`, their first L - 1 rows `bn_*`"""
-        rb, b = self.replay_buffer, self.burn_in_step
+        rb, b = getattr(self, 'replay_buffer', None), self.burn_in_step
         # Polyak of every step rides in the step's first launch, together with every uniform / Gaussian draw and
         # ensemble subset of the step (recorded test noise: a plain Polyak launch, draws injected by the test)
         polyak = None
         if self.update_target_per_step == 1 and self._polyak_len > 0:
             polyak = (self._target_params.flat[:self._polyak_len], self._params.flat[:self._polyak_len], self.tau)
         zero = None if self._grads_overwrite else self._params.grad
+        if not self.use_replay_buffer:
+            # batch mode: no PER draws; the oldest queued batch -> the static batch (one launch)
+            self.noise.begin_step(self._opt_steps, None, self._eps_all, self._subsets_all, self.ensemble_q_num,
+                                  polyak=polyak, zero=zero)
+            self.batch_buffer.gather_into_static()
+            return self._window_views(self.batch_buffer._batch, None, None, None)
         if self._lookahead:
             # the batch this step trains on was drawn during the previous step (`train` swapped the sets); the NEXT one
             # is drawn now, from the tree and the rows as the previous step left them, before this step's first write to
@@ -1843,10 +1880,15 @@ class SAC_Base(AuxHeadsMixin):
                 self.noise.begin_step(self._opt_steps, rb._u if rb.uniform_source is self.noise else None, self._eps_all,
                                       self._subsets_all, self.ensemble_q_num, polyak=polyak, zero=zero)
             rb.sample_into_static(sampled=sampled)
-        batch = rb._batch
+        derived = rb.derived if rb.derived is not None and rb.sharded is None else None
+        return self._window_views(rb._batch, rb._ids, rb._w.unsqueeze(-1) if self.use_priority else None, derived,
+                                  rb.joint_pre_action)
+
+    def _window_views(self, batch, ids, priority_is, derived, joint_pre_action=None):
+        b = self.burn_in_step
         w = _Window()
-        w.ids = rb._ids
-        w.priority_is = rb._w.unsqueeze(-1) if self.use_priority else None
+        w.ids = ids
+        w.priority_is = priority_is
         w.bnx_obses_list = [batch[f'obs_{name}'] for name in self.obs_names]
         w.bnx_actions, w.bnx_pad = batch['action'], batch['padding_mask']
         w.bn_indexes, w.bn_last, w.bn_pad = batch['index'][:, :-1], batch['last_mask'][:, :-1], w.bnx_pad[:, :-1]
@@ -1862,13 +1904,13 @@ class SAC_Base(AuxHeadsMixin):
             # the stock concatenation rep ignores index / mask / previous actions: do not build them
             w.rep_in = (None, None, w.bnx_obses_list, None, w.bnx_hidden)
         else:
-            if rb.derived is not None and rb.sharded is None:
+            if derived is not None:
                 # (the gather delivered them as derived keys of its launch: no `asac_window_aux`)
-                d = rb.derived
+                d = derived
                 bnx_indexes, bnx_padding_masks, bnx_pre_actions = d['index_x'], d['padding_mask_x'], d['pre_action']
             else:
                 bnx_indexes, bnx_padding_masks, bnx_pre_actions = self.get_bnx_data(
-                    w.bn_indexes, w.bn_pad, w.bn_actions, pre_action_out=rb.joint_pre_action)
+                    w.bn_indexes, w.bn_pad, w.bn_actions, pre_action_out=joint_pre_action)
             w.rep_in = (bnx_indexes, bnx_padding_masks, w.bnx_obses_list, bnx_pre_actions, w.bnx_hidden)
         return w
 
@@ -2234,6 +2276,8 @@ class SAC_Base(AuxHeadsMixin):
         throughput mode needs every rank's shard above its own batch; parity mode needs the UNION above the global batch
         (and every rank to know the transition layout: it allocates its batch from it) — a rank with a short shard
         takes part from the first step."""
+        if not self.use_replay_buffer:
+            return self.batch_buffer.has_batch      # (the host mirror of the queue: no synchronisation)
         rb = self.replay_buffer
         if self._dist is None:
             return rb.is_lg_batch_size
@@ -2269,12 +2313,16 @@ class SAC_Base(AuxHeadsMixin):
     @unified_elapsed_timer('train a step', 10)
     def train(self) -> int:
         step = self.get_global_step()
-        rb = self.replay_buffer
+        rb = getattr(self, 'replay_buffer', None)
         if not self._ready_to_train():
             self._profiler('train a step').ignore()
             return step
         self._drop_graphs_if_hp_changed()
-        if rb._gather_keys is None:
+        if rb is None:
+            if self.batch_buffer._batch is None:
+                self.batch_buffer.build_static()
+                self._graph = None
+        elif rb._gather_keys is None:
             rb._build_batch()
             self._graph = None
             self._la_graphs = {}
@@ -2304,6 +2352,8 @@ class SAC_Base(AuxHeadsMixin):
             else:
                 self._device_step()
                 self._eager_steps += 1
+        if rb is None:
+            self.batch_buffer.pop_host()
         if self._lookahead:
             self._la_graphs[rb.parity] = (self._graph, self._graph_exec, self._graph_exec_checked, self._graph_stats_src)
             rb.next_valid = True
@@ -2312,7 +2362,8 @@ class SAC_Base(AuxHeadsMixin):
         # read back, so a diverged run raises the reference's 'td_error has nan' (replay_buffer.py:418-420) within
         # `write_summary_per_step` steps instead of training on with frozen priorities
         if step % self.write_summary_per_step == 0:
-            rb.check_health()
+            if rb is not None:
+                rb.check_health()
             if self.summary_writer is not None:
                 self._write_train_summaries(step)
         if step % self.save_model_per_step == 0:
@@ -2328,12 +2379,15 @@ class SAC_Base(AuxHeadsMixin):
         run is that of the `train()` calls bit for bit.  Episodes enter between runs, not between the steps of one."""
         k = int(n_steps)
         step = self.get_global_step()
-        rb = self.replay_buffer
+        rb = getattr(self, 'replay_buffer', None)
         self._drop_graphs_if_hp_changed()
         due = any((step + i) % self.write_summary_per_step == 0 or (step + i) % self.save_model_per_step == 0
                   for i in range(k))
+        # (batch mode: each step of the run pops a batch — at least k must be queued)
+        data_ok = (len(self.batch_buffer) >= k and self.batch_buffer._batch is not None) if rb is None else \
+            (rb.is_lg_batch_size and rb._gather_keys is not None)
         if (k <= 1 or due or self._lookahead or self._graph is None or self._graph_exec is None or self.update_target_per_step != 1
-                or not rb.is_lg_batch_size or rb._gather_keys is None):
+                or not data_ok):
             for _ in range(k):
                 step = self.train()
             return step
@@ -2360,6 +2414,9 @@ class SAC_Base(AuxHeadsMixin):
         self._pi_stats_src = cached[3]      # the run's last step left its (logp, scale) in the run graph's pool
         with self._profiler('train', repeat=10):
             native.graph_launch(cached[2])
+        if rb is None:
+            for _ in range(k):
+                self.batch_buffer.pop_host()
         self.global_step.add_(k)
         return self.global_step.item()
 
@@ -2383,7 +2440,8 @@ class SAC_Base(AuxHeadsMixin):
         self.summary_available = True
         self._refresh_policy_stats()
         w = self.summary_writer
-        w.add_scalar('metric/replay_id', self.replay_buffer.get_curr_id(), step)
+        if self.use_replay_buffer:
+            w.add_scalar('metric/replay_id', self.replay_buffer.get_curr_id(), step)
         w.add_scalar('loss/q', self._stats['loss_q'].item(), step)
         if self.d_action_sizes:
             w.add_scalar('loss/d_entropy', self._stats['d_entropy'].item(), step)

@@ -594,6 +594,8 @@ int64_t asac_struct_size(const char* name) {
     ASAC_SZ(asac_gather_key_t);
     ASAC_SZ(asac_partial_sum_t);
     ASAC_SZ(asac_row_move_t);
+    ASAC_SZ(asac_batch_put_key_t);
+    ASAC_SZ(asac_batch_gather_key_t);
     ASAC_SZ(asac_sidecar_t);
     ASAC_SZ(asac_squash_job_t);
     ASAC_SZ(asac_vtrace_args_t);

@@ -14,7 +14,7 @@ PKG_DIR = Path(__file__).resolve().parent
 import os as _os
 
 LIB_PATH = Path(_os.environ.get('ASAC_HIP_LIB', PKG_DIR / 'lib' / 'libasac_hip.so'))   # env override: debugging builds
-ABI_VERSION = 81
+ABI_VERSION = 82
 
 MAX_GATHER_KEYS = 16
 PAD_KEEP, PAD_WORD, PAD_BYTE, PAD_ROW, PAD_EMIT_MASK = 0, 1, 2, 3, 4
@@ -60,6 +60,15 @@ class RowMove(C.Structure):
                 ('dst_stride0', C.c_int64), ('dst_stride1', C.c_int64),
                 ('row_bytes', C.c_int32), ('src_mode', C.c_int32), ('dst_mode', C.c_int32),
                 ('src_row_offset', C.c_int32), ('pad_word', C.c_uint32), ('reserved_', C.c_int32)]
+
+
+class BatchPutKey(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('pool', C.c_void_p), ('pad_row', C.c_void_p), ('src_stride', C.c_int64),
+                ('row_bytes', C.c_int32), ('pad_mode', C.c_int32), ('pad_word', C.c_uint32), ('reserved_', C.c_int32)]
+
+
+class BatchGatherKey(C.Structure):
+    _fields_ = [('pool', C.c_void_p), ('dst', C.c_void_p), ('row_bytes', C.c_int32), ('convert', C.c_int32)]
 
 
 class VtraceArgs(C.Structure):
@@ -197,6 +206,11 @@ _SIGNATURES = {
     'asac_gather_rows': (C.c_int, [C.POINTER(GatherKey), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     'asac_rows_move': (C.c_int, [C.POINTER(RowMove), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                  C.c_void_p]),
+    'asac_batch_put': (C.c_int, [C.POINTER(BatchPutKey), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                 C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                 C.c_void_p, C.c_int32, C.c_void_p]),
+    'asac_batch_pop_gather': (C.c_int, [C.POINTER(BatchGatherKey), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_int, C.c_int, C.c_void_p]),
     'asac_window_aux': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
                                   C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'asac_scatter_rows_if_id_match': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
@@ -694,6 +708,52 @@ def rows_move(keys, slot, src_row, dst_row, n_items):
     """one launch: every key of `keys` (ctypes array from `make_row_moves`) moves `n_items` rows"""
     _check(load().asac_rows_move(keys, len(keys), _p(slot), _p(src_row), _p(dst_row), int(n_items), _stream()),
            'asac_rows_move')
+
+
+def make_batch_put_keys(specs):
+    """specs: list of dicts(src (tensor or None), src_stride (bytes), pool, row_bytes, pad_mode, pad_word=0,
+    pad_row=None); keep the tensors alive while the array is in use."""
+    assert 0 < len(specs) <= MAX_GATHER_KEYS
+    arr = (BatchPutKey * len(specs))()
+    for k, s in zip(arr, specs):
+        k.src = s['src'].data_ptr() if s.get('src') is not None else None
+        k.pool = s['pool'].data_ptr()
+        k.pad_row = s['pad_row'].data_ptr() if s.get('pad_row') is not None else None
+        k.src_stride = int(s.get('src_stride', 0))
+        k.row_bytes = int(s['row_bytes'])
+        k.pad_mode = int(s['pad_mode'])
+        k.pad_word = int(s.get('pad_word', 0)) & 0xffffffff
+    return arr
+
+
+@_profiled
+def batch_put(keys, ep_len, burn_in, L, win_start, win_slot, n_windows, pool_slots, queue_rows, queue_slots,
+              n_queue_rows, batch, queue, head, new_head):
+    """one launch: an episode's surviving windows -> their pool slots, the new queue rows, the head (csrc/batch.hip)"""
+    assert queue.dtype == torch.int32 and head.dtype == torch.int32 and queue.is_contiguous()
+    _check(load().asac_batch_put(keys, len(keys), int(ep_len), int(burn_in), int(L), _p(win_start), _p(win_slot),
+                                 int(n_windows), int(pool_slots), _p(queue_rows), _p(queue_slots), int(n_queue_rows),
+                                 int(batch), _p(queue), queue.shape[0], _p(head), int(new_head), _stream()),
+           'asac_batch_put')
+
+
+def make_batch_gather_keys(specs):
+    """specs: list of dicts(pool, dst, row_bytes, convert=CVT_NONE)"""
+    assert 0 < len(specs) <= MAX_GATHER_KEYS
+    arr = (BatchGatherKey * len(specs))()
+    for k, s in zip(arr, specs):
+        k.pool, k.dst = s['pool'].data_ptr(), s['dst'].data_ptr()
+        k.row_bytes = int(s['row_bytes'])
+        k.convert = int(s.get('convert', CVT_NONE))
+    return arr
+
+
+@_profiled
+def batch_pop_gather(keys, queue, head, batch, L, pool_slots):
+    """one launch: the windows of queue[head % rows] -> the keys' dense [batch, L] destinations (csrc/batch.hip)"""
+    assert queue.dtype == torch.int32 and head.dtype == torch.int32 and queue.is_contiguous()
+    _check(load().asac_batch_pop_gather(keys, len(keys), _p(queue), _p(head), queue.shape[0], int(batch), int(L),
+                                        int(pool_slots), _stream()), 'asac_batch_pop_gather')
 
 
 def make_gather_keys(specs):

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ASAC_ABI_VERSION 81
+#define ASAC_ABI_VERSION 82
 #define ASAC_MAX_GATHER_KEYS 16
 #define ASAC_MAX_ENSEMBLE 16
 #define ASAC_MAX_ACTION 64
@@ -1329,6 +1329,50 @@ typedef struct {
     int32_t slabs, slices, accumulate, pad_;
 } asac_partial_sum_t;
 int asac_sum_partials_multi(int n_jobs, const asac_partial_sum_t* jobs_host, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Episode batch queue: training without a replay buffer (SAC_Base(use_replay_buffer=False), reference
+ * algorithm/batch_buffer.py, utils/operators.py:105-206 `episode_to_batch`, sac_base.py:2496-2609).
+ * HBM layout (algorithm/batch_buffer.py): per key a window pool [P][L][row_bytes] (L = burn_in + n_step + 1, every
+ * live window stored once, already padded), the queue i32[ring_rows][batch] of pool slots, a head i32[1] holding the
+ * ABSOLUTE number of the next batch to pop (its queue row: head % ring_rows).  The host planner decides every slot,
+ * queue row and head value.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    const void* src;     /* episode rows, src_stride bytes apart (NULL with ASAC_PAD_EMIT_MASK)               */
+    void* pool;          /* [P][L][row_bytes]                                                                */
+    const void* pad_row; /* ASAC_PAD_ROW only                                                                */
+    int64_t src_stride;
+    int32_t row_bytes;   /* ASAC_PAD_EMIT_MASK: 1                                                            */
+    int32_t pad_mode;    /* ASAC_PAD_WORD / _BYTE / _ROW: rows outside the episode; ASAC_PAD_EMIT_MASK: the
+                            padding mask itself (1 on the rows in front of the episode, 0 from its first row on:
+                            the reference's mask, utils/operators.py:151-153)                                */
+    uint32_t pad_word;
+    int32_t reserved_;
+} asac_batch_put_key_t;
+
+/* One launch per episode (BatchBuffer.put_episode + episode_to_batch): window w (pool slot win_slot[w]) row j of
+ * every key := episode row win_start[w] + j (win_start = window start - burn_in), or the key's padding where that row
+ * lies outside [0, ep_len); the same launch writes queue[queue_rows[q]][:] := queue_slots[q][:] and head := new_head.
+ *   win_start, win_slot  i32[n_windows];  queue_rows i32[n_queue_rows], queue_slots i32[n_queue_rows][batch]
+ * Slots outside [0, pool_slots) and queue rows outside [0, ring_rows) are skipped. */
+int asac_batch_put(const asac_batch_put_key_t* keys_host, int n_keys, int ep_len, int burn_in, int L,
+                   const int32_t* win_start, const int32_t* win_slot, int n_windows, int pool_slots,
+                   const int32_t* queue_rows, const int32_t* queue_slots, int n_queue_rows, int batch,
+                   int32_t* queue, int ring_rows, int32_t* head, int32_t new_head, void* stream);
+
+typedef struct {
+    const void* pool;    /* [P][L][row_bytes]                                                                */
+    void* dst;           /* [batch][L][row_bytes] (f32 [batch][L][row_bytes] elements with a conversion)     */
+    int32_t row_bytes;
+    int32_t convert;     /* ASAC_CVT_*                                                                       */
+} asac_batch_gather_key_t;
+
+/* The per-step launch (BatchBuffer.get_batch; captured in the train step's hipGraph): dst_k[b][j] := pool_k[
+ * queue[head % ring_rows][b]][j] for every key, uint8 / bool observations widened to f32 (ASAC_CVT_*).  Reads the head,
+ * does not advance it (the step does, after its last launch). */
+int asac_batch_pop_gather(const asac_batch_gather_key_t* keys_host, int n_keys, const int32_t* queue,
+                          const int32_t* head, int ring_rows, int batch, int L, int pool_slots, void* stream);
 
 #ifdef __cplusplus
 }

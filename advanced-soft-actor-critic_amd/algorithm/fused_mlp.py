@@ -579,11 +579,15 @@ class StockMLP:
         gp = ws = None
         mode = self._reduce_mode(defer and param_grads)
         if param_grads:
-            gp, ws = self.grad_params, self._workspace_for(N)
+            gp = self.grad_params
             self._deferred_rows = N if defer else None
             if grad_target is not None:
                 assert not defer
                 gp, mode = grad_target, native.MLP_REDUCE_OVERWRITE
+            if later is None or defer:
+                # (only a pass that USES the cached workspace may grow it: a captured step holds its address, and a
+                # re-allocation on behalf of a pass that brings its own would leave that step writing into freed memory)
+                ws = self._workspace_for(N)
             if later is not None and not defer:
                 # the partials stay in a workspace of this call's own until `later.flush()` sums them into the target — the
                 # scratch buffer autograd would have been handed, or (direct mode) the flat gradient views

@@ -14,7 +14,7 @@ PKG_DIR = Path(__file__).resolve().parent
 import os as _os
 
 LIB_PATH = Path(_os.environ.get('ASAC_HIP_LIB', PKG_DIR / 'lib' / 'libasac_hip.so'))   # env override: debugging builds
-ABI_VERSION = 82
+ABI_VERSION = 83
 
 MAX_GATHER_KEYS = 16
 PAD_KEEP, PAD_WORD, PAD_BYTE, PAD_ROW, PAD_EMIT_MASK = 0, 1, 2, 3, 4
@@ -467,6 +467,10 @@ _SIGNATURES = {
     'asac_obs_decoder_backward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.POINTER(ObsDecoderParams), C.c_int, C.c_void_p,
                                             C.c_void_p]),
+    'asac_bc_loss_grad_workspace': (C.c_int64, []),
+    'asac_bc_loss_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int,
+                                    C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                    C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -2378,3 +2382,45 @@ def xty_multi(jobs, accumulate=False):
                                  ptr(*[j[2].data_ptr() for j in jobs]),
                                  ptr(*[None if j[3] is None else j[3].data_ptr() for j in jobs]), int(bool(accumulate)),
                                  _p(ws), _stream()), 'asac_xty_multi')
+
+
+# ------------------------------------------------------------------------------------------------
+# behaviour cloning (csrc/imitation.hip)
+# ------------------------------------------------------------------------------------------------
+BC_MAX_ELEMENTS = 1 << 24
+_BC_WS = {}
+
+
+def bc_loss_grad_workspace(device) -> torch.Tensor:
+    """the zeroed exchange words of `bc_loss_grad` on `device` (every launch leaves them ready for the next)"""
+    key = torch.device(device)
+    if key not in _BC_WS:
+        _BC_WS[key] = torch.zeros(int(load().asac_bc_loss_grad_workspace()), dtype=torch.float32, device=key)
+    return _BC_WS[key]
+
+
+@_profiled
+def bc_loss_grad(loc, scale, action, action_offset, t_valid, entropy_coef, loss_out, dloc, dscale, raw_head=False,
+                 workspace=None):
+    """loss_out[0] <- mean over rows < t_valid[0] of -Normal(loc, scale).log_prob(action[:, action_offset:]) -
+    entropy_coef * entropy, dloc / dscale <- its gradients (zero for the other rows).  loc, scale, dloc, dscale: [Tp, A]
+    views with a dense last dimension (loc / scale share a row stride, so do dloc / dscale: the halves of a [Tp, 2A] buffer
+    qualify); action [Tp, >= action_offset + A]; t_valid: device int32[1].  `raw_head`: see include/asac_hip.h."""
+    Tp, A = loc.shape
+    assert scale.shape == (Tp, A) and dloc.shape == (Tp, A) and dscale.shape == (Tp, A) and action.shape[0] == Tp
+    assert all(t.dtype == torch.float32 and (t.stride(1) == 1 or A == 1) for t in (loc, scale, dloc, dscale))
+    assert action.dim() == 2 and action.dtype == torch.float32 and (action.stride(1) == 1 or action.shape[1] == 1)
+    assert action.shape[1] >= action_offset + A and t_valid.dtype == torch.int32 and t_valid.numel() == 1
+    assert Tp * A <= BC_MAX_ELEMENTS and loss_out.dtype == torch.float32 and loss_out.numel() == 1
+
+    def ld(a, b, width):      # the common row stride of a pair (a single row has none: any stride >= its width does)
+        if Tp == 1:
+            return width
+        assert a.stride(0) == b.stride(0) >= width
+        return a.stride(0)
+    ld_in, ld_out = ld(loc, scale, A), ld(dloc, dscale, A)
+    a_stride = action.stride(0) if Tp > 1 else action.shape[1]
+    ws = workspace if workspace is not None else bc_loss_grad_workspace(loc.device)
+    _check(load().asac_bc_loss_grad(_p(loc), _p(scale), ld_in, _p(action), a_stride, int(action_offset), _p(t_valid), Tp, A,
+                                    float(entropy_coef), int(bool(raw_head)), _p(loss_out), _p(dloc), _p(dscale), ld_out,
+                                    _p(ws), _stream()), 'asac_bc_loss_grad')

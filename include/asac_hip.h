@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ASAC_ABI_VERSION 82
+#define ASAC_ABI_VERSION 83
 #define ASAC_MAX_GATHER_KEYS 16
 #define ASAC_MAX_ENSEMBLE 16
 #define ASAC_MAX_ACTION 64
@@ -1373,6 +1373,27 @@ typedef struct {
  * does not advance it (the step does, after its last launch). */
 int asac_batch_pop_gather(const asac_batch_gather_key_t* keys_host, int n_keys, const int32_t* queue,
                           const int32_t* head, int ring_rows, int batch, int L, int pool_slots, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Behaviour cloning (ImitationBase.train, imitation_base.py:57-59): over rows [0, *t_valid) of one padded episode
+ *   loss = mean(-Normal(loc, scale).log_prob(a) - entropy_coef * Normal(loc, scale).entropy()),   a = action[:, offset:]
+ * with z = (a - loc) / scale:  dloss/dloc = -z / scale,  dloss/dscale = (1 - entropy_coef - z^2) / scale, each over
+ * (*t_valid * A); rows >= *t_valid add nothing and get zero gradients.  ONE launch; the sum has a fixed order (lane,
+ * wave, workgroup, then the workgroups' sums in workgroup order by the last to arrive: no float atomics), so equal inputs
+ * give equal bits.  t_valid is read on the device: one captured launch serves every episode length up to Tp.
+ *   loc, scale   rows ld_in floats apart;   dloc, dscale   rows ld_out floats apart;   action rows action_stride apart
+ *   raw_head != 0: loc / scale hold the stock policy's raw (mean | logstd) head outputs, the launch applies
+ *     loc = 5 tanh(mean / 5), scale = exp(clamp(logstd, -20, 0.5)) (nn_models/policy.py:169) and the gradients are
+ *     with respect to the raw values
+ *   workspace    asac_bc_loss_grad_workspace() floats, zero before the first launch (every launch leaves them usable)
+ *                one launch at a time per workspace: launches on different streams need workspaces of their own
+ * Tp * A <= ASAC_BC_MAX_ELEMENTS. */
+#define ASAC_BC_MAX_BLOCKS 64
+#define ASAC_BC_MAX_ELEMENTS (1 << 24)
+int64_t asac_bc_loss_grad_workspace(void);
+int asac_bc_loss_grad(const float* loc, const float* scale, int64_t ld_in, const float* action, int64_t action_stride,
+                      int action_offset, const int32_t* t_valid, int Tp, int A, float entropy_coef, int raw_head,
+                      float* loss, float* dloc, float* dscale, int64_t ld_out, float* workspace, void* stream);
 
 #ifdef __cplusplus
 }

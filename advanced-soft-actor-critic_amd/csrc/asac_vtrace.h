@@ -50,7 +50,10 @@ __device__ __forceinline__ float masked_prod4(const float (&v)[4], int A) {
     return out;
 }
 
-__device__ __forceinline__ VtraceStepRaw vtrace_step_load(const asac_vtrace_args_t& a, int b, int t) {
+// (`Args`: asac_vtrace_args_t, or the same struct read in place from the kernel-argument segment — `ASAC_KARG
+// asac_vtrace_args_t`, asac_common.h — by a kernel that keeps its argument block out of the scalar registers)
+template <typename Args>
+__device__ __forceinline__ VtraceStepRaw vtrace_step_load(const Args& a, int b, int t) {
     VtraceStepRaw r;
     const int n = a.n;
     const float* q0 = a.q + (int64_t)b * a.q_stride_b + (int64_t)t * a.q_stride_t;
@@ -119,9 +122,11 @@ __device__ __forceinline__ VtraceStepRaw vtrace_step_load(const asac_vtrace_args
     return r;
 }
 
-__device__ __forceinline__ float vtrace_step_finish(const asac_vtrace_args_t& a, const VtraceStepRaw& r, float alpha,
-                                                    float* d, float* c) {
-    const float v_t = r.m0 - alpha * r.lp0, v_next = r.m1 - alpha * r.lp1;
+// the step's arithmetic from V(s_t) and V(s_t+1) on: shared by the plain return and the option return (option.hip), which
+// only differ in how V(s_t+1) is formed
+template <typename Args>
+__device__ __forceinline__ float vtrace_step_finish_v(const Args& a, const VtraceStepRaw& r, float v_t,
+                                                      float v_next, float* d, float* c) {
     float td = r.reward + r.g * v_next - v_t;
     td = r.gamma_ratio * td;
     float cc = 1.f;
@@ -133,6 +138,22 @@ __device__ __forceinline__ float vtrace_step_finish(const asac_vtrace_args_t& a,
     *d = td * r.keep;
     *c = cc;
     return v_t;
+}
+
+__device__ __forceinline__ float vtrace_step_finish(const asac_vtrace_args_t& a, const VtraceStepRaw& r, float alpha,
+                                                    float* d, float* c) {
+    const float v_t = r.m0 - alpha * r.lp0, v_next = r.m1 - alpha * r.lp1;
+    return vtrace_step_finish_v(a, r, v_t, v_next, d, c);
+}
+
+// ... with the option's termination mix in front (reference algorithm/oc/option_base.py:409-411):
+//   V(s_t+1) = (1 - beta_t) * (min Q(s_t+1) - alpha logpi_t+1) + beta_t * vbar_t,   vbar_t = mean_o V_o(s_t+1)
+template <typename Args>
+__device__ __forceinline__ float vtrace_step_finish_option(const Args& a, const VtraceStepRaw& r,
+                                                           float alpha, float beta, float vbar, float* d, float* c) {
+    const float v_t = r.m0 - alpha * r.lp0;
+    const float v_next = (1.f - beta) * (r.m1 - alpha * r.lp1) + beta * vbar;
+    return vtrace_step_finish_v(a, r, v_t, v_next, d, c);
 }
 
 __device__ __forceinline__ float vtrace_step_terms(const asac_vtrace_args_t& a, int b, int t, float alpha,

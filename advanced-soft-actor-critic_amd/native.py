@@ -14,7 +14,7 @@ PKG_DIR = Path(__file__).resolve().parent
 import os as _os
 
 LIB_PATH = Path(_os.environ.get('ASAC_HIP_LIB', PKG_DIR / 'lib' / 'libasac_hip.so'))   # env override: debugging builds
-ABI_VERSION = 83
+ABI_VERSION = 84
 
 MAX_GATHER_KEYS = 16
 PAD_KEEP, PAD_WORD, PAD_BYTE, PAD_ROW, PAD_EMIT_MASK = 0, 1, 2, 3, 4
@@ -471,6 +471,12 @@ _SIGNATURES = {
     'asac_bc_loss_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int,
                                     C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                     C.c_void_p]),
+    'asac_option_return': (C.c_int, [C.POINTER(VtraceArgs), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                     C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
+    'asac_termination_loss_grad_workspace': (C.c_int64, []),
+    'asac_termination_loss_grad': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                             C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -2424,3 +2430,56 @@ def bc_loss_grad(loc, scale, action, action_offset, t_valid, entropy_coef, loss_
     _check(load().asac_bc_loss_grad(_p(loc), _p(scale), ld_in, _p(action), a_stride, int(action_offset), _p(t_valid), Tp, A,
                                     float(entropy_coef), int(bool(raw_head)), _p(loss_out), _p(dloc), _p(dscale), ld_out,
                                     _p(ws), _stream()), 'asac_bc_loss_grad')
+
+
+# ------------------------------------------------------------------------------------------------
+# the option-critic's per-option learner (csrc/option.hip)
+# ------------------------------------------------------------------------------------------------
+OPTION_MAX_OPTIONS = 1024
+TERMINATION_MAX_ROWS = 1 << 24
+_TERM_WS = {}
+
+
+@_profiled
+def option_return(args: VtraceArgs, beta, v_options):
+    """`vtrace_return_min` with the option's termination mix: beta [B, n] and v_options [B, n, O] float32 views (any
+    strides); V(s_t+1) = (1 - beta) * (min Q - alpha logpi) + beta * mean_o v_options.  `args` as for `vtrace_return_min`
+    (with `q_online` / `td_error_out` set the launch writes the TD error too)."""
+    if beta is not None:
+        assert beta.dtype == torch.float32 and beta.shape == (args.B, args.n), (tuple(beta.shape), args.B, args.n)
+    if v_options is not None:
+        assert v_options.dtype == torch.float32 and v_options.dim() == 3 and v_options.shape[:2] == (args.B, args.n)
+    bs = (beta.stride(0), beta.stride(1)) if beta is not None else (0, 0)
+    vs = tuple(v_options.stride()) if v_options is not None else (0, 0, 0)
+    O = v_options.shape[2] if v_options is not None else 0
+    _check(load().asac_option_return(C.byref(args), _p(beta), bs[0], bs[1], _p(v_options), vs[0], vs[1], vs[2], O,
+                                     _stream()), 'asac_option_return')
+
+
+def termination_loss_grad_workspace(device) -> torch.Tensor:
+    """the zeroed exchange words of `termination_loss_grad` on `device` (every launch leaves them ready for the next)"""
+    key = torch.device(device)
+    if key not in _TERM_WS:
+        _TERM_WS[key] = torch.zeros(int(load().asac_termination_loss_grad_workspace()), dtype=torch.float32, device=key)
+    return _TERM_WS[key]
+
+
+@_profiled
+def termination_loss_grad(beta, y, v_options, done, priority_is, terminal_entropy, loss_out, dbeta, workspace=None):
+    """loss_out[0] <- mean_b(beta * (y - mean_o v_options + terminal_entropy) * ~done * priority_is), dbeta [B] <- its
+    gradient with respect to beta.  beta, y, priority_is (optional): B float32 elements each ([B] or [B, 1], any row
+    stride); v_options [B, O] float32 (any strides); done: bool / uint8 [B] contiguous."""
+    B = beta.shape[0]
+
+    def col(t, name):
+        assert t.dtype == torch.float32 and t.numel() == B and t.shape[0] == B, name
+        return t.stride(0) if B > 1 else 1
+    assert v_options.dtype == torch.float32 and v_options.dim() == 2 and v_options.shape[0] == B
+    assert done.dtype in (torch.bool, torch.uint8) and done.numel() == B and done.is_contiguous()
+    assert dbeta.dtype == torch.float32 and dbeta.numel() == B and dbeta.is_contiguous()
+    assert loss_out.dtype == torch.float32 and loss_out.numel() == 1 and B <= TERMINATION_MAX_ROWS
+    ws = workspace if workspace is not None else termination_loss_grad_workspace(beta.device)
+    _check(load().asac_termination_loss_grad(
+        _p(beta), col(beta, 'beta'), _p(y), col(y, 'y'), _p(v_options), v_options.stride(0), v_options.stride(1),
+        v_options.shape[1], _p(done), _p(priority_is), col(priority_is, 'priority_is') if priority_is is not None else 0,
+        float(terminal_entropy), B, _p(loss_out), _p(dbeta), _p(ws), _stream()), 'asac_termination_loss_grad')

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ASAC_ABI_VERSION 83
+#define ASAC_ABI_VERSION 84
 #define ASAC_MAX_GATHER_KEYS 16
 #define ASAC_MAX_ENSEMBLE 16
 #define ASAC_MAX_ACTION 64
@@ -1394,6 +1394,44 @@ int64_t asac_bc_loss_grad_workspace(void);
 int asac_bc_loss_grad(const float* loc, const float* scale, int64_t ld_in, const float* action, int64_t action_stride,
                       int action_offset, const int32_t* t_valid, int Tp, int A, float entropy_coef, int raw_head,
                       float* loss, float* dloc, float* dscale, int64_t ld_out, float* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The option-critic's per-option learner (OptionBase, algorithm/oc/option_base.py).
+ *
+ * asac_option_return: asac_vtrace_return_min with the option's termination mix in front of the scan — OptionBase._get_y's
+ * continuous branch (option_base.py:287, 376-427 + sac_base.py _v_trace 1244-1295) in ONE launch:
+ *   V(s_t)   = min_{e in subset_n}    Q_e(s_t, a_t) - alpha logpi_t
+ *   V(s_t+1) = (1 - beta[b, t]) * (min_{e in subset_next} Q_e(s_t+1, a_t+1) - alpha logpi_t+1)
+ *              + beta[b, t] * mean_o v_options[b, t, o]
+ * `args_host` as for asac_vtrace_return_min (q, logp, log_alpha, masks, ratios, optional q_online / td_error_out:
+ * td[b] = mean_e |q_online[e][b] - y[b]|, option_base.py:788-800 for continuous-only action spaces); beta [B, n] and
+ * v_options [B, n, num_options] with their strides in floats.  The mean over the options is the sum in option order by
+ * one lane, divided by num_options; neither it nor V(s_t) / V(s_t+1) reach memory.  Same step arithmetic and scan
+ * association as asac_vtrace_return_min: with beta == 0 the two produce the same bits.
+ * Bad arguments (null beta / v_options, num_options <= 0 or > ASAC_OPTION_MAX_OPTIONS, importance sampling without
+ * probabilities, n too large for 64 KB of LDS) return hipErrorInvalidValue without a launch. */
+#define ASAC_OPTION_MAX_OPTIONS 1024
+int asac_option_return(const asac_vtrace_args_t* args_host, const float* beta, int64_t beta_stride_b,
+                       int64_t beta_stride_t, const float* v_options, int64_t v_stride_b, int64_t v_stride_t,
+                       int64_t v_stride_o, int num_options, void* stream);
+
+/* asac_termination_loss_grad: OptionBase.compute_termination_grads behind the head's forward (option_base.py:695-703):
+ *   loss = mean_b(beta[b] * (y[b] - mean_o v_options[b, o] + terminal_entropy) * ~done[b] * priority_is[b])
+ *   dbeta[b] = d loss / d beta[b] = (y[b] - mean_o v_options[b, o] + terminal_entropy) * ~done[b] * priority_is[b] / B
+ * value and gradient from ONE launch for any B <= ASAC_TERMINATION_MAX_ROWS; priority_is may be NULL.  The sum has a
+ * fixed order (lane, wave, workgroup, then the workgroups' sums in workgroup order by the last to arrive: no float
+ * atomics): equal inputs give equal bits.  Rows with done set add an exact 0 and get an exact 0 gradient.
+ *   beta, y, priority_is   element b at b * stride (floats);   v_options element (b, o) at b * v_stride_b + o * v_stride_o
+ *   dbeta f32[B] contiguous;  loss f32[1]
+ *   workspace    asac_termination_loss_grad_workspace() floats, zero before the first launch (every launch leaves them
+ *                usable); one launch at a time per workspace */
+#define ASAC_TERMINATION_MAX_BLOCKS 64
+#define ASAC_TERMINATION_MAX_ROWS (1 << 24)
+int64_t asac_termination_loss_grad_workspace(void);
+int asac_termination_loss_grad(const float* beta, int64_t beta_stride, const float* y, int64_t y_stride,
+                               const float* v_options, int64_t v_stride_b, int64_t v_stride_o, int num_options,
+                               const uint8_t* done, const float* priority_is, int64_t is_stride, float terminal_entropy,
+                               int B, float* loss, float* dbeta, float* workspace, void* stream);
 
 #ifdef __cplusplus
 }

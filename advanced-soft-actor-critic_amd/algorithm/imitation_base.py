@@ -23,6 +23,8 @@ import torch
 
 from asac_amd import native
 
+from .captured_step import CapturedStep
+
 
 ENTROPY_COEF = 0.1      # imitation_base.py:58
 BUCKET = 64
@@ -184,8 +186,7 @@ class _Bucket:
         self.hidden = torch.zeros((1, Tp, *sac.seq_hidden_state_shape), dtype=torch.float32, device=dev)
         self.t_valid = torch.zeros(1, dtype=torch.int32, device=dev)
         self.uses, self.last_T = 0, None      # (last_T: the valid length staged last, None before the first episode)
-        self.graph = self.graph_exec = self.loss = None
-        self.exec_checked = self.graph_failed = False
+        self.graph, self.graph_failed = None, False      # (graph: a CapturedStep whose payload is the step's loss tensor)
 
 
 def _as_device(x, device, dtype=None):
@@ -312,21 +313,12 @@ class ImitationBase:
 
     def _capture(self, bk) -> None:
         sac = self._sac
-        if not sac._graph_api_ok():
+        if not CapturedStep.api_ok():
             self._graph_failed = True       # (a property of the torch build: no bucket can be captured)
             sac._logger.warning('this torch build cannot repair captured memset nodes: imitation steps run eagerly')
             return
         try:
-            side = torch.cuda.Stream(device=sac.device)
-            side.wait_stream(torch.cuda.current_stream())
-            graph = torch.cuda.CUDAGraph(keep_graph=True)
-            with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
-                bk.loss = self._device_step(bk)
-            memsets = getattr(sac, '_graph_memsets', None)
-            sac._finish_graph(graph)            # memset nodes -> fill kernels, then instantiate (as the learner's step)
-            if memsets is not None:
-                sac._graph_memsets = memsets    # (the learner's own record describes its step graph)
-            bk.graph, bk.graph_exec, bk.exec_checked = graph, None, False
+            bk.graph = CapturedStep.capture(lambda: self._device_step(bk), sac.device, logger=sac._logger)
             self.captures += 1
         except Exception as e:
             # a user model with a host synchronisation etc.: THIS bucket stays eager (as the learner's step does after a
@@ -336,24 +328,6 @@ class ImitationBase:
             torch.cuda.synchronize()
             sac._logger.warning(f'hipGraph capture of the imitation step (episodes padded to {bk.Tp}) failed; these '
                                 f'episodes run eagerly, several times slower: {e!r}')
-
-    def _replay(self, bk) -> None:
-        if bk.graph_exec is not None:
-            native.graph_launch(bk.graph_exec)
-            return
-        sac = self._sac
-        if bk.exec_checked or not sac._direct_graph_launch:
-            bk.graph.replay()
-            return
-        gen = torch.cuda.default_generators[sac.device.index or 0]
-        before = gen.get_offset()
-        bk.graph.replay()
-        bk.exec_checked = True
-        if gen.get_offset() == before and hasattr(bk.graph, 'raw_cuda_graph_exec'):
-            try:        # (the step draws no torch random numbers: later replays skip torch's generator bookkeeping)
-                bk.graph_exec = int(bk.graph.raw_cuda_graph_exec())
-            except Exception:
-                pass
 
     def _train_one(self, ep_obses_list, ep_actions) -> None:
         sac = self._sac
@@ -376,15 +350,15 @@ class ImitationBase:
         hp = (self.opt.lr, tuple(self.opt.betas), self.opt.eps)
         if hp != self._graph_hp:        # a captured step holds them as kernel arguments
             for b in self._buckets.values():
-                b.graph = b.graph_exec = None
+                b.graph = None
             self._graph_hp = hp
         bk = self._bucket_for(Tp)
         with torch.cuda.device(dev):
             self._stage(bk, T, obses, actions)
             graph_ok = self._use_graph and not self._graph_failed and not bk.graph_failed
             if graph_ok and bk.graph is not None:
-                self._replay(bk)
-                self._last_loss = bk.loss
+                bk.graph.replay(direct=sac._direct_graph_launch)
+                self._last_loss = bk.graph.payload
             else:
                 self._last_loss = self._device_step(bk)
                 if graph_ok and bk.graph is None:

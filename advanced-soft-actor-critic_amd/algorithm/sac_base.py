@@ -26,7 +26,7 @@ has no PER draws, no IS weights and no step 6 (the reference's `train` skips the
 import contextlib
 import logging
 import random
-from collections import defaultdict
+from collections import defaultdict, namedtuple
 from pathlib import Path
 
 import numpy as np
@@ -43,6 +43,7 @@ from .nn_models import *  # noqa: F401,F403
 from .nn_models.layers.seq_layers import step_mask_cache
 from .nn_models.representation import ModelSimpleRep
 from .batch_buffer import BatchBuffer
+from .captured_step import CapturedStep
 from .replay_buffer import PrioritizedReplayBuffer
 from .sac_aux import AuxHeadsMixin
 from .utils import *  # noqa: F401,F403
@@ -81,6 +82,10 @@ def _real(x):
     formed here: nothing outside the representation ever sees an `adjacent_cat.DeferredCat`"""
     from .adjacent_cat import DeferredCat
     return x.materialize() if isinstance(x, DeferredCat) else x
+
+
+# a captured k-step run (`train_steps`): the step graph it was captured beside, its CapturedStep (None: the capture failed)
+_GraphRun = namedtuple('_GraphRun', 'beside run')
 
 
 class _Window:
@@ -326,10 +331,10 @@ class SAC_Base(AuxHeadsMixin):
 
         self._profiler = UnifiedElapsedTimer(self._logger)
         self.noise = DeviceNoise()
-        self._graph = None
+        self._graph = None        # the train step's CapturedStep: the only holder of its graph's state
         self._graph_hp, self._all_optimizers = None, None     # `_optimizer_hp()` the captured graphs were made with
-        self._graph_runs = {}           # run length -> (the step graph it was captured beside, graph, exec handle)
-        self._la_graphs = {}      # hip_config['lookahead']
+        self._graph_runs = {}     # run length -> _GraphRun
+        self._la_graphs = {}      # hip_config['lookahead']: set parity -> CapturedStep
         self._graph_failed = False
         self._eager_steps = 0
 
@@ -515,7 +520,6 @@ class SAC_Base(AuxHeadsMixin):
         self._cq_buf, self._tq_buf, self._cq_td_buf = (torch.zeros(E, B, 1, **f32) for _ in range(3))
         self._pi_q, self._pi_stats_src = torch.zeros(E, B, 1, **f32), None
         self._pi_a, self._pi_logp, self._pi_sampled = torch.zeros(B, A1, **f32), torch.zeros(B, **f32), False
-        self._graph_exec, self._graph_exec_checked, self._graph_stats_src = None, False, None
         # online + target representation over the same window: fused GRU layers pair up in one launch
         self._rep_twin = None
         if self._twin_rep and type(self.model_rep) is not ModelSimpleRep:
@@ -2192,54 +2196,20 @@ class SAC_Base(AuxHeadsMixin):
         if self.use_n_step_is and not post.mu_written:
             rb.update_window_transitions(ids, -b, b + n, w.bnx_pad, 'mu_prob', pi_probs)
 
-    def _finish_graph(self, graph) -> None:
-        """A captured (kept, not yet instantiated) graph -> executable: its memset nodes become kernel nodes first — on this
-        ROCm a captured hipMemsetAsync takes effect on the first launch only, and ATen's split reductions (every
-        nn.Linear's bias gradient) zero their semaphores with one (csrc/graph_fix.hip)."""
-        replaced, kept = native.graph_replace_memset_nodes(int(graph.raw_cuda_graph()))
-        if kept:
-            # a pitched (2-D) memset has the same replay fault the pass exists to repair and is not rewritten: a step that
-            # captured one must not be replayed (no kernel of the library or of ATen's step issues one today)
-            raise RuntimeError(f'{kept} 2-D memset node(s) in the captured step: not replayable on this ROCm')
-        graph.instantiate()
-        if replaced or kept:
-            self._logger.info(f'captured graph: {replaced} memset node(s) replaced by fill kernels' +
-                              (f', {kept} 2-D memset node(s) left as captured' if kept else ''))
-        self._graph_memsets = (replaced, kept)
-
-    @staticmethod
-    def _graph_api_ok() -> bool:
-        """`CUDAGraph(keep_graph=True)` / `raw_cuda_graph()` / `instantiate()`: the memset-node repair needs the graph before
-        instantiation.  A torch build without them cannot replay a captured step correctly here."""
-        import inspect
-        try:
-            return ('keep_graph' in inspect.signature(torch.cuda.CUDAGraph.__new__).parameters or
-                    'keep_graph' in (torch.cuda.CUDAGraph.__new__.__doc__ or '') or
-                    hasattr(torch.cuda.CUDAGraph, 'raw_cuda_graph')) and hasattr(torch.cuda.CUDAGraph, 'instantiate')
-        except (TypeError, ValueError):
-            return hasattr(torch.cuda.CUDAGraph, 'raw_cuda_graph') and hasattr(torch.cuda.CUDAGraph, 'instantiate')
-
     def _try_capture(self) -> None:
         """Warm up on a side stream, then capture `_device_step` into one hipGraph."""
-        if not self._graph_api_ok():
+        if not CapturedStep.api_ok():
             self._graph_failed = True
             self._logger.warning('this torch build has no CUDAGraph(keep_graph=True) / raw_cuda_graph() / instantiate(): captured '
                                  'memset nodes could not be repaired (they take effect on the first replay only on this '
                                  'ROCm), so the train step is NOT captured and runs eagerly — several times slower')
             return
         try:
-            side = torch.cuda.Stream(device=self.device)
-            side.wait_stream(torch.cuda.current_stream())
-            graph = torch.cuda.CUDAGraph(keep_graph=True)
-            # thread_local: the RCCL watchdog thread may query events while this thread captures
-            with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
-                self._device_step()
-            self._finish_graph(graph)
-            self._graph = graph
-            self._graph_exec, self._graph_exec_checked = None, False
+            self._graph = CapturedStep.capture(self._device_step, self.device, logger=self._logger)
+            self._graph_memsets = self._graph.memsets
             # (logp, scale) of the policy step live in THIS graph's private pool: whichever graph ran last is the one
             # whose tensors `_refresh_policy_stats` must read (a k-step run has its own, `train_steps`)
-            self._graph_stats_src = self._pi_stats_src
+            self._graph.payload = self._pi_stats_src
             self._logger.info('train step captured into a hipGraph')
         except Exception as e:   # user models with host syncs etc.: stay eager, loudly
             self._graph_failed = True
@@ -2248,27 +2218,8 @@ class SAC_Base(AuxHeadsMixin):
             self._logger.warning(f'hipGraph capture of the train step failed, staying eager: {e!r}')
 
     def _replay_graph(self) -> None:
-        """torch's `CUDAGraph.replay()` re-seeds its Philox generator before every launch (two fill
-        kernels).  The first replay goes through torch and watches the generator offset: if the
-        captured step consumed no torch random numbers (all draws come from `asac_noise_fill`), later
-        steps launch the instantiated graph directly."""
-        self._pi_stats_src = self._graph_stats_src
-        if self._graph_exec is not None:
-            native.graph_launch(self._graph_exec)
-            return
-        if self._graph_exec_checked or not self._direct_graph_launch:
-            self._graph.replay()
-            return
-        gen = torch.cuda.default_generators[self.device.index or 0]
-        before = gen.get_offset()
-        self._graph.replay()
-        self._graph_exec_checked = True
-        if gen.get_offset() == before and hasattr(self._graph, 'raw_cuda_graph_exec'):
-            try:
-                self._graph_exec = int(self._graph.raw_cuda_graph_exec())
-                self._logger.info('captured step draws no torch random numbers: launching the graph directly')
-            except Exception as e:   # older torch: keep torch's replay
-                self._logger.warning(f'raw graph handle unavailable, using CUDAGraph.replay(): {e!r}')
+        self._pi_stats_src = self._graph.payload
+        self._graph.replay(self._direct_graph_launch, self._logger)
 
     def _ready_to_train(self) -> bool:
         """Reference `train` 2503-2506: no step until the buffer holds more than a batch.  A data-parallel step holds
@@ -2298,6 +2249,10 @@ class SAC_Base(AuxHeadsMixin):
                 [o for o in self.optimizer_q_list if o is not None]
         return tuple((o.lr, o.betas, o.eps) for o in opts)
 
+    def _drop_graphs(self) -> None:
+        """every captured graph of the learner: the step's, the lookahead's per parity, the k-step runs'"""
+        self._graph, self._la_graphs, self._graph_runs = None, {}, {}
+
     def _drop_graphs_if_hp_changed(self) -> None:
         """a learning rate (betas, eps) changed after capture — a schedule, a user edit — would otherwise go unnoticed by
         every replay: the graphs are dropped and the step is captured again with the new values"""
@@ -2305,9 +2260,7 @@ class SAC_Base(AuxHeadsMixin):
         if hp != self._graph_hp:
             if self._graph_hp is not None and (self._graph is not None or self._la_graphs or self._graph_runs):
                 self._logger.info('optimizer hyper-parameters changed: the captured step is dropped and captured again')
-                self._graph, self._graph_exec, self._graph_exec_checked = None, None, False
-                self._la_graphs = {}
-                self._graph_runs.clear()
+                self._drop_graphs()
             self._graph_hp = hp
 
     @unified_elapsed_timer('train a step', 10)
@@ -2321,11 +2274,10 @@ class SAC_Base(AuxHeadsMixin):
         if rb is None:
             if self.batch_buffer._batch is None:
                 self.batch_buffer.build_static()
-                self._graph = None
+                self._drop_graphs()
         elif rb._gather_keys is None:
             rb._build_batch()
-            self._graph = None
-            self._la_graphs = {}
+            self._drop_graphs()
 
         if self._lookahead:
             if not rb.lookahead:
@@ -2336,8 +2288,7 @@ class SAC_Base(AuxHeadsMixin):
                     rb.sample_next_into_static()
             rb.swap_sets()
             # the captured step holds the sets' addresses: one graph per arrangement, taken in turn
-            self._graph, self._graph_exec, self._graph_exec_checked, self._graph_stats_src = \
-                self._la_graphs.get(rb.parity, (None, None, False, None))
+            self._graph = self._la_graphs.get(rb.parity)
             rb.next_valid = False
 
         with self._profiler('train', repeat=10):
@@ -2355,7 +2306,7 @@ class SAC_Base(AuxHeadsMixin):
         if rb is None:
             self.batch_buffer.pop_host()
         if self._lookahead:
-            self._la_graphs[rb.parity] = (self._graph, self._graph_exec, self._graph_exec_checked, self._graph_stats_src)
+            self._la_graphs[rb.parity] = self._graph
             rb.next_valid = True
 
         # host synchronisation points the reference has too: here the NaN flag of the priority update kernels is
@@ -2386,34 +2337,32 @@ class SAC_Base(AuxHeadsMixin):
         # (batch mode: each step of the run pops a batch — at least k must be queued)
         data_ok = (len(self.batch_buffer) >= k and self.batch_buffer._batch is not None) if rb is None else \
             (rb.is_lg_batch_size and rb._gather_keys is not None)
-        if (k <= 1 or due or self._lookahead or self._graph is None or self._graph_exec is None or self.update_target_per_step != 1
-                or not data_ok):
+        if (k <= 1 or due or self._lookahead or self._graph is None or self._graph.exec_handle is None
+                or self.update_target_per_step != 1 or not data_ok):
             for _ in range(k):
                 step = self.train()
             return step
         cached = self._graph_runs.get(k)
-        if cached is None or cached[0] is not self._graph:      # (captured per run length; dropped with the step's graph)
+        if cached is None or cached.beside is not self._graph:      # (captured per run length; dropped with the step's graph)
+            def k_steps():
+                for _ in range(k):
+                    self._device_step()
             try:
-                side = torch.cuda.Stream(device=self.device)
-                side.wait_stream(torch.cuda.current_stream())
-                graph = torch.cuda.CUDAGraph(keep_graph=True)
-                with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
-                    for _ in range(k):
-                        self._device_step()
-                self._finish_graph(graph)
-                torch.cuda.current_stream().wait_stream(side)
-                cached = self._graph_runs[k] = (self._graph, graph, int(graph.raw_cuda_graph_exec()), self._pi_stats_src)
+                run = CapturedStep.capture(k_steps, self.device, take_exec=True, logger=self._logger)
+                self._graph_memsets = run.memsets
+                run.payload = self._pi_stats_src      # the run's last step leaves its (logp, scale) in the run graph's pool
             except Exception as e:
+                run = None
                 torch.cuda.synchronize()
                 self._logger.warning(f'hipGraph capture of a {k}-step run failed, replaying single steps: {e!r}')
-                self._graph_runs[k] = cached = (self._graph, None, None, None)
-        if cached[2] is None:
+            cached = self._graph_runs[k] = _GraphRun(self._graph, run)
+        if cached.run is None:
             for _ in range(k):
                 step = self.train()
             return step
-        self._pi_stats_src = cached[3]      # the run's last step left its (logp, scale) in the run graph's pool
+        self._pi_stats_src = cached.run.payload
         with self._profiler('train', repeat=10):
-            native.graph_launch(cached[2])
+            cached.run.replay()
         if rb is None:
             for _ in range(k):
                 self.batch_buffer.pop_host()
@@ -2459,8 +2408,7 @@ class SAC_Base(AuxHeadsMixin):
         self._closed = True
         # captured graphs go first (they hold the collectives' kernels of a data-parallel step: a process group must
         # not be torn down under them)
-        self._graph = self._graph_exec = None
-        self._graph_runs.clear()
+        self._drop_graphs()
         if self.device.type == 'cuda':
             torch.cuda.synchronize(self.device)
         if hasattr(self, 'replay_buffer'):

@@ -190,7 +190,7 @@ def _run_schedule(case_kw, hidden, use_graph, runs):
     out = (agent.get_global_step(), agent._params.flat.clone(), agent._target_params.flat.clone(),
            agent._opt_steps.clone(), agent.batch_buffer._head.clone(), len(agent.batch_buffer))
     captured = agent._graph is not None
-    runs_used = any(c[2] is not None for c in agent._graph_runs.values())
+    runs_used = any(c.run is not None and c.run.exec_handle is not None for c in agent._graph_runs.values())
     agent.close()
     return out, captured, runs_used
 

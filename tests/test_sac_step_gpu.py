@@ -307,12 +307,12 @@ def test_train_steps_is_the_train_calls_bit_for_bit(case):
         torch.manual_seed(4)
         for _ in range(8):          # eager warm-up, capture, first replays (the raw graph handle is taken)
             agent.train()
-        assert agent._graph is not None and agent._graph_exec is not None
+        assert agent._graph is not None and agent._graph.exec_handle is not None
         if runs:
             agent.train_steps(4)
             agent.train_steps(4)
             agent.train_steps(3)
-            assert agent._graph_runs[4][2] is not None and agent._graph_runs[3][2] is not None
+            assert agent._graph_runs[4].run.exec_handle is not None and agent._graph_runs[3].run.exec_handle is not None
         else:
             for _ in range(11):
                 agent.train()

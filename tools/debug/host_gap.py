@@ -22,7 +22,7 @@ for _ in range(300):
 torch.cuda.synchronize()
 N = 4000
 for name, fn in (('train()', agent.train),
-                 ('bare asac_graph_launch', (lambda: native.graph_launch(agent._graph_exec)) if getattr(agent, '_graph_exec', None) else None)):
+                 ('bare asac_graph_launch', (lambda: native.graph_launch(agent._graph.exec_handle)) if agent._graph is not None and agent._graph.exec_handle else None)):
     if fn is None:
         print(name, 'n/a (no raw exec handle)')
         continue

@@ -5,7 +5,8 @@ encoded; `train()` is not an entry point of this class.
 
 What runs where:
   * `_get_y`, continuous branch: policy over the window, rsample / tanh / log-prob and pi(stored actions) in one launch
-    (`asac_squash_sample_fwd`), the target critics, then ONE launch for subset minimum, termination mix, mean over the
+    (`asac_squash_sample_fwd`: the parent's `_window_sample`), the target critics, the return's arguments assembled by
+    the parent's `_c_return`, then ONE launch for subset minimum, termination mix, mean over the
     options, ratios and the V-trace scan (`asac_option_return`, csrc/option.hip); with the online critics' values handed
     in (`_get_td_error`, continuous-only action spaces) the same launch writes mean_e |q_e - y|.  The discrete branches
     are torch compositions that end in `asac_vtrace_return_direct` / `get_dqn_like_d_y`, as the parent's.
@@ -44,8 +45,7 @@ from ..fused_mlp import DeferredPartialSums, direct_param_grads
 from ..imitation_base import SpanAdam
 from ..sac_base import SAC_Base
 from ..utils.enums import SEQ_ENCODER
-from ..utils.operators import (get_last_false_indexes, squash_correction_log_prob, squash_correction_prob,
-                               sum_log_prob)
+from ..utils.operators import get_last_false_indexes
 
 _UNSUPPORTED = "OptionBase does not support {what}: {why}"
 
@@ -231,7 +231,7 @@ class OptionBase(SAC_Base):
         this class's: the noise buffer and the ensemble subsets to draw into, where the continuous return goes, and the
         online critics' values [E, batch] whose TD error the return's launch forms as well."""
         B, n = n_rewards.shape
-        dsum, A, E, Es = self.d_action_summed_size, self.c_action_size, self.ensemble_q_num, self.ensemble_q_sample
+        A = self.c_action_size
         f32 = dict(dtype=torch.float32, device=self.device)
         if y_out is None:       # (a fresh tensor per call: the selector keeps the returned y for the termination step)
             y_out = torch.empty(B, **f32)
@@ -243,21 +243,7 @@ class OptionBase(SAC_Base):
         if A:
             if eps_buf is None or eps_buf.shape != (B, n + 1, A):
                 eps_buf = torch.empty((B, n + 1, A), **f32)
-            self.noise.normal_(eps_buf)
-            if plain:   # one launch: rsample, tanh, log-prob and the stored actions' probabilities
-                a_tanh, logp = torch.empty((B, n + 1, A), **f32), torch.empty((B, n + 1), **f32)
-                if self.use_n_step_is:
-                    c_pi = torch.empty((B, n + 1, A), **f32)
-                    native.squash_sample_fwd(loc, scale, eps_buf, a_tanh, logp, None, nx_actions, dsum, c_pi, 0)
-                else:
-                    native.squash_sample_fwd(loc, scale, eps_buf, a_tanh, logp)
-            else:
-                sampled = self._rsample(c_policy, eps_buf)
-                a_tanh = torch.tanh(sampled)
-                logp = sum_log_prob(squash_correction_log_prob(c_policy, sampled)).contiguous()
-                if self.use_n_step_is:
-                    c_pi = squash_correction_prob(
-                        c_policy, torch.atanh(torch.clamp(nx_actions[..., dsum:], -0.999, 0.999))).contiguous()
+            a_tanh, logp, c_pi = self._window_sample(loc, scale, plain, c_policy, eps_buf, nx_actions)
         else:
             a_tanh = torch.zeros(0, device=self.device)
 
@@ -288,11 +274,7 @@ class OptionBase(SAC_Base):
                 tmp_next = (1 - beta) * (min_next - d_alpha * torch.log(next_p.clamp(min=1e-8))) + beta * vbar.unsqueeze(-1)
                 v_n = torch.sum(n_p * tmp_n_vs, dim=-1) / self.d_action_branch_size
                 v_next = torch.sum(next_p * tmp_next, dim=-1) / self.d_action_branch_size
-                mu = pi = None
-                if self.use_n_step_is:
-                    mu = n_mu_probs[..., :dsum] * n_actions[..., :dsum]
-                    mu = torch.where(mu == 0., torch.ones_like(mu), mu).prod(-1).contiguous()
-                    pi = torch.exp(d_policy.log_prob(nx_actions[..., :dsum]).sum(-1))[:, :-1].contiguous()
+                pi, mu = self._stored_action_ratios(d_policy, n_mu_probs, nx_actions) if self.use_n_step_is else (None, None)
                 d_y = torch.empty(B, **f32)
                 args = self._vtrace_args(n_rewards, n_dones, n_last_masks, n_padding_masks, d_y)
                 native.vtrace_return_direct(args, v_n.contiguous(), v_next.contiguous(), pi, mu)
@@ -304,22 +286,9 @@ class OptionBase(SAC_Base):
                 q_tab = torch.stack([q[1] for q in nx_qs]).squeeze(-1)                      # [E, B, n+1]
             else:
                 q_tab = self._c_q_values(True, nx_states, a_tanh, nx_obses_list)
-            args = self._vtrace_args(n_rewards, n_dones, n_last_masks, n_padding_masks, y_out)
-            args.q = q_tab.data_ptr()
-            args.q_stride_e, args.q_stride_b, args.q_stride_t = q_tab.stride(0), q_tab.stride(1), q_tab.stride(2)
-            args.subset_n, args.subset_next, args.E_sample = \
-                (sub_n.data_ptr(), sub_next.data_ptr(), Es) if Es != E else (None, None, Es)
-            logp = logp.contiguous()
-            args.logp, args.log_alpha = logp.data_ptr(), self.log_c_alpha.data_ptr()
-            if self.use_n_step_is:
-                args.pi_prob, args.pi_stride_b, args.pi_stride_t = c_pi.data_ptr(), c_pi.stride(0), c_pi.stride(1)
-                args.mu_prob, args.mu_stride_b, args.mu_stride_t = \
-                    n_mu_probs.data_ptr(), n_mu_probs.stride(0), n_mu_probs.stride(1)
-                args.mu_offset, args.A = dsum, A
-            if q_online is not None and not self.d_action_sizes:
-                q_online = q_online.contiguous()
-                args.q_online, args.E_online, args.td_error_out = q_online.data_ptr(), q_online.shape[0], td_out.data_ptr()
-            native.option_return(args, n_terminations, next_n_vs_over_options)
+            ret = self._c_return(q_tab, logp, c_pi, n_mu_probs, sub_n, sub_next, n_rewards, n_dones, n_last_masks,
+                                 n_padding_masks, y_out, q_online, td_out)
+            native.option_return(ret.args, n_terminations, next_n_vs_over_options)
             c_y = y_out.unsqueeze(-1)
         return d_y, c_y
 

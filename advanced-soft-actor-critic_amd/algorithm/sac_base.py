@@ -86,6 +86,7 @@ def _real(x):
 
 # a captured k-step run (`train_steps`): the step graph it was captured beside, its CapturedStep (None: the capture failed)
 _GraphRun = namedtuple('_GraphRun', 'beside run')
+_Return = namedtuple('_Return', 'args keep')     # `SAC_Base._c_return`
 
 
 class _Window:
@@ -98,6 +99,8 @@ class _AfterPolicy:
     ls_win = alpha_logp = probs_win = td_sample = None      # (loc | scale) [B, L, 2A]; log pi of the temperature sample;
     #                                                           pi(stored actions) [B, L, A]; the TD target's (action, log pi)
     sc_write = sc_alpha = None                               # sidecar jobs still waiting for a host launch
+    td_riders = td_alpha = None                              # for the TD error's return launch (`_launch_return`): the
+    #                                                           sidecar jobs it hosts, the temperature step it anticipates
     side_cq = td_q_table = ls_td = td_pi = None              # online Q(s_b, a_b); target Q on the TD sample; the TD
     #                                                           target's own policy pass (over target states) and its pi
     mu_written = False                                       # the mu-probability write-back is issued / riding
@@ -254,9 +257,6 @@ class SAC_Base(AuxHeadsMixin):
         self._fused_td_chain = bool(hip_config.get('fused_td_chain', True))
         self._fused_td_update = bool(hip_config.get('fused_td_update', True))
         self._fused_q_return = bool(hip_config.get('fused_q_return', True))
-        self._defer_return = False      # `_get_y`: hand the return's arguments back (`_deferred_return`) instead of launching
-        self._deferred_return = None
-        self._td_update_with = None     # (replay buffer, ids): the TD error's return launch also updates the priorities
         self._fused_q_state_grads = bool(hip_config.get('fused_q_state_grads', True))
         self._gru_backward_at = bool(hip_config.get('gru_backward_at', True))
         self._adjacent_cat = bool(hip_config.get('adjacent_cat', True))
@@ -285,7 +285,6 @@ class SAC_Base(AuxHeadsMixin):
         self._rep_epilogue, self._rep_epilogue_hp = False, None      # (False: not looked at yet; None: not applicable)
         self._cat_mode = None
         self._g_state_base = None
-        self._vtrace_sidecars = self._pending_alpha = None
         self._dist_sampling = hip_config.get('dist_sampling', 'throughput')     # 'throughput' | 'parity' 
         self._dist_ready = False        # (collective decision, `_ready_to_train`)
         assert self._dist_sampling in ('throughput', 'parity')
@@ -516,6 +515,10 @@ class SAC_Base(AuxHeadsMixin):
         # zeroed exchange words of `asac_mse_mean_grad` (the observation model's frame loss, sac_aux._train_rpm)
         self._mse_big_ws = torch.zeros(native.mse_mean_grad_workspace(), **f32) if self.use_prediction else None
         self._grad_logp = torch.zeros(B, **f32)
+        # the one hand-over between steps that goes through `self`, from the Q step's return target to the policy step
+        # (`_train_policy` has the reference's signature: no room for either): `_ls_y` = the policy's output over the
+        # return's window, read by `_step_policy`; `_pi_sampled` = the return's sampling launch also drew the policy
+        # step's action at t = 0 into `_pi_a` / `_pi_logp`, taken and cleared by `_train_policy_stock`
         self._ls_y = None
         self._cq_buf, self._tq_buf, self._cq_td_buf = (torch.zeros(E, B, 1, **f32) for _ in range(3))
         self._pi_q, self._pi_stats_src = torch.zeros(E, B, 1, **f32), None
@@ -1015,11 +1018,85 @@ class SAC_Base(AuxHeadsMixin):
         a.y_out = y_out.data_ptr()
         return a
 
+    def _window_sample(self, loc, scale, plain, c_policy, eps_buf, nx_actions, t0_ls=None):
+        """Draws into `eps_buf` and samples the policy over the window -> (a_tanh [B, n+1, A], logp [B, n+1], c_pi =
+        pi(stored actions) [B, n+1, A] under `use_n_step_is`, else None).  `plain`: one launch; with `t0_ls` (the [B, n+1,
+        2A] output `loc | scale` are views of) that launch also draws the policy step's action for t = 0."""
+        dsum, A = self.d_action_summed_size, self.c_action_size
+        self.noise.normal_(eps_buf)
+        if not plain:
+            sampled = self._rsample(c_policy, eps_buf)
+            c_pi = None
+            if self.use_n_step_is:
+                c_pi = squash_correction_prob(
+                    c_policy, torch.atanh(torch.clamp(nx_actions[..., dsum:], -0.999, 0.999))).contiguous()
+            return torch.tanh(sampled), sum_log_prob(squash_correction_log_prob(c_policy, sampled)), c_pi
+        f32 = dict(dtype=torch.float32, device=self.device)
+        a_tanh, logp = torch.empty(loc.shape, **f32), torch.empty(loc.shape[:-1], **f32)
+        c_pi = torch.empty(loc.shape, **f32) if self.use_n_step_is else None
+        stored = dict(action=nx_actions, action_offset=dsum, prob_out=c_pi) if self.use_n_step_is else {}
+        if t0_ls is not None:
+            self.noise.normal_(self._eps_pi)
+            native.squash_multi([
+                native.squash_job(loc, scale, eps_buf, a_tanh, logp, **stored),
+                native.squash_job(t0_ls[:, 0, :A], t0_ls[:, 0, A:], self._eps_pi, self._pi_a, self._pi_logp)])
+            self._pi_sampled = True
+        else:
+            native.squash_sample_fwd(loc, scale, eps_buf, a_tanh, logp, **stored)
+        return a_tanh, logp, c_pi
+
+    def _stored_action_ratios(self, d_policy, n_mu_probs, nx_actions):
+        """discrete branches -> (pi, mu) [B, n]: the stored actions' probability under the policy and under the behaviour
+        policy, as products over the branches"""
+        dsum = self.d_action_summed_size
+        mu = n_mu_probs[..., :dsum] * nx_actions[:, :-1, :dsum]
+        mu = torch.where(mu == 0., torch.ones_like(mu), mu).prod(-1).contiguous()
+        pi = torch.exp(d_policy.log_prob(nx_actions[..., :dsum]).sum(-1))[:, :-1].contiguous()
+        return pi, mu
+
+    def _c_return(self, q_tab, logp, c_pi, n_mu_probs, sub_n, sub_next, n_rewards, n_dones, n_last, n_pad, y_out,
+                  q_online=None, td_out=None):
+        """The continuous return's arguments -> `_Return(args, keep)`: the filled `VtraceArgs` and the tensors it points
+        into that are not the caller's static buffers (alive as long as the record is).  q_tab [E, B, n+1], any strides;
+        with `q_online` [E, B] the launch that takes `args` also writes mean_e |q_e - y| into `td_out`."""
+        E, Es = self.ensemble_q_num, self.ensemble_q_sample
+        args = self._vtrace_args(n_rewards, n_dones, n_last, n_pad, y_out)
+        args.q = q_tab.data_ptr()
+        args.q_stride_e, args.q_stride_b, args.q_stride_t = q_tab.stride(0), q_tab.stride(1), q_tab.stride(2)
+        # (the whole ensemble: the minimum does not depend on the order, no index loads in front of the values)
+        args.subset_n, args.subset_next, args.E_sample = (sub_n.data_ptr(), sub_next.data_ptr(), Es) if Es != E else (None, None, Es)
+        logp = logp.contiguous()
+        args.logp, args.log_alpha = logp.data_ptr(), self.log_c_alpha.data_ptr()
+        if self.use_n_step_is:
+            args.pi_prob, args.pi_stride_b, args.pi_stride_t = c_pi.data_ptr(), c_pi.stride(0), c_pi.stride(1)
+            args.mu_prob, args.mu_stride_b, args.mu_stride_t = \
+                n_mu_probs.data_ptr(), n_mu_probs.stride(0), n_mu_probs.stride(1)
+            args.mu_offset, args.A = self.d_action_summed_size, self.c_action_size
+        if q_online is not None and not self.d_action_sizes:
+            q_online = q_online.contiguous()
+            args.q_online, args.E_online, args.td_error_out = q_online.data_ptr(), q_online.shape[0], td_out.data_ptr()
+        return _Return(args, (q_tab, logp, c_pi, n_mu_probs, sub_n, sub_next, q_online))
+
+    @staticmethod
+    def _launch_return(ret, *, sidecars=None, pending_alpha=None, td_update=None) -> bool:
+        """Issues the ONE launch that forms the return `ret` (`_c_return`) describes, with `sidecars` as extra workgroups
+        and evaluated with the temperature the not-yet-run step `pending_alpha` will write.  `td_update` = (replay buffer,
+        ids): where `ret` asks for the TD error that launch is the buffer's priority update too (it then runs the
+        temperature step itself) -> True, else False."""
+        if td_update is not None and ret.args.td_error_out:
+            rb, ids = td_update
+            rb.td_update(ret.args, ids, sidecars=sidecars, alpha_step=pending_alpha)
+            return True
+        native.vtrace_return_min(ret.args, sidecars=sidecars, pending_alpha=pending_alpha)
+        return False
+
     @torch.no_grad()
     def _get_y(self, n_last_masks, n_padding_masks, nx_obses_list, nx_states, nx_actions, n_rewards,
                n_dones, n_mu_probs, *, eps_buf, subset_prefix, y_out, q_online=None, td_out=None, ls=None,
-               sample=None, stored_pi=None, policy_sample=False, q_table=None):
-        """-> (d_y [B,1] | None, c_y [B,1] | None).
+               sample=None, stored_pi=None, policy_sample=False, q_table=None, launch=True):
+        """-> (d_y [B,1] | None, c_y [B,1] | None);  with `launch=False` -> (d_y, c_y, ret): the continuous return's
+        launch is NOT issued, `c_y` is where it will write and `ret` what `_launch_return` (or a launch that forms the
+        return itself) needs — None without continuous actions.
 
         Stock continuous-only networks may hand over work they already did: `ls` = the policy's
         [B, n+1, 2A] (loc | scale) output for `nx_states`; `sample` = (a_tanh [B, n+1, A], logp [B, n+1])
@@ -1033,7 +1110,6 @@ class SAC_Base(AuxHeadsMixin):
         ([E, B], continuous-only action spaces) the TD error mean_e|q_e - y| is produced by the
         same launch into `td_out`.
         """
-        dsum = self.d_action_summed_size
         n_actions = nx_actions[:, :-1]
         if ls is None and sample is None and self._fpi is not None and self.c_action_size and nx_states.dim() == 3:
             # the stock policy over the window and the window's sample as ONE launch (`_return_sample_epilogue`)
@@ -1065,40 +1141,18 @@ class SAC_Base(AuxHeadsMixin):
                 bonus = torch.sum(d.mul_(d), dim=-1).mul_(0.5)       # 0.5 * sum (approx - actual)^2
                 n_rewards.add_(bonus, alpha=self.curiosity_strength)
 
-        logp = None
+        logp = c_pi = None
         if self.c_action_size and sample is not None:
-            a_tanh, logp = sample
-            c_pi = stored_pi
+            (a_tanh, logp), c_pi = sample, stored_pi
         elif self.c_action_size:
-            self.noise.normal_(eps_buf)
-            c_pi = None
-            if plain:   # one launch: rsample, tanh, log-prob and the stored-action probabilities
-                a_tanh = torch.empty(loc.shape, dtype=torch.float32, device=self.device)
-                logp = torch.empty(loc.shape[:-1], dtype=torch.float32, device=self.device)
-                if policy_sample and ls is not None and ls.dim() == 3:
-                    A = self.c_action_size
-                    self.noise.normal_(self._eps_pi)
-                    if self.use_n_step_is:
-                        c_pi = torch.empty(loc.shape, dtype=torch.float32, device=self.device)
-                    native.squash_multi([
-                        native.squash_job(loc, scale, eps_buf, a_tanh, logp, nx_actions if self.use_n_step_is else None,
-                                          dsum, c_pi, 0),
-                        native.squash_job(ls[:, 0, :A], ls[:, 0, A:], self._eps_pi, self._pi_a, self._pi_logp)])
-                    self._pi_sampled = True
-                elif self.use_n_step_is:
-                    c_pi = torch.empty(loc.shape, dtype=torch.float32, device=self.device)
-                    native.squash_sample_fwd(loc, scale, eps_buf, a_tanh, logp, None, nx_actions, dsum, c_pi, 0)
-                else:
-                    native.squash_sample_fwd(loc, scale, eps_buf, a_tanh, logp)
-            else:
-                sampled = self._rsample(c_policy, eps_buf)
-                a_tanh = torch.tanh(sampled)
-                logp = sum_log_prob(squash_correction_log_prob(c_policy, sampled))
+            a_tanh, logp, c_pi = self._window_sample(
+                loc, scale, plain, c_policy, eps_buf, nx_actions,
+                t0_ls=ls if plain and policy_sample and ls is not None and ls.dim() == 3 else None)
         else:
             a_tanh = torch.zeros(0, device=self.device)
 
-        d_y = c_y = None
-        E, Es = self.ensemble_q_num, self.ensemble_q_sample
+        d_y = c_y = ret = None
+        E = self.ensemble_q_num
         nx_qs = None
         if self.d_action_sizes:
             nx_qs = [q(nx_states, a_tanh, nx_obses_list) for q in self.model_target_q_list]
@@ -1126,11 +1180,7 @@ class SAC_Base(AuxHeadsMixin):
             v_n = torch.sum(n_p * (mean_n - d_alpha * torch.log(n_p.clamp(min=1e-8))), -1) / self.d_action_branch_size
             v_next = torch.sum(next_p * (mean_next - d_alpha * torch.log(next_p.clamp(min=1e-8))), -1) \
                 / self.d_action_branch_size
-            mu = pi = None
-            if self.use_n_step_is:
-                mu = n_mu_probs[..., :dsum] * n_actions[..., :dsum]
-                mu = torch.where(mu == 0., torch.ones_like(mu), mu).prod(-1).contiguous()
-                pi = torch.exp(d_policy.log_prob(nx_actions[..., :dsum]).sum(-1))[:, :-1].contiguous()
+            pi, mu = self._stored_action_ratios(d_policy, n_mu_probs, nx_actions) if self.use_n_step_is else (None, None)
             d_y = torch.empty(n_rewards.shape[0], dtype=torch.float32, device=self.device)
             args = self._vtrace_args(n_rewards, n_dones, n_last_masks, n_padding_masks, d_y)
             native.vtrace_return_direct(args, v_n.contiguous(), v_next.contiguous(), pi, mu)
@@ -1146,42 +1196,50 @@ class SAC_Base(AuxHeadsMixin):
                 q_tab = torch.stack([q[1] for q in nx_qs]).squeeze(-1)        # [E, B, n+1]
             else:
                 q_tab = self._c_q_values(True, nx_states, a_tanh, nx_obses_list)
-            args = self._vtrace_args(n_rewards, n_dones, n_last_masks, n_padding_masks, y_out)
-            args.q = q_tab.data_ptr()
-            args.q_stride_e, args.q_stride_b, args.q_stride_t = q_tab.stride(0), q_tab.stride(1), q_tab.stride(2)
-            # (the whole ensemble: the minimum does not depend on the order, no index loads in front of the values)
-            args.subset_n, args.subset_next, args.E_sample = (sub_n.data_ptr(), sub_next.data_ptr(), Es) if Es != E else (None, None, Es)
-            logp = logp.contiguous()
-            args.logp, args.log_alpha = logp.data_ptr(), self.log_c_alpha.data_ptr()
-            if self.use_n_step_is:
-                if not plain:
-                    c_pi = squash_correction_prob(
-                        c_policy, torch.atanh(torch.clamp(nx_actions[..., dsum:], -0.999, 0.999))).contiguous()
-                args.pi_prob, args.pi_stride_b, args.pi_stride_t = c_pi.data_ptr(), c_pi.stride(0), c_pi.stride(1)
-                args.mu_prob, args.mu_stride_b, args.mu_stride_t = \
-                    n_mu_probs.data_ptr(), n_mu_probs.stride(0), n_mu_probs.stride(1)
-                args.mu_offset, args.A = dsum, self.c_action_size
-            if q_online is not None and not self.d_action_sizes:
-                args.q_online, args.E_online, args.td_error_out = q_online.data_ptr(), q_online.shape[0], td_out.data_ptr()
-            sidecars = None
-            if q_online is not None and self._vtrace_sidecars:     # the TD error's launch hosts the pending write-backs
-                sidecars, self._vtrace_sidecars = self._vtrace_sidecars, None
-            if self._defer_return and q_online is None and sidecars is None:
-                # (the caller's Q-loss backward forms this return itself; everything `args` points to is the caller's)
-                self._deferred_return = (args, (q_tab, logp, c_pi, sub_n, sub_next))
-            elif q_online is not None and self._td_update_with is not None and args.td_error_out:
-                (rb, ids), self._td_update_with = self._td_update_with, None
-                rb.td_update(args, ids, sidecars=sidecars, alpha_step=self._pending_alpha)
-                self._pending_alpha = None
-            else:
-                native.vtrace_return_min(args, sidecars=sidecars,
-                                         pending_alpha=self._pending_alpha if q_online is not None else None)
+            ret = self._c_return(q_tab, logp, c_pi, n_mu_probs, sub_n, sub_next, n_rewards, n_dones, n_last_masks,
+                                 n_padding_masks, y_out, q_online, td_out)
+            if launch:
+                self._launch_return(ret)
             c_y = y_out.unsqueeze(-1)
-        return d_y, c_y
+        return (d_y, c_y) if launch else (d_y, c_y, ret)
 
     # ==========================================================================================
     # losses / updates (reference _train_rep_q 1468-1605, _train_policy 1841-1911, _train_alpha 1913-1949)
     # ==========================================================================================
+    def _stock_q_targets(self, job_tq, job_pi, ls, window, policy_sample):
+        """One launch: the target Q of the stored pair (`job_tq`, for the clipped loss) beside the policy over the window
+        (`job_pi`, `ls` its output) — whose lanes also draw the window's sample (`_return_sample_epilogue`; otherwise an
+        elementwise launch in `_get_y`).  Then the return target over `window` (`_get_y`'s positional arguments), its
+        launch not issued -> (c_y, ret)."""
+        nx_states, nx_actions = window[3], window[4]
+        ls = ls[0].view(*nx_states.shape[:2], 2 * self.c_action_size)
+        pre = self._return_sample_epilogue([job_tq, job_pi], 1, ls, nx_actions, self._eps_y, policy_sample)
+        if pre is None:
+            native.mlp_forward_multi([job_tq, job_pi])
+        sample, stored_pi = pre or (None, None)
+        _, c_y, ret = self._get_y(*window, eps_buf=self._eps_y, subset_prefix='y', y_out=self._y_buf, ls=ls,
+                                  sample=sample, stored_pi=stored_pi, policy_sample=policy_sample and pre is None,
+                                  launch=False)
+        return c_y, ret
+
+    def _stock_q_backward(self, x0, a0, ret, c_y, priority_is, fold, fused_return, state_grads=False):
+        """[online critics forward, clipped double-Q loss, backward] in one launch (the backward recomputes the forward
+        on chip anyway).  With `fused_return` its own workgroups form the return target `ret` where that form applies
+        (short windows); otherwise the return's launch goes first.  `fold`: the tile reduction of the parameter
+        gradients is folded into the Adam launch, issued here.  -> d loss / d x0 [E, B, S] with `state_grads`."""
+        w = priority_is.reshape(-1).contiguous() if priority_is is not None else None
+        t_q = self._tq_buf.view(self.ensemble_q_num, -1)
+        if fused_return and self._fq.backward_qloss_return_ok(x0.shape[-2], ret.args):
+            g0 = self._fq.backward_qloss_return(x0, a0, t_q, ret.args, w, self.clip_epsilon, self._loss_q_e,
+                                                defer=fold, state_grads=state_grads)
+        else:
+            self._launch_return(ret)
+            g0 = self._fq.backward_qloss(x0, a0, t_q, c_y.reshape(-1), w, self.clip_epsilon, self._loss_q_e,
+                                         defer=fold, state_grads=state_grads)
+        if fold:
+            self._fq.adam_partials(self.optimizer_q_list[0], loss_out=self._loss_q_e)
+        return g0
+
     @torch.no_grad()
     def _train_rep_q_stock(self, n_last_masks, n_padding_masks, nx_obses_list, nx_states, nx_actions, n_rewards,
                            n_dones, n_mu_probs, priority_is, policy_sample):
@@ -1195,6 +1253,8 @@ class SAC_Base(AuxHeadsMixin):
         job_tq, _ = self._ftq.job(x0, a0, out=self._tq_buf)
         job_pi, ls = self._fpi.job(xs, None)
         T, A = nx_states.shape[1], self.c_action_size
+        window = (n_last_masks, n_padding_masks, nx_obses_list, nx_states, nx_actions, n_rewards, n_dones,
+                  n_mu_probs if self.use_n_step_is else None)
         fused = None
         if self._fused_forward_chain and self.curiosity is None:
             # policy over the window -> target sample (+ pi(stored actions), + the policy step's sample at t = 0) ->
@@ -1217,46 +1277,17 @@ class SAC_Base(AuxHeadsMixin):
                 self.noise.normal_(self._eps_pi)
                 self._pi_sampled = True
             native.policy_sample_q_forward(fused, [job_tq], sidecars=self._take_la_gather())
-            ls = ls[0].view(B, T, 2 * A)
-            # the return target is formed by the Q-loss backward's own workgroups where that form applies: its
-            # arguments are assembled as always, its launch is not issued
-            self._defer_return, self._deferred_return = self._fused_q_return, None
-            _, c_y = self._get_y(n_last_masks, n_padding_masks, nx_obses_list, nx_states, nx_actions, n_rewards,
-                                 n_dones, n_mu_probs if self.use_n_step_is else None, eps_buf=self._eps_y,
-                                 subset_prefix='y', y_out=self._y_buf, ls=ls, sample=(a_y, logp_y), stored_pi=c_pi,
-                                 q_table=q_tab.view(E, B, T))
-            self._defer_return = False
+            _, c_y, ret = self._get_y(*window, eps_buf=self._eps_y, subset_prefix='y', y_out=self._y_buf,
+                                      ls=ls[0].view(B, T, 2 * A), sample=(a_y, logp_y), stored_pi=c_pi,
+                                      q_table=q_tab.view(E, B, T), launch=False)
         else:
-            # one launch: target Q of the stored pair (for the clipped loss) beside the policy over the window — whose
-            # lanes also draw the window's sample (`_return_sample_epilogue`; otherwise an elementwise launch in `_get_y`)
-            ls = ls[0].view(*nx_states.shape[:2], 2 * self.c_action_size)
-            pre = self._return_sample_epilogue([job_tq, job_pi], 1, ls, nx_actions, self._eps_y, policy_sample)
-            if pre is not None:
-                _, c_y = self._get_y(n_last_masks, n_padding_masks, nx_obses_list, nx_states, nx_actions, n_rewards,
-                                     n_dones, n_mu_probs if self.use_n_step_is else None, eps_buf=self._eps_y,
-                                     subset_prefix='y', y_out=self._y_buf, ls=ls, sample=pre[0], stored_pi=pre[1])
-            else:
-                native.mlp_forward_multi([job_tq, job_pi])
-                _, c_y = self._get_y(n_last_masks, n_padding_masks, nx_obses_list, nx_states, nx_actions, n_rewards,
-                                     n_dones, n_mu_probs if self.use_n_step_is else None, eps_buf=self._eps_y,
-                                     subset_prefix='y', y_out=self._y_buf, policy_sample=policy_sample, ls=ls)
-        w = priority_is.reshape(-1).contiguous() if priority_is is not None else None
-        # loss + backward in one launch (the backward recomputes the forward on chip anyway); on a single
-        # GPU the tile reduction of the parameter gradients is folded into the Adam launch
+            c_y, ret = self._stock_q_targets(job_tq, job_pi, ls, window, policy_sample)
+        # on a single GPU the tile reduction of the parameter gradients is folded into the Adam launch
         opt = self.optimizer_q_list[0]
         fold = self._dist is None and opt.start == self._fq._start and self._params.span('rep')[0] == self._params.span('rep')[1]
-        ret, self._deferred_return = self._deferred_return, None
-        if ret is not None and self._fq.backward_qloss_return_ok(B, ret[0]):
-            self._fq.backward_qloss_return(x0, a0, self._tq_buf.view(E, B), ret[0], w, self.clip_epsilon, self._loss_q_e,
-                                           defer=fold)
-        else:
-            if ret is not None:
-                native.vtrace_return_min(ret[0])
-            self._fq.backward_qloss(x0, a0, self._tq_buf.view(E, B), c_y.reshape(-1), w, self.clip_epsilon,
-                                    self._loss_q_e, defer=fold)
-        if fold:
-            self._fq.adam_partials(opt, loss_out=self._loss_q_e)
-        else:
+        # (behind the one-launch forward the backward may form the return itself; behind the chain form it never did)
+        self._stock_q_backward(x0, a0, ret, c_y, priority_is, fold, fused_return=fused is not None and self._fused_q_return)
+        if not fold:
             self._finish_rep_q(None, None)
 
     def _train_rep_q(self, n_last_masks, n_padding_masks, nx_obses_list, nx_states, nx_actions, n_rewards,
@@ -1286,40 +1317,17 @@ class SAC_Base(AuxHeadsMixin):
             with torch.no_grad():
                 x0 = StockMLP._rows(base.detach()[:, t], self.state_size)
                 a0 = StockMLP._rows(c_action, self.c_action_size)
-                # one launch: target Q of the stored pair (for the clipped loss) beside the policy over the window
                 states_y = nx_states.detach()
-                job_tq, t_q = self._ftq.job(x0, a0, out=self._tq_buf)
+                job_tq, _ = self._ftq.job(x0, a0, out=self._tq_buf)
                 job_pi, ls_y = self._fpi.job(StockMLP._rows_in_place(states_y, self.state_size), None)
-                ls_y = ls_y[0].view(*states_y.shape[:2], 2 * self.c_action_size)
-                # ... whose lanes also draw the window's sample (`_return_sample_epilogue`): no elementwise launch behind it
-                pre = self._return_sample_epilogue([job_tq, job_pi], 1, ls_y, nx_actions, self._eps_y, policy_sample)
-                sampled = pre is not None
-                if not sampled:
-                    native.mlp_forward_multi([job_tq, job_pi])
-                self._defer_return, self._deferred_return = self._fused_q_return, None
-                _, c_y = self._get_y(n_last_masks, n_padding_masks, nx_obses_list, states_y, nx_actions,
-                                     n_rewards, n_dones, n_mu_probs if self.use_n_step_is else None,
-                                     eps_buf=self._eps_y, subset_prefix='y', y_out=self._y_buf,
-                                     policy_sample=policy_sample and not sampled, ls=ls_y,
-                                     sample=pre[0] if sampled else None, stored_pi=pre[1] if sampled else None)
-                self._defer_return = False
-                w = priority_is.reshape(-1).contiguous() if priority_is is not None else None
-                ret, self._deferred_return = self._deferred_return, None
+                c_y, ret = self._stock_q_targets(
+                    job_tq, job_pi, ls_y, (n_last_masks, n_padding_masks, nx_obses_list, states_y, nx_actions, n_rewards,
+                                           n_dones, n_mu_probs if self.use_n_step_is else None), policy_sample)
                 # one GPU: the critics' tile reduction is folded into their Adam launch (as without a trainable
                 # representation), which then no longer waits for the representation's backward
-                opt = self.optimizer_q_list[0]
                 fold = self._dist is None and self._fold_rep_q_adam and self._rep_q_adam_alike()
-                if ret is not None and self._fq.backward_qloss_return_ok(x0.shape[-2], ret[0]):
-                    # (short windows: the return target is formed by the backward's own workgroups, no launch of its own)
-                    g0 = self._fq.backward_qloss_return(x0, a0, t_q.view(self.ensemble_q_num, -1), ret[0], w,
-                                                        self.clip_epsilon, self._loss_q_e, state_grads=True, defer=fold)
-                else:
-                    if ret is not None:
-                        native.vtrace_return_min(ret[0])
-                    g0 = self._fq.backward_qloss(x0, a0, t_q.view(self.ensemble_q_num, -1), c_y.reshape(-1), w,
-                                                 self.clip_epsilon, self._loss_q_e, state_grads=True, defer=fold)
-                if fold:
-                    self._fq.adam_partials(opt, loss_out=self._loss_q_e)
+                g0 = self._stock_q_backward(x0, a0, ret, c_y, priority_is, fold, fused_return=self._fused_q_return,
+                                            state_grads=True)
                 # d loss / d (window states): zero except at position t — a buffer that stays zero elsewhere, so only the
                 # slice is written each step (no memset launch)
                 g_base = self._g_state_base
@@ -1718,9 +1726,10 @@ class SAC_Base(AuxHeadsMixin):
 
     @torch.no_grad()
     def _get_td_error(self, n_last_masks, n_padding_masks, nx_obses_list, state, nx_target_states, nx_actions,
-                      n_rewards, n_dones, n_mu_probs, ls=None, sample=None, stored_pi=None, c_q=None, q_table=None):
-        """mean_e |Q_e(s0, a0) - y(target states)| -> self._td_error [B] (reference 2182-2245).
-        `ls`: see `_get_y`."""
+                      n_rewards, n_dones, n_mu_probs, ls=None, sample=None, stored_pi=None, c_q=None, q_table=None, *,
+                      sidecars=None, pending_alpha=None, td_update=None):
+        """mean_e |Q_e(s0, a0) - y(target states)| -> (self._td_error [B], the launch that formed it was the priority
+        update too) (reference 2182-2245).  `ls` .. `q_table`: see `_get_y`; the keywords: see `_launch_return`."""
         dsum = self.d_action_summed_size
         obs_list = [o[:, 0] for o in nx_obses_list]
         action = nx_actions[:, 0]
@@ -1734,12 +1743,16 @@ class SAC_Base(AuxHeadsMixin):
         else:
             c_q = self._c_q_values(False, state, c_action, obs_list).contiguous()
         fused_td = bool(self.c_action_size) and not self.d_action_sizes
-        d_y, c_y = self._get_y(n_last_masks, n_padding_masks, nx_obses_list, nx_target_states, nx_actions,
-                               n_rewards, n_dones, n_mu_probs, eps_buf=self._eps_td, subset_prefix='td',
-                               y_out=self._y_td_buf, q_online=c_q if fused_td else None, td_out=self._td_error,
-                               ls=ls, sample=sample, stored_pi=stored_pi, q_table=q_table)
-        if fused_td:
-            return self._td_error
+        d_y, c_y, ret = self._get_y(n_last_masks, n_padding_masks, nx_obses_list, nx_target_states, nx_actions,
+                                    n_rewards, n_dones, n_mu_probs, eps_buf=self._eps_td, subset_prefix='td',
+                                    y_out=self._y_td_buf, q_online=c_q if fused_td else None, td_out=self._td_error,
+                                    ls=ls, sample=sample, stored_pi=stored_pi, q_table=q_table, launch=False)
+        if fused_td:    # (only then are there riders: they come from the stock continuous-only chain)
+            return self._td_error, self._launch_return(ret, sidecars=sidecars, pending_alpha=pending_alpha,
+                                                       td_update=td_update)
+        assert not sidecars and pending_alpha is None and td_update is None
+        if ret is not None:
+            self._launch_return(ret)
         err = torch.zeros((self.ensemble_q_num, state.shape[0], 1), device=self.device)
         if self.d_action_sizes:
             d_q = torch.stack([torch.sum(d_action * q[0], dim=-1, keepdim=True) / self.d_action_branch_size
@@ -1748,7 +1761,7 @@ class SAC_Base(AuxHeadsMixin):
         if self.c_action_size:
             err = err + torch.abs(c_q.unsqueeze(-1) - c_y)
         self._td_error.copy_(err.mean(dim=0).reshape(-1))
-        return self._td_error
+        return self._td_error, False
 
     # ==========================================================================================
     # episode ingress (reference sac_base.py:2303-2396)
@@ -1809,7 +1822,6 @@ class SAC_Base(AuxHeadsMixin):
         self._step_rep_and_q(w)
         self._step_policy(w)
         post = _AfterPolicy()
-        self._vtrace_sidecars = self._pending_alpha = None
         if not self.use_replay_buffer:
             # batch mode (reference train 2536-2539): no TD error, no priorities, no mu-probability / hidden-state
             # write-back — only the temperature step follows the policy step
@@ -2031,12 +2043,12 @@ class SAC_Base(AuxHeadsMixin):
         native.policy_sample_q_forward(job, [job_q], sidecars=[sc_elect])
         if post.sc_alpha is not None:
             self._alpha_logp_over_ranks(alpha_logp)
-        self._pending_alpha = post.sc_alpha      # (None: a wider optimizer -> `_train_alpha`)
+        post.td_alpha = post.sc_alpha      # (None: a wider optimizer -> `_train_alpha`)
         post.ls_win = ls_out[0].view(B_, L_, 2 * A)
         post.probs_win, post.td_sample, post.alpha_logp = probs_win, td_sample, alpha_logp
         post.td_q_table = td_q_table.view(self.ensemble_q_num, B_, L_)
         post.side_cq = self._cq_td_buf.view(self.ensemble_q_num, -1)
-        self._vtrace_sidecars = [post.sc_write]
+        post.td_riders = [post.sc_write]
         post.mu_written = True
         return True
 
@@ -2116,8 +2128,8 @@ class SAC_Base(AuxHeadsMixin):
             if riders and self._wide_critics:
                 # no critic launch to ride in: the write-back's second pass goes with the TD error's return, the temperature
                 # step with the priority update (the return evaluates the value that step will write)
-                self._vtrace_sidecars = [post.sc_write] if post.sc_write is not None else None
-                self._pending_alpha = post.sc_alpha
+                post.td_riders = [post.sc_write] if post.sc_write is not None else None
+                post.td_alpha = post.sc_alpha
                 riders = []
             if post.td_sample is not None:
                 job_q, _ = self._fq.job(xb, ab, out=self._cq_td_buf)
@@ -2159,13 +2171,14 @@ class SAC_Base(AuxHeadsMixin):
         # priority update (the step's last two launches; its own election scratch: the mu-probability write pass may
         # share the return launch)
         hidden_write = None
+        td_riders = list(post.td_riders or ())
         if (self.seq_hidden_state_shape[-1] != 0 and self.use_priority and self._use_sidecars
                 and rb.sharded is None and bool(self.c_action_size) and not self.d_action_sizes
-                and len(self._vtrace_sidecars or ()) < native.MAX_SIDECARS):
+                and len(td_riders) < native.MAX_SIDECARS):
             hidden_rows = w.next_hidden.detach().contiguous()
             h_elect, hidden_write = rb.window_scatter_sidecars(ids, 1 - b, b + n, w.bnx_pad, 'pre_seq_hidden_state',
                                                                hidden_rows, side=True)
-            self._vtrace_sidecars = list(self._vtrace_sidecars or ()) + [h_elect]
+            td_riders.append(h_elect)
         if self.use_priority:
             # no write pass waiting for the update's launch: the TD error's return and the priority update are one launch
             # (one workgroup forms every return: it pays while each of its threads has at most one step of one window —
@@ -2173,23 +2186,17 @@ class SAC_Base(AuxHeadsMixin):
             merged = (self._fused_td_update and hidden_write is None and self._use_sidecars
                       and bool(self.c_action_size) and not self.d_action_sizes and ids.numel() * n <= 1024
                       and rb.td_update_ok(ids, n))
-            self._td_update_with = (rb, ids) if merged else None
             own_td_policy = post.td_pi is not None     # the TD target's policy ran over the target states
-            td = self._get_td_error(w.bn_last[:, b:], w.bn_pad[:, b:], w.nx_obs, bn_states[:, b],
-                                    w.nx_target_states, w.bnx_actions[:, b:], w.bn_rewards[:, b:],
-                                    w.bn_dones[:, b:], pi_probs[:, b:] if self.use_n_step_is else None,
-                                    ls=None if post.td_sample is None else (post.ls_td if own_td_policy else post.ls_win),
-                                    sample=post.td_sample,
-                                    stored_pi=None if post.td_sample is None else (post.td_pi if own_td_policy else post.probs_win),
-                                    c_q=post.side_cq,
-                                    q_table=post.td_q_table)
-            assert not self._vtrace_sidecars, 'the TD error\'s return launch did not take its sidecars'
-            if merged and self._td_update_with is None:
-                assert self._pending_alpha is None      # the return's launch ran the temperature step and the update
-            else:
-                self._td_update_with = None
-                rb.update(ids, td, sidecars=[sc for sc in (self._pending_alpha, hidden_write) if sc is not None] or None)
-                self._pending_alpha = None
+            td, updated = self._get_td_error(
+                w.bn_last[:, b:], w.bn_pad[:, b:], w.nx_obs, bn_states[:, b], w.nx_target_states, w.bnx_actions[:, b:],
+                w.bn_rewards[:, b:], w.bn_dones[:, b:], pi_probs[:, b:] if self.use_n_step_is else None,
+                ls=None if post.td_sample is None else (post.ls_td if own_td_policy else post.ls_win),
+                sample=post.td_sample,
+                stored_pi=None if post.td_sample is None else (post.td_pi if own_td_policy else post.probs_win),
+                c_q=post.side_cq, q_table=post.td_q_table,
+                sidecars=td_riders or None, pending_alpha=post.td_alpha, td_update=(rb, ids) if merged else None)
+            if not updated:     # (else the return's launch ran the temperature step and the update)
+                rb.update(ids, td, sidecars=[sc for sc in (post.td_alpha, hidden_write) if sc is not None] or None)
         if self.seq_hidden_state_shape[-1] != 0 and hidden_write is None:
             rb.update_window_transitions(ids, 1 - b, b + n, w.bnx_pad, 'pre_seq_hidden_state',
                                          w.next_hidden.detach().contiguous())

@@ -373,3 +373,51 @@ def test_data_parallel_path_single_rank_nccl():
                 np.testing.assert_allclose(a, b, rtol=1e-5, atol=1e-6)
     finally:
         dist.destroy_process_group()
+
+
+def test_return_launched_from_its_record_is_get_y_bit_for_bit():
+    """`_get_y(launch=False)` + `_launch_return(ret)` == `_get_y` launching itself: the same draws consumed, the same
+    bits in `y_out`, and the record alone keeps what its `VtraceArgs` point into alive until the launch.  Windows are
+    slices of longer ones, so the strided q / pi / mu fields and the mask strides all matter (B 8, n 3, A 2, E 2 of 2)."""
+    import asac_amd  # noqa: F401
+    from algorithm.fused import RecordedNoise
+    SAC_Base = pu.hooked_learner()
+    B, n, A, S, b = 8, 3, 2, 6, 2
+    agent = SAC_Base(['vector'], [(S,)], [], A, None, nn_vec, device='cuda:0', batch_size=B, n_step=n,
+                     ensemble_q_num=2, ensemble_q_sample=2, use_n_step_is=True, replay_config={'capacity': 64},
+                     hip_config={'use_graph': False})
+    assert agent._stock_c_only() and agent.use_n_step_is
+    rng = np.random.default_rng(11)
+    dev = lambda x: torch.from_numpy(x).to('cuda:0')  # noqa: E731
+    f32 = lambda *shape: dev(rng.standard_normal(shape).astype(np.float32))  # noqa: E731
+    L = b + n + 1
+    states, actions = f32(B, L, S), torch.tanh(f32(B, L, A))
+    mu = dev(rng.uniform(0.2, 2., (B, L - 1, A)).astype(np.float32))
+    rewards = f32(B, L - 1)
+    dones, last, pad = (dev(rng.random((B, L - 1)) < p) for p in (0.1, 0.1, 0.15))
+    window = (last[:, b:], pad[:, b:], [states[:, b:]], states[:, b:], actions[:, b:], rewards[:, b:], dones[:, b:],
+              mu[:, b:])
+    eps, perm = rng.standard_normal((B, n + 1, A)).astype(np.float32), [rng.permutation(2) for _ in range(2)]
+
+    def get_y(**kw):
+        agent.noise = RecordedNoise(eps=[eps], perm=perm)
+        y_out = torch.full((B,), float('nan'), device='cuda:0')
+        out = agent._get_y(*window, eps_buf=torch.empty((B, n + 1, A), device='cuda:0'), subset_prefix='y', y_out=y_out, **kw)
+        assert agent.noise.exhausted(), 'the same draws either way'
+        return y_out, out
+
+    y_direct, (d_y, c_y) = get_y()
+    assert d_y is None and c_y.data_ptr() == y_direct.data_ptr() and torch.isfinite(y_direct).all()
+    y_later, (d_y, c_y, ret) = get_y(launch=False)
+    assert d_y is None and c_y.data_ptr() == y_later.data_ptr()
+    assert torch.isnan(y_later).all(), 'launch=False issues no return launch'
+    # nothing but the record refers to the sample, its log-probability, pi(stored actions) and the target values now: were
+    # one of them released, the allocations below would land on it
+    del d_y, c_y
+    torch.cuda.empty_cache()
+    junk = [torch.full((B, n + 1, A), float('nan'), device='cuda:0') for _ in range(64)]
+    assert {t.data_ptr() for t in ret.keep if t is not None} >= {ret.args.q, ret.args.logp, ret.args.pi_prob, ret.args.mu_prob}
+    assert not {t.data_ptr() for t in junk} & {t.data_ptr() for t in ret.keep if t is not None}
+    assert agent._launch_return(ret) is False       # (no priority update asked for: the plain return launch)
+    assert torch.equal(y_later.view(torch.int32), y_direct.view(torch.int32))
+    agent.close()

@@ -109,6 +109,18 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
+// the sum over a workgroup of THREADS lanes, valid in thread 0: wave_sum, then the waves in order
+template <int THREADS>
+__device__ __forceinline__ float block_sum_waves(float v) {
+    __shared__ float s_wave[THREADS / 64];
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float t = 0.f;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < THREADS / 64; ++w) t += s_wave[w];
+    return t;
+}
 
 // Kernel arguments read WHERE THEY ARE USED.  A by-value struct parameter is loaded whole in the kernel's entry block:
 // with argument blocks of 0.5 - 2 KB the kernel starts with dozens of scalar loads in several dependent wait groups and

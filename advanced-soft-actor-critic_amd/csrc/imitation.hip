@@ -5,9 +5,10 @@
 // loc = 5 tanh(m / 5), scale = exp(clamp(s, -20, 0.5))) itself and the gradients are with respect to the raw values.
 //
 // The sum has a fixed order: lane partial (elements in index order) -> wave (xor butterfly) -> workgroup (waves in order)
-// -> the last workgroup to arrive adds the workgroups' sums in workgroup order.  The arrival counter is an integer; no
-// float atomics, so two launches on the same input give the same bits.  -ffp-contract=off.
+// -> the last workgroup to arrive adds the workgroups' sums in workgroup order (asac_ordered_finish.h).  The arrival
+// counter is an integer; no float atomics, so two launches on the same input give the same bits.  -ffp-contract=off.
 #include "asac_common.h"
+#include "asac_ordered_finish.h"
 #include "asac_squash.h"
 
 namespace asac {
@@ -28,9 +29,7 @@ struct BcArgs {
 };
 
 __global__ __launch_bounds__(kBcThreads) void k_bc_loss_grad(const BcArgs a) {
-    __shared__ float s_wave[kBcThreads / 64];
-    __shared__ bool s_last;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int A = a.A, n = a.Tp * A;                      // (n < 2^31 checked by the host)
     int tv = *a.t_valid;
     tv = tv < 0 ? 0 : (tv > a.Tp ? a.Tp : tv);
@@ -74,27 +73,12 @@ __global__ __launch_bounds__(kBcThreads) void k_bc_loss_grad(const BcArgs a) {
             a.dscale[row * a.ld_out + d] = gs;
         }
     }
-    s = wave_sum(s);
-    if (lane == 0) s_wave[wave] = s;
-    __syncthreads();
-    if (tid == 0) {
-        float v = 0.f;
-        for (int w = 0; w < kBcThreads / 64; ++w) v += s_wave[w];
-        __hip_atomic_store(a.partial + blockIdx.x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __threadfence();                                  // the sum is visible before the arrival is
-        s_last = atomicAdd(a.counter, 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!s_last || wave != 0) return;
-    __threadfence();
-    // one ordered pass: lane w holds workgroup w's sum, added in workgroup order by lane 0
-    float mine = lane < (int)gridDim.x ? __hip_atomic_load(a.partial + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-    float v = 0.f;
-    for (int w = 0; w < (int)gridDim.x; ++w) v += __shfl(mine, w, 64);
-    if (lane == 0) {
-        *a.loss = tv > 0 ? v / ((float)tv * (float)A) : 0.f;      // torch.mean: the sum over the count
-        __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next launch
-    }
+    s = block_sum_waves<kBcThreads>(s);
+    if (tid == 0) finish_publish(a.partial + blockIdx.x, s);
+    if (!finish_arrive(a.counter) || tid != 0) return;
+    const float v = finish_sum_in_order(a.partial, 1, (int)gridDim.x);
+    *a.loss = tv > 0 ? v / ((float)tv * (float)A) : 0.f;          // torch.mean: the sum over the count
+    finish_reset(a.counter);
 }
 
 }  // namespace asac

@@ -7,10 +7,11 @@
 // A workgroup (4 waves) owns 64 rows: staged in LDS as they lie in memory (coalesced, whatever the row strides and the
 // two-part input), then every product on 16x16x4 f32 MFMA with the rows as the N dimension — forward x W^T, backward g W
 // (input gradient) and G^T (X | 1) (per-workgroup partial parameter gradients).  The partials are summed in workgroup order
-// (deterministic; no float atomics): by the last workgroup to finish when they are few, else by csrc/xty.hip's slice reduction
+// (deterministic; no float atomics): by the last workgroup to finish when they are few (asac_ordered_finish.h), else by csrc/xty.hip's slice reduction
 // as a second launch.  (Rounds 1-4 ran one lane per row with the weights broadcast from LDS: at K = 64 the 64-step scalar
 // loops of a lane made the backward 35 us for 9 216 rows; the MFMA form is 9.)
 #include "asac_common.h"
+#include "asac_ordered_finish.h"
 
 namespace asac {
 
@@ -135,7 +136,6 @@ __global__ __launch_bounds__(kLinThreads) void k_linear_tanh_bwd(const LinArgs a
     __shared__ __attribute__((aligned(16))) float gs[kLinRows * kLinMaxO];          // g = gy * (1 - y^2), [row][16]
     __shared__ float xs[kLinRows * kXsPitch];          // the workgroup's input rows and a column of ones, [row][K + 1]
     __shared__ int64_t roff[kLinRows], roff1[kLinRows];
-    __shared__ bool last;
     const int64_t r0 = (int64_t)blockIdx.x * kLinRows;
     const int rows = (int)min((int64_t)kLinRows, a.N - r0);
     stage_wt(a, wt);
@@ -224,39 +224,21 @@ __global__ __launch_bounds__(kLinThreads) void k_linear_tanh_bwd(const LinArgs a
                 const int o = 4 * kk + rr;
                 if (o < a.O && col <= a.K) {
                     float* dst = mine + (col < a.K ? o * a.K + col : a.O * a.K + o);
-                    // (TAIL: written through to where every workgroup sees it — no release fence, which would write back
-                    // this XCD's whole L2)
-                    if (TAIL) __hip_atomic_store(dst, acc[rr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (TAIL) finish_publish(dst, acc[rr]);
                     else *dst = acc[rr];
                 }
             }
         }
     }
     if (!TAIL) return;
-    // the last workgroup to arrive sums the partials in workgroup order (relaxed device-scope accesses ordered by the wait
-    // for this wave's stores and the barrier)
-    __builtin_amdgcn_s_waitcnt(0);
-    __syncthreads();
-    if (threadIdx.x == 0) last = __hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-    __syncthreads();
-    if (!last) return;
-    // sixteen partials requested at a time, then added in workgroup order
-    const int nb = (int)gridDim.x;
+    // the last workgroup to arrive sums the partials in workgroup order, one gradient element per lane
+    if (!finish_arrive(a.counter)) return;
     for (int t = threadIdx.x; t < P; t += kLinThreads) {
-        float* col = a.partial + t;
-        float s = 0.f;
-        for (int b0 = 0; b0 < nb; b0 += 16) {
-            float v[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u)
-                v[u] = __hip_atomic_load(col + (int64_t)min(b0 + u, nb - 1) * P, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-            for (int u = 0; u < 16; ++u) s += b0 + u < nb ? v[u] : 0.f;
-        }
+        const float s = finish_sum_in_order(a.partial + t, P, (int)gridDim.x);
         float* dst = a.gp + t;
         *dst = a.accumulate ? *dst + s : s;
     }
-    if (threadIdx.x == 0) __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // ready for the next launch
+    if (threadIdx.x == 0) finish_reset(a.counter);
 }
 
 static bool lin_dims_ok(int64_t N, int K, int O) { return N > 0 && K > 0 && K <= kLinMaxK && O > 0 && O <= kLinMaxO; }

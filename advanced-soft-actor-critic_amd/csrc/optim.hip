@@ -3,6 +3,7 @@
 // 16-byte loads/stores, grid capped at 2048 workgroups with a grid-stride loop.
 #include "asac_common.h"
 #include "asac_gelu.h"
+#include "asac_ordered_finish.h"
 #include "asac_sidecar.h"
 
 #include <cmath>
@@ -143,20 +144,45 @@ __global__ __launch_bounds__(256) void k_curiosity_bonus(const float* __restrict
 // Loss of the curiosity model (reference sac_base.py:1951-1976): mean over ALL N = B T K elements of the squared
 // error with padded rows zeroed, and its gradient with respect to the prediction:
 //   d = (pred - target) * !mask[b][t];  loss = sum d^2 / N;  grad = d * 2 / N
-// Eight elements per lane; the workgroups' sums are added in workgroup order by the last one to arrive.
+// Eight elements per lane; the workgroups' sums are added in workgroup order by the last one to arrive
+// (asac_ordered_finish.h).
 constexpr int kMseThreads = 256, kMsePerLane = 8;
+
+// Q sums over the workgroup's lanes, valid in thread 0: an LDS tree down to 64, the last strides inside wave 0
+template <int Q>
+__device__ __forceinline__ void block_sums_tree(float (&red)[Q][kMseThreads], float (&v)[Q]) {
+#pragma unroll
+    for (int q = 0; q < Q; ++q) red[q][threadIdx.x] = v[q];
+    __syncthreads();
+    for (int h = kMseThreads / 2; h >= 64; h >>= 1) {
+        if ((int)threadIdx.x < h) {
+#pragma unroll
+            for (int q = 0; q < Q; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + h];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 64) {
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            float x = red[q][threadIdx.x];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
+            v[q] = x;
+        }
+    }
+}
+
 __global__ __launch_bounds__(kMseThreads) void k_masked_mse(const float* __restrict__ pred, const float* __restrict__ target,
                                                             int64_t target_sb, int64_t target_st,
                                                             const uint8_t* __restrict__ mask, int64_t mask_sb, int B, int T,
                                                             int K, float* __restrict__ grad, float* __restrict__ loss,
-                                                            float* __restrict__ partial, unsigned int* __restrict__ counter) {
-    __shared__ float red[kMseThreads];
-    __shared__ bool last;
+                                                            float* partial, unsigned int* counter) {
+    __shared__ float red[1][kMseThreads];
     const int N = B * T * K;                         // (N <= 2^20: 32-bit index arithmetic)
     const float scale = 2.f / (float)N;
     const int base = blockIdx.x * kMseThreads * kMsePerLane;
     // eight elements per lane, their loads requested together (a rolled loop waits for every pair in turn)
-    float pv[kMsePerLane], qv[kMsePerLane], s = 0.f;
+    float pv[kMsePerLane], qv[kMsePerLane], s[1] = {0.f};
     bool pad[kMsePerLane];
 #pragma unroll
     for (int u = 0; u < kMsePerLane; ++u) {
@@ -171,44 +197,22 @@ __global__ __launch_bounds__(kMseThreads) void k_masked_mse(const float* __restr
         const int i = base + u * kMseThreads + (int)threadIdx.x;
         if (i < N) {
             const float d = pad[u] ? 0.f : pv[u] - qv[u];
-            s += d * d;
+            s[0] += d * d;
             grad[i] = d * scale;
         }
     }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = kMseThreads / 2; w >= 64; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x < 64) {                          // the last strides inside wave 0
-        float v = red[threadIdx.x];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-        if (threadIdx.x == 0) partial[blockIdx.x] = v;
-    }
-    // the last workgroup to arrive adds the workgroups' sums in workgroup order (deterministic)
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(counter, 1u) == gridDim.x - 1;
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
-    if (threadIdx.x == 0) {
-        float v = 0.f;
-        for (unsigned int w = 0; w < gridDim.x; ++w) v += partial[w];
-        *loss = v / (float)N;
-        *counter = 0u;                               // ready for the next launch
-    }
+    block_sums_tree(red, s);
+    if (threadIdx.x == 0) finish_publish(partial + blockIdx.x, s[0]);
+    if (!finish_arrive(counter) || threadIdx.x != 0) return;
+    *loss = finish_sum_in_order(partial, 1, (int)gridDim.x) / (float)N;
+    finish_reset(counter);
 }
 
 // The same loss over MILLIONS of elements — a plugin's observation loss `mse_loss(decoded frames, frames)`, 11 M floats at
 // BASELINE configs[4] (sac_base.py:1817 through `ModelObservation.get_loss`) — for which ATen runs a 44 MB elementwise
 // pass, a split reduction and, backwards, a fill and another elementwise pass: one launch, loss and gradient (the scaled
 // difference) from ONE read of both operands.  Rows of K % 4 == 0 floats, 16-byte loads, a bounded grid of persistent
-// workgroups; the workgroups' sums are added in a fixed order by the last to arrive.  The exchange uses relaxed
-// agent-scope atomics only: an agent-scope release would write back every dirty line of the XCD's L2, i.e. the
-// gradient this very launch is streaming out (sumtree.hip, SampleSync).
+// workgroups; the workgroups' sums are added in a fixed order by the last to arrive (asac_ordered_finish.h).
 constexpr int kMseBigGrid = 2048;
 __global__ __launch_bounds__(kMseThreads) void k_mse_big(const float* __restrict__ pred, const float* __restrict__ target,
                                                          int64_t target_sb, int64_t target_st, int T, int K4,
@@ -216,7 +220,6 @@ __global__ __launch_bounds__(kMseThreads) void k_mse_big(const float* __restrict
                                                          float* __restrict__ grad, float* __restrict__ loss, float* partial,
                                                          unsigned int* counter) {
     __shared__ float red[kMseThreads];
-    __shared__ bool last;
     const float scale = 2.f * inv_n * grad_scale;
     const float4* p4 = reinterpret_cast<const float4*>(pred);
     float4* g4 = reinterpret_cast<float4*>(grad);
@@ -271,13 +274,8 @@ __global__ __launch_bounds__(kMseThreads) void k_mse_big(const float* __restrict
         if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
         __syncthreads();
     }
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(partial + blockIdx.x, red[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __builtin_amdgcn_s_waitcnt(0);
-        last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last) return;
+    if (threadIdx.x == 0) finish_publish(partial + blockIdx.x, red[0]);
+    if (!finish_arrive(counter)) return;
     // fixed order: lane t adds partials [8 t, 8 t + 8) in turn, then the tree above
     // (all eight requested before the first is added: one by one each waited for its own trip to memory)
     constexpr int PER = kMseBigGrid / kMseThreads;
@@ -285,7 +283,7 @@ __global__ __launch_bounds__(kMseThreads) void k_mse_big(const float* __restrict
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
         const unsigned int w = min(threadIdx.x * PER + j, gridDim.x - 1);
-        t[j] = __hip_atomic_load(partial + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        t[j] = finish_load(partial + w);
     }
     float v = 0.f;
 #pragma unroll
@@ -298,7 +296,7 @@ __global__ __launch_bounds__(kMseThreads) void k_mse_big(const float* __restrict
     }
     if (threadIdx.x == 0) {
         *loss = red[0] * inv_n;
-        __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next launch
+        finish_reset(counter);
     }
 }
 
@@ -307,18 +305,17 @@ __global__ __launch_bounds__(kMseThreads) void k_mse_big(const float* __restrict
 //   loss = -mean(log N(x; loc, scale)) + w * mean(KL(N(loc, scale) || N(0, 1))),  entropy = mean(H(N(loc, scale)))
 // with torch.distributions' formulas, and d loss / d loc, d loss / d scale — the forward AND the backward of ATen's
 // ~25 + ~35 elementwise launches over [B, n, S] tensors as one launch.  Sums over several workgroups, added in workgroup
-// order by the last to arrive.
+// order by the last to arrive (asac_ordered_finish.h).
 __global__ __launch_bounds__(kMseThreads) void k_normal_nll_kl(const float* __restrict__ loc, int64_t loc_sb, int64_t loc_st,
                                                                const float* __restrict__ scale, int64_t scale_sb,
                                                                int64_t scale_st, const float* __restrict__ target,
                                                                int64_t target_sb, int64_t target_st, int B, int T, int K,
                                                                float w, float* __restrict__ grad_loc,
                                                                float* __restrict__ grad_scale, float* __restrict__ out,
-                                                               float* __restrict__ partial, unsigned int* __restrict__ counter,
+                                                               float* partial, unsigned int* counter,
                                                                int log_scale, float scale_min, float scale_max,
                                                                int64_t grad_pitch) {
     __shared__ float red[3][kMseThreads];
-    __shared__ bool last;
     const int N = B * T * K;
     const float inv_n = 1.f / (float)N;
     const float c_lp = 0.918938533204672742f;        // log(sqrt(2 pi))
@@ -360,36 +357,20 @@ __global__ __launch_bounds__(kMseThreads) void k_normal_nll_kl(const float* __re
             grad_scale[at] = gs;
         }
     }
-    red[0][threadIdx.x] = s_lp, red[1][threadIdx.x] = s_kl, red[2][threadIdx.x] = s_ent;
-    __syncthreads();
-    for (int h = kMseThreads / 2; h >= 64; h >>= 1) {
-        if ((int)threadIdx.x < h) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + h];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < 64) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            float v = red[q][threadIdx.x];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-            if (threadIdx.x == 0) partial[blockIdx.x * 3 + q] = v;
-        }
-    }
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(counter, 1u) == gridDim.x - 1;
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
+    float sums[3] = {s_lp, s_kl, s_ent};
+    block_sums_tree(red, sums);
     if (threadIdx.x == 0) {
-        float a = 0.f, b2 = 0.f, e = 0.f;
-        for (unsigned int g = 0; g < gridDim.x; ++g) a += partial[g * 3], b2 += partial[g * 3 + 1], e += partial[g * 3 + 2];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) finish_publish(partial + blockIdx.x * 3 + q, sums[q]);
+    }
+    if (!finish_arrive(counter) || threadIdx.x >= 64) return;
+    // lanes 0, 1, 2 of wave 0 add one of the three interleaved sums each
+    const float mine = threadIdx.x < 3 ? finish_sum_in_order(partial + threadIdx.x, 3, (int)gridDim.x) : 0.f;
+    const float a = __shfl(mine, 0, 64), b2 = __shfl(mine, 1, 64), e = __shfl(mine, 2, 64);
+    if (threadIdx.x == 0) {
         out[0] = -(a * inv_n) + w * (b2 * inv_n);
         out[1] = e * inv_n;
-        *counter = 0u;
+        finish_reset(counter);
     }
 }
 

@@ -14,9 +14,10 @@
 // asac_termination_loss_grad — compute_termination_grads behind the head's forward (option_base.py:695-703):
 //   loss = mean_b(beta_b * (y_b - mean_o V_bo + terminal_entropy) * ~done_b * is_b),  d loss / d beta_b
 // Summation order of the loss: lane partial (elements in index order) -> wave (xor butterfly) -> workgroup (waves in
-// order) -> the last workgroup to arrive adds the workgroups' sums in workgroup order.  The arrival counter is an integer;
-// no float atomics: equal inputs give equal bits.  -ffp-contract=off.
+// order) -> the last workgroup to arrive adds the workgroups' sums in workgroup order (asac_ordered_finish.h).  The
+// arrival counter is an integer; no float atomics: equal inputs give equal bits.  -ffp-contract=off.
 #include "asac_common.h"
+#include "asac_ordered_finish.h"
 #include "asac_vtrace.h"
 
 namespace asac {
@@ -132,9 +133,7 @@ struct TermArgs {
 };
 
 __global__ __launch_bounds__(kTermThreads) void k_termination_loss_grad(const TermArgs a) {
-    __shared__ float s_wave[kTermThreads / 64];
-    __shared__ bool s_last;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int B = a.B;
     const float inv = 1.f / (float)B;
     const int stride = gridDim.x * kTermThreads;
@@ -167,27 +166,11 @@ __global__ __launch_bounds__(kTermThreads) void k_termination_loss_grad(const Te
             a.dbeta[i] = g;
         }
     }
-    s = wave_sum(s);
-    if (lane == 0) s_wave[wave] = s;
-    __syncthreads();
-    if (tid == 0) {
-        float w = 0.f;
-        for (int k = 0; k < kTermThreads / 64; ++k) w += s_wave[k];
-        __hip_atomic_store(a.partial + blockIdx.x, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __threadfence();                                  // the sum is visible before the arrival is
-        s_last = atomicAdd(a.counter, 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!s_last || wave != 0) return;
-    __threadfence();
-    // one ordered pass: lane w holds workgroup w's sum, added in workgroup order by lane 0
-    float mine = lane < (int)gridDim.x ? __hip_atomic_load(a.partial + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-    float total = 0.f;
-    for (int w = 0; w < (int)gridDim.x; ++w) total += __shfl(mine, w, 64);
-    if (lane == 0) {
-        *a.loss = total / (float)B;                       // torch.mean: the sum over the count
-        __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next launch
-    }
+    s = block_sum_waves<kTermThreads>(s);
+    if (tid == 0) finish_publish(a.partial + blockIdx.x, s);
+    if (!finish_arrive(a.counter) || tid != 0) return;
+    *a.loss = finish_sum_in_order(a.partial, 1, (int)gridDim.x) / (float)B;      // torch.mean: the sum over the count
+    finish_reset(a.counter);
 }
 
 }  // namespace asac

@@ -1411,7 +1411,16 @@ def linear_tanh_backward(x, weight, y, grad_y, grad_x, grad_params, accumulate, 
 
 
 MASKED_MSE_MAX = 1 << 20
-_MSE_WS = {}
+_EXCHANGE_WS = {}
+
+
+def _exchange_words(entry: str, device, *size) -> torch.Tensor:
+    """the cached exchange words (workgroup partials + arrival counter, csrc/asac_ordered_finish.h) of one entry point on one
+    device, `<entry>_workspace(*size)` floats (asked once per size): zero before first use, left ready by every launch"""
+    key = (entry, size, torch.device(device))
+    if key not in _EXCHANGE_WS:
+        _EXCHANGE_WS[key] = torch.zeros(int(getattr(load(), entry + '_workspace')(*size)), dtype=torch.float32, device=key[2])
+    return _EXCHANGE_WS[key]
 
 
 def _window3(t):
@@ -1432,8 +1441,9 @@ def curiosity_bonus(approx, actual, reward, strength):
 
 
 @_profiled
-def masked_mse(pred, target, padding_mask, grad_out, loss_out):
-    """loss_out <- mean over all elements of ((pred - target) * ~mask)^2, grad_out <- its gradient w.r.t. pred"""
+def masked_mse(pred, target, padding_mask, grad_out, loss_out, workspace=None):
+    """loss_out <- mean over all elements of ((pred - target) * ~mask)^2, grad_out <- its gradient w.r.t. pred
+    (`workspace`, here and below: the caller's own zeroed exchange words instead of the cached ones)"""
     B, T, K = pred.shape
     assert pred.is_contiguous() and grad_out.is_contiguous() and grad_out.shape == pred.shape and target.shape == pred.shape
     pt, sb, st = _window3(target)
@@ -1441,10 +1451,8 @@ def masked_mse(pred, target, padding_mask, grad_out, loss_out):
     if padding_mask is not None:
         assert padding_mask.shape == (B, T) and padding_mask.element_size() == 1 and (padding_mask.stride(1) == 1 or T == 1)
         pm, ms = _p(padding_mask), padding_mask.stride(0)
-    key = (pred.numel(), pred.device)
-    if key not in _MSE_WS:      # zero before first use, left zero by every launch
-        _MSE_WS[key] = torch.zeros(int(load().asac_masked_mse_workspace(pred.numel())), dtype=torch.float32, device=pred.device)
-    _check(load().asac_masked_mse(_p(pred), pt, sb, st, pm, ms, B, T, K, _p(grad_out), _p(loss_out), _p(_MSE_WS[key]),
+    ws = workspace if workspace is not None else _exchange_words('asac_masked_mse', pred.device, pred.numel())
+    _check(load().asac_masked_mse(_p(pred), pt, sb, st, pm, ms, B, T, K, _p(grad_out), _p(loss_out), _p(ws),
                                   _stream()), 'asac_masked_mse')
 
 
@@ -1469,11 +1477,8 @@ def mse_mean_grad_ok(pred, target) -> bool:
             and target.data_ptr() % 16 == 0 and 0 < pred.numel() < 2 ** 33)
 
 
-_NLL_WS = {}
-
-
 @_profiled
-def normal_nll_kl(loc, scale, target, kl_weight, grad_loc, grad_scale, out):
+def normal_nll_kl(loc, scale, target, kl_weight, grad_loc, grad_scale, out, workspace=None):
     """out[0] <- -mean(log N(target; loc, scale)) + kl_weight * mean(KL(N(loc, scale) || N(0, 1))), out[1] <- mean
     entropy, grad_loc / grad_scale <- d out[0] / d loc, / d scale ([B, T, K] views in, dense gradients out)"""
     B, T, K = loc.shape
@@ -1482,15 +1487,13 @@ def normal_nll_kl(loc, scale, target, kl_weight, grad_loc, grad_scale, out):
     pl, lb, lt = _window3(loc)
     ps, sb, st = _window3(scale)
     pt, tb, tt = _window3(target)
-    key = (loc.numel(), loc.device)
-    if key not in _NLL_WS:
-        _NLL_WS[key] = torch.zeros(int(load().asac_normal_nll_kl_workspace(loc.numel())), dtype=torch.float32, device=loc.device)
+    ws = workspace if workspace is not None else _exchange_words('asac_normal_nll_kl', loc.device, loc.numel())
     _check(load().asac_normal_nll_kl(pl, lb, lt, ps, sb, st, pt, tb, tt, B, T, K, float(kl_weight), _p(grad_loc),
-                                     _p(grad_scale), _p(out), _p(_NLL_WS[key]), _stream()), 'asac_normal_nll_kl')
+                                     _p(grad_scale), _p(out), _p(ws), _stream()), 'asac_normal_nll_kl')
 
 
 @_profiled
-def normal_nll_kl_logstd(raw, scale_min, scale_max, target, kl_weight, grad_raw, out):
+def normal_nll_kl_logstd(raw, scale_min, scale_max, target, kl_weight, grad_raw, out, workspace=None):
     """`normal_nll_kl` of N(mean, clamp(exp(logstd), scale_min, scale_max)) with (mean | logstd) = the halves of raw
     [B, T, 2K]; grad_raw [B, T, 2K] dense <- d out[0] / d raw"""
     B, T, K2 = raw.shape
@@ -1498,12 +1501,10 @@ def normal_nll_kl_logstd(raw, scale_min, scale_max, target, kl_weight, grad_raw,
     assert K2 == 2 * K and raw.stride(2) == 1 and target.shape == (B, T, K) and target.stride(2) == 1
     assert grad_raw.is_contiguous() and grad_raw.shape == raw.shape and out.numel() == 2 and out.is_contiguous()
     _dense_f32(grad_raw, out)
-    key = (B * T * K, raw.device)
-    if key not in _NLL_WS:
-        _NLL_WS[key] = torch.zeros(int(load().asac_normal_nll_kl_workspace(B * T * K)), dtype=torch.float32, device=raw.device)
+    ws = workspace if workspace is not None else _exchange_words('asac_normal_nll_kl', raw.device, B * T * K)  # (its kernel)
     _check(load().asac_normal_nll_kl_logstd(_p(raw), raw.stride(0), raw.stride(1), float(scale_min), float(scale_max),
                                             _p(target), target.stride(0), target.stride(1), B, T, K, float(kl_weight),
-                                            _p(grad_raw), _p(out), _p(_NLL_WS[key]), _stream()), 'asac_normal_nll_kl_logstd')
+                                            _p(grad_raw), _p(out), _p(ws), _stream()), 'asac_normal_nll_kl_logstd')
 
 
 @_profiled
@@ -2394,15 +2395,11 @@ def xty_multi(jobs, accumulate=False):
 # behaviour cloning (csrc/imitation.hip)
 # ------------------------------------------------------------------------------------------------
 BC_MAX_ELEMENTS = 1 << 24
-_BC_WS = {}
 
 
 def bc_loss_grad_workspace(device) -> torch.Tensor:
     """the zeroed exchange words of `bc_loss_grad` on `device` (every launch leaves them ready for the next)"""
-    key = torch.device(device)
-    if key not in _BC_WS:
-        _BC_WS[key] = torch.zeros(int(load().asac_bc_loss_grad_workspace()), dtype=torch.float32, device=key)
-    return _BC_WS[key]
+    return _exchange_words('asac_bc_loss_grad', device)
 
 
 @_profiled
@@ -2437,7 +2434,6 @@ def bc_loss_grad(loc, scale, action, action_offset, t_valid, entropy_coef, loss_
 # ------------------------------------------------------------------------------------------------
 OPTION_MAX_OPTIONS = 1024
 TERMINATION_MAX_ROWS = 1 << 24
-_TERM_WS = {}
 
 
 @_profiled
@@ -2458,10 +2454,7 @@ def option_return(args: VtraceArgs, beta, v_options):
 
 def termination_loss_grad_workspace(device) -> torch.Tensor:
     """the zeroed exchange words of `termination_loss_grad` on `device` (every launch leaves them ready for the next)"""
-    key = torch.device(device)
-    if key not in _TERM_WS:
-        _TERM_WS[key] = torch.zeros(int(load().asac_termination_loss_grad_workspace()), dtype=torch.float32, device=key)
-    return _TERM_WS[key]
+    return _exchange_words('asac_termination_loss_grad', device)
 
 
 @_profiled

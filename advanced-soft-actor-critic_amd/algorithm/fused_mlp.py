@@ -456,15 +456,11 @@ class StockMLP:
         return StockMLP._rows(x, width)
 
     def _launch_forward(self, x0, x1, out=None):
-        if isinstance(x0, native.WindowRows):
-            job, out = self.job(x0, x1, out)
+        job, out = self.job(x0, x1, out)
+        if isinstance(x0, native.WindowRows):       # (window addressing: the multi-job launch has it)
             native.mlp_forward_multi([job])
-            return out
-        N = x0.shape[-2]
-        if out is None:
-            out = torch.empty((self.E, N, self.out_cols), dtype=torch.float32, device=self.device)
-        assert out.shape == (self.E, N, self.out_cols) and out.is_contiguous()
-        native.mlp_forward(self.desc, self.params, self.member_stride, self.E, x0, x1, N, out)
+        else:
+            native.mlp_forward(job)
         return out
 
     def _workspace_for(self, N):
@@ -484,22 +480,20 @@ class StockMLP:
         members' gradients w.r.t. x0 (a trainable representation continues the backward from their sum)."""
         N = x0.shape[-2]
         g0 = torch.empty((self.E, N, self.in0), dtype=torch.float32, device=self.device) if state_grads else None
-        native.mlp_backward_qloss(self.desc, self.params, self.member_stride, self.E, x0, x1, N, target_q, y, weights,
-                                  clip_eps, loss_out, self.grad_params, self._workspace_for(N), self._reduce_mode(defer),
-                                  grad_x0=g0)
+        native.mlp_backward_qloss(self._pass(x0, x1), target_q, y, weights, clip_eps, loss_out, self.grad_params,
+                                  self._workspace_for(N), self._reduce_mode(defer), grad_x0=g0)
         self._deferred_rows = N if defer else None
         return g0
 
     def backward_qloss_return_ok(self, N: int, ret) -> bool:
-        return native.mlp_backward_qloss_return_ok(self.desc, self.params, self.member_stride, self.E, N, ret)
+        return native.mlp_backward_qloss_return_ok(self._pass(None, None, N=N), ret)
 
     def backward_qloss_return(self, x0, x1, target_q, ret, weights, clip_eps, loss_out, defer=False, state_grads=False):
         """`backward_qloss` with the return target `ret` (native.VtraceArgs, its launch not issued) formed inside."""
         N = x0.shape[-2]
         g0 = torch.empty((self.E, N, self.in0), dtype=torch.float32, device=self.device) if state_grads else None
-        native.mlp_backward_qloss_return(self.desc, self.params, self.member_stride, self.E, x0, x1, N, target_q, ret,
-                                         weights, clip_eps, loss_out, self.grad_params, self._workspace_for(N),
-                                         self._reduce_mode(defer), grad_x0=g0)
+        native.mlp_backward_qloss_return(self._pass(x0, x1), target_q, ret, weights, clip_eps, loss_out, self.grad_params,
+                                         self._workspace_for(N), self._reduce_mode(defer), grad_x0=g0)
         self._deferred_rows = N if defer else None
         return g0
 
@@ -508,16 +502,15 @@ class StockMLP:
         forward on the same inputs)."""
         N = x0.shape[-2]
         g1 = torch.empty((self.E, N, self.in1), dtype=torch.float32, device=self.device)
-        native.mlp_backward_policy_q(self.desc, self.params, self.member_stride, self.E, x0, x1, N, q_table, subset,
-                                     E_sample, g1)
+        native.mlp_backward_policy_q(self._pass(x0, x1), q_table, subset, E_sample, g1)
         return g1
 
     def backward_policy_sample(self, x0, eps, grad_a, log_alpha, defer=False):
         """Gaussian-head policy (E = 1): sampling backward + network backward in one launch; `grad_a`
         [members, N, A] are the action gradients of the ensemble members."""
         N = x0.shape[-2]
-        native.mlp_backward_policy_sample(self.desc, self.params, self.member_stride, x0, N, eps, grad_a, log_alpha,
-                                          self.grad_params, self._workspace_for(N), self._reduce_mode(defer))
+        native.mlp_backward_policy_sample(self._pass(x0, None), eps, grad_a, log_alpha, self.grad_params,
+                                          self._workspace_for(N), self._reduce_mode(defer))
         self._deferred_rows = N if defer else None
 
     def policy_step_fused_ok(self, critics: 'StockMLP', N: int) -> bool:
@@ -556,15 +549,21 @@ class StockMLP:
                                   self.accumulate, loss_out, N if loss_out is not None else 0)
         self._deferred_rows = None
 
+    def _pass(self, x0, x1, out=None, N=None) -> 'native.MlpJob':
+        """this network over the rows of x0 (| x1) as the native wrappers take it (`native.mlp_job`); forward passes: `job`"""
+        if N is None:
+            N = x0.shape[0] if isinstance(x0, native.WindowRows) else x0.shape[-2]
+        return native.mlp_job(self.desc, self.params, self.member_stride, self.E, x0, x1, N, out)
+
     def job(self, x0, x1, out=None):
-        """A forward pass of this network as one job of `native.mlp_forward_multi` -> (job, out)."""
+        """A forward pass of this network (for `native.mlp_forward` / a job of `native.mlp_forward_multi`) -> (job, out)."""
         N = x0.shape[0] if isinstance(x0, native.WindowRows) else x0.shape[-2]
         if self.wide and isinstance(x0, native.WindowRows):      # (the wide forward has no window addressing)
             x0 = x0.t.reshape(N, x0.t.shape[-1])
         if out is None:
             out = torch.empty((self.E, N, self.out_cols), dtype=torch.float32, device=self.device)
         assert out.shape == (self.E, N, self.out_cols) and out.is_contiguous()
-        return native.mlp_job(self.desc, self.params, self.member_stride, self.E, x0, x1, N, out), out
+        return self._pass(x0, x1, out), out
 
     def _launch_backward(self, x0, x1, grad_out, need0, need1, param_grads, reduce_members=True, defer=False,
                          grad_target=None, later=None):
@@ -599,8 +598,7 @@ class StockMLP:
                     later.add(ws[e * self.member_stride:], tiles, 16 if tiles >= 64 else 1, E * self.member_stride, used,
                               gp[e * self.member_stride:], accumulate=mode == native.MLP_REDUCE_ACCUMULATE)
                 mode = native.MLP_REDUCE_DEFER
-        native.mlp_backward(self.desc, self.params, self.member_stride, E, x0, x1, N, grad_out, g0, g1, gp, ws,
-                            reduce_mode=mode)
+        native.mlp_backward(self._pass(x0, x1), grad_out, g0, g1, gp, ws, reduce_mode=mode)
         if reduce_members:
             if g0 is not None and x0.dim() == 2:
                 g0 = g0.sum(0) if E > 1 else g0[0]     # input shared by the ensemble

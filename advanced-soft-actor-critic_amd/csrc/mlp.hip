@@ -2077,6 +2077,8 @@ static bool desc_ok(const asac_mlp_desc_t& d) {
     const int O = d.head_cols[0] + d.head_cols[1];
     return d.head_cols[0] > 0 && d.head_cols[1] >= 0 && O <= kHeadPad;
 }
+// a first layer of more than 64 inputs: two 64-column halves, its own instantiations
+static bool wide_input(const asac_mlp_desc_t& d) { return d.in0 + d.in1 > kMaxW; }
 
 static int set_lds_limit(const void* fn, size_t bytes, bool& done, const char* where) {
     if (done) return 0;
@@ -2089,16 +2091,32 @@ static int set_lds_limit(const void* fn, size_t bytes, bool& done, const char* w
     return 0;
 }
 
-static MlpArgs make_args(const asac_mlp_desc_t* desc, const float* params, int64_t member_stride,
-                         const float* x0, int64_t x0_rs, int64_t x0_ms, const float* x1, int64_t x1_rs,
-                         int64_t x1_ms, int64_t N) {
+// a pass the kernels can run: a valid network, rows, its inputs and (forward passes) somewhere to write
+static bool job_ok(const asac_mlp_job_t& j, bool need_out) {
+    return j.desc && desc_ok(*j.desc) && j.E > 0 && j.N > 0 && j.x0 && (j.desc->in1 <= 0 || j.x1) && (j.out || !need_out);
+}
+// ... of a backward entry point: `out` is not read, and no backward kernel has window addressing
+static bool bwd_job_ok(const asac_mlp_job_t* j) { return j && job_ok(*j, false) && j->x0_window_T == 0; }
+
+// every row of the inputs within the 32-bit element offsets of the stock instantiations
+static bool job_fits32(const asac_mlp_job_t& j) {
+    return j.N * (j.x0_row_stride + j.x1_row_stride + 1) < 0x1fffffffLL &&
+           (j.x0_window_T == 0 || (j.N / j.x0_window_T + 1) * j.x0_sample_stride < 0x1fffffffLL);
+}
+
+// one raw output column (a critic) / (loc | scale) of the policy's Normal
+static bool scalar_head(const asac_mlp_desc_t& d) { return d.head_cols[0] == 1 && d.head_cols[1] == 0 && d.head_transform == 0; }
+static bool gauss_head(const asac_mlp_desc_t& d) { return d.head_transform == 1 && d.head_cols[0] == d.head_cols[1]; }
+
+// the network and its rows (a forward adds `out` and the window fields, a backward its operands)
+static MlpArgs make_args(const asac_mlp_job_t& j) {
     MlpArgs a{};
-    a.d = *desc;
-    a.params = params;
-    a.member_stride = member_stride;
-    a.x0 = x0; a.x0_rs = x0_rs; a.x0_ms = x0_ms;
-    a.x1 = x1; a.x1_rs = x1_rs; a.x1_ms = x1_ms;
-    a.N = N;
+    a.d = *j.desc;
+    a.params = j.params;
+    a.member_stride = j.member_stride;
+    a.x0 = j.x0; a.x0_rs = j.x0_row_stride; a.x0_ms = j.x0_member_stride;
+    a.x1 = j.x1; a.x1_rs = j.x1_row_stride; a.x1_ms = j.x1_member_stride;
+    a.N = j.N;
     return a;
 }
 
@@ -2124,27 +2142,21 @@ static bool offsets32(const MlpFwdArgs& a) {
 
 template <int TM>
 static int launch_forward(const asac_mlp_desc_t* desc, const MlpFwdArgs& a, int E, int64_t N, hipStream_t s) {
-    const bool wide = desc->in0 + desc->in1 > kMaxW;
+    const bool wide = wide_input(*desc);
     const size_t lds = mlp_fwd_lds_bytes(desc->n_blocks, wide, TM);
     const dim3 grid((unsigned)mlp_tile_groups(N, E, lds <= 80 * 1024 ? 2 : 1, TM), (unsigned)E);
     static bool attr_done = false, attr_wide = false, attr_stock = false;
-    if (wide) {
-        if (int rc = set_lds_limit(reinterpret_cast<const void*>(k_mlp_fwd<TM, true, 0>),
-                                   mlp_fwd_lds_bytes(kMaxB - 1, true, TM), attr_wide, "asac_mlp_forward: hipFuncSetAttribute"))
-            return rc;
-        ASAC_LAUNCH((k_mlp_fwd<TM, true, 0>), grid, dim3(threads_of<TM>()), lds, s, a);
-    } else if (stock3(*desc, a.params, a.member_stride) && offsets32(a)) {
-        if (int rc = set_lds_limit(reinterpret_cast<const void*>(k_mlp_fwd<TM, false, 3>), sizeof(MlpLds<TM>), attr_stock,
+    auto launch = [&](auto kernel, size_t lds_limit, bool& attr) -> int {
+        if (int rc = set_lds_limit(reinterpret_cast<const void*>(kernel), lds_limit, attr,
                                    "asac_mlp_forward: hipFuncSetAttribute"))
             return rc;
-        ASAC_LAUNCH((k_mlp_fwd<TM, false, 3>), grid, dim3(threads_of<TM>()), lds, s, a);
-    } else {
-        if (int rc = set_lds_limit(reinterpret_cast<const void*>(k_mlp_fwd<TM, false, 0>), sizeof(MlpLds<TM>), attr_done,
-                                   "asac_mlp_forward: hipFuncSetAttribute"))
-            return rc;
-        ASAC_LAUNCH((k_mlp_fwd<TM, false, 0>), grid, dim3(threads_of<TM>()), lds, s, a);
-    }
-    return finish_launch("asac_mlp_forward");
+        ASAC_LAUNCH(kernel, grid, dim3(threads_of<TM>()), lds, s, a);
+        return finish_launch("asac_mlp_forward");
+    };
+    if (wide) return launch(k_mlp_fwd<TM, true, 0>, mlp_fwd_lds_bytes(kMaxB - 1, true, TM), attr_wide);
+    if (stock3(*desc, a.params, a.member_stride) && offsets32(a))
+        return launch(k_mlp_fwd<TM, false, 3>, sizeof(MlpLds<TM>), attr_stock);
+    return launch(k_mlp_fwd<TM, false, 0>, sizeof(MlpLds<TM>), attr_done);
 }
 
 template <int TM, int NB>
@@ -2167,8 +2179,7 @@ static int launch_forward_multi(const asac_mlp_job_t* jobs, int n_jobs, const Si
     const int per_cu = lds <= 80 * 1024 ? 2 : 1;
     for (int k = 0; k < n_jobs; ++k) {
         const asac_mlp_job_t& j = jobs[k];
-        m.job[k] = make_args(j.desc, j.params, j.member_stride, j.x0, j.x0_row_stride, j.x0_member_stride, j.x1,
-                             j.x1_row_stride, j.x1_member_stride, j.N);
+        m.job[k] = make_args(j);
         m.job[k].x0_T = j.x0_window_T;
         m.job[k].x0_sb = j.x0_sample_stride;
         m.job[k].out = j.out;
@@ -2200,123 +2211,71 @@ template <int TM>
 static int launch_backward(const char* where, const asac_mlp_desc_t* desc, MlpArgs& a, int E, int tiles, hipStream_t s,
                            const RetIn<true>* ret = nullptr) {
     static bool attr_done = false, attr_wide = false, attr_stock = false, attr_ret = false;
-    const bool wide = desc->in0 + desc->in1 > kMaxW;
+    const bool wide = wide_input(*desc);
     const bool stock = !wide && stock3(*desc, a.params, a.member_stride) && offsets32(a);
-    if (ret) {             // (asac_mlp_backward_qloss_return_ok has said yes: stock network, the tile's steps fit)
-        const size_t lds = sizeof(MlpBwdLds<TM>) + (size_t)(2 * ((ret->v.n + 1) | 1) + 2) * TM * sizeof(float);
-        constexpr int w8 = TM == 16 ? ASAC_BWD_WAVES : 0;            // (16-row tiles of the stock networks: see k_mlp_bwd)
-        // one thread per (row, step) of the tile: the launch's own thread count bounds n (16 waves: n <= 64)
-        if (!stock || TM * ret->v.n > (w8 ? 64 * w8 : threads_of<TM>()) || lds > 128 * 1024) return bad_arg(where);
-        if (int rc = set_lds_limit(reinterpret_cast<const void*>(k_mlp_bwd<TM, false, 3, true, w8>), 128 * 1024, attr_ret, where))
-            return rc;
-        ASAC_LAUNCH((k_mlp_bwd<TM, false, 3, true, w8>), dim3(tiles, E), dim3(w8 ? 64 * w8 : threads_of<TM>()), lds, s, a, *ret);
+    constexpr int w8 = TM == 16 ? ASAC_BWD_WAVES : 0;                // (16-row tiles of the stock networks: see k_mlp_bwd)
+    constexpr int stock_threads = w8 ? 64 * w8 : threads_of<TM>();
+    auto launch = [&](auto kernel, bool& attr, size_t lds_limit, int threads, size_t lds,
+                      const auto& ret_in) -> int {
+        if (int rc = set_lds_limit(reinterpret_cast<const void*>(kernel), lds_limit, attr, where)) return rc;
+        ASAC_LAUNCH(kernel, dim3(tiles, E), dim3(threads), lds, s, a, ret_in);
         return 0;
+    };
+    const size_t lds = sizeof(MlpBwdLds<TM>);
+    if (ret) {             // (asac_mlp_backward_qloss_return_ok has said yes: stock network, the tile's steps fit)
+        const size_t lds_ret = lds + (size_t)(2 * ((ret->v.n + 1) | 1) + 2) * TM * sizeof(float);
+        // one thread per (row, step) of the tile: the launch's own thread count bounds n (16 waves: n <= 64)
+        if (!stock || TM * ret->v.n > stock_threads || lds_ret > 128 * 1024) return bad_arg(where);
+        return launch(k_mlp_bwd<TM, false, 3, true, w8>, attr_ret, 128 * 1024, stock_threads, lds_ret, *ret);
     }
-    if (int rc = wide    ? set_lds_limit(reinterpret_cast<const void*>(k_mlp_bwd<TM, true, 0>), sizeof(MlpBwdLds<TM>), attr_wide, where)
-                 : stock ? set_lds_limit(reinterpret_cast<const void*>(k_mlp_bwd<TM, false, 3, false, TM == 16 ? ASAC_BWD_WAVES : 0>), sizeof(MlpBwdLds<TM>), attr_stock, where)
-                         : set_lds_limit(reinterpret_cast<const void*>(k_mlp_bwd<TM, false, 0>), sizeof(MlpBwdLds<TM>), attr_done, where))
-        return rc;
-    if (wide)
-        ASAC_LAUNCH((k_mlp_bwd<TM, true, 0>), dim3(tiles, E), dim3(threads_of<TM>()), sizeof(MlpBwdLds<TM>), s, a, RetIn<false>{});
-    else if (stock)
-        ASAC_LAUNCH((k_mlp_bwd<TM, false, 3, false, TM == 16 ? ASAC_BWD_WAVES : 0>), dim3(tiles, E),
-                    dim3(TM == 16 ? 64 * ASAC_BWD_WAVES : threads_of<TM>()),
-                    sizeof(MlpBwdLds<TM>), s, a, RetIn<false>{});
-    else
-        ASAC_LAUNCH((k_mlp_bwd<TM, false, 0>), dim3(tiles, E), dim3(threads_of<TM>()), sizeof(MlpBwdLds<TM>), s, a, RetIn<false>{});
-    return 0;
+    if (wide) return launch(k_mlp_bwd<TM, true, 0>, attr_wide, lds, threads_of<TM>(), lds, RetIn<false>{});
+    if (stock) return launch(k_mlp_bwd<TM, false, 3, false, w8>, attr_stock, lds, stock_threads, lds, RetIn<false>{});
+    return launch(k_mlp_bwd<TM, false, 0>, attr_done, lds, threads_of<TM>(), lds, RetIn<false>{});
 }
 
-static int mlp_backward_common(const char* where, const asac_mlp_desc_t* desc, MlpArgs& a, int E, int64_t N,
-                               int64_t member_stride, float* grad_params, float* workspace, int reduce_mode,
-                               float* loss_out, hipStream_t s, const RetIn<true>* ret = nullptr) {
-    const int tiles = (int)asac_mlp_backward_tiles(N, E);
+// the tiles' partial sums of [E] parameter blocks -> grad, in a fixed order (+ the loss, with loss_out).  Launched once
+// (not under the repeat knob: it may accumulate)
+static void reduce_partials(const asac_mlp_desc_t* desc, const float* workspace, int tiles, int E, int64_t member_stride,
+                            float* grad, int reduce_mode, const float* loss_partial, float* loss_out, float inv_n,
+                            hipStream_t s) {
+    const int64_t used = asac_mlp_param_extent(desc);
+    const int accumulate = reduce_mode == ASAC_MLP_REDUCE_ACCUMULATE ? 1 : 0;
+    if (tiles >= kSlicedFrom)
+        hipLaunchKernelGGL(k_mlp_reduce_partials_sliced, dim3((unsigned)((used + 63) / 64), (unsigned)E),
+                           dim3(64 * kReduceSlices), 0, s, workspace, tiles, E, member_stride, used, grad, accumulate,
+                           loss_partial, loss_out, inv_n);
+    else
+        hipLaunchKernelGGL(k_mlp_reduce_partials, dim3((unsigned)((used + 255) / 256), (unsigned)E), dim3(256), 0, s,
+                           workspace, tiles, E, member_stride, used, grad, accumulate, loss_partial, loss_out, inv_n);
+}
+
+static int mlp_backward_common(const char* where, const asac_mlp_job_t& j, MlpArgs& a, float* grad_params, float* workspace,
+                               int reduce_mode, float* loss_out, hipStream_t s, const RetIn<true>* ret = nullptr) {
+    const int tiles = (int)asac_mlp_backward_tiles(j.N, j.E);
     a.partial = grad_params ? workspace : nullptr;
-    a.loss_partial = workspace ? workspace + (int64_t)tiles * E * member_stride : nullptr;
-    if (int rc = mlp_tile_rows(N, E) == 16 ? launch_backward<16>(where, desc, a, E, tiles, s, ret)
-                                           : launch_backward<32>(where, desc, a, E, tiles, s, ret))
+    a.loss_partial = workspace ? workspace + (int64_t)tiles * j.E * j.member_stride : nullptr;
+    if (int rc = mlp_tile_rows(j.N, j.E) == 16 ? launch_backward<16>(where, j.desc, a, j.E, tiles, s, ret)
+                                               : launch_backward<32>(where, j.desc, a, j.E, tiles, s, ret))
         return rc;
-    if (grad_params && reduce_mode != ASAC_MLP_REDUCE_DEFER) {
-        const int64_t used = asac_mlp_param_extent(desc);
-        // launched once (not under the repeat knob: it may accumulate)
-        if (tiles >= kSlicedFrom)
-            hipLaunchKernelGGL(k_mlp_reduce_partials_sliced, dim3((unsigned)((used + 63) / 64), (unsigned)E),
-                               dim3(64 * kReduceSlices), 0, s, workspace, tiles, E, member_stride, used, grad_params,
-                               reduce_mode == ASAC_MLP_REDUCE_ACCUMULATE ? 1 : 0, loss_out ? a.loss_partial : nullptr,
-                               loss_out, 1.f / (float)N);
-        else
-            hipLaunchKernelGGL(k_mlp_reduce_partials, dim3((unsigned)((used + 255) / 256), (unsigned)E), dim3(256), 0, s,
-                               workspace, tiles, E, member_stride, used, grad_params,
-                               reduce_mode == ASAC_MLP_REDUCE_ACCUMULATE ? 1 : 0, loss_out ? a.loss_partial : nullptr,
-                               loss_out, 1.f / (float)N);
-    }
+    if (grad_params && reduce_mode != ASAC_MLP_REDUCE_DEFER)
+        reduce_partials(j.desc, workspace, tiles, j.E, j.member_stride, grad_params, reduce_mode,
+                        loss_out ? a.loss_partial : nullptr, loss_out, 1.f / (float)j.N, s);
     return finish_launch(where);
 }
 
 extern "C" {
 
-int asac_mlp_forward(const asac_mlp_desc_t* desc, const float* params, int64_t member_stride, int E,
-                     const float* x0, int64_t x0_row_stride, int64_t x0_member_stride,
-                     const float* x1, int64_t x1_row_stride, int64_t x1_member_stride, int64_t N,
-                     float* out, void* stream) {
-    if (!desc || !desc_ok(*desc) || E <= 0 || N <= 0 || !x0 || (desc->in1 > 0 && !x1) || !out)
-        return bad_arg("asac_mlp_forward");
-    MlpArgs a = make_args(desc, params, member_stride, x0, x0_row_stride, x0_member_stride, x1, x1_row_stride,
-                          x1_member_stride, N);
-    a.out = out;
-    return mlp_tile_rows(N, E) == 16 ? launch_forward<16>(desc, a, E, N, as_stream(stream))
-                                     : launch_forward<32>(desc, a, E, N, as_stream(stream));
-}
-
-int asac_mlp_forward_multi(const asac_mlp_job_t* jobs, int n_jobs, const asac_sidecar_t* sidecars_host, int n_sidecars,
-                           void* stream) {
-    if (!jobs || n_jobs < 1 || n_jobs > ASAC_MLP_MAX_JOBS) return bad_arg("asac_mlp_forward_multi");
-    SidecarsDev sc{};
-    if (sidecars_prepare(sidecars_host, n_sidecars, sc)) return bad_arg("asac_mlp_forward_multi: sidecar");
-    int64_t groups16 = 0;       // workgroups of the whole launch with 16-row tiles
-    bool all_stock = true, any_wide = false;
-    for (int k = 0; k < n_jobs; ++k)
-        if (jobs[k].desc && desc_ok(*jobs[k].desc) && jobs[k].desc->in0 + jobs[k].desc->in1 > kMaxW) any_wide = true;
-    if (any_wide) {
-        // a first layer wider than 64 inputs (critics on a 64-wide state + the action): the jobs go one launch each through
-        // the wide instantiation of the single-network forward; no window addressing, no sidecars there
-        if (n_sidecars > 0) return bad_arg("asac_mlp_forward_multi: sidecars beside a wide job");
-        for (int k = 0; k < n_jobs; ++k) {
-            const asac_mlp_job_t& j = jobs[k];
-            if (j.desc && desc_ok(*j.desc) && j.desc->in0 + j.desc->in1 <= kMaxW) {       // a narrow job beside a wide one
-                if (int rc = asac_mlp_forward_multi(&j, 1, nullptr, 0, stream)) return rc;
-                continue;
-            }
-            if (!j.desc || !desc_ok(*j.desc) || j.E <= 0 || j.N <= 0 || !j.x0 || (j.desc->in1 > 0 && !j.x1) || !j.out ||
-                j.x0_window_T != 0)
-                return bad_arg("asac_mlp_forward_multi: wide job");
-            if (int rc = asac_mlp_forward(j.desc, static_cast<const float*>(j.params), j.member_stride, j.E,
-                                          static_cast<const float*>(j.x0), j.x0_row_stride, j.x0_member_stride,
-                                          static_cast<const float*>(j.x1), j.x1_row_stride, j.x1_member_stride, j.N,
-                                          static_cast<float*>(j.out), stream))
-                return rc;
-        }
-        return 0;
-    }
-    for (int k = 0; k < n_jobs; ++k) {
-        const asac_mlp_job_t& j = jobs[k];
-        if (!j.desc || !desc_ok(*j.desc) || j.desc->in0 + j.desc->in1 > kMaxW)
-            return bad_arg("asac_mlp_forward_multi: job");
-        if (j.E <= 0 || j.N <= 0 || !j.x0 || (j.desc->in1 > 0 && !j.x1) || !j.out || j.x0_window_T < 0)
-            return bad_arg("asac_mlp_forward_multi: job");
-        groups16 += ((j.N + 15) / 16) * j.E;
-        all_stock = all_stock && stock3(*j.desc, j.params, j.member_stride) && j.N * (j.x0_row_stride + j.x1_row_stride + 1) < 0x1fffffffLL &&
-                    (j.x0_window_T == 0 || (j.N / j.x0_window_T + 1) * j.x0_sample_stride < 0x1fffffffLL);
-    }
-    hipStream_t s = as_stream(stream);
-    if (groups16 <= 256)
-        return all_stock ? launch_forward_multi<16, 3>(jobs, n_jobs, sc, s) : launch_forward_multi<16, 0>(jobs, n_jobs, sc, s);
-    return all_stock ? launch_forward_multi<32, 3>(jobs, n_jobs, sc, s) : launch_forward_multi<32, 0>(jobs, n_jobs, sc, s);
+int asac_mlp_forward(const asac_mlp_job_t* job, void* stream) {
+    if (!job || !job_ok(*job, true) || job->x0_window_T != 0) return bad_arg("asac_mlp_forward");
+    MlpArgs a = make_args(*job);
+    a.out = job->out;
+    return mlp_tile_rows(job->N, job->E) == 16 ? launch_forward<16>(job->desc, a, job->E, job->N, as_stream(stream))
+                                               : launch_forward<32>(job->desc, a, job->E, job->N, as_stream(stream));
 }
 
 static bool sample_epilogue_ok(const asac_mlp_job_t& j, const asac_mlp_sample_epilogue_t& h) {
     const asac_squash_job_t& q = h.sample;
-    if (!j.desc || j.desc->head_transform != 1 || j.desc->head_cols[0] != j.desc->head_cols[1] || j.E != 1) return false;
+    if (!j.desc || !gauss_head(*j.desc) || j.E != 1) return false;
     const int A = j.desc->head_cols[0];
     if (A < 1 || 2 * A > 16 || q.A != A || q.rows != j.N || j.N * (int64_t)A >= 0x7fffffffLL) return false;
     if (!q.eps && !q.action && !h.eps2) return false;
@@ -2334,12 +2293,77 @@ static bool sample_epilogue_ok(const asac_mlp_job_t& j, const asac_mlp_sample_ep
     return true;
 }
 
+// the epilogues of asac_mlp_forward_multi_sampled in the kernel's form (asac_mlp_forward_multi_sampled_ok has said yes)
+static SampleEpis sample_epis(const asac_mlp_sample_epilogue_t* epilogues, int n_jobs) {
+    SampleEpis epis{};
+    for (int k = 0; k < n_jobs; ++k) {
+        const asac_mlp_sample_epilogue_t& h = epilogues[k];
+        const asac_squash_job_t& q = h.sample;
+        SampleEpi& d = epis.e[k];
+        d.on = (q.eps || q.action || h.eps2) ? 1 : 0;
+        if (!d.on) continue;
+        d.eps = q.eps, d.eps2 = h.eps2, d.a_out = q.a_tanh_out, d.logp_out = q.logp_out, d.a2_out = h.a2_out, d.logp2_out = h.logp2_out;
+        d.action = q.action, d.prob_out = q.prob_out;
+        d.a_sb = (int32_t)q.action_stride_b, d.a_st = (int32_t)q.action_stride_t, d.a_off = q.action_offset;
+        d.p_sb = (int32_t)q.prob_stride_b, d.p_st = (int32_t)q.prob_stride_t, d.p_off = q.prob_offset;
+        d.A = q.A, d.T = q.T > 0 ? q.T : 1, d.t2 = h.t2;
+    }
+    return epis;
+}
+
+// asac_mlp_forward_multi (epis == nullptr) and asac_mlp_forward_multi_sampled behind their own first checks
+static int forward_multi(const asac_mlp_job_t* jobs, int n_jobs, const SampleEpis* epis, const asac_sidecar_t* sidecars_host,
+                         int n_sidecars, void* stream) {
+    SidecarsDev sc{};
+    if (sidecars_prepare(sidecars_host, n_sidecars, sc))
+        return bad_arg(epis ? "asac_mlp_forward_multi_sampled: sidecar" : "asac_mlp_forward_multi: sidecar");
+    bool any_wide = false;      // (never with epilogues: asac_mlp_forward_multi_sampled_ok refuses wide jobs)
+    for (int k = 0; k < n_jobs; ++k)
+        any_wide = any_wide || (jobs[k].desc && desc_ok(*jobs[k].desc) && wide_input(*jobs[k].desc));
+    if (any_wide) {
+        // a first layer wider than 64 inputs (critics on a 64-wide state + the action): the jobs go one launch each through
+        // the wide instantiation of the single-network forward; no window addressing, no sidecars there
+        if (n_sidecars > 0) return bad_arg("asac_mlp_forward_multi: sidecars beside a wide job");
+        for (int k = 0; k < n_jobs; ++k) {
+            const asac_mlp_job_t& j = jobs[k];
+            if (j.desc && desc_ok(*j.desc) && !wide_input(*j.desc)) {       // a narrow job beside a wide one
+                if (int rc = asac_mlp_forward_multi(&j, 1, nullptr, 0, stream)) return rc;
+                continue;
+            }
+            if (!job_ok(j, true) || j.x0_window_T != 0) return bad_arg("asac_mlp_forward_multi: wide job");
+            if (int rc = asac_mlp_forward(&j, stream)) return rc;
+        }
+        return 0;
+    }
+    int64_t groups16 = 0;       // workgroups of the whole launch with 16-row tiles
+    bool all_stock = true;
+    for (int k = 0; k < n_jobs; ++k) {
+        const asac_mlp_job_t& j = jobs[k];
+        if (!job_ok(j, true) || wide_input(*j.desc) || j.x0_window_T < 0)
+            return bad_arg(epis ? "asac_mlp_forward_multi_sampled: job" : "asac_mlp_forward_multi: job");
+        groups16 += ((j.N + 15) / 16) * j.E;
+        all_stock = all_stock && stock3(*j.desc, j.params, j.member_stride) && job_fits32(j);
+    }
+    hipStream_t s = as_stream(stream);
+    if (groups16 <= 256)
+        return all_stock ? launch_forward_multi<16, 3>(jobs, n_jobs, sc, s, epis)
+                         : launch_forward_multi<16, 0>(jobs, n_jobs, sc, s, epis);
+    return all_stock ? launch_forward_multi<32, 3>(jobs, n_jobs, sc, s, epis)
+                     : launch_forward_multi<32, 0>(jobs, n_jobs, sc, s, epis);
+}
+
+int asac_mlp_forward_multi(const asac_mlp_job_t* jobs, int n_jobs, const asac_sidecar_t* sidecars_host, int n_sidecars,
+                           void* stream) {
+    if (!jobs || n_jobs < 1 || n_jobs > ASAC_MLP_MAX_JOBS) return bad_arg("asac_mlp_forward_multi");
+    return forward_multi(jobs, n_jobs, nullptr, sidecars_host, n_sidecars, stream);
+}
+
 int asac_mlp_forward_multi_sampled_ok(const asac_mlp_job_t* jobs, int n_jobs, const asac_mlp_sample_epilogue_t* epilogues) {
     if (!jobs || !epilogues || n_jobs < 1 || n_jobs > ASAC_MLP_MAX_JOBS) return 0;
     bool any = false;
     for (int k = 0; k < n_jobs; ++k) {
         const asac_mlp_job_t& j = jobs[k];
-        if (!j.desc || !desc_ok(*j.desc) || j.desc->in0 + j.desc->in1 > kMaxW || j.E <= 0 || j.N <= 0) return 0;
+        if (!j.desc || !desc_ok(*j.desc) || wide_input(*j.desc) || j.E <= 0 || j.N <= 0) return 0;
         const asac_mlp_sample_epilogue_t& h = epilogues[k];
         const bool on = h.sample.eps || h.sample.action || h.eps2;
         if (on && !sample_epilogue_ok(j, h)) return 0;
@@ -2355,32 +2379,8 @@ int asac_mlp_forward_multi_sampled_ok(const asac_mlp_job_t* jobs, int n_jobs, co
 int asac_mlp_forward_multi_sampled(const asac_mlp_job_t* jobs, int n_jobs, const asac_mlp_sample_epilogue_t* epilogues,
                                    const asac_sidecar_t* sidecars_host, int n_sidecars, void* stream) {
     if (!asac_mlp_forward_multi_sampled_ok(jobs, n_jobs, epilogues)) return bad_arg("asac_mlp_forward_multi_sampled");
-    SidecarsDev sc{};
-    if (sidecars_prepare(sidecars_host, n_sidecars, sc)) return bad_arg("asac_mlp_forward_multi_sampled: sidecar");
-    int64_t groups16 = 0;
-    bool all_stock = true;
-    SampleEpis epis{};
-    for (int k = 0; k < n_jobs; ++k) {
-        const asac_mlp_job_t& j = jobs[k];
-        if (!j.x0 || (j.desc->in1 > 0 && !j.x1) || !j.out || j.x0_window_T < 0) return bad_arg("asac_mlp_forward_multi_sampled: job");
-        groups16 += ((j.N + 15) / 16) * j.E;
-        all_stock = all_stock && stock3(*j.desc, j.params, j.member_stride) && j.N * (j.x0_row_stride + j.x1_row_stride + 1) < 0x1fffffffLL &&
-                    (j.x0_window_T == 0 || (j.N / j.x0_window_T + 1) * j.x0_sample_stride < 0x1fffffffLL);
-        const asac_mlp_sample_epilogue_t& h = epilogues[k];
-        const asac_squash_job_t& q = h.sample;
-        SampleEpi& d = epis.e[k];
-        d.on = (q.eps || q.action || h.eps2) ? 1 : 0;
-        if (!d.on) continue;
-        d.eps = q.eps, d.eps2 = h.eps2, d.a_out = q.a_tanh_out, d.logp_out = q.logp_out, d.a2_out = h.a2_out, d.logp2_out = h.logp2_out;
-        d.action = q.action, d.prob_out = q.prob_out;
-        d.a_sb = (int32_t)q.action_stride_b, d.a_st = (int32_t)q.action_stride_t, d.a_off = q.action_offset;
-        d.p_sb = (int32_t)q.prob_stride_b, d.p_st = (int32_t)q.prob_stride_t, d.p_off = q.prob_offset;
-        d.A = q.A, d.T = q.T > 0 ? q.T : 1, d.t2 = h.t2;
-    }
-    hipStream_t s = as_stream(stream);
-    if (groups16 <= 256)
-        return all_stock ? launch_forward_multi<16, 3>(jobs, n_jobs, sc, s, &epis) : launch_forward_multi<16, 0>(jobs, n_jobs, sc, s, &epis);
-    return all_stock ? launch_forward_multi<32, 3>(jobs, n_jobs, sc, s, &epis) : launch_forward_multi<32, 0>(jobs, n_jobs, sc, s, &epis);
+    const SampleEpis epis = sample_epis(epilogues, n_jobs);
+    return forward_multi(jobs, n_jobs, &epis, sidecars_host, n_sidecars, stream);
 }
 
 /* row tiles (= workgroups along the row axis, = per-tile partial slabs) the backward of this shape uses */
@@ -2416,67 +2416,53 @@ int64_t asac_mlp_param_extent(const asac_mlp_desc_t* desc) {
     return used;
 }
 
-int asac_mlp_backward(const asac_mlp_desc_t* desc, const float* params, int64_t member_stride, int E,
-                      const float* x0, int64_t x0_row_stride, int64_t x0_member_stride,
-                      const float* x1, int64_t x1_row_stride, int64_t x1_member_stride, int64_t N,
-                      const float* grad_out, float* grad_x0, float* grad_x1, float* grad_params,
+int asac_mlp_backward(const asac_mlp_job_t* job, const float* grad_out, float* grad_x0, float* grad_x1, float* grad_params,
                       float* workspace, int reduce_mode, void* stream) {
-    if (!desc || !desc_ok(*desc) || E <= 0 || N <= 0 || !x0 || (desc->in1 > 0 && !x1) || !grad_out)
-        return bad_arg("asac_mlp_backward");
+    if (!bwd_job_ok(job) || !grad_out) return bad_arg("asac_mlp_backward");
     if (grad_params && !workspace) return bad_arg("asac_mlp_backward: workspace");
-    MlpArgs a = make_args(desc, params, member_stride, x0, x0_row_stride, x0_member_stride, x1, x1_row_stride,
-                          x1_member_stride, N);
+    MlpArgs a = make_args(*job);
     a.gout = grad_out;
     a.gx0 = grad_x0;
     a.gx1 = grad_x1;
-    return mlp_backward_common("asac_mlp_backward", desc, a, E, N, member_stride, grad_params, workspace,
-                               reduce_mode, nullptr, as_stream(stream));
+    return mlp_backward_common("asac_mlp_backward", *job, a, grad_params, workspace, reduce_mode, nullptr, as_stream(stream));
 }
 
-int asac_mlp_backward_policy_q(const asac_mlp_desc_t* desc, const float* params, int64_t member_stride, int E,
-                               const float* x0, int64_t x0_row_stride, int64_t x0_member_stride,
-                               const float* x1, int64_t x1_row_stride, int64_t x1_member_stride, int64_t N,
-                               const float* q_table, const int32_t* subset, int E_sample, float* grad_x1,
-                               void* stream) {
-    if (!desc || !desc_ok(*desc) || E <= 0 || N <= 0 || !x0 || desc->in1 <= 0 || !x1 || !q_table || !grad_x1 ||
-        E_sample < 1 || E_sample > E)
+int asac_mlp_backward_policy_q(const asac_mlp_job_t* job, const float* q_table, const int32_t* subset, int E_sample,
+                               float* grad_x1, void* stream) {
+    if (!bwd_job_ok(job) || job->desc->in1 <= 0 || !q_table || !grad_x1 || E_sample < 1 || E_sample > job->E)
         return bad_arg("asac_mlp_backward_policy_q");
-    if (desc->head_cols[0] != 1 || desc->head_cols[1] != 0 || desc->head_transform != 0)
-        return bad_arg("asac_mlp_backward_policy_q: not a scalar-head network");
-    MlpArgs a = make_args(desc, params, member_stride, x0, x0_row_stride, x0_member_stride, x1, x1_row_stride,
-                          x1_member_stride, N);
+    if (!scalar_head(*job->desc)) return bad_arg("asac_mlp_backward_policy_q: not a scalar-head network");
+    MlpArgs a = make_args(*job);
     a.q_table = q_table;
     a.subset = subset;
     a.E_sample = E_sample;
     a.gx1 = grad_x1;
-    return mlp_backward_common("asac_mlp_backward_policy_q", desc, a, E, N, member_stride, nullptr, nullptr,
-                               ASAC_MLP_REDUCE_OVERWRITE, nullptr, as_stream(stream));
+    return mlp_backward_common("asac_mlp_backward_policy_q", *job, a, nullptr, nullptr, ASAC_MLP_REDUCE_OVERWRITE, nullptr,
+                               as_stream(stream));
 }
 
-int asac_mlp_backward_policy_sample(const asac_mlp_desc_t* desc, const float* params, int64_t member_stride,
-                                    const float* x0, int64_t x0_row_stride, int64_t N, const float* eps,
-                                    const float* grad_a, int grad_a_members, const float* log_alpha,
-                                    float* grad_params, float* workspace, int reduce_mode, void* stream) {
-    if (!desc || !desc_ok(*desc) || N <= 0 || !x0 || desc->in1 != 0 || !eps || !grad_a || grad_a_members < 1 ||
+int asac_mlp_backward_policy_sample(const asac_mlp_job_t* job, const float* eps, const float* grad_a, int grad_a_members,
+                                    const float* log_alpha, float* grad_params, float* workspace, int reduce_mode,
+                                    void* stream) {
+    if (!bwd_job_ok(job) || job->E != 1 || job->x1 || job->desc->in1 != 0 || !eps || !grad_a || grad_a_members < 1 ||
         !log_alpha || !grad_params || !workspace)
         return bad_arg("asac_mlp_backward_policy_sample");
-    if (desc->head_transform != 1 || desc->head_cols[0] != desc->head_cols[1] || desc->head_cols[0] > 16)
+    if (!gauss_head(*job->desc) || job->desc->head_cols[0] > 16)
         return bad_arg("asac_mlp_backward_policy_sample: not a Gaussian-head policy");
-    MlpArgs a = make_args(desc, params, member_stride, x0, x0_row_stride, 0, nullptr, 0, 0, N);
+    MlpArgs a = make_args(*job);
     a.eps = eps;
     a.grad_a = grad_a;
     a.grad_a_members = grad_a_members;
     a.log_alpha = log_alpha;
-    return mlp_backward_common("asac_mlp_backward_policy_sample", desc, a, 1, N, member_stride, grad_params,
-                               workspace, reduce_mode, nullptr, as_stream(stream));
+    return mlp_backward_common("asac_mlp_backward_policy_sample", *job, a, grad_params, workspace, reduce_mode, nullptr,
+                               as_stream(stream));
 }
 
 int asac_policy_step_fused_ok(const asac_mlp_desc_t* q_desc, const float* q_params, int64_t q_member_stride,
                               const asac_mlp_desc_t* pi_desc, const float* pi_params, int64_t pi_member_stride, int64_t N) {
     if (!q_desc || !pi_desc || !desc_ok(*q_desc) || !desc_ok(*pi_desc) || N <= 0) return 0;
     if (!stock3(*q_desc, q_params, q_member_stride) || !stock3(*pi_desc, pi_params, pi_member_stride)) return 0;
-    if (q_desc->head_cols[0] != 1 || q_desc->head_cols[1] != 0 || q_desc->head_transform != 0) return 0;
-    if (pi_desc->head_transform != 1 || pi_desc->head_cols[0] != pi_desc->head_cols[1] || pi_desc->in1 != 0) return 0;
+    if (!scalar_head(*q_desc) || !gauss_head(*pi_desc) || pi_desc->in1 != 0) return 0;
     if (q_desc->in0 != pi_desc->in0 || q_desc->in1 != pi_desc->head_cols[0] || 2 * pi_desc->head_cols[0] > kHeadPad) return 0;
     return mlp_tile_rows(N, 1) == kPsRows ? 1 : 0;        // the partials' tile count is asac_mlp_backward_tiles(N, 1)
 }
@@ -2491,9 +2477,13 @@ int asac_policy_step_fused(const asac_mlp_desc_t* q_desc, const float* q_params,
         !x || !eps || !log_alpha || !pi_grad_params || !workspace || (!action && (!a_tanh_out || !logp_out)))
         return bad_arg("asac_policy_step_fused");
     PolicyStepArgs a{};
-    const int A = pi_desc->head_cols[0];
-    a.q = make_args(q_desc, q_params, q_member_stride, x, x_row_stride, 0, action, A, 0, N);
-    a.pi = make_args(pi_desc, pi_params, pi_member_stride, x, x_row_stride, 0, nullptr, 0, 0, N);
+    asac_mlp_job_t pi{}, q{};           // both networks on the rows of x; the critics' second input: the [N][A] actions
+    pi.desc = pi_desc, pi.params = pi_params, pi.member_stride = pi_member_stride;
+    q.desc = q_desc, q.params = q_params, q.member_stride = q_member_stride;
+    pi.x0 = q.x0 = x, pi.x0_row_stride = q.x0_row_stride = x_row_stride, pi.N = q.N = N;
+    q.x1 = action, q.x1_row_stride = pi_desc->head_cols[0];
+    a.q = make_args(q);
+    a.pi = make_args(pi);
     if (!offsets32(a.q) || !offsets32(a.pi)) return bad_arg("asac_policy_step_fused: offsets");
     a.q.subset = subset;
     a.a_out = a_tanh_out;
@@ -2510,31 +2500,22 @@ int asac_policy_step_fused(const asac_mlp_desc_t* q_desc, const float* q_params,
     const int tiles = (int)((N + kPsRows - 1) / kPsRows);
     hipStream_t s = as_stream(stream);
     ASAC_LAUNCH(k_policy_step, dim3((unsigned)tiles), dim3(kPsThreads), sizeof(PsLds), s, a);
-    if (reduce_mode != ASAC_MLP_REDUCE_DEFER) {
-        const int64_t used = asac_mlp_param_extent(pi_desc);
-        if (tiles >= kSlicedFrom)
-            hipLaunchKernelGGL(k_mlp_reduce_partials_sliced, dim3((unsigned)((used + 63) / 64), 1u), dim3(64 * kReduceSlices),
-                               0, s, workspace, tiles, 1, pi_member_stride, used, pi_grad_params,
-                               reduce_mode == ASAC_MLP_REDUCE_ACCUMULATE ? 1 : 0, nullptr, nullptr, 0.f);
-        else
-            hipLaunchKernelGGL(k_mlp_reduce_partials, dim3((unsigned)((used + 255) / 256), 1u), dim3(256), 0, s, workspace,
-                               tiles, 1, pi_member_stride, used, pi_grad_params,
-                               reduce_mode == ASAC_MLP_REDUCE_ACCUMULATE ? 1 : 0, nullptr, nullptr, 0.f);
-    }
+    if (reduce_mode != ASAC_MLP_REDUCE_DEFER)
+        reduce_partials(pi_desc, workspace, tiles, 1, pi_member_stride, pi_grad_params, reduce_mode, nullptr, nullptr, 0.f, s);
     return finish_launch("asac_policy_step_fused");
 }
 
 static bool fits32(int64_t v) { return v >= 0 && v < 0x1fffffffLL; }
 
-// asac_mlp_desc_t + addressing -> the compact kernel-argument form (callers have checked stock3 and the 32-bit ranges)
-static StockJobArg stock_job_arg(const asac_mlp_desc_t* d, const float* params, int64_t member_stride, const float* x0,
-                                 int64_t x0_rs, int64_t x0_ms, const float* x1, int64_t x1_rs, int64_t x1_ms, int64_t N,
-                                 int64_t x0_T, int64_t x0_sb, float* out) {
+// a pass -> the compact kernel-argument form (callers have checked stock3 and the 32-bit ranges)
+static StockJobArg stock_job_arg(const asac_mlp_job_t& p) {
+    const asac_mlp_desc_t* d = p.desc;
     StockJobArg j{};
-    j.P = params, j.x0 = x0, j.x1 = x1, j.out = out;
-    j.member_stride = (int32_t)member_stride, j.N = (int32_t)N;
-    j.x0_rs = (int32_t)x0_rs, j.x0_ms = (int32_t)x0_ms, j.x1_rs = (int32_t)x1_rs, j.x1_ms = (int32_t)x1_ms;
-    j.x0_sb = (int32_t)x0_sb, j.x0_T = (int32_t)x0_T;
+    j.P = p.params, j.x0 = p.x0, j.x1 = p.x1, j.out = p.out;
+    j.member_stride = (int32_t)p.member_stride, j.N = (int32_t)p.N;
+    j.x0_rs = (int32_t)p.x0_row_stride, j.x0_ms = (int32_t)p.x0_member_stride;
+    j.x1_rs = (int32_t)p.x1_row_stride, j.x1_ms = (int32_t)p.x1_member_stride;
+    j.x0_sb = (int32_t)p.x0_sample_stride, j.x0_T = (int32_t)p.x0_window_T;
     j.in0 = d->in0, j.in1 = d->in1, j.h0 = d->head_cols[0], j.h1 = d->head_cols[1];
     j.hw0 = (int32_t)d->head_w_off[0], j.hw1 = (int32_t)d->head_w_off[1];
     j.hb0 = (int32_t)d->head_b_off[0], j.hb1 = (int32_t)d->head_b_off[1];
@@ -2546,12 +2527,18 @@ static StockJobArg stock_job_arg(const asac_mlp_desc_t* d, const float* params, 
     return j;
 }
 
+// the policy's rows as both networks of asac_policy_sample_q_forward read them: no second input in memory
+static asac_mlp_job_t pi_rows(const asac_mlp_job_t& p) {
+    asac_mlp_job_t r = p;
+    r.x1 = nullptr, r.x1_row_stride = r.x1_member_stride = 0;
+    return r;
+}
+
 static bool pi_q_job_ok(const asac_pi_q_job_t& j) {
     const asac_mlp_job_t &p = j.pi, &q = j.q;
     if (!p.desc || !q.desc || !desc_ok(*p.desc) || !desc_ok(*q.desc) || p.N <= 0 || q.N != p.N || p.E != 1 || q.E < 1) return false;
     if (!stock3(*p.desc, p.params, p.member_stride) || !stock3(*q.desc, q.params, q.member_stride)) return false;
-    if (q.desc->head_cols[0] != 1 || q.desc->head_cols[1] != 0 || q.desc->head_transform != 0) return false;
-    if (p.desc->head_transform != 1 || p.desc->head_cols[0] != p.desc->head_cols[1] || p.desc->in1 != 0) return false;
+    if (!scalar_head(*q.desc) || !gauss_head(*p.desc) || p.desc->in1 != 0) return false;
     const int A = p.desc->head_cols[0];
     if (q.desc->in0 != p.desc->in0 || q.desc->in1 != A || 2 * A > kHeadPad || A > 8) return false;
     if (!p.x0 || q.x0 != p.x0 || q.x0_row_stride != p.x0_row_stride || q.x0_window_T != p.x0_window_T ||
@@ -2565,8 +2552,7 @@ static bool pi_q_job_ok(const asac_pi_q_job_t& j) {
     if (s.action && (!fits32((p.N / s.T + 1) * s.action_stride_b) || !fits32((p.N / s.T + 1) * s.prob_stride_b) ||
                      !fits32(s.T * s.action_stride_t) || !fits32(s.T * s.prob_stride_t)))
         return false;
-    return p.N * (p.x0_row_stride + 1) < 0x1fffffffLL &&
-           (p.x0_window_T == 0 || (p.N / p.x0_window_T + 1) * p.x0_sample_stride < 0x1fffffffLL);
+    return job_fits32(pi_rows(p));
 }
 
 int asac_policy_sample_q_forward_ok(const asac_pi_q_job_t* job) { return job && pi_q_job_ok(*job) ? 1 : 0; }
@@ -2578,11 +2564,11 @@ int asac_policy_sample_q_forward(const asac_pi_q_job_t* job, const asac_mlp_job_
     SidecarsDev sc{};
     if (sidecars_prepare(sidecars_host, n_sidecars, sc)) return bad_arg("asac_policy_sample_q_forward: sidecar");
     PiQLaunch m{};
-    const asac_mlp_job_t &p = job->pi, &q = job->q;
-    m.pi = stock_job_arg(p.desc, p.params, p.member_stride, p.x0, p.x0_row_stride, 0, nullptr, 0, 0, p.N, p.x0_window_T,
-                         p.x0_sample_stride, p.out);
-    m.q = stock_job_arg(q.desc, q.params, q.member_stride, p.x0, p.x0_row_stride, 0, p.x0, 0, 0, p.N, p.x0_window_T,
-                        p.x0_sample_stride, q.out);            // (x1: the sampled actions, on chip)
+    const asac_mlp_job_t p = pi_rows(job->pi);
+    asac_mlp_job_t q = pi_rows(job->q);         // (its rows are the policy's: pi_q_job_ok)
+    q.x1 = p.x0;                                // (x1: the sampled actions, on chip)
+    m.pi = stock_job_arg(p);
+    m.q = stock_job_arg(q);
     m.E = q.E;
     const int tiles = (int)((p.N + 15) / 16);
     const int cap = 256 / q.E > 0 ? 256 / q.E : 1;
@@ -2603,14 +2589,10 @@ int asac_policy_sample_q_forward(const asac_pi_q_job_t* job, const asac_mlp_job_
     int blocks = 0;
     for (int k = 0; k < n_extra; ++k) {
         const asac_mlp_job_t& j = extra_jobs[k];
-        if (!j.desc || !desc_ok(*j.desc) || !stock3(*j.desc, j.params, j.member_stride) || j.E <= 0 || j.N <= 0 || !j.x0 ||
-            (j.desc->in1 > 0 && !j.x1) || !j.out || j.x0_window_T < 0 ||
-            j.N * (j.x0_row_stride + j.x1_row_stride + 1) >= 0x1fffffffLL ||
-            (j.x0_window_T > 0 && (j.N / j.x0_window_T + 1) * j.x0_sample_stride >= 0x1fffffffLL) ||
+        if (!job_ok(j, true) || !stock3(*j.desc, j.params, j.member_stride) || j.x0_window_T < 0 || !job_fits32(j) ||
             !fits32(j.member_stride) || !fits32(j.x0_member_stride) || !fits32(j.x1_member_stride))
             return bad_arg("asac_policy_sample_q_forward: extra job");
-        m.x_job[k] = stock_job_arg(j.desc, j.params, j.member_stride, j.x0, j.x0_row_stride, j.x0_member_stride, j.x1,
-                                   j.x1_row_stride, j.x1_member_stride, j.N, j.x0_window_T, j.x0_sample_stride, j.out);
+        m.x_job[k] = stock_job_arg(j);
         m.x_E[k] = j.E;
         m.x_first_block[k] = blocks;
         m.x_tile_stride[k] = mlp_tile_groups(j.N, j.E, 1, 16);
@@ -2639,24 +2621,12 @@ int asac_policy_sample_q_forward(const asac_pi_q_job_t* job, const asac_mlp_job_
     return finish_launch("asac_policy_sample_q_forward");
 }
 
-int asac_mlp_backward_qloss(const asac_mlp_desc_t* desc, const float* params, int64_t member_stride, int E,
-                            const float* x0, int64_t x0_row_stride, int64_t x0_member_stride,
-                            const float* x1, int64_t x1_row_stride, int64_t x1_member_stride, int64_t N,
-                            const float* target_q, const float* y, const float* weights, float clip_eps,
-                            float* loss_out, float* grad_params, float* workspace, int reduce_mode,
-                            void* stream) {
-    return asac_mlp_backward_qloss_gx(desc, params, member_stride, E, x0, x0_row_stride, x0_member_stride, x1, x1_row_stride,
-                                      x1_member_stride, N, target_q, y, weights, clip_eps, loss_out, nullptr, grad_params,
-                                      workspace, reduce_mode, stream);
-}
-
-int asac_mlp_backward_qloss_return_ok(const asac_mlp_desc_t* desc, const float* params, int64_t member_stride, int E,
-                                      int64_t N, const asac_vtrace_args_t* ret) {
-    if (!desc || !desc_ok(*desc) || !ret || E <= 0 || N <= 0 || ret->B != N || ret->n <= 0 || !ret->q || !ret->y_out ||
-        ret->E_sample <= 0 || ret->E_sample > ASAC_MAX_ENSEMBLE || ret->td_error_out)
+int asac_mlp_backward_qloss_return_ok(const asac_mlp_job_t* job, const asac_vtrace_args_t* ret) {
+    if (!job || !job->desc || !desc_ok(*job->desc) || !ret || job->E <= 0 || job->N <= 0 || ret->B != job->N || ret->n <= 0 ||
+        !ret->q || !ret->y_out || ret->E_sample <= 0 || ret->E_sample > ASAC_MAX_ENSEMBLE || ret->td_error_out)
         return 0;
-    if (desc->in0 + desc->in1 > kMaxW || !stock3(*desc, params, member_stride)) return 0;
-    const int tm = mlp_tile_rows(N, E);
+    if (wide_input(*job->desc) || !stock3(*job->desc, job->params, job->member_stride)) return 0;
+    const int tm = mlp_tile_rows(job->N, job->E);
     const size_t lds = (tm == 16 ? sizeof(MlpBwdLds<16>) : sizeof(MlpBwdLds<32>)) +
                        (size_t)(2 * ((ret->n + 1) | 1) + 2) * tm * sizeof(float);
     // one thread per (row, step) of a tile: 16-row tiles run ASAC_BWD_WAVES waves (n <= 64 with 16), 32-row tiles 512 threads
@@ -2664,23 +2634,16 @@ int asac_mlp_backward_qloss_return_ok(const asac_mlp_desc_t* desc, const float* 
     return tm * ret->n <= threads && lds <= 128 * 1024;
 }
 
-int asac_mlp_backward_qloss_return(const asac_mlp_desc_t* desc, const float* params, int64_t member_stride, int E,
-                                   const float* x0, int64_t x0_row_stride, int64_t x0_member_stride,
-                                   const float* x1, int64_t x1_row_stride, int64_t x1_member_stride, int64_t N,
-                                   const float* target_q, const asac_vtrace_args_t* ret, const float* weights,
-                                   float clip_eps, float* loss_out, float* grad_x0, float* grad_params, float* workspace,
-                                   int reduce_mode, void* stream) {
-    if (!desc || !desc_ok(*desc) || E <= 0 || N <= 0 || !x0 || (desc->in1 > 0 && !x1) || !target_q || !ret ||
-        !grad_params || !workspace || clip_eps <= 0.f)
+int asac_mlp_backward_qloss_return(const asac_mlp_job_t* job, const float* target_q, const asac_vtrace_args_t* ret,
+                                   const float* weights, float clip_eps, float* loss_out, float* grad_x0, float* grad_params,
+                                   float* workspace, int reduce_mode, void* stream) {
+    if (!bwd_job_ok(job) || !target_q || !ret || !grad_params || !workspace || clip_eps <= 0.f)
         return bad_arg("asac_mlp_backward_qloss_return");
-    if (desc->head_cols[0] != 1 || desc->head_cols[1] != 0 || desc->head_transform != 0)
-        return bad_arg("asac_mlp_backward_qloss_return: not a scalar-head network");
+    if (!scalar_head(*job->desc)) return bad_arg("asac_mlp_backward_qloss_return: not a scalar-head network");
     if (reduce_mode != ASAC_MLP_REDUCE_DEFER && !loss_out) return bad_arg("asac_mlp_backward_qloss_return: loss_out");
-    if (!asac_mlp_backward_qloss_return_ok(desc, params, member_stride, E, N, ret) ||
-        (ret->use_n_step_is && (!ret->mu_prob || !ret->pi_prob || ret->A <= 0)))
+    if (!asac_mlp_backward_qloss_return_ok(job, ret) || (ret->use_n_step_is && (!ret->mu_prob || !ret->pi_prob || ret->A <= 0)))
         return bad_arg("asac_mlp_backward_qloss_return: return arguments");
-    MlpArgs a = make_args(desc, params, member_stride, x0, x0_row_stride, x0_member_stride, x1, x1_row_stride,
-                          x1_member_stride, N);
+    MlpArgs a = make_args(*job);
     if (!offsets32(a)) return bad_arg("asac_mlp_backward_qloss_return: offsets");
     a.tq = target_q;
     a.y = ret->y_out;
@@ -2688,31 +2651,25 @@ int asac_mlp_backward_qloss_return(const asac_mlp_desc_t* desc, const float* par
     a.clip_eps = clip_eps;
     a.gx0 = grad_x0;
     RetIn<true> rv{*ret, vtrace_scan_lanes(ret->B, ret->n)};
-    return mlp_backward_common("asac_mlp_backward_qloss_return", desc, a, E, N, member_stride, grad_params, workspace,
-                               reduce_mode, loss_out, as_stream(stream), &rv);
+    return mlp_backward_common("asac_mlp_backward_qloss_return", *job, a, grad_params, workspace, reduce_mode, loss_out,
+                               as_stream(stream), &rv);
 }
 
-int asac_mlp_backward_qloss_gx(const asac_mlp_desc_t* desc, const float* params, int64_t member_stride, int E,
-                               const float* x0, int64_t x0_row_stride, int64_t x0_member_stride,
-                               const float* x1, int64_t x1_row_stride, int64_t x1_member_stride, int64_t N,
-                               const float* target_q, const float* y, const float* weights, float clip_eps,
-                               float* loss_out, float* grad_x0, float* grad_params, float* workspace, int reduce_mode,
-                               void* stream) {
-    if (!desc || !desc_ok(*desc) || E <= 0 || N <= 0 || !x0 || (desc->in1 > 0 && !x1) || !target_q || !y ||
-        !grad_params || !workspace || clip_eps <= 0.f)
+int asac_mlp_backward_qloss(const asac_mlp_job_t* job, const float* target_q, const float* y, const float* weights,
+                            float clip_eps, float* loss_out, float* grad_x0, float* grad_params, float* workspace,
+                            int reduce_mode, void* stream) {
+    if (!bwd_job_ok(job) || !target_q || !y || !grad_params || !workspace || clip_eps <= 0.f)
         return bad_arg("asac_mlp_backward_qloss");
-    if (desc->head_cols[0] != 1 || desc->head_cols[1] != 0 || desc->head_transform != 0)
-        return bad_arg("asac_mlp_backward_qloss: not a scalar-head network");
+    if (!scalar_head(*job->desc)) return bad_arg("asac_mlp_backward_qloss: not a scalar-head network");
     if (reduce_mode != ASAC_MLP_REDUCE_DEFER && !loss_out) return bad_arg("asac_mlp_backward_qloss: loss_out");
-    MlpArgs a = make_args(desc, params, member_stride, x0, x0_row_stride, x0_member_stride, x1, x1_row_stride,
-                          x1_member_stride, N);
+    MlpArgs a = make_args(*job);
     a.tq = target_q;
     a.y = y;
     a.w = weights;
     a.clip_eps = clip_eps;
     a.gx0 = grad_x0;
-    return mlp_backward_common("asac_mlp_backward_qloss", desc, a, E, N, member_stride, grad_params, workspace,
-                               reduce_mode, loss_out, as_stream(stream));
+    return mlp_backward_common("asac_mlp_backward_qloss", *job, a, grad_params, workspace, reduce_mode, loss_out,
+                               as_stream(stream));
 }
 
 }  // extern "C"

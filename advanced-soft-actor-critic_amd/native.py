@@ -14,7 +14,7 @@ PKG_DIR = Path(__file__).resolve().parent
 import os as _os
 
 LIB_PATH = Path(_os.environ.get('ASAC_HIP_LIB', PKG_DIR / 'lib' / 'libasac_hip.so'))   # env override: debugging builds
-ABI_VERSION = 84
+ABI_VERSION = 85
 
 MAX_GATHER_KEYS = 16
 PAD_KEEP, PAD_WORD, PAD_BYTE, PAD_ROW, PAD_EMIT_MASK = 0, 1, 2, 3, 4
@@ -240,36 +240,22 @@ _SIGNATURES = {
                                             C.c_void_p, C.c_void_p]),
     'asac_q_loss_fwd_bwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                       C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_mlp_forward': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
-                                   C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    'asac_mlp_forward': (C.c_int, [C.POINTER(MlpJob), C.c_void_p]),
     'asac_mlp_forward_multi': (C.c_int, [C.POINTER(MlpJob), C.c_int, C.POINTER(Sidecar), C.c_int, C.c_void_p]),
     'asac_mlp_forward_multi_sampled_ok': (C.c_int, [C.POINTER(MlpJob), C.c_int, C.POINTER(SampleEpilogue)]),
     'asac_mlp_forward_multi_sampled': (C.c_int, [C.POINTER(MlpJob), C.c_int, C.POINTER(SampleEpilogue), C.POINTER(Sidecar),
                                                  C.c_int, C.c_void_p]),
     'asac_mlp_backward_workspace': (C.c_int64, [C.c_int64, C.c_int, C.c_int64]),
     'asac_mlp_backward_tiles': (C.c_int64, [C.c_int64, C.c_int]),
-    'asac_mlp_backward': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
-                                    C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    'asac_mlp_backward_qloss': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
-                                          C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_int, C.c_void_p]),
-    'asac_mlp_backward_qloss_gx': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
-                                             C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_int, C.c_void_p]),
-    'asac_mlp_backward_qloss_return_ok': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.c_int, C.c_int64,
-                                                    C.POINTER(VtraceArgs)]),
-    'asac_mlp_backward_qloss_return': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
-                                                 C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
-                                                 C.POINTER(VtraceArgs), C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    'asac_mlp_backward_policy_q': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
-                                             C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
-                                             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    'asac_mlp_backward_policy_sample': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                                  C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+    'asac_mlp_backward': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                    C.c_void_p]),
+    'asac_mlp_backward_qloss': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    'asac_mlp_backward_qloss_return_ok': (C.c_int, [C.POINTER(MlpJob), C.POINTER(VtraceArgs)]),
+    'asac_mlp_backward_qloss_return': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.POINTER(VtraceArgs), C.c_void_p, C.c_float,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    'asac_mlp_backward_policy_q': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'asac_mlp_backward_policy_sample': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     'asac_struct_size': (C.c_int64, [C.c_char_p]),
     'asac_policy_sample_q_forward_ok': (C.c_int, [C.POINTER(PiQJob)]),
@@ -854,6 +840,23 @@ def squash_sample_bwd(loc, scale, eps, grad_a, grad_logp, grad_loc, grad_scale, 
                                          _stream()), 'asac_squash_sample_bwd')
 
 
+def _stored_action(s: SquashJob, rows, action, action_offset, prob_out, prob_offset):
+    """the stored-action fields of `s`: `action` / `prob_out` are [samples, T, >= offset + A] views (dense last dim) of
+    the job's `rows` = samples * T rows; sets s.T"""
+    assert action.dim() == 3 and prob_out.dim() == 3 and action.stride(-1) == 1 and prob_out.stride(-1) == 1
+    assert action.shape[0] * action.shape[1] == rows and prob_out.shape[:2] == action.shape[:2]
+    s.action, s.T = action.data_ptr(), action.shape[1]
+    s.action_stride_b, s.action_stride_t, s.action_offset = action.stride(0), action.stride(1), action_offset
+    s.prob_out, s.prob_stride_b, s.prob_stride_t, s.prob_offset = \
+        prob_out.data_ptr(), prob_out.stride(0), prob_out.stride(1), prob_offset
+
+
+def _second_sample(j, samples, A, eps2, t2, a2_out, logp2_out):
+    """the second-sample fields of a `SampleEpilogue` / `PiQJob`: eps2 [samples, A] -> a2_out, logp2_out at position t2"""
+    assert eps2.is_contiguous() and a2_out.is_contiguous() and eps2.numel() == samples * A
+    j.eps2, j.t2, j.a2_out, j.logp2_out = eps2.data_ptr(), t2, a2_out.data_ptr(), logp2_out.data_ptr()
+
+
 def squash_job(loc, scale, eps=None, a_out=None, logp_out=None, action=None, action_offset=0, prob_out=None,
                prob_offset=0) -> SquashJob:
     """One job of `squash_multi`: a sampling job (eps, a_out, logp_out; optionally also the stored-action
@@ -866,12 +869,7 @@ def squash_job(loc, scale, eps=None, a_out=None, logp_out=None, action=None, act
         assert eps.is_contiguous() and a_out.is_contiguous() and eps.numel() == rows * A
         j.eps, j.a_tanh_out, j.logp_out = eps.data_ptr(), a_out.data_ptr(), logp_out.data_ptr()
     if action is not None:
-        assert action.dim() == 3 and prob_out.dim() == 3 and action.stride(-1) == 1 and prob_out.stride(-1) == 1
-        assert action.shape[0] * action.shape[1] == rows and prob_out.shape[:2] == action.shape[:2]
-        j.action, j.T = action.data_ptr(), action.shape[1]
-        j.action_stride_b, j.action_stride_t, j.action_offset = action.stride(0), action.stride(1), action_offset
-        j.prob_out, j.prob_stride_b, j.prob_stride_t, j.prob_offset = \
-            prob_out.data_ptr(), prob_out.stride(0), prob_out.stride(1), prob_offset
+        _stored_action(j, rows, action, action_offset, prob_out, prob_offset)
     else:
         assert eps is not None, 'a job needs eps (sampling) or action (stored-action probabilities)'
     return j
@@ -987,16 +985,6 @@ def mlp_flops(desc, E, N, backward=False, param_grads=True) -> float:
     return 2.0 * mac * N * E * passes
 
 
-@_profiled
-def mlp_forward(desc, params, member_stride, E, x0, x1, N, out):
-    global _last_work
-    _last_work = mlp_flops(desc, E, N)
-    p0, rs0, ms0 = _rows_view(x0)
-    p1, rs1, ms1 = _rows_view(x1)
-    _check(load().asac_mlp_forward(C.byref(desc), _p(params), member_stride, E, p0, rs0, ms0, p1, rs1, ms1,
-                                   N, _p(out), _stream()), 'asac_mlp_forward')
-
-
 class WindowRows:
     """Marks a non-collapsible [samples, T, K] view (dense last dim) as the row source of a forward job:
     the kernel addresses rows as (sample, t) instead of the caller staging a contiguous copy."""
@@ -1006,9 +994,11 @@ class WindowRows:
         self.shape = (t.shape[0] * t.shape[1], t.shape[2])
 
 
-def mlp_job(desc, params, member_stride, E, x0, x1, N, out) -> MlpJob:
-    """One forward pass of `mlp_forward_multi` (arguments as `mlp_forward`; raw pointers: keep the tensors
-    and the descriptor alive until the launch)."""
+def mlp_job(desc, params, member_stride, E, x0, x1, N, out=None) -> MlpJob:
+    """One pass of E networks (`desc`; parameter segments `member_stride` floats apart in `params`) over N rows: x0 / x1
+    [N, K] (shared by every member) or [E, N, K], x1 None when in1 == 0; `out` [E, N, head columns] for the forward
+    passes.  What the mlp_* wrappers below take first.  Raw pointers: keep the tensors and the descriptor alive until
+    the launch."""
     j = MlpJob()
     j.desc, j.params, j.member_stride, j.E, j.N = C.pointer(desc), params.data_ptr(), member_stride, E, N
     if isinstance(x0, WindowRows):      # [samples, T, K] view shared by every member, read in place
@@ -1020,9 +1010,21 @@ def mlp_job(desc, params, member_stride, E, x0, x1, N, out) -> MlpJob:
         p0, j.x0_row_stride, j.x0_member_stride = _rows_view(x0)
     p1, j.x1_row_stride, j.x1_member_stride = _rows_view(x1)
     j.x0, j.x1 = p0.value if p0 is not None else None, p1.value if p1 is not None else None
-    assert out.is_cuda and out.is_contiguous()
-    j.out = out.data_ptr()
+    if out is not None:
+        assert out.is_cuda and out.is_contiguous()
+        j.out = out.data_ptr()
     return j
+
+
+def _pass_flops(job: MlpJob, backward=False, param_grads=True) -> float:
+    return mlp_flops(job.desc.contents, job.E, job.N, backward, param_grads)
+
+
+@_profiled
+def mlp_forward(job: MlpJob):
+    global _last_work
+    _last_work = _pass_flops(job)
+    _check(load().asac_mlp_forward(C.byref(job), _stream()), 'asac_mlp_forward')
 
 
 @_profiled
@@ -1051,18 +1053,11 @@ def sample_epilogue(job: MlpJob | None = None, eps=None, a_out=None, logp_out=No
         assert logp_out.is_contiguous()
         s.eps, s.a_tanh_out, s.logp_out = eps.data_ptr(), a_out.data_ptr(), logp_out.data_ptr()
     if action is not None:
-        assert action.dim() == 3 and prob_out.dim() == 3 and action.stride(-1) == 1 and prob_out.stride(-1) == 1
-        assert action.shape[0] * action.shape[1] == N and prob_out.shape[:2] == action.shape[:2]
-        s.T = action.shape[1]
+        _stored_action(s, N, action, action_offset, prob_out, prob_offset)
         assert T in (0, s.T)
-        s.action, s.action_stride_b, s.action_stride_t, s.action_offset = \
-            action.data_ptr(), action.stride(0), action.stride(1), action_offset
-        s.prob_out, s.prob_stride_b, s.prob_stride_t, s.prob_offset = \
-            prob_out.data_ptr(), prob_out.stride(0), prob_out.stride(1), prob_offset
     if eps2 is not None:
-        assert s.T > 0 and eps2.is_contiguous() and a2_out.is_contiguous() and eps2.numel() == (N // s.T) * A
-        assert logp2_out.is_contiguous() and logp2_out.numel() == N // s.T
-        e.eps2, e.t2, e.a2_out, e.logp2_out = eps2.data_ptr(), t2, a2_out.data_ptr(), logp2_out.data_ptr()
+        assert s.T > 0 and logp2_out.is_contiguous() and logp2_out.numel() == N // s.T
+        _second_sample(e, N // s.T, A, eps2, t2, a2_out, logp2_out)
     return e
 
 
@@ -1098,15 +1093,10 @@ def pi_q_job(pi_job: MlpJob, q_job: MlpJob, eps, a_out, logp_out, T, action=None
     s = j.sample
     s.eps, s.a_tanh_out, s.logp_out, s.rows, s.A, s.T = eps.data_ptr(), a_out.data_ptr(), logp_out.data_ptr(), N, A, T
     if action is not None:
-        assert action.dim() == 3 and prob_out.dim() == 3 and action.stride(-1) == 1 and prob_out.stride(-1) == 1
-        assert action.shape[0] * action.shape[1] == N and action.shape[1] == T and prob_out.shape[:2] == action.shape[:2]
-        s.action, s.action_stride_b, s.action_stride_t, s.action_offset = \
-            action.data_ptr(), action.stride(0), action.stride(1), action_offset
-        s.prob_out, s.prob_stride_b, s.prob_stride_t, s.prob_offset = \
-            prob_out.data_ptr(), prob_out.stride(0), prob_out.stride(1), prob_offset
+        assert action.dim() == 3 and action.shape[1] == T
+        _stored_action(s, N, action, action_offset, prob_out, prob_offset)
     if eps2 is not None:
-        assert eps2.is_contiguous() and a2_out.is_contiguous() and eps2.numel() == (N // T) * A
-        j.eps2, j.t2, j.a2_out, j.logp2_out = eps2.data_ptr(), t2, a2_out.data_ptr(), logp2_out.data_ptr()
+        _second_sample(j, N // T, A, eps2, t2, a2_out, logp2_out)
     return j
 
 
@@ -1145,68 +1135,59 @@ def mlp_param_extent(desc) -> int:
 
 
 @_profiled
-def mlp_backward_qloss(desc, params, member_stride, E, x0, x1, N, target_q, y, weights, clip_eps, loss_out,
-                       grad_params, workspace, reduce_mode, grad_x0=None):
+def mlp_backward_qloss(job: MlpJob, target_q, y, weights, clip_eps, loss_out, grad_params, workspace, reduce_mode,
+                       grad_x0=None):
     """Q loss + backward of the stock Q ensemble in one launch (parameter gradients; with `grad_x0` [E, N, in0] also
     the members' gradients w.r.t. the state input)."""
     global _last_work
-    _last_work = mlp_flops(desc, E, N, backward=True, param_grads=True)
-    p0, rs0, ms0 = _rows_view(x0)
-    p1, rs1, ms1 = _rows_view(x1)
+    _last_work = _pass_flops(job, backward=True)
+    E, N = job.E, job.N
     assert target_q.is_contiguous() and target_q.numel() == E * N and y.is_contiguous() and y.numel() == N
-    assert grad_x0 is None or (grad_x0.is_contiguous() and grad_x0.numel() == E * N * desc.in0)
-    _check(load().asac_mlp_backward_qloss_gx(C.byref(desc), _p(params), member_stride, E, p0, rs0, ms0, p1, rs1, ms1, N,
-                                             _p(target_q), _p(y), _p(weights), float(clip_eps), _p(loss_out), _p(grad_x0),
-                                             _p(grad_params), _p(workspace), int(reduce_mode), _stream()),
+    assert grad_x0 is None or (grad_x0.is_contiguous() and grad_x0.numel() == E * N * job.desc.contents.in0)
+    _check(load().asac_mlp_backward_qloss(C.byref(job), _p(target_q), _p(y), _p(weights), float(clip_eps), _p(loss_out),
+                                          _p(grad_x0), _p(grad_params), _p(workspace), int(reduce_mode), _stream()),
            'asac_mlp_backward_qloss')
 
 
-def mlp_backward_qloss_return_ok(desc, params, member_stride, E, N, ret: VtraceArgs) -> bool:
-    return bool(load().asac_mlp_backward_qloss_return_ok(C.byref(desc), _p(params), member_stride, E, N, C.byref(ret)))
+def mlp_backward_qloss_return_ok(job: MlpJob, ret: VtraceArgs) -> bool:
+    """(reads the job's network, E and N only: its inputs may be unset)"""
+    return bool(load().asac_mlp_backward_qloss_return_ok(C.byref(job), C.byref(ret)))
 
 
 @_profiled
-def mlp_backward_qloss_return(desc, params, member_stride, E, x0, x1, N, target_q, ret: VtraceArgs, weights, clip_eps,
-                              loss_out, grad_params, workspace, reduce_mode, grad_x0=None):
+def mlp_backward_qloss_return(job: MlpJob, target_q, ret: VtraceArgs, weights, clip_eps, loss_out, grad_params, workspace,
+                              reduce_mode, grad_x0=None):
     """`mlp_backward_qloss` whose workgroups form the return target `ret` describes themselves (no return launch)"""
     global _last_work
-    _last_work = mlp_flops(desc, E, N, backward=True, param_grads=True)
-    p0, rs0, ms0 = _rows_view(x0)
-    p1, rs1, ms1 = _rows_view(x1)
+    _last_work = _pass_flops(job, backward=True)
+    E, N = job.E, job.N
     assert target_q.is_contiguous() and target_q.numel() == E * N
-    assert grad_x0 is None or (grad_x0.is_contiguous() and grad_x0.numel() == E * N * desc.in0)
-    _check(load().asac_mlp_backward_qloss_return(C.byref(desc), _p(params), member_stride, E, p0, rs0, ms0, p1, rs1, ms1,
-                                                 N, _p(target_q), C.byref(ret), _p(weights), float(clip_eps),
+    assert grad_x0 is None or (grad_x0.is_contiguous() and grad_x0.numel() == E * N * job.desc.contents.in0)
+    _check(load().asac_mlp_backward_qloss_return(C.byref(job), _p(target_q), C.byref(ret), _p(weights), float(clip_eps),
                                                  _p(loss_out), _p(grad_x0), _p(grad_params), _p(workspace), int(reduce_mode),
                                                  _stream()), 'asac_mlp_backward_qloss_return')
 
 
 @_profiled
-def mlp_backward_policy_q(desc, params, member_stride, E, x0, x1, N, q_table, subset, E_sample, grad_x1):
+def mlp_backward_policy_q(job: MlpJob, q_table, subset, E_sample, grad_x1):
     """Policy step: action gradients of mean_b(-min_{e in subset} q_e) through the stock Q ensemble."""
     global _last_work
-    _last_work = mlp_flops(desc, E, N, backward=True, param_grads=False)
-    p0, rs0, ms0 = _rows_view(x0)
-    p1, rs1, ms1 = _rows_view(x1)
-    assert q_table.is_contiguous() and q_table.numel() == E * N and grad_x1.is_contiguous()
-    _check(load().asac_mlp_backward_policy_q(C.byref(desc), _p(params), member_stride, E, p0, rs0, ms0, p1, rs1, ms1,
-                                             N, _p(q_table), _p(subset), E_sample, _p(grad_x1), _stream()),
+    _last_work = _pass_flops(job, backward=True, param_grads=False)
+    assert q_table.is_contiguous() and q_table.numel() == job.E * job.N and grad_x1.is_contiguous()
+    _check(load().asac_mlp_backward_policy_q(C.byref(job), _p(q_table), _p(subset), E_sample, _p(grad_x1), _stream()),
            'asac_mlp_backward_policy_q')
 
 
 @_profiled
-def mlp_backward_policy_sample(desc, params, member_stride, x0, N, eps, grad_a, log_alpha, grad_params, workspace,
-                               reduce_mode):
-    """Policy step: sampling backward + policy backward of the stock Gaussian-head policy in one launch."""
+def mlp_backward_policy_sample(job: MlpJob, eps, grad_a, log_alpha, grad_params, workspace, reduce_mode):
+    """Policy step: sampling backward + policy backward of the stock Gaussian-head policy (E = 1, no x1) in one launch."""
     global _last_work
-    _last_work = mlp_flops(desc, 1, N, backward=True, param_grads=True)
-    p0, rs0, _ = _rows_view(x0)
-    A = desc.head_cols[0]
+    _last_work = _pass_flops(job, backward=True)
+    N, A = job.N, job.desc.contents.head_cols[0]
     assert eps.is_contiguous() and eps.numel() == N * A and grad_a.is_contiguous() and grad_a.numel() % (N * A) == 0
-    _check(load().asac_mlp_backward_policy_sample(C.byref(desc), _p(params), member_stride, p0, rs0, N, _p(eps),
-                                                  _p(grad_a), grad_a.numel() // (N * A), _p(log_alpha),
-                                                  _p(grad_params), _p(workspace), int(reduce_mode), _stream()),
-           'asac_mlp_backward_policy_sample')
+    _check(load().asac_mlp_backward_policy_sample(C.byref(job), _p(eps), _p(grad_a), grad_a.numel() // (N * A),
+                                                  _p(log_alpha), _p(grad_params), _p(workspace), int(reduce_mode),
+                                                  _stream()), 'asac_mlp_backward_policy_sample')
 
 
 def policy_step_fused_ok(q_desc, q_params, q_member_stride, pi_desc, pi_params, pi_member_stride, N) -> bool:
@@ -1252,14 +1233,10 @@ def adam_step_partials(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, 
 
 
 @_profiled
-def mlp_backward(desc, params, member_stride, E, x0, x1, N, grad_out, grad_x0, grad_x1, grad_params, workspace,
-                 reduce_mode=MLP_REDUCE_ACCUMULATE):
+def mlp_backward(job: MlpJob, grad_out, grad_x0, grad_x1, grad_params, workspace, reduce_mode=MLP_REDUCE_ACCUMULATE):
     global _last_work
-    _last_work = mlp_flops(desc, E, N, backward=True, param_grads=grad_params is not None)
-    p0, rs0, ms0 = _rows_view(x0)
-    p1, rs1, ms1 = _rows_view(x1)
-    _check(load().asac_mlp_backward(C.byref(desc), _p(params), member_stride, E, p0, rs0, ms0, p1, rs1, ms1, N,
-                                    _p(grad_out), _p(grad_x0), _p(grad_x1), _p(grad_params), _p(workspace),
+    _last_work = _pass_flops(job, backward=True, param_grads=grad_params is not None)
+    _check(load().asac_mlp_backward(C.byref(job), _p(grad_out), _p(grad_x0), _p(grad_x1), _p(grad_params), _p(workspace),
                                     int(reduce_mode), _stream()), 'asac_mlp_backward')
 
 

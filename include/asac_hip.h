@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ASAC_ABI_VERSION 84
+#define ASAC_ABI_VERSION 85
 #define ASAC_MAX_GATHER_KEYS 16
 #define ASAC_MAX_ENSEMBLE 16
 #define ASAC_MAX_ACTION 64
@@ -490,19 +490,11 @@ typedef struct {
     int32_t reserved_;
 } asac_mlp_desc_t;
 
-/* out[e][row][0:head_cols0+head_cols1] for e < E, row < N.
+/* One pass of E networks over N rows: what every entry point below takes first (host memory; device pointers inside).
  *   x0 element (e, row, c) at x0 + e*x0_member_stride + row*x0_row_stride + c (member stride 0 =
- *   the same input for every ensemble member); same for x1. */
-int asac_mlp_forward(const asac_mlp_desc_t* desc_host, const float* params, int64_t member_stride,
-                     int E, const float* x0, int64_t x0_row_stride, int64_t x0_member_stride,
-                     const float* x1, int64_t x1_row_stride, int64_t x1_member_stride, int64_t N,
-                     float* out, void* stream);
-
-/* floats of scratch `asac_mlp_backward` needs when parameter gradients are requested */
-/* Up to ASAC_MLP_MAX_JOBS independent forward passes (different networks and / or inputs) in ONE launch:
- * e.g. the target-Q of the stored (s, a) pairs beside the policy's forward over the window, or the online
- * and the target ensemble of the TD error.  Fields as the arguments of asac_mlp_forward. */
-#define ASAC_MLP_MAX_JOBS 2
+ *   the same input for every ensemble member); same for x1 (NULL when in1 == 0).
+ *   out[e][row][0:head_cols0+head_cols1] for e < E, row < N: written by the forward passes; the backward passes
+ *   ignore it (may be NULL). */
 typedef struct {
     const asac_mlp_desc_t* desc;
     const float* params;
@@ -514,12 +506,22 @@ typedef struct {
     int64_t N;
     float* out;
     int32_t E;
-    /* window addressing of x0: with x0_window_T > 0, row = s * T + t is read at
+    /* window addressing of x0 (forward_multi / forward_multi_sampled / policy_sample_q_forward only; every other
+     * entry point refuses a non-zero value): with x0_window_T > 0, row = s * T + t is read at
      * x0 + s * x0_sample_stride + t * x0_row_stride — a [samples, T, in0] view of a larger replay window
      * (states[:, b:]) without a staging copy; 0: flat rows */
     int32_t x0_window_T;
     int64_t x0_sample_stride;
 } asac_mlp_job_t;
+
+/* job->out = the networks' outputs.  Also serves first layers of 65..128 inputs (at most ASAC_MLP_MAX_BLOCKS - 1 blocks,
+ * the first not residual). */
+int asac_mlp_forward(const asac_mlp_job_t* job, void* stream);
+
+/* Up to ASAC_MLP_MAX_JOBS independent forward passes (different networks and / or inputs) in ONE launch:
+ * e.g. the target-Q of the stored (s, a) pairs beside the policy's forward over the window, or the online
+ * and the target ensemble of the TD error. */
+#define ASAC_MLP_MAX_JOBS 2
 int asac_mlp_forward_multi(const asac_mlp_job_t* jobs_host, int n_jobs, const asac_sidecar_t* sidecars_host,
                            int n_sidecars, void* stream);
 
@@ -575,13 +577,14 @@ int asac_policy_sample_q_forward(const asac_pi_q_job_t* job, const asac_mlp_job_
 #define ASAC_MLP_REDUCE_OVERWRITE 0
 #define ASAC_MLP_REDUCE_ACCUMULATE 1
 #define ASAC_MLP_REDUCE_DEFER 2
+/* floats of scratch `asac_mlp_backward` needs when parameter gradients are requested */
 int64_t asac_mlp_backward_workspace(int64_t member_stride, int E, int64_t N);
 /* Row tiles the backward of an [E][N] pass is cut into (16-row tiles while E * ceil(N / 16) workgroups fit one
  * resident round on the 256 CUs, else 32-row tiles): the number of per-tile partial slabs in `workspace`, i.e. the
  * `tiles` argument asac_adam_step_partials needs after an ASAC_MLP_REDUCE_DEFER backward. */
 int64_t asac_mlp_backward_tiles(int64_t N, int E);
 
-/* Backward of the above (the forward is recomputed on chip; nothing is saved between the two).
+/* Backward of the pass `job` (the forward is recomputed on chip; nothing is saved between the two).
  *   grad_out     [E][N][head columns]
  *   grad_x0/x1   [E][N][in0] / [E][N][in1], written (not accumulated); either may be NULL
  *   grad_params  flat gradient buffer with the SAME layout as `params`: the tiles' partial sums are
@@ -590,58 +593,40 @@ int64_t asac_mlp_backward_tiles(int64_t N, int E);
  *                workspace for asac_adam_step_partials (ASAC_MLP_REDUCE_DEFER); NULL = input
  *                gradients only
  *   workspace    asac_mlp_backward_workspace() floats (only with grad_params) */
-int asac_mlp_backward(const asac_mlp_desc_t* desc_host, const float* params, int64_t member_stride,
-                      int E, const float* x0, int64_t x0_row_stride, int64_t x0_member_stride,
-                      const float* x1, int64_t x1_row_stride, int64_t x1_member_stride, int64_t N,
-                      const float* grad_out, float* grad_x0, float* grad_x1, float* grad_params,
+int asac_mlp_backward(const asac_mlp_job_t* job, const float* grad_out, float* grad_x0, float* grad_x1, float* grad_params,
                       float* workspace, int reduce_mode, void* stream);
 
 /* The Q step's loss and backward in ONE launch (sac_base.py:1539-1570 for the stock ModelQ ensemble):
  * the forward is recomputed on chip anyway, so q = Q_e(x0, x1) is formed there, the clipped double-Q
  * loss  l = max((tq + clamp(q - tq, +-clip_eps) - y)^2, (q - y)^2) * w  and d(mean_b l)/dq replace
- * grad_out, and back-propagation continues as in asac_mlp_backward (parameter gradients only).
+ * grad_out, and back-propagation continues as in asac_mlp_backward (parameter gradients).
  *   target_q [E][N], y [N], weights [N] or NULL;  loss_out [E] = mean_b l  (written by the reducing
- *   launch: this call, or asac_adam_step_partials with ASAC_MLP_REDUCE_DEFER) */
-int asac_mlp_backward_qloss(const asac_mlp_desc_t* desc_host, const float* params, int64_t member_stride,
-                            int E, const float* x0, int64_t x0_row_stride, int64_t x0_member_stride,
-                            const float* x1, int64_t x1_row_stride, int64_t x1_member_stride, int64_t N,
-                            const float* target_q, const float* y, const float* weights, float clip_eps,
-                            float* loss_out, float* grad_params, float* workspace, int reduce_mode,
-                            void* stream);
-/* ... also returning the gradient of the summed member losses w.r.t. the STATE input, grad_x0 [E][N][in0] (one per
- * member; the caller sums them): a trainable representation's Q step needs no separate critic forward / loss launch
- * (sac_base.py:1539-1570 with the representation in the graph). */
-int asac_mlp_backward_qloss_gx(const asac_mlp_desc_t* desc_host, const float* params, int64_t member_stride, int E,
-                               const float* x0, int64_t x0_row_stride, int64_t x0_member_stride,
-                               const float* x1, int64_t x1_row_stride, int64_t x1_member_stride, int64_t N,
-                               const float* target_q, const float* y, const float* weights, float clip_eps,
-                               float* loss_out, float* grad_x0, float* grad_params, float* workspace, int reduce_mode,
-                               void* stream);
+ *   launch: this call, or asac_adam_step_partials with ASAC_MLP_REDUCE_DEFER)
+ *   grad_x0 [E][N][in0] or NULL: the gradient of the summed member losses w.r.t. the STATE input (one per member; the
+ *   caller sums them) — a trainable representation's Q step needs no separate critic forward / loss launch
+ *   (sac_base.py:1539-1570 with the representation in the graph). */
+int asac_mlp_backward_qloss(const asac_mlp_job_t* job, const float* target_q, const float* y, const float* weights,
+                            float clip_eps, float* loss_out, float* grad_x0, float* grad_params, float* workspace,
+                            int reduce_mode, void* stream);
 
 /* asac_mlp_backward_qloss forming its own return target (sac_base.py:1423-1464 + 1244-1295 inside 1539-1570): every
  * workgroup evaluates the n-step V-trace return `ret` describes for ITS tile's rows — the loads travel under the weight
  * staging, the per-step terms and the scan association are asac_vtrace_return_min's (bit-identical y) — so no return
  * launch precedes the Q step.  ret->y_out [N] is written as well (member 0's workgroups); ret->td_error_out must be
- * NULL, ret->B == N; grad_x0 as in asac_mlp_backward_qloss_gx (or NULL).  `_ok`: stock three-block network, n <= 16, the tile's steps fit LDS (otherwise: the two launches). */
-int asac_mlp_backward_qloss_return_ok(const asac_mlp_desc_t* desc_host, const float* params, int64_t member_stride, int E,
-                                      int64_t N, const asac_vtrace_args_t* ret);
-int asac_mlp_backward_qloss_return(const asac_mlp_desc_t* desc_host, const float* params, int64_t member_stride, int E,
-                                   const float* x0, int64_t x0_row_stride, int64_t x0_member_stride,
-                                   const float* x1, int64_t x1_row_stride, int64_t x1_member_stride, int64_t N,
-                                   const float* target_q, const asac_vtrace_args_t* ret, const float* weights,
-                                   float clip_eps, float* loss_out, float* grad_x0, float* grad_params, float* workspace,
-                                   int reduce_mode, void* stream);
+ * NULL, ret->B == N; grad_x0 as in asac_mlp_backward_qloss.  `_ok`: stock three-block network, n <= 16, the tile's steps
+ * fit LDS (otherwise: the two launches); it reads the job's desc, params, member_stride, E and N only. */
+int asac_mlp_backward_qloss_return_ok(const asac_mlp_job_t* job, const asac_vtrace_args_t* ret);
+int asac_mlp_backward_qloss_return(const asac_mlp_job_t* job, const float* target_q, const asac_vtrace_args_t* ret,
+                                   const float* weights, float clip_eps, float* loss_out, float* grad_x0, float* grad_params,
+                                   float* workspace, int reduce_mode, void* stream);
 
 /* The policy step's Q backward (sac_base.py:1896-1903): the gradient of mean_b(-min_{e in subset} q_e)
  * w.r.t. the ensemble outputs is formed on chip from the value table q_table [E][N] the preceding
  * asac_mlp_forward produced (-1/N at the first arg-min member of the subset, else 0) and pushed back to
  * the ACTION input only: grad_x1 [E][N][in1] (one gradient per member; asac_squash_sample_bwd sums them).
  * subset: device i32[E_sample] or NULL (= members 0..E_sample-1). */
-int asac_mlp_backward_policy_q(const asac_mlp_desc_t* desc_host, const float* params, int64_t member_stride,
-                               int E, const float* x0, int64_t x0_row_stride, int64_t x0_member_stride,
-                               const float* x1, int64_t x1_row_stride, int64_t x1_member_stride, int64_t N,
-                               const float* q_table, const int32_t* subset, int E_sample, float* grad_x1,
-                               void* stream);
+int asac_mlp_backward_policy_q(const asac_mlp_job_t* job, const float* q_table, const int32_t* subset, int E_sample,
+                               float* grad_x1, void* stream);
 
 /* The WHOLE policy step of the stock networks with two critics in one launch (sac_base.py:1883-1906): the critics'
  * forward on (x, action), d(mean_b -min_e q_e)/dq, both critics' backward to the action, the rsample / tanh /
@@ -671,11 +656,11 @@ int asac_policy_step_fused(const asac_mlp_desc_t* q_desc, const float* q_params,
 /* The policy step's policy backward (sac_base.py:1883-1906, stock Gaussian-head ModelPolicy): the
  * gradient of the objective w.r.t. (loc | scale) — asac_squash_sample_bwd's math with dL/dlogp =
  * exp(*log_alpha) / N and dL/da = sum over grad_a_members of grad_a [m][N][A] — is formed on chip from the
- * forward the backward recomputes, then back-propagated (parameter gradients only; reduce_mode as above). */
-int asac_mlp_backward_policy_sample(const asac_mlp_desc_t* desc_host, const float* params, int64_t member_stride,
-                                    const float* x0, int64_t x0_row_stride, int64_t N, const float* eps,
-                                    const float* grad_a, int grad_a_members, const float* log_alpha,
-                                    float* grad_params, float* workspace, int reduce_mode, void* stream);
+ * forward the backward recomputes, then back-propagated (parameter gradients only; reduce_mode as above).
+ * The pass is one policy on its state rows: job->E == 1, job->x1 == NULL. */
+int asac_mlp_backward_policy_sample(const asac_mlp_job_t* job, const float* eps, const float* grad_a, int grad_a_members,
+                                    const float* log_alpha, float* grad_params, float* workspace, int reduce_mode,
+                                    void* stream);
 
 /* floats of one member's parameter block that the network actually uses (<= member_stride) */
 int64_t asac_mlp_param_extent(const asac_mlp_desc_t* desc_host);

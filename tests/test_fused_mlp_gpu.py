@@ -547,3 +547,74 @@ def test_wide_job_beside_a_narrow_one_goes_launch_by_launch():
     native.mlp_forward_multi([job_q, job_pi])
     assert torch.equal(q_out, fq._launch_forward(xs, a))
     assert torch.equal(pi_out, fpi._launch_forward(base[:, 2:].reshape(B * T, 8), None))
+
+
+def _setup_stacks(E, in0, in1, widths):
+    """E `LinearLayers` stacks on (in0 | in1) inputs with one output column, in one flat buffer -> (modules, group, StockMLP)"""
+    import asac_amd  # noqa: F401
+    import algorithm.nn_models as m
+    from algorithm.fused import FlatParamGroup
+    from algorithm.fused_mlp import StockMLP, describe_dense
+    torch.manual_seed(0)
+    mods = [m.LinearLayers(in0 + in1, widths, len(widths), 1).cuda() for _ in range(E)]
+    with torch.no_grad():
+        for mod in mods:
+            for p in mod.parameters():
+                if p.dim() == 1:
+                    p.normal_(0, 0.3)
+    group = FlatParamGroup([(f'm{i}', list(mod.parameters())) for i, mod in enumerate(mods)], 'cuda')
+    desc = describe_dense(mods[0])
+    desc.in0, desc.in1 = in0, in1       # the stack's input arrives as two tensors
+    stride = group.segments['m0'][1] - group.segments['m0'][0]
+    return mods, group, StockMLP(desc, group.flat, group.grad, 0, stride, E, torch.device('cuda'))
+
+
+# what the host code behind `asac_mlp_forward` / `asac_mlp_backward` decides from the pass it is handed: the instantiation
+# (three 64-wide blocks: the fixed-shape one; two 32-wide blocks: the generic one; 66 inputs: the wide one), the tile
+# height (E = 2: 16 rows up to N = 2048, then 32) and the parameter-gradient sum (csrc/mlp.hip kSlicedFrom = 64 tiles:
+# 1008 rows are 63 tiles, 1009 rows 64)
+@pytest.mark.parametrize('in0,widths', [(6, [64, 64, 64]), (6, [32, 32]), (64, [64, 64, 64])])
+def test_one_job_per_pass_launches_and_computes_as_before(in0, widths):
+    from asac_amd import native
+    E, A = 2, 2
+    mods, group, mlp = _setup_stacks(E, in0, A, widths)
+    assert mlp.wide == (in0 == 64)
+    for N in (33, 1008, 1009, 4100):
+        assert native.mlp_backward_tiles(N, E) == {33: 3, 1008: 63, 1009: 64, 4100: 129}[N]
+        x = torch.randn(N, in0, device='cuda', requires_grad=True)
+        a = torch.randn(N, A, device='cuda').tanh().requires_grad_()
+        gout = torch.randn(E, N, 1, device='cuda')
+        group.grad.zero_()
+        ref = torch.stack([mod(torch.cat([x, a], -1)) for mod in mods])
+        (ref * gout).sum().backward()
+        ref_gx, ref_ga, ref_gp = x.grad.clone(), a.grad.clone(), group.grad.clone()
+        x.grad = a.grad = None
+        group.grad.zero_()
+        with native.LaunchProfiler(repeat=1) as prof:
+            out = mlp(x, a)
+            (out * gout).sum().backward()
+        assert {k: v['calls'] for k, v in prof.summary().items()} == {'asac_mlp_forward': 1, 'asac_mlp_backward': 1}
+        # (the bounds of test_q_ensemble_forward_backward: the same two entry points)
+        np.testing.assert_allclose(out.detach().cpu().numpy(), ref.detach().cpu().numpy(), rtol=2e-5,
+                                   atol=2e-6 if in0 <= 16 else 6e-6, err_msg=f'N={N}')
+        np.testing.assert_allclose(x.grad.cpu().numpy(), ref_gx.cpu().numpy(), rtol=1e-4, atol=1e-5, err_msg=f'N={N}')
+        np.testing.assert_allclose(a.grad.cpu().numpy(), ref_ga.cpu().numpy(), rtol=1e-4, atol=1e-5, err_msg=f'N={N}')
+        gp_scale = max(1.0, float(ref_gp.abs().max()))
+        np.testing.assert_allclose(group.grad.cpu().numpy(), ref_gp.cpu().numpy(), rtol=1e-4, atol=2e-5 * gp_scale,
+                                   err_msg=f'N={N}')
+
+
+def test_wide_job_beside_a_narrow_one_is_one_entry_point_call():
+    """the wide job's detour inside `asac_mlp_forward_multi` hands the job on as it is: one recorded call, the results of
+    the single-network forwards"""
+    from asac_amd import native
+    _, _, fq = _setup_stacks(2, 64, 2, [64, 64, 64])
+    _, _, fn = _setup_stacks(2, 6, 2, [32, 32])
+    N = 33
+    xs, x, a = torch.randn(N, 64, device='cuda'), torch.randn(N, 6, device='cuda'), torch.randn(N, 2, device='cuda').tanh()
+    job_q, q_out = fq.job(xs, a)
+    job_n, n_out = fn.job(x, a)
+    with native.LaunchProfiler(repeat=1) as prof:
+        native.mlp_forward_multi([job_q, job_n])
+    assert {k: v['calls'] for k, v in prof.summary().items()} == {'asac_mlp_forward_multi': 1}
+    assert torch.equal(q_out, fq._launch_forward(xs, a)) and torch.equal(n_out, fn._launch_forward(x, a))

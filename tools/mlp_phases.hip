@@ -46,17 +46,20 @@ int main() {
     const int64_t wsn = asac_mlp_backward_workspace(stride, E, N);
     hipMalloc(&ws, wsn * 4); hipMalloc(&grad, E * stride * 4); hipMalloc(&loss, E * 4);
     const asac_mlp_desc_t dq = stock(S, A, 1, 0, 0), dp = stock(S, 0, A, A, 1);
+    asac_mlp_job_t jq{}, jp{};          // the critics on (x0 | x1), the policy on x0
+    jq.desc = &dq, jq.params = params, jq.member_stride = stride, jq.E = E, jq.N = N;
+    jq.x0 = x0, jq.x0_row_stride = S, jq.x1 = x1, jq.x1_row_stride = A;
+    jp = jq, jp.desc = &dp, jp.E = 1, jp.x1 = nullptr, jp.x1_row_stride = 0;
     for (int mode = 0; mode < 3; ++mode) {
         double acc[24] = {0};
         const int reps = 200;
         for (int r = 0; r < reps; ++r) {
             if (mode == 0)
-                asac_mlp_backward_qloss(&dq, params, stride, E, x0, S, 0, x1, A, 0, N, tq, y, nullptr, 0.2f, loss, grad, ws,
-                                        ASAC_MLP_REDUCE_DEFER, nullptr);
+                asac_mlp_backward_qloss(&jq, tq, y, nullptr, 0.2f, loss, nullptr, grad, ws, ASAC_MLP_REDUCE_DEFER, nullptr);
             else if (mode == 1)
-                asac_mlp_backward_policy_q(&dq, params, stride, E, x0, S, 0, x1, A, 0, N, qt, nullptr, E, g1, nullptr);
+                asac_mlp_backward_policy_q(&jq, qt, nullptr, E, g1, nullptr);
             else
-                asac_mlp_backward_policy_sample(&dp, params, stride, x0, S, N, eps, ga, E, la, grad, ws, ASAC_MLP_REDUCE_DEFER, nullptr);
+                asac_mlp_backward_policy_sample(&jp, eps, ga, E, la, grad, ws, ASAC_MLP_REDUCE_DEFER, nullptr);
             hipDeviceSynchronize();
             unsigned long long st[32];
             hipMemcpyFromSymbol(st, HIP_SYMBOL(asac::g_mlp_stamps), sizeof st);

@@ -188,6 +188,10 @@ FUSED_ROWS_PROJ = os.environ.get('ASAC_ROWS_PROJ', '1') != '0'
 FUSED_QKV_IN_CORE = os.environ.get('ASAC_QKV_IN_CORE', '1') != '0'
 # ... and the block's backward as one launch too   (0: ResBlock backward, core backward, projections' backward)
 FUSED_BLOCK_BACKWARD = os.environ.get('ASAC_ATTN_BLOCK_BWD', '1') != '0'
+# the gate behind an episode block's attention, with the padded-row factor, as one launch per pass (csrc/rows_gate.hip)
+# (False: the gate layer's module code — tests and tools/gate_bench.py).  On for all three kinds: the captured step of each is
+# faster than with the module code by far more than the box spread (NOTES.md, gate round: 1.15x / 1.59x / 3.2x)
+FUSED_GATE = True
 
 
 class _AttnCoreFn(torch.autograd.Function):
@@ -344,22 +348,36 @@ class _AttnProjFn(torch.autograd.Function):
         return (g_xq, g_xk, None, None, *grads)
 
 
-def _rows_param_grads(ctx_needs, params, g2, x2):
-    """weight / bias gradient of one Linear from its output gradient rows g2 and input rows x2 (`asac_xty`): added straight
-    into the `.grad` views under the learner's direct mode, else returned"""
+def _rows_param_grads(ctx_needs, params, g2, x2, jobs=None):
+    """weight / bias gradient of one Linear (bias: None without one) from its output gradient rows g2 and input rows x2
+    (`asac_xty`): added straight into the `.grad` views under the learner's direct mode, else returned.  With a list `jobs` the
+    returned product is not launched but appended to it: the caller has several and runs them together (`_run_xty_jobs`)"""
     from asac_amd import native
     from algorithm.fused_mlp import direct_enabled, direct_skips
     weight, bias = params
-    if not any(ctx_needs) or direct_skips(weight, bias):
+    held = [p for p in params if p is not None]
+    if not any(ctx_needs) or direct_skips(*held):
         return None, None
-    w_grad, b_grad = weight.grad, bias.grad
-    if direct_enabled() and w_grad is not None and b_grad is not None and w_grad.is_contiguous() and b_grad.is_contiguous():
+    if direct_enabled() and all(p.grad is not None and p.grad.is_contiguous() for p in held):
         from algorithm.fused_rows_linear import queue_param_grads
-        queue_param_grads(g2, x2, w_grad, b_grad)
+        queue_param_grads(g2, x2, weight.grad, None if bias is None else bias.grad)
         return None, None
-    gw, gb = torch.empty_like(weight), torch.empty_like(bias)
-    native.xty(g2, x2, gw, gb)
+    gw, gb = torch.empty_like(weight), None if bias is None else torch.empty_like(bias)
+    if jobs is None:
+        native.xty(g2, x2, gw, gb)
+    else:
+        jobs.append((g2, x2, gw, gb))
     return gw, gb
+
+
+def _run_xty_jobs(jobs):
+    """the products `_rows_param_grads` left in `jobs`, up to four a launch pair (`asac_xty_multi`: their outputs are distinct)"""
+    from asac_amd import native
+    for i in range(0, len(jobs), 4):
+        if len(jobs[i:i + 4]) == 1:
+            native.xty(*jobs[i])
+        else:
+            native.xty_multi(jobs[i:i + 4])
 
 
 class _QkvRowsFn(torch.autograd.Function):
@@ -576,6 +594,109 @@ class _OutResSavedFn(torch.autograd.Function):
     def backward(ctx, gy):
         gx, gw, gb, _ = _OutResRowsFn.backward(ctx, gy)
         return gx, gw, gb, None, None
+
+
+class _GateRowsFn(torch.autograd.Function):
+    """`gatedlayer(x, y) * ~row_zero[..., None]` for a RESIDUAL / OUTPUT / RECURRENT gate — the gate behind an episode block's
+    attention and its padded-row factor — as one launch per pass (`asac_rows_gate_*`, csrc/rows_gate.hip); the parameter
+    gradients from `asac_xty` over the pre-activation gradients the backward launch writes.
+    params: () / (W,) / (Wxr, Wyr, Wxz, Wyz, Wxg, Wyg, bz)"""
+
+    @staticmethod
+    def forward(ctx, kind, x, y, row_zero, *params):
+        from asac_amd import native
+        B, L, E = y.shape
+        # (a view expanded along the batch or the positions — a stride of 0 — is made dense like a misaligned one: the launch
+        # takes rows that do not overlap)
+        if (x.stride(2) != 1 or (x.stride(0) | x.stride(1) | (x.data_ptr() >> 2)) & 3 or (L > 1 and x.stride(1) < E)
+                or (B > 1 and x.stride(0) < E)):
+            x = x.contiguous()
+        if not y.is_contiguous() or y.data_ptr() & 15:
+            y = y.clone(memory_format=torch.contiguous_format)
+        if row_zero is not None and ((L > 1 and row_zero.stride(1) != 1) or (B > 1 and row_zero.stride(0) < L)):
+            row_zero = row_zero.contiguous()
+        weights = [w.detach() for w in params[:6]]
+        bz = params[6].detach() if len(params) == 7 else None
+        out = torch.empty(y.shape, dtype=y.dtype, device=y.device)
+        need = any(ctx.needs_input_grad)
+        saved = [torch.empty_like(out) for _ in range({1: 0, 2: 1, 3: 3}[kind])] if need else []
+        native.rows_gate_forward(kind, x, y, row_zero, weights, bz, out, saved or None)
+        if need:
+            ctx.save_for_backward(x, y, *saved, *([row_zero] if row_zero is not None else []))
+        ctx.kind, ctx.params, ctx.masked = kind, params, row_zero is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        from asac_amd import native
+        kind, params = ctx.kind, ctx.params
+        x, y, *saved = ctx.saved_tensors
+        row_zero = saved.pop() if ctx.masked else None
+        E = y.shape[-1]
+        if not g_out.is_contiguous() or g_out.data_ptr() & 15:
+            g_out = g_out.clone(memory_format=torch.contiguous_format)
+        weights = [w.detach() for w in params[:6]]
+        g_x = torch.empty_like(y)
+        if kind == GATE.RESIDUAL.value:
+            native.rows_gate_backward(kind, g_out, x, y, row_zero, weights, [], g_x, g_x, [])
+            return None, g_x, g_x, None
+        g_y = torch.empty_like(y)
+        g_pre = [torch.empty_like(y) for _ in saved]
+        rx = torch.empty_like(y) if kind == GATE.RECURRENT.value else None
+        native.rows_gate_backward(kind, g_out, x, y, row_zero, weights, saved, g_x, g_y, g_pre, rx)
+        needs = ctx.needs_input_grad[4:]
+        if not any(needs):
+            return (None, g_x, g_y, None, *([None] * len(params)))
+        x2, y2, jobs = x.reshape(-1, E), y.view(-1, E), []
+        if kind == GATE.OUTPUT.value:
+            gw, _ = _rows_param_grads(needs[:1], (params[0], None), g_pre[0].view(-1, E), x2, jobs)
+            _run_xty_jobs(jobs)
+            return None, g_x, g_y, None, gw
+        dr, dz, dh = (g.view(-1, E) for g in g_pre)
+        wxr, wyr, wxz, wyz, wxg, wyg, bz = params
+        # six products with six distinct outputs, the bias gradient the column sums of dz_pre beside the first product over it
+        gxr, _ = _rows_param_grads(needs[0:1], (wxr, None), dr, x2, jobs)
+        gyr, _ = _rows_param_grads(needs[1:2], (wyr, None), dr, y2, jobs)
+        gxz, gbz = _rows_param_grads((needs[2], needs[6]), (wxz, bz), dz, x2, jobs)
+        gyz, _ = _rows_param_grads(needs[3:4], (wyz, None), dz, y2, jobs)
+        gxg, _ = _rows_param_grads(needs[4:5], (wxg, None), dh, rx.view(-1, E), jobs)
+        gyg, _ = _rows_param_grads(needs[5:6], (wyg, None), dh, y2, jobs)
+        _run_xty_jobs(jobs)
+        return None, g_x, g_y, None, gxr, gyr, gxz, gyz, gxg, gyg, gbz
+
+
+def _gate_linear_ok(lin, width, bias) -> bool:
+    return (type(lin) is nn.Linear and lin.in_features == lin.out_features == width and (lin.bias is not None) == bias
+            and lin.weight.dtype == torch.float32 and _params_aligned16(lin))
+
+
+def _fused_gate_params(block, x, y, key_padding_mask):
+    """the parameters `_GateRowsFn` takes for the gate of `block`, or None: the gate layer's module code runs (CPU, other
+    dtypes, widths the kernel does not have, parameters that are misaligned views, CAT, a subclassed gate layer)"""
+    gate, layer = block.gate, block.gatedlayer
+    if not (FUSED_GATE and isinstance(gate, GATE) and gate in (GATE.RESIDUAL, GATE.OUTPUT, GATE.RECURRENT)
+            and x.is_cuda and y.is_cuda and x.dtype == y.dtype == torch.float32 and x.dim() == 3 and x.shape == y.shape):
+        return None
+    if key_padding_mask is not None and not (key_padding_mask.dtype == torch.bool and key_padding_mask.is_cuda
+                                             and key_padding_mask.dim() == 2 and key_padding_mask.shape[0] == x.shape[0]
+                                             and key_padding_mask.shape[1] >= x.shape[1]):
+        return None
+    E = x.shape[2]
+    from asac_amd import native
+    if not native.rows_gate_supported(gate.value, E):
+        return None
+    if gate == GATE.RESIDUAL:
+        return () if type(layer) is GatedResidualLayer else None
+    if gate == GATE.OUTPUT:
+        if type(layer) is GatedOutputLayer and _gate_linear_ok(layer.dense, E, False):
+            return (layer.dense.weight,)
+        return None
+    if type(layer) is not GatedRecurrentLayer:
+        return None
+    lins = (layer.dense_x_r, layer.dense_y_r, layer.dense_x_z, layer.dense_y_z, layer.dense_x_g, layer.dense_y_g)
+    if not all(_gate_linear_ok(lin, E, lin is layer.dense_x_z) for lin in lins):
+        return None
+    return (*(lin.weight for lin in lins), layer.dense_x_z.bias)
 
 
 def _rows_proj_ok(module, query, key) -> bool:
@@ -1024,6 +1145,11 @@ class EpisodeMultiheadAttentionBlock(nn.Module):
         output, weights = self.attn(query, key, key, query_index=query_index, key_index=key_index,
                                     attn_mask=attn_mask, out_row_mask=row_mask)
         if self.gate is not None:
+            gate_params = _fused_gate_params(self, residual_src, output, key_padding_mask)
+            if gate_params is not None:
+                # the gate and the padded-row factor: one launch per pass (csrc/rows_gate.hip), the mask read where it lies
+                row_zero = None if key_padding_mask is None else key_padding_mask[:, -output.shape[1]:]
+                return _GateRowsFn.apply(self.gate.value, residual_src, output, row_zero, *gate_params), weights
             output = self.gatedlayer(residual_src, output)
             if key_padding_mask is not None:
                 output = output * (~key_padding_mask[:, -output.shape[1]:]).to(output.dtype).unsqueeze(-1)

@@ -14,7 +14,7 @@ PKG_DIR = Path(__file__).resolve().parent
 import os as _os
 
 LIB_PATH = Path(_os.environ.get('ASAC_HIP_LIB', PKG_DIR / 'lib' / 'libasac_hip.so'))   # env override: debugging builds
-ABI_VERSION = 85
+ABI_VERSION = 86
 
 MAX_GATHER_KEYS = 16
 PAD_KEEP, PAD_WORD, PAD_BYTE, PAD_ROW, PAD_EMIT_MASK = 0, 1, 2, 3, 4
@@ -428,6 +428,12 @@ _SIGNATURES = {
                                              C.c_void_p, C.c_void_p, C.c_void_p]),
     'asac_rows_resblock_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),
+    'asac_rows_gate_supported': (C.c_int, [C.c_int, C.c_int]),
+    'asac_rows_gate_forward': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                         C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_rows_gate_backward': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
     'asac_rows_affine_supported': (C.c_int, [C.c_int, C.c_int]),
     'asac_rows_affine_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
                                            C.c_void_p]),
@@ -2266,6 +2272,64 @@ def rows_resblock_backward(grad_y, pre, weight, row_scale, grad_x, grad_pre):
     _last_work = 2.0 * rows * E * E
     _check(load().asac_rows_resblock_backward(_p(grad_y), _p(pre), _p(weight), _p(row_scale), rows, E, _p(grad_x), _p(grad_pre),
                                               _stream()), 'asac_rows_resblock_backward')
+
+
+# ------------------------------------------------------------------------------------------------
+# the gate behind an episode attention block, with its padded-row factor (csrc/rows_gate.hip)
+# ------------------------------------------------------------------------------------------------
+GATE_RESIDUAL, GATE_OUTPUT, GATE_RECURRENT = 1, 2, 3      # (the values of seq_layers.GATE)
+_GATE_WEIGHTS = {GATE_RESIDUAL: 0, GATE_OUTPUT: 1, GATE_RECURRENT: 6}
+_GATE_SAVED = {GATE_RESIDUAL: 0, GATE_OUTPUT: 1, GATE_RECURRENT: 3}
+
+
+def rows_gate_supported(kind, width) -> bool:
+    return bool(load().asac_rows_gate_supported(int(kind), int(width)))
+
+
+def _gate_operands(kind, x, y, row_zero, weights):
+    B, L, E = x.shape
+    assert x.is_cuda and x.dtype == torch.float32 and x.stride(2) == 1 and y.shape == (B, L, E)
+    assert len(weights) == _GATE_WEIGHTS[kind]
+    _dense_f32(y, *weights)
+    for w in weights:
+        assert w.shape == (E, E)
+    rz_stride = 0
+    if row_zero is not None:
+        assert row_zero.is_cuda and row_zero.dtype in (torch.bool, torch.uint8) and row_zero.shape == (B, L)
+        assert L == 1 or row_zero.stride(1) == 1
+        rz_stride = row_zero.stride(0) if B > 1 else L
+    return B, L, E, rz_stride
+
+
+@_profiled
+def rows_gate_forward(kind, x, y, row_zero, weights, bias_z, out, saved):
+    """out = gate(x, y) * ~row_zero[..., None] for kind RESIDUAL / OUTPUT / RECURRENT, one launch (formulas: asac_hip.h).
+    x [B][L][E] with feature stride 1 (batch / position strides multiples of 4); y, out and the `saved` buffers ([a] /
+    [r, z, h]; None: not kept) dense; row_zero bool [B][L] or None; weights [] / [W] / [Wxr, Wyr, Wxz, Wyz, Wxg, Wyg]"""
+    global _last_work
+    B, L, E, rz_stride = _gate_operands(kind, x, y, row_zero, weights)
+    _dense_f32(out, bias_z, *(saved or ()))
+    assert out.shape == (B, L, E) and (not saved or len(saved) == _GATE_SAVED[kind])
+    _last_work = 2.0 * B * L * E * E * len(weights)
+    _check(load().asac_rows_gate_forward(int(kind), _p(x), x.stride(0), x.stride(1), _p(y), _p(row_zero), rz_stride, B, L, E,
+                                         _ptr_array(weights) if weights else None, _p(bias_z), _p(out),
+                                         _ptr_array(saved) if saved else None, _stream()), 'asac_rows_gate_forward')
+
+
+@_profiled
+def rows_gate_backward(kind, grad_out, x, y, row_zero, weights, saved, grad_x, grad_y, grad_pre, rx=None):
+    """the backward of `rows_gate_forward`: grad_x, grad_y (RESIDUAL: may be one tensor), the dense pre-activation gradients
+    grad_pre ([grad_a] / [dr_pre, dz_pre, dh_pre]) and, RECURRENT, rx = r * x — the operands of the weight-gradient products"""
+    global _last_work
+    B, L, E, rz_stride = _gate_operands(kind, x, y, row_zero, weights)
+    _dense_f32(grad_out, grad_x, grad_y, rx, *saved, *grad_pre)
+    assert grad_out.shape == (B, L, E) and len(saved) == len(grad_pre) == _GATE_SAVED[kind]
+    _last_work = 2.0 * B * L * E * E * len(weights)
+    _check(load().asac_rows_gate_backward(int(kind), _p(grad_out), _p(x), x.stride(0), x.stride(1), _p(y), _p(row_zero), rz_stride,
+                                          B, L, E, _ptr_array(weights) if weights else None,
+                                          _ptr_array(saved) if saved else None, _p(grad_x), _p(grad_y),
+                                          _ptr_array(grad_pre) if grad_pre else None, _p(rx), _stream()),
+           'asac_rows_gate_backward')
 
 
 # ------------------------------------------------------------------------------------------------

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ASAC_ABI_VERSION 85
+#define ASAC_ABI_VERSION 86
 #define ASAC_MAX_GATHER_KEYS 16
 #define ASAC_MAX_ENSEMBLE 16
 #define ASAC_MAX_ACTION 64
@@ -991,6 +991,41 @@ int asac_rows_resblock_forward(const float* x, int64_t x_row_stride, const float
                                const float* row_scale, int64_t rows, int width, float* y, float* pre, void* stream);
 int asac_rows_resblock_backward(const float* grad_y, const float* pre, const float* weight, const float* row_scale,
                                 int64_t rows, int width, float* grad_x, float* grad_pre, void* stream);
+/* The gate an episode attention block puts behind its attention, with the padded-row factor, one launch per pass
+ * (csrc/rows_gate.hip) — replaces, in `EpisodeMultiheadAttentionBlock.forward` (nn_models/layers/seq_layers.py:460-547),
+ * `self.gatedlayer(residual_src, output)` (the gate layers of seq_layers.py:297-345) and the
+ * `output * (~key_padding_mask[...]).to(dtype).unsqueeze(-1)` behind it.
+ * kind = 1 RESIDUAL, 2 OUTPUT, 3 RECURRENT (the values of `GATE`); width = E in {32, 64, 128}; every pointer 16-byte aligned
+ * (row_zero excepted).  x [batch][window][E] = the residual source, read through its strides in floats (feature stride 1;
+ * multiples of 4); y [batch][window][E] = the attention output, dense; row_zero uint8 / bool [batch][window] with its own batch
+ * stride in bytes (position stride 1), or NULL; s = 1 - row_zero (NULL: 1).  weights = HOST array, read at the call, of the
+ * kind's [E][E] device matrices (out x in): none (may be NULL) / {W} / {Wxr, Wyr, Wxz, Wyz, Wxg, Wyg}; bias_z [E] (RECURRENT,
+ * else ignored).  Every output is dense [batch][window][E].
+ *
+ * asac_rows_gate_forward:
+ *   RESIDUAL   out = (x + y) s
+ *   OUTPUT     a = x W^T;  out = (x + sigmoid(a * y)) s;  saved = {a}
+ *   RECURRENT  r = sigmoid(x Wxr^T + y Wyr^T);  z = sigmoid(x Wxz^T + y Wyz^T + bias_z);  h = tanh(y Wyg^T + (r * x) Wxg^T);
+ *              out = ((1 - z) x + z h) s;  saved = {r, z, h}
+ *   saved = HOST array of the device buffers to fill, or NULL (no backward will follow).
+ * asac_rows_gate_backward: g = grad_out s (grad_out dense), with the buffers the forward saved:
+ *   RESIDUAL   grad_x = grad_y = g (grad_y may BE grad_x)
+ *   OUTPUT     p = sigmoid(a y);  d = g p (1 - p);  grad_y = d a;  grad_pre = {d y};  grad_x = g + (d y) W
+ *   RECURRENT  dz_pre = g (h - x) z (1 - z);  dh_pre = g z (1 - h^2);  q = dh_pre Wxg;  dr_pre = q x r (1 - r);
+ *              grad_x = (g (1 - z) + q r) + (dr_pre Wxr + dz_pre Wxz);  grad_y = dr_pre Wyr + dz_pre Wyz + dh_pre Wyg;
+ *              grad_pre = {dr_pre, dz_pre, dh_pre};  rx = r * x (the left operand of Wxg's gradient; else ignored)
+ *   The weight gradients are the products of grad_pre over the rows with x, y and rx, bias_z's the column sums of dz_pre
+ *   (asac_xty / asac_xty_multi).  Summation order: each product over the input features in ascending blocks of 16, the lower
+ *   and the upper half of the features in an accumulator each (E = 32: one), lower + upper; products that feed one result are
+ *   formed on their own and added in the order written, left to right; the other terms as bracketed. */
+int asac_rows_gate_supported(int kind, int width);
+int asac_rows_gate_forward(int kind, const float* x, int64_t x_stride_b, int64_t x_stride_t, const float* y,
+                           const uint8_t* row_zero, int64_t row_zero_stride_b, int batch, int window, int width,
+                           const float* const* weights, const float* bias_z, float* out, float* const* saved, void* stream);
+int asac_rows_gate_backward(int kind, const float* grad_out, const float* x, int64_t x_stride_b, int64_t x_stride_t,
+                            const float* y, const uint8_t* row_zero, int64_t row_zero_stride_b, int batch, int window, int width,
+                            const float* const* weights, const float* const* saved, float* grad_x, float* grad_y,
+                            float* const* grad_pre, float* rx, void* stream);
 /* y [rows][N] = x [rows][K] weight[N][K]^T + bias[N] for a narrow input (K <= 64) and a wide output (N a multiple of 16, <= 1024):
  * the input products `x W_ih^T + b_ih` of every step in front of a recurrence (reference seq_layers.py:14-114 through nn.GRU;
  * observation ++ action -> 3 x hidden); x with a row stride in floats, y dense and 16-byte aligned. */

@@ -192,6 +192,10 @@ FUSED_BLOCK_BACKWARD = os.environ.get('ASAC_ATTN_BLOCK_BWD', '1') != '0'
 # (False: the gate layer's module code — tests and tools/gate_bench.py).  On for all three kinds: the captured step of each is
 # faster than with the module code by far more than the box spread (NOTES.md, gate round: 1.15x / 1.59x / 3.2x)
 FUSED_GATE = True
+# a rotary position encoding (ROPE / ROPE2) as the epilogue of the q / k / v projection launch (csrc/rows_proj.hip), or as one
+# launch per pass behind other projections (csrc/rope.hip)   (False: `self.rope(...)` as module code behind library GEMMs —
+# tests and tools/rope_bench.py)
+FUSED_ROPE = True
 
 
 class _AttnCoreFn(torch.autograd.Function):
@@ -418,6 +422,108 @@ class _QkvRowsFn(torch.autograd.Function):
             out.extend(_rows_param_grads(ctx.needs_input_grad[2 + 2 * j:4 + 2 * j], ctx.params[2 * j:2 * j + 2],
                                          g.view(-1, E), xin))
         return tuple(out)
+
+
+class _QkvRopeRowsFn(torch.autograd.Function):
+    """`_QkvRowsFn` with `self.rope(index[:, -tail:], index, q, k)` behind it in the same launch, and the un-rotation of the
+    gradients in front of the backward launch's products (`asac_rows_proj_rope_*`, csrc/rows_proj.hip); the parameter gradients
+    are products of the un-rotated gradients the backward launch writes.  `tables`: `_fused_rope_tables`"""
+
+    @staticmethod
+    def forward(ctx, x, tail, index, kind, tables, wq, bq, wk, bk, wv, bv):
+        from asac_amd import native
+        if x.stride(2) != 1 or (x.stride(0) | x.stride(1) | (x.data_ptr() >> 2)) & 3:
+            x = x.contiguous()
+        B, L, E = x.shape
+        q = torch.empty(B, tail, E, dtype=x.dtype, device=x.device)
+        k, v = torch.empty(B, L, E, dtype=x.dtype, device=x.device), torch.empty(B, L, E, dtype=x.dtype, device=x.device)
+        native.rows_proj_rope_forward(kind, tables, index, x, [wq.detach(), wk.detach(), wv.detach()],
+                                      [bq.detach(), bk.detach(), bv.detach()], [tail, L, L], [q, k, v])
+        ctx.save_for_backward(x, index)
+        ctx.tail, ctx.kind, ctx.tables, ctx.params = tail, kind, tables, (wq, bq, wk, bk, wv, bv)
+        return q, k, v
+
+    @staticmethod
+    def backward(ctx, gq, gk, gv):
+        from asac_amd import native
+        x, index = ctx.saved_tensors
+        B, L, E = x.shape
+        wq, bq, wk, bk, wv, bv = ctx.params
+        grads = [g.contiguous() for g in (gq, gk, gv)]
+        plain = [torch.empty_like(grads[0]), torch.empty_like(grads[1])]
+        gx = torch.empty(B, L, E, dtype=x.dtype, device=x.device)
+        native.rows_proj_rope_backward(ctx.kind, ctx.tables, index, grads, [ctx.tail, L, L],
+                                       [wq.detach(), wk.detach(), wv.detach()], gx, plain)
+        x2 = x.reshape(-1, E)
+        xq2 = x2 if ctx.tail == L else x[:, -ctx.tail:].reshape(-1, E)
+        out = [gx if ctx.needs_input_grad[0] else None, None, None, None, None]
+        for j, (g, xin) in enumerate(zip((*plain, grads[2]), (xq2, x2, x2))):
+            out.extend(_rows_param_grads(ctx.needs_input_grad[5 + 2 * j:7 + 2 * j], ctx.params[2 * j:2 * j + 2],
+                                         g.view(-1, E), xin))
+        return tuple(out)
+
+
+class _RopeFn(torch.autograd.Function):
+    """`self.rope(q_index, k_index, q, k)` as one launch per pass for both tensors (`asac_rope_*`, csrc/rope.hip)"""
+
+    @staticmethod
+    def forward(ctx, q, k, q_index, k_index, kind, tables):
+        from asac_amd import native
+        q, k = (t if t.stride(2) == 1 else t.contiguous() for t in (q, k))
+        out_q, out_k = torch.empty(q.shape, dtype=q.dtype, device=q.device), torch.empty(k.shape, dtype=k.dtype, device=k.device)
+        native.rope_forward(kind, tables, q, k, q_index, k_index, out_q, out_k)
+        ctx.save_for_backward(q_index, k_index)
+        ctx.kind, ctx.tables = kind, tables
+        return out_q, out_k
+
+    @staticmethod
+    def backward(ctx, gq, gk):
+        from asac_amd import native
+        q_index, k_index = ctx.saved_tensors
+        gq, gk = (g if g.stride(2) == 1 else g.contiguous() for g in (gq, gk))
+        out_q, out_k = torch.empty(gq.shape, dtype=gq.dtype, device=gq.device), torch.empty(gk.shape, dtype=gk.dtype, device=gk.device)
+        native.rope_backward(ctx.kind, ctx.tables, gq, gk, q_index, k_index, out_q, out_k)
+        return out_q, out_k, None, None, None, None
+
+
+def _fused_rope_tables(module, query, key, query_index, key_index):
+    """the tables `_RopeFn` / `_QkvRopeRowsFn` read for the rotary encoding of `module`, or None: `self.rope` runs as module
+    code (CPU, other dtypes, odd widths, tables that are not contiguous f32 / complex64 buffers on the tensors' device, indexes
+    that are not int32 / int64 [batch, len] there, a subclassed rope module)"""
+    rope, E = module.rope, module.embed_dim
+    if not (FUSED_ROPE and query.is_cuda and key.is_cuda and query.dtype == key.dtype == torch.float32
+            and query.dim() == key.dim() == 3 and E % 2 == 0):
+        return None
+    for index, t in ((query_index, query), (key_index, key)):
+        if not (index.device == t.device and index.dtype in (torch.int32, torch.int64) and index.dtype == key_index.dtype
+                and index.shape == t.shape[:2]):
+            return None
+    if type(rope) is RotaryPositionalEncoding:
+        tables = (rope.freqs_cis,)
+        if rope.freqs_cis.dtype != torch.complex64 or rope.freqs_cis.dim() != 2 or rope.freqs_cis.shape[1] != E // 2:
+            return None
+    elif type(rope) is RotaryPositionalEncoding2:
+        tables = (rope.cos_cached, rope.sin_cached)
+        if any(t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != E for t in tables) or rope.d_model != E \
+                or rope.cos_cached.shape != rope.sin_cached.shape:
+            return None
+    else:
+        return None
+    if not all(t.device == key.device and t.is_contiguous() and t.data_ptr() % 16 == 0 for t in tables):
+        return None
+    from asac_amd import native
+    if not native.rope_supported(module.pe.value, E):
+        return None
+    return (torch.view_as_real(tables[0]),) if len(tables) == 1 else tables
+
+
+def _is_index_tail(query_index, key_index):
+    """query_index is `key_index[:, -q:]` (the 2-D sibling of `_is_tail_view`): one index array serves the projection launch"""
+    q = query_index.shape[1]
+    return (query_index.dim() == key_index.dim() == 2 and q <= key_index.shape[1] and query_index.shape[0] == key_index.shape[0]
+            and query_index.dtype == key_index.dtype and query_index.stride() == key_index.stride()
+            and query_index.untyped_storage().data_ptr() == key_index.untyped_storage().data_ptr()
+            and query_index.storage_offset() == key_index.storage_offset() + (key_index.shape[1] - q) * key_index.stride(1))
 
 
 class _QkvAttnMhFn(torch.autograd.Function):
@@ -812,6 +918,7 @@ class MultiheadAttention(nn.Module):
         if attn_mask is not None:
             assert attn_mask.dim() in (2, 3)
 
+        own_index = query_index is None and key_index is None
         if self.pe:       # (None and False both mean no positional encoding)
             if query_index is None:
                 query_index = torch.arange(q_len, device=query.device).unsqueeze(0).expand(bsz, -1)
@@ -858,10 +965,20 @@ class MultiheadAttention(nn.Module):
                 return out.reshape(*lead, *out.shape[1:]), weights.reshape(*lead, *weights.shape[1:])
 
         fused_qkv = None
-        if (self.pe is None or self.pe is False) and same_kv and _rows_proj_ok(self, query, key):
+        rotary = self.pe in (POSITIONAL_ENCODING.ROPE, POSITIONAL_ENCODING.ROPE2)
+        rope_tables = _fused_rope_tables(self, query, key, query_index, key_index) if rotary else None
+        if (self.pe is None or self.pe is False or rope_tables is not None) and same_kv and _rows_proj_ok(self, query, key):
             qkv_params = [t for ll in (self.q_proj, self.k_proj, self.v_proj) for t in (_plain_linear(ll).weight, _plain_linear(ll).bias)]
             from asac_amd import native
-            if (FUSED_MULTIHEAD and FUSED_QKV_IN_CORE and (self.num_heads > 1 or self.head_dim > 16)
+            if rotary:
+                # (without indexes the query's positions count from 0: the key's newest entries only when the lengths agree)
+                if (own_index and q_len == k_len) or query_index is key_index or _is_index_tail(query_index, key_index):
+                    # projections and rotation: one launch per pass (csrc/rows_proj.hip)
+                    q, k, v = _QkvRopeRowsFn.apply(key, q_len, key_index, self.pe.value, rope_tables, *qkv_params)
+                    rotary = False
+                else:
+                    q, k, v = _QkvRowsFn.apply(key, q_len, *qkv_params)
+            elif (FUSED_MULTIHEAD and FUSED_QKV_IN_CORE and (self.num_heads > 1 or self.head_dim > 16)
                     and not (self.training and self.dropout > 0.)
                     and native.attention_mh_proj_supported(q_len, k_len, self.num_heads, self.head_dim)):
                 fused_qkv = qkv_params      # windows of <= 16 positions: the projections run inside the core's forward launch
@@ -870,7 +987,9 @@ class MultiheadAttention(nn.Module):
                 q, k, v = _QkvRowsFn.apply(key, q_len, *qkv_params)
         else:
             q, k, v = self.q_proj(query), self.k_proj(key), self.v_proj(value)
-        if self.pe in (POSITIONAL_ENCODING.ROPE, POSITIONAL_ENCODING.ROPE2):
+        if rotary and rope_tables is not None:
+            q, k = _RopeFn.apply(q, k, query_index, key_index, self.pe.value, rope_tables)      # one launch per pass (csrc/rope.hip)
+        elif rotary:
             q, k = self.rope(query_index, key_index, q, k)
         if (FUSED_MULTIHEAD and (self.num_heads > 1 or self.head_dim > 16) and q.is_cuda and q.dtype == torch.float32
                 and not (self.training and self.dropout > 0.)):

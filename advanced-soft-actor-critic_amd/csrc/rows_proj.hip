@@ -6,7 +6,10 @@
 //     backward: the input gradient of the three as one launch (three GEMMs and two accumulations);
 //   * the output ResBlock  y = (x + gelu(x W^T + b)) * row_scale  (LinearLayers(E, E, depth 1) + the dead-row / padded-row
 //     factor: a GEMM and three elementwise launches), backward to grad_x and the pre-activation gradient (whose products
-//     over the rows — weight and bias gradients — are csrc/xty.hip's).
+//     over the rows — weight and bias gradients — are csrc/xty.hip's);
+//   * with a rotary position encoding (ROPE / ROPE2: `self.rope(query_index, key_index, q, k)` behind the projections), the
+//     rotation of q and k as the epilogue of the projection launch and the un-rotation of their gradients as the prologue of
+//     its backward (arithmetic: asac_rope.h — the bits of csrc/rope.hip behind / in front of the plain launches).
 //
 // A workgroup (4 waves) owns 16 rows; wave w the output feature tiles w, w + 4, ...  The ROWS are the N dimension of the
 // MFMA (B operand = 16 bytes of a row's features, as they lie in memory), the weights the A operand: forward a weight row's
@@ -14,6 +17,7 @@
 // lane -> 16-byte stores.  Everything is L2-resident (weights 16 KB a matrix); the launches are latency, not bandwidth.
 #include "asac_common.h"
 #include "asac_gelu.h"
+#include "asac_rope.h"
 
 namespace asac {
 namespace rowsp {
@@ -43,6 +47,10 @@ struct ProjArgs {
     float* y[kMaxJobs];
     const float* g[kMaxJobs];                // backward: gradients of y
     float* gx;                               // [B][L][E] dense
+    // rotary kinds: jobs 0 and 1 (q, k) are rotated by the table row of ONE index array [B][L] (the query's: its newest entries)
+    rope::Tables tab;
+    rope::Index ix;
+    float* gu[2];                            // backward: the un-rotated gradients of jobs 0 and 1, dense like g
 };
 
 struct ResArgs {
@@ -63,9 +71,12 @@ __device__ __forceinline__ f32x4 wcol4(const float* w, int n0, int k) {
     return v;
 }
 
-template <int EC>
+// KIND 0: the projections.  KIND ROPE: the lane's four consecutive features are two of the encoding's pairs.  KIND ROPE2: a wave
+// takes the n-tiles nt and nt + EC / 2 together, so feature j and its partner j + E / 2 are in the same lane.
+template <int EC, int KIND>
 __global__ void __launch_bounds__(kThreads) k_rows_proj_fwd(const ProjArgs a) {
     constexpr int E = 16 * EC;
+    constexpr int NP = KIND == rope::kRope2 ? 2 : 1, NT = EC / NP;
     const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, q = l >> 4, x = l & 15;
     const int64_t rows = (int64_t)a.B * a.L, row = (int64_t)blockIdx.x * 16 + x;
     const bool live = row < rows;
@@ -75,29 +86,56 @@ __global__ void __launch_bounds__(kThreads) k_rows_proj_fwd(const ProjArgs a) {
     f32x4 xv[EC];
 #pragma unroll
     for (int c = 0; c < EC; ++c) xv[c] = live ? ld4(xp + 16 * c) : zero4();
+    const int64_t tr = KIND ? rope::table_row(a.ix, b, t, a.tab.T) * E + 4 * q : 0;
     // one job per workgroup (blockIdx.y): the launch is a dependent chain per wave (rows -> weights -> products -> store), not
     // bandwidth — three times the waves, a third of the chain each (10 -> 6 us at 9 216 rows x 64)
-    for (int nt = wv; nt < EC; nt += kWaves) {
+    for (int nt = wv; nt < NT; nt += kWaves) {
 #pragma unroll
         for (int j = 0; j < kMaxJobs; ++j) {
             if (j != (int)blockIdx.y) continue;
-            const float* wp = a.w[j] + (16 * nt + x) * E + 4 * q;
-            f32x4 wa[EC];
+            f32x4 acc[NP];
 #pragma unroll
-            for (int c = 0; c < EC; ++c) wa[c] = ld4(wp + 16 * c);
-            const f32x4 bias = ld4(a.b[j] + 16 * nt + 4 * q);
-            f32x4 acc = zero4();
+            for (int h = 0; h < NP; ++h) {
+                const int n = nt + h * NT;
+                const float* wp = a.w[j] + (16 * n + x) * E + 4 * q;
+                f32x4 wa[EC];
 #pragma unroll
-            for (int c = 0; c < EC; ++c) acc = mfma4(wa[c], xv[c], acc);      // acc[r] = y[row x][16 nt + 4 q + r]
-            acc += bias;
+                for (int c = 0; c < EC; ++c) wa[c] = ld4(wp + 16 * c);
+                const f32x4 bias = ld4(a.b[j] + 16 * n + 4 * q);
+                acc[h] = zero4();
+#pragma unroll
+                for (int c = 0; c < EC; ++c) acc[h] = mfma4(wa[c], xv[c], acc[h]);      // acc[r] = y[row x][16 n + 4 q + r]
+                acc[h] += bias;
+            }
+            if (KIND == rope::kRope && j < 2) {
+                const f32x4 cs = ld4(a.tab.t0 + tr + 16 * nt), v = acc[0];      // (c, s) of the pairs 8 nt + 2 q, + 1
+                float y0, y1, y2, y3;
+                rope::pair_fwd(v[0], v[1], cs[0], cs[1], y0, y1);
+                rope::pair_fwd(v[2], v[3], cs[2], cs[3], y2, y3);
+                acc[0] = (f32x4){y0, y1, y2, y3};
+            }
+            if (KIND == rope::kRope2 && j < 2) {
+                const f32x4 cl = ld4(a.tab.t0 + tr + 16 * nt), sl = ld4(a.tab.t1 + tr + 16 * nt);
+                const f32x4 ch = ld4(a.tab.t0 + tr + 16 * nt + E / 2), sh = ld4(a.tab.t1 + tr + 16 * nt + E / 2);
+                const f32x4 vl = acc[0], vh = acc[NP - 1];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float yl, yh;
+                    rope::half_fwd(vl[r], vh[r], cl[r], sl[r], ch[r], sh[r], yl, yh);
+                    acc[0][r] = yl, acc[NP - 1][r] = yh;
+                }
+            }
             const int skip = a.L - a.tail[j];
-            if (live && t >= skip) st4(a.y[j] + ((int64_t)b * a.tail[j] + (t - skip)) * E + 16 * nt + 4 * q, acc);
+#pragma unroll
+            for (int h = 0; h < NP; ++h)
+                if (live && t >= skip) st4(a.y[j] + ((int64_t)b * a.tail[j] + (t - skip)) * E + 16 * (nt + h * NT) + 4 * q, acc[h]);
         }
     }
 }
 
 // gx[row][k] = sum_j sum_n g_j[row][n] W_j[n][k]   (jobs in order, features in order)
-template <int EC>
+// (rotary KIND: the gradients of jobs 0 and 1 are un-rotated as they are loaded and written to gu, one wave per tile)
+template <int EC, int KIND>
 __global__ void __launch_bounds__(kThreads) k_rows_proj_bwd(const ProjArgs a) {
     constexpr int E = 16 * EC;
     const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, q = l >> 4, x = l & 15;
@@ -105,15 +143,45 @@ __global__ void __launch_bounds__(kThreads) k_rows_proj_bwd(const ProjArgs a) {
     const bool live = row < rows;
     const int64_t rc = live ? row : rows - 1;
     const int b = (int)(rc / a.L), t = (int)(rc - (int64_t)b * a.L);
+    const int64_t tr = KIND ? rope::table_row(a.ix, b, t, a.tab.T) * E + 4 * q : 0;
     f32x4 gv[kMaxJobs][EC];
 #pragma unroll
     for (int j = 0; j < kMaxJobs; ++j) {
         if (j >= a.J) continue;
         const int skip = a.L - a.tail[j];
         const bool on = live && t >= skip;
-        const float* gp = a.g[j] + ((int64_t)b * a.tail[j] + (on ? t - skip : 0)) * E + 4 * q;
+        const int64_t at = ((int64_t)b * a.tail[j] + (on ? t - skip : 0)) * E + 4 * q;
+        const float* gp = a.g[j] + at;
 #pragma unroll
         for (int c = 0; c < EC; ++c) gv[j][c] = on ? ld4(gp + 16 * c) : zero4();
+        if (KIND && j < 2) {
+            if (KIND == rope::kRope) {
+#pragma unroll
+                for (int c = 0; c < EC; ++c) {
+                    const f32x4 cs = ld4(a.tab.t0 + tr + 16 * c), v = gv[j][c];
+                    float y0, y1, y2, y3;
+                    rope::pair_bwd(v[0], v[1], cs[0], cs[1], y0, y1);
+                    rope::pair_bwd(v[2], v[3], cs[2], cs[3], y2, y3);
+                    gv[j][c] = (f32x4){y0, y1, y2, y3};
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < EC / 2; ++c) {
+                    const f32x4 cl = ld4(a.tab.t0 + tr + 16 * c), sl = ld4(a.tab.t1 + tr + 16 * c);
+                    const f32x4 ch = ld4(a.tab.t0 + tr + 16 * c + E / 2), sh = ld4(a.tab.t1 + tr + 16 * c + E / 2);
+                    const f32x4 vl = gv[j][c], vh = gv[j][c + EC / 2];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float yl, yh;
+                        rope::half_bwd(vl[r], vh[r], cl[r], sl[r], ch[r], sh[r], yl, yh);
+                        gv[j][c][r] = yl, gv[j][c + EC / 2][r] = yh;
+                    }
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < EC; ++c)
+                if (on && (c & (kWaves - 1)) == wv) st4(a.gu[j] + at + 16 * c, gv[j][c]);
+        }
     }
     for (int kt = wv; kt < EC; kt += kWaves) {
         f32x4 acc = zero4();
@@ -266,6 +334,64 @@ using namespace asac::rowsp;
         else ASAC_LAUNCH(kernel<8>, grid, dim3(kThreads), 0, stream, args);                         \
     } while (0)
 
+#define RP_LAUNCH_KIND(kernel, KIND, E, grid, stream, args)                                         \
+    do {                                                                                            \
+        if ((E) == 32) ASAC_LAUNCH((kernel<2, KIND>), grid, dim3(kThreads), 0, stream, args);       \
+        else if ((E) == 64) ASAC_LAUNCH((kernel<4, KIND>), grid, dim3(kThreads), 0, stream, args);  \
+        else ASAC_LAUNCH((kernel<8, KIND>), grid, dim3(kThreads), 0, stream, args);                 \
+    } while (0)
+
+// the checks and the launch of the projections' forward, plain (kind 0) or with the rotation behind jobs 0 and 1
+static int proj_forward(const char* what, int kind, const ProjArgs& rot, const float* x, int64_t x_stride_b, int64_t x_stride_t,
+                        int batch, int window, int width, int n_jobs, const float* const* weights, const float* const* biases,
+                        const int* tails, float* const* outs, void* stream) {
+    if (!x || !weights || !biases || !tails || !outs || batch <= 0 || window <= 0 || !width_ok(width) || n_jobs < 1 ||
+        n_jobs > kMaxJobs || !aligned16(x) || (x_stride_b & 3) || (x_stride_t & 3) || x_stride_t < width)
+        return bad_arg(what);
+    ProjArgs a = rot;
+    a.x = x, a.xs_b = x_stride_b, a.xs_t = x_stride_t, a.B = batch, a.L = window, a.J = n_jobs;
+    for (int j = 0; j < n_jobs; ++j) {
+        if (!weights[j] || !biases[j] || !outs[j] || tails[j] < 1 || tails[j] > window || !aligned16(weights[j]) ||
+            !aligned16(biases[j]) || !aligned16(outs[j]))
+            return bad_arg(what);
+        a.w[j] = weights[j], a.b[j] = biases[j], a.tail[j] = tails[j], a.y[j] = outs[j];
+    }
+    const dim3 grid((unsigned)(((int64_t)batch * window + 15) / 16), (unsigned)n_jobs);
+    if (kind == rope::kRope) RP_LAUNCH_KIND(k_rows_proj_fwd, rope::kRope, width, grid, as_stream(stream), a);
+    else if (kind == rope::kRope2) RP_LAUNCH_KIND(k_rows_proj_fwd, rope::kRope2, width, grid, as_stream(stream), a);
+    else RP_LAUNCH_KIND(k_rows_proj_fwd, 0, width, grid, as_stream(stream), a);
+    return finish_launch(what);
+}
+
+static int proj_backward(const char* what, int kind, const ProjArgs& rot, const float* const* grads, const int* tails, int n_jobs,
+                         const float* const* weights, int batch, int window, int width, float* grad_x, void* stream) {
+    if (!grads || !tails || !weights || !grad_x || batch <= 0 || window <= 0 || !width_ok(width) || n_jobs < 1 ||
+        n_jobs > kMaxJobs || !aligned16(grad_x))
+        return bad_arg(what);
+    ProjArgs a = rot;
+    a.B = batch, a.L = window, a.J = n_jobs, a.gx = grad_x;
+    for (int j = 0; j < n_jobs; ++j) {
+        if (!weights[j] || !grads[j] || tails[j] < 1 || tails[j] > window || !aligned16(grads[j])) return bad_arg(what);
+        a.w[j] = weights[j], a.g[j] = grads[j], a.tail[j] = tails[j];
+    }
+    const dim3 grid((unsigned)(((int64_t)batch * window + 15) / 16));
+    if (kind == rope::kRope) RP_LAUNCH_KIND(k_rows_proj_bwd, rope::kRope, width, grid, as_stream(stream), a);
+    else if (kind == rope::kRope2) RP_LAUNCH_KIND(k_rows_proj_bwd, rope::kRope2, width, grid, as_stream(stream), a);
+    else RP_LAUNCH_KIND(k_rows_proj_bwd, 0, width, grid, as_stream(stream), a);
+    return finish_launch(what);
+}
+
+// the rotary operands both passes share: the kind's tables (read as 16-byte vectors) and the index array
+static bool rope_operands(ProjArgs& a, int kind, const float* table0, const float* table1, int table_rows, const void* index,
+                          int64_t index_stride_b, int64_t index_stride_t, int index_bytes) {
+    if (!rope::kind_ok(kind) || !table0 || !aligned16(table0) || (kind == rope::kRope2 && (!table1 || !aligned16(table1))) ||
+        table_rows < 1 || !index || (index_bytes != 4 && index_bytes != 8) || index_stride_b < 0 || index_stride_t < 0)
+        return false;
+    a.tab = rope::Tables{table0, table1, table_rows};
+    a.ix = rope::Index{index, index_stride_b, index_stride_t, index_bytes};
+    return true;
+}
+
 extern "C" {
 
 int asac_rows_proj_supported(int width) { return width_ok(width); }
@@ -273,37 +399,40 @@ int asac_rows_proj_supported(int width) { return width_ok(width); }
 int asac_rows_proj_forward(const float* x, int64_t x_stride_b, int64_t x_stride_t, int batch, int window, int width, int n_jobs,
                            const float* const* weights, const float* const* biases, const int* tails, float* const* outs,
                            void* stream) {
-    if (!x || !weights || !biases || !tails || !outs || batch <= 0 || window <= 0 || !width_ok(width) || n_jobs < 1 ||
-        n_jobs > kMaxJobs || !aligned16(x) || (x_stride_b & 3) || (x_stride_t & 3) || x_stride_t < width)
-        return bad_arg("asac_rows_proj_forward");
-    ProjArgs a{};
-    a.x = x, a.xs_b = x_stride_b, a.xs_t = x_stride_t, a.B = batch, a.L = window, a.J = n_jobs;
-    for (int j = 0; j < n_jobs; ++j) {
-        if (!weights[j] || !biases[j] || !outs[j] || tails[j] < 1 || tails[j] > window || !aligned16(weights[j]) ||
-            !aligned16(biases[j]) || !aligned16(outs[j]))
-            return bad_arg("asac_rows_proj_forward: job");
-        a.w[j] = weights[j], a.b[j] = biases[j], a.tail[j] = tails[j], a.y[j] = outs[j];
-    }
-    const dim3 grid((unsigned)(((int64_t)batch * window + 15) / 16), (unsigned)n_jobs);
-    RP_LAUNCH(k_rows_proj_fwd, width, grid, as_stream(stream), a);
-    return finish_launch("asac_rows_proj_forward");
+    return proj_forward("asac_rows_proj_forward", 0, ProjArgs{}, x, x_stride_b, x_stride_t, batch, window, width, n_jobs, weights,
+                        biases, tails, outs, stream);
 }
 
 int asac_rows_proj_backward(const float* const* grads, const int* tails, int n_jobs, const float* const* weights, int batch,
                             int window, int width, float* grad_x, void* stream) {
-    if (!grads || !tails || !weights || !grad_x || batch <= 0 || window <= 0 || !width_ok(width) || n_jobs < 1 ||
-        n_jobs > kMaxJobs || !aligned16(grad_x))
-        return bad_arg("asac_rows_proj_backward");
-    ProjArgs a{};
-    a.B = batch, a.L = window, a.J = n_jobs, a.gx = grad_x;
-    for (int j = 0; j < n_jobs; ++j) {
-        if (!weights[j] || !grads[j] || tails[j] < 1 || tails[j] > window || !aligned16(grads[j]))
-            return bad_arg("asac_rows_proj_backward: job");
-        a.w[j] = weights[j], a.g[j] = grads[j], a.tail[j] = tails[j];
-    }
-    const dim3 grid((unsigned)(((int64_t)batch * window + 15) / 16));
-    RP_LAUNCH(k_rows_proj_bwd, width, grid, as_stream(stream), a);
-    return finish_launch("asac_rows_proj_backward");
+    return proj_backward("asac_rows_proj_backward", 0, ProjArgs{}, grads, tails, n_jobs, weights, batch, window, width, grad_x,
+                         stream);
+}
+
+int asac_rows_proj_rope_forward(int kind, const float* table0, const float* table1, int table_rows, const void* index,
+                                int64_t index_stride_b, int64_t index_stride_t, int index_bytes, const float* x,
+                                int64_t x_stride_b, int64_t x_stride_t, int batch, int window, int width,
+                                const float* const* weights, const float* const* biases, const int* tails, float* const* outs,
+                                void* stream) {
+    ProjArgs rot{};
+    if (!rope_operands(rot, kind, table0, table1, table_rows, index, index_stride_b, index_stride_t, index_bytes))
+        return bad_arg("asac_rows_proj_rope_forward");
+    return proj_forward("asac_rows_proj_rope_forward", kind, rot, x, x_stride_b, x_stride_t, batch, window, width, kMaxJobs,
+                        weights, biases, tails, outs, stream);
+}
+
+int asac_rows_proj_rope_backward(int kind, const float* table0, const float* table1, int table_rows, const void* index,
+                                 int64_t index_stride_b, int64_t index_stride_t, int index_bytes, const float* const* grads,
+                                 const int* tails, const float* const* weights, int batch, int window, int width, float* grad_x,
+                                 float* const* grads_unrotated, void* stream) {
+    ProjArgs rot{};
+    if (!rope_operands(rot, kind, table0, table1, table_rows, index, index_stride_b, index_stride_t, index_bytes) ||
+        !grads_unrotated || !grads_unrotated[0] || !grads_unrotated[1] || !aligned16(grads_unrotated[0]) ||
+        !aligned16(grads_unrotated[1]))
+        return bad_arg("asac_rows_proj_rope_backward");
+    rot.gu[0] = grads_unrotated[0], rot.gu[1] = grads_unrotated[1];
+    return proj_backward("asac_rows_proj_rope_backward", kind, rot, grads, tails, kMaxJobs, weights, batch, window, width, grad_x,
+                         stream);
 }
 
 int asac_rows_resblock_forward(const float* x, int64_t x_row_stride, const float* weight, const float* bias,

@@ -14,7 +14,7 @@ PKG_DIR = Path(__file__).resolve().parent
 import os as _os
 
 LIB_PATH = Path(_os.environ.get('ASAC_HIP_LIB', PKG_DIR / 'lib' / 'libasac_hip.so'))   # env override: debugging builds
-ABI_VERSION = 86
+ABI_VERSION = 87
 
 MAX_GATHER_KEYS = 16
 PAD_KEEP, PAD_WORD, PAD_BYTE, PAD_ROW, PAD_EMIT_MASK = 0, 1, 2, 3, 4
@@ -434,6 +434,21 @@ _SIGNATURES = {
     'asac_rows_gate_backward': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                           C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
+    'asac_rope_supported': (C.c_int, [C.c_int, C.c_int]),
+    'asac_rope_forward': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                    C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                    C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_rope_backward': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                     C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_rows_proj_rope_forward': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
+                                              C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_rows_proj_rope_backward': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
     'asac_rows_affine_supported': (C.c_int, [C.c_int, C.c_int]),
     'asac_rows_affine_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
                                            C.c_void_p]),
@@ -2330,6 +2345,92 @@ def rows_gate_backward(kind, grad_out, x, y, row_zero, weights, saved, grad_x, g
                                           _ptr_array(saved) if saved else None, _p(grad_x), _p(grad_y),
                                           _ptr_array(grad_pre) if grad_pre else None, _p(rx), _stream()),
            'asac_rows_gate_backward')
+
+
+# ------------------------------------------------------------------------------------------------
+# rotary position encodings: on their own (csrc/rope.hip) and behind the q / k / v projections (csrc/rows_proj.hip)
+# ------------------------------------------------------------------------------------------------
+ROPE, ROPE2 = 3, 4      # (the values of seq_layers.POSITIONAL_ENCODING)
+
+
+def rope_supported(kind, width) -> bool:
+    return bool(load().asac_rope_supported(int(kind), int(width)))
+
+
+def _rope_tables(kind, tables, E):
+    """(table0, table1, T): ROPE `view_as_real(freqs_cis)` [T][E/2][2]; ROPE2 (`cos_cached`, `sin_cached`) [T][E] each"""
+    t0, t1 = tables if kind == ROPE2 else (tables[0], None)
+    _dense_f32(t0, t1)
+    assert t0.shape[1:] == ((E // 2, 2) if kind == ROPE else (E,)) and (t1 is None or t1.shape == t0.shape)
+    return t0, t1, t0.shape[0]
+
+
+def _rope_index(index, B, L):
+    assert index.is_cuda and index.dtype in (torch.int32, torch.int64) and index.shape == (B, L)
+    return _p(index), index.stride(0), index.stride(1)
+
+
+def _rope_launch(fn, what, kind, tables, q, k, q_index, k_index, out_q, out_k):
+    B, Lq, E = q.shape
+    Lk = k.shape[1]
+    assert k.shape == (B, Lk, E) and q.stride(2) == 1 and k.stride(2) == 1 and q.dtype == k.dtype == torch.float32
+    assert q_index.dtype == k_index.dtype and out_q.shape == (B, Lq, E) and out_k.shape == (B, Lk, E)
+    _dense_f32(out_q, out_k)
+    t0, t1, T = _rope_tables(kind, tables, E)
+    _check(fn(int(kind), _p(t0), _p(t1), T, E, B, _p(q), q.stride(0), q.stride(1), Lq, *_rope_index(q_index, B, Lq),
+              _p(k), k.stride(0), k.stride(1), Lk, *_rope_index(k_index, B, Lk), q_index.element_size(), _p(out_q), _p(out_k),
+              _stream()), what)
+
+
+@_profiled
+def rope_forward(kind, tables, q, k, q_index, k_index, out_q, out_k):
+    """out_q, out_k (dense) = q [B][Lq][E], k [B][Lk][E] (feature stride 1) rotated by the table rows of their int32 / int64
+    indexes [B][L] (any strides; negative: from the table's end), one launch; kind ROPE / ROPE2, `tables` as `_rope_tables`"""
+    _rope_launch(load().asac_rope_forward, 'asac_rope_forward', kind, tables, q, k, q_index, k_index, out_q, out_k)
+
+
+@_profiled
+def rope_backward(kind, tables, grad_q, grad_k, q_index, k_index, out_q, out_k):
+    """the transpose of `rope_forward`: the gradients of its outputs -> the gradients of its inputs, one launch"""
+    _rope_launch(load().asac_rope_backward, 'asac_rope_backward', kind, tables, grad_q, grad_k, q_index, k_index, out_q, out_k)
+
+
+@_profiled
+def rows_proj_rope_forward(kind, tables, index, x, weights, biases, tails, outs):
+    """`rows_proj_forward` for the jobs q, k, v with q and k rotated behind it in the same launch; the table row of a position
+    comes from `index` [B][L] (the key's: the query's indexes are its newest tails[0] entries).  Same bits as
+    `rows_proj_forward` + `rope_forward`"""
+    global _last_work
+    B, L, E = x.shape
+    assert x.stride(2) == 1 and len(weights) == len(biases) == len(tails) == len(outs) == 3
+    _dense_f32(*weights, *biases, *outs)
+    for o, n in zip(outs, tails):
+        assert o.shape == (B, n, E)
+    t0, t1, T = _rope_tables(kind, tables, E)
+    _last_work = 2.0 * B * sum(tails) * E * E
+    _check(load().asac_rows_proj_rope_forward(int(kind), _p(t0), _p(t1), T, *_rope_index(index, B, L), index.element_size(), _p(x),
+                                              x.stride(0), x.stride(1), B, L, E, _ptr_array(weights), _ptr_array(biases),
+                                              (C.c_int * 3)(*tails), _ptr_array(outs), _stream()), 'asac_rows_proj_rope_forward')
+
+
+@_profiled
+def rows_proj_rope_backward(kind, tables, index, grads, tails, weights, grad_x, grads_unrotated):
+    """`rows_proj_backward` of the gradients of the ROTATED q, k and of v: the first two are un-rotated on the way in and written
+    to `grads_unrotated` (two dense buffers: the operands of the parameter gradients).  Same bits as `rope_backward` +
+    `rows_proj_backward`"""
+    global _last_work
+    B, L, E = grad_x.shape
+    assert len(grads) == len(tails) == len(weights) == 3 and len(grads_unrotated) == 2
+    _dense_f32(*grads, *weights, grad_x, *grads_unrotated)
+    for g, n in zip(grads, tails):
+        assert g.shape == (B, n, E)
+    for u, g in zip(grads_unrotated, grads):
+        assert u.shape == g.shape
+    t0, t1, T = _rope_tables(kind, tables, E)
+    _last_work = 2.0 * B * sum(tails) * E * E
+    _check(load().asac_rows_proj_rope_backward(int(kind), _p(t0), _p(t1), T, *_rope_index(index, B, L), index.element_size(),
+                                               _ptr_array(grads), (C.c_int * 3)(*tails), _ptr_array(weights), B, L, E,
+                                               _p(grad_x), _ptr_array(grads_unrotated), _stream()), 'asac_rows_proj_rope_backward')
 
 
 # ------------------------------------------------------------------------------------------------

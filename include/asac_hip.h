@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ASAC_ABI_VERSION 86
+#define ASAC_ABI_VERSION 87
 #define ASAC_MAX_GATHER_KEYS 16
 #define ASAC_MAX_ENSEMBLE 16
 #define ASAC_MAX_ACTION 64
@@ -1026,6 +1026,54 @@ int asac_rows_gate_backward(int kind, const float* grad_out, const float* x, int
                             const float* y, const uint8_t* row_zero, int64_t row_zero_stride_b, int batch, int window, int width,
                             const float* const* weights, const float* const* saved, float* grad_x, float* grad_y,
                             float* const* grad_pre, float* rx, void* stream);
+/* The rotary position encodings of `MultiheadAttention.forward` (nn_models/layers/seq_layers.py:239-333:
+ * `q, k = self.rope(query_index, key_index, q, k)` with `RotaryPositionalEncoding` / `RotaryPositionalEncoding2`, 140-215), one
+ * launch per pass — on their own (csrc/rope.hip) or as the epilogue of the q / k / v projection launch (csrc/rows_proj.hip).
+ * kind = 3 ROPE, 4 ROPE2 (the values of `POSITIONAL_ENCODING`).  The tables are the module's own buffers, table_rows = T rows;
+ * no sine or cosine is computed on the device:
+ *   ROPE   table0 = `freqs_cis` (complex64 [T][E/2]) read as floats [T][E/2][2] = (c, s); table1 ignored
+ *   ROPE2  table0 = `cos_cached`, table1 = `sin_cached`, float [T][E]
+ * Indexes: int32 or int64 (index_bytes = 4 / 8) arrays [batch][positions] with their own strides in ELEMENTS (a batch stride of
+ * 0: one row of positions for every batch entry).  Index i reads table row i, i < 0 row i + T (the module's `table[i]`: the
+ * episode block's -1 reads row T - 1); an index outside [-T, T) is clamped into the table, the values of such rows are
+ * unspecified.  With c, s the values of the row at column i (ROPE) or cos / sin at the row's column j (ROPE2, h = E / 2):
+ *   forward   ROPE   y[2i] = x[2i] c - x[2i+1] s;  y[2i+1] = x[2i] s + x[2i+1] c
+ *             ROPE2  y[j] = x[j] cos[j] + (-x[j+h]) sin[j]  (j < h);  y[j] = x[j] cos[j] + x[j-h] sin[j]  (j >= h)
+ *   backward  ROPE   gx[2i] = g[2i] c + g[2i+1] s;  gx[2i+1] = g[2i+1] c - g[2i] s
+ *             ROPE2  gx[j] = g[j] cos[j] + g[j+h] sin[j+h]  (j < h);  gx[j] = g[j] cos[j] - g[j-h] sin[j-h]  (j >= h)
+ * every result two products and one sum in that order, no contraction: both forms give the same bits.
+ *
+ * asac_rope_forward: q [batch][q_len][E] and k [batch][k_len][E] (f32, feature stride 1, batch / position strides in floats, no
+ * alignment asked) with an index array each -> out_q, out_k dense; width = E any even number (asac_rope_supported).
+ * asac_rope_backward: the same operands with the gradients of out_q / out_k in place of q / k -> the gradients of q / k, dense.
+ * asac_rows_proj_rope_forward: asac_rows_proj_forward for the three jobs q, k, v (tails[0] = the query's newest positions) with
+ * the rotation behind jobs 0 and 1; the table row of BOTH comes from ONE index array [batch][window] (the query's indexes are its
+ * newest tails[0] entries); job 2 (v) is untouched.  width in {32, 64, 128}, the tables 16-byte aligned as every other pointer.
+ * Same bits as asac_rows_proj_forward followed by asac_rope_forward.
+ * asac_rows_proj_rope_backward: grads = the gradients of the rotated q, k and of v; the first two are un-rotated as they are
+ * loaded and written to grads_unrotated[0], [1] (HOST array of two dense device buffers shaped like grads[0], grads[1]: with
+ * grads[2] and x the operands of the parameter gradients, asac_xty); grad_x as asac_rows_proj_backward forms it from the
+ * un-rotated gradients, same summation order. */
+int asac_rope_supported(int kind, int width);
+int asac_rope_forward(int kind, const float* table0, const float* table1, int table_rows, int width, int batch, const float* q,
+                      int64_t q_stride_b, int64_t q_stride_t, int q_len, const void* q_index, int64_t q_index_stride_b,
+                      int64_t q_index_stride_t, const float* k, int64_t k_stride_b, int64_t k_stride_t, int k_len,
+                      const void* k_index, int64_t k_index_stride_b, int64_t k_index_stride_t, int index_bytes, float* out_q,
+                      float* out_k, void* stream);
+int asac_rope_backward(int kind, const float* table0, const float* table1, int table_rows, int width, int batch,
+                       const float* grad_q, int64_t grad_q_stride_b, int64_t grad_q_stride_t, int q_len, const void* q_index,
+                       int64_t q_index_stride_b, int64_t q_index_stride_t, const float* grad_k, int64_t grad_k_stride_b,
+                       int64_t grad_k_stride_t, int k_len, const void* k_index, int64_t k_index_stride_b, int64_t k_index_stride_t,
+                       int index_bytes, float* out_q, float* out_k, void* stream);
+int asac_rows_proj_rope_forward(int kind, const float* table0, const float* table1, int table_rows, const void* index,
+                                int64_t index_stride_b, int64_t index_stride_t, int index_bytes, const float* x,
+                                int64_t x_stride_b, int64_t x_stride_t, int batch, int window, int width,
+                                const float* const* weights, const float* const* biases, const int* tails, float* const* outs,
+                                void* stream);
+int asac_rows_proj_rope_backward(int kind, const float* table0, const float* table1, int table_rows, const void* index,
+                                 int64_t index_stride_b, int64_t index_stride_t, int index_bytes, const float* const* grads,
+                                 const int* tails, const float* const* weights, int batch, int window, int width, float* grad_x,
+                                 float* const* grads_unrotated, void* stream);
 /* y [rows][N] = x [rows][K] weight[N][K]^T + bias[N] for a narrow input (K <= 64) and a wide output (N a multiple of 16, <= 1024):
  * the input products `x W_ih^T + b_ih` of every step in front of a recurrence (reference seq_layers.py:14-114 through nn.GRU;
  * observation ++ action -> 3 x hidden); x with a row stride in floats, y dense and 16-byte aligned. */

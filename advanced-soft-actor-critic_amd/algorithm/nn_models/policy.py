@@ -126,6 +126,12 @@ class ModelPolicy(ModelBasePolicy):
         h = self.c_dense(self.dense(state))
         return self.mean_dense(h), self.logstd_dense(h)
 
+    def d_head_raw(self, state):
+        """the discrete branches' head outputs, concatenated [.., D]: logits before `OneHotCategorical` normalises them;
+        the fused discrete kernels (`native.discrete_*`) form the branch softmax themselves."""
+        h = self.dense(state)
+        return torch.cat([head(h) for head in self.d_dense_list], dim=-1)
+
     def forward(self, state, obs_list):
         h = self.dense(state)
         d_policy = c_policy = None

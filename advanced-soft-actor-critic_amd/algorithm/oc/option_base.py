@@ -77,6 +77,9 @@ class OptionBase(SAC_Base):
         self.random_q = random_q
         _reject_unsupported(args, kwargs)
         super().__init__(*args, **kwargs)
+        # the option's discrete branches stay on the eager arithmetic (its own `_get_y` / `_get_td_error` mix the
+        # termination in; the parent's one-launch discrete path is the plain learner's)
+        self._fused_discrete = False
 
     # -- construction (option_base.py:27-86) ----------------------------------------------------------------------------
     def _sample_thread(self):

@@ -89,6 +89,19 @@ _GraphRun = namedtuple('_GraphRun', 'beside run')
 _Return = namedtuple('_Return', 'args keep')     # `SAC_Base._c_return`
 
 
+def fused_discrete_applies(*, enabled, plain_learner, d_action_sizes, c_action_size, discrete_dqn_like, offline_loss,
+                           siamese, use_prediction, data_parallel, float32_on_device, ensemble_q_num, n_step,
+                           batch_size) -> bool:
+    """Does a step of this configuration run the pure-discrete, policy-based learner's arithmetic on the
+    `asac_discrete_*` launches (`hip_config['fused_discrete']`)?  Only a plain `SAC_Base` step (`plain_learner`: not an
+    `OptionBase`) with discrete branches alone and a policy (no DQN-like target), without an offline loss, a siamese or a
+    prediction head or a data-parallel context, on float32 device tensors, within the entry points' size limits.
+    Everything else runs the eager code."""
+    return bool(enabled and plain_learner and len(d_action_sizes) > 0 and c_action_size == 0 and not discrete_dqn_like
+                and not offline_loss and not siamese and not use_prediction and not data_parallel and float32_on_device
+                and native.discrete_sizes_ok(d_action_sizes, ensemble_q_num, n_step, batch_size))
+
+
 class _Window:
     """views of the step's static batch tensors and what the phases of `_device_step_body` hand to each other"""
 
@@ -265,6 +278,7 @@ class SAC_Base(AuxHeadsMixin):
         self._deferred_cat = bool(hip_config.get('deferred_cat', True))
         self._rep_from_burn_in = bool(hip_config.get('rep_from_burn_in', True))
         self._fused_curiosity = bool(hip_config.get('fused_curiosity', True))
+        self._fused_discrete = bool(hip_config.get('fused_discrete', True))     # asac_discrete_* (pure-discrete learner)
         self._fused_rpm_loss = bool(hip_config.get('fused_rpm_loss', True))
         # one backward walk per prediction model (gates and model gradients from it): sac_aux._train_rpm
         self._rpm_single_backward = bool(hip_config.get('rpm_single_backward', True))
@@ -515,6 +529,9 @@ class SAC_Base(AuxHeadsMixin):
         # zeroed exchange words of `asac_mse_mean_grad` (the observation model's frame loss, sac_aux._train_rpm)
         self._mse_big_ws = torch.zeros(native.mse_mean_grad_workspace(), **f32) if self.use_prediction else None
         self._grad_logp = torch.zeros(B, **f32)
+        # pure-discrete learner (`_discrete_fused`): the branch table and d loss / d (head outputs) of its two loss launches
+        self._branches = native.branches(self.d_action_sizes) if self.d_action_sizes else None
+        self._discrete_grads = {}       # batch rows -> (d loss_q / d q [E, B, D], d loss_policy / d logits [B, D])
         # the one hand-over between steps that goes through `self`, from the Q step's return target to the policy step
         # (`_train_policy` has the reference's signature: no room for either): `_ls_y` = the policy's output over the
         # return's window, read by `_step_policy`; `_pi_sampled` = the return's sampling launch also drew the policy
@@ -1045,6 +1062,30 @@ class SAC_Base(AuxHeadsMixin):
             native.squash_sample_fwd(loc, scale, eps_buf, a_tanh, logp, **stored)
         return a_tanh, logp, c_pi
 
+    def _discrete_fused(self, B: int) -> bool:
+        """the step's discrete arithmetic runs on the `asac_discrete_*` launches (`fused_discrete_applies`), B rows a batch"""
+        return fused_discrete_applies(
+            enabled=self._fused_discrete, plain_learner=True, d_action_sizes=self.d_action_sizes,
+            c_action_size=self.c_action_size, discrete_dqn_like=self.discrete_dqn_like,
+            offline_loss=self.offline_enabled and self.offline_loss, siamese=self.siamese is not None,
+            use_prediction=self.use_prediction, data_parallel=self._dist is not None,
+            float32_on_device=self._params.flat.dtype == torch.float32 and self._params.flat.is_cuda,
+            ensemble_q_num=self.ensemble_q_num, n_step=self.n_step, batch_size=B)
+
+    def _discrete_logits(self, state, obs_list):
+        """the discrete branches' logits [.., D] (the launches normalise them per branch themselves): the stock policy's
+        raw head outputs, a plugin policy's distribution logits"""
+        if type(self.model_policy).forward is ModelPolicy.forward:
+            return self.model_policy.d_head_raw(state)
+        return self.model_policy(state, obs_list)[0].logits
+
+    def _discrete_grad_buffers(self, B: int):
+        if B not in self._discrete_grads:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            self._discrete_grads[B] = (torch.zeros(self.ensemble_q_num, B, self.d_action_summed_size, **f32),
+                                       torch.zeros(B, self.d_action_summed_size, **f32))
+        return self._discrete_grads[B]
+
     def _stored_action_ratios(self, d_policy, n_mu_probs, nx_actions):
         """discrete branches -> (pi, mu) [B, n]: the stored actions' probability under the policy and under the behaviour
         policy, as products over the branches"""
@@ -1093,7 +1134,7 @@ class SAC_Base(AuxHeadsMixin):
     @torch.no_grad()
     def _get_y(self, n_last_masks, n_padding_masks, nx_obses_list, nx_states, nx_actions, n_rewards,
                n_dones, n_mu_probs, *, eps_buf, subset_prefix, y_out, q_online=None, td_out=None, ls=None,
-               sample=None, stored_pi=None, policy_sample=False, q_table=None, launch=True):
+               sample=None, stored_pi=None, policy_sample=False, q_table=None, launch=True, d_q_online=None):
         """-> (d_y [B,1] | None, c_y [B,1] | None);  with `launch=False` -> (d_y, c_y, ret): the continuous return's
         launch is NOT issued, `c_y` is where it will write and `ret` what `_launch_return` (or a launch that forms the
         return itself) needs — None without continuous actions.
@@ -1108,9 +1149,12 @@ class SAC_Base(AuxHeadsMixin):
         `nx_actions` is the stored-action window [B, n+1, A] (the reference appends a zero row
         instead, 1329: the extra row's probability is discarded either way).  With `q_online`
         ([E, B], continuous-only action spaces) the TD error mean_e|q_e - y| is produced by the
-        same launch into `td_out`.
+        same launch into `td_out`; with `d_q_online` (the online critics' discrete head outputs [B, D] each, pure-discrete
+        learner on the `asac_discrete_*` launches) likewise.
         """
         n_actions = nx_actions[:, :-1]
+        fused_d = self._discrete_fused(n_rewards.shape[0])
+        d_logits = None
         if ls is None and sample is None and self._fpi is not None and self.c_action_size and nx_states.dim() == 3:
             # the stock policy over the window and the window's sample as ONE launch (`_return_sample_epilogue`)
             job_pi, ls_out = self._fpi.job(StockMLP._rows_in_place(nx_states, self.state_size), None)
@@ -1121,6 +1165,9 @@ class SAC_Base(AuxHeadsMixin):
         if ls is not None:
             d_policy = c_policy = None
             loc, scale, plain = ls[..., :self.c_action_size], ls[..., self.c_action_size:], True
+        elif fused_d:   # the return's launch forms the branch probabilities from the logits: no distribution objects
+            d_policy = c_policy = loc = scale = None
+            plain, d_logits = False, self._discrete_logits(nx_states, nx_obses_list)
         else:
             d_policy, c_policy, loc, scale, plain = self._policy(nx_states, nx_obses_list)
             ls = self._ls
@@ -1167,6 +1214,21 @@ class SAC_Base(AuxHeadsMixin):
             self.noise.subset_(sub_eval, E)
             d_y = self.get_dqn_like_d_y(n_last_masks, n_padding_masks, n_rewards, n_dones,
                                         eval_next.index_select(0, sub_eval.long()), target_next)
+        elif fused_d:   # 1383-1421, policy-based branch: subset means, branch softmax, V, ratios and the scan in ONE launch
+            sub_next, sub_n = self._subsets[subset_prefix + '_dnext'], self._subsets[subset_prefix + '_dn']
+            self.noise.subset_(sub_next, E)
+            self.noise.subset_(sub_n, E)
+            args = self._vtrace_args(n_rewards, n_dones, n_last_masks, n_padding_masks, y_out)
+            args.subset_n, args.subset_next, args.E_sample = sub_n.data_ptr(), sub_next.data_ptr(), self.ensemble_q_sample
+            args.log_alpha = self.log_d_alpha.data_ptr()
+            if self.use_n_step_is:
+                args.mu_prob, args.mu_stride_b, args.mu_stride_t = \
+                    n_mu_probs.data_ptr(), n_mu_probs.stride(0), n_mu_probs.stride(1)
+            if d_q_online is not None:    # the TD error mean_e |(1/K) sum_j a_j q_e - y| from the same launch
+                args.td_error_out = td_out.data_ptr()
+            native.discrete_return(args, self._branches, [q[0] for q in nx_qs], d_logits, action=nx_actions,
+                                   q_online=d_q_online)
+            d_y = y_out.unsqueeze(-1)
         elif self.d_action_sizes:   # 1383-1421, policy-based branch, eager ops + the scan kernel
             sub_next, sub_n = self._subsets[subset_prefix + '_dnext'], self._subsets[subset_prefix + '_dn']
             self.noise.subset_(sub_next, E)
@@ -1370,6 +1432,16 @@ class SAC_Base(AuxHeadsMixin):
                                policy_sample=policy_sample)
 
         losses = None
+        if self.d_action_sizes and aux is None and self._discrete_fused(state.shape[0]):
+            # loss values and d(sum_e l_e) / d(head outputs) from one launch; back-propagation starts at the heads
+            heads = [q[0] for q in q_list]
+            grad_q, _ = self._discrete_grad_buffers(state.shape[0])
+            native.discrete_q_loss_grad(self._branches, [h.detach() for h in heads], d_action, d_y, priority_is,
+                                        self._loss_q_e, grad_q)
+            with direct_param_grads(), DeferredPartialSums() as sums_later:
+                torch.autograd.backward(heads, list(grad_q.unbind(0)))
+            sums_later.flush()
+            return self._finish_rep_q(None, None)
         if self.d_action_sizes:
             qs = torch.stack([torch.sum(d_action * q[0], dim=-1, keepdim=True) / self.d_action_branch_size
                               for q in q_list])                                   # [E, B, 1]
@@ -1535,6 +1607,23 @@ class SAC_Base(AuxHeadsMixin):
         if self._stock_c_only():
             return self._train_policy_stock(state, ls)
         dsum, E = self.d_action_summed_size, self.ensemble_q_num
+        if self._discrete_fused(state.shape[0]):
+            # pure-discrete: the critics only supply values; objective, entropy statistic and d loss / d logits from one
+            # launch; back-propagation starts at the logits
+            logits = self._discrete_logits(state, obs_list)
+            with torch.no_grad():
+                d_qs = [q(state, action[..., dsum:], obs_list)[0] for q in self.model_q_list]
+            sub = self._subsets['pi_d']
+            self.noise.subset_(sub, E)
+            _, grad_logits = self._discrete_grad_buffers(state.shape[0])
+            native.discrete_policy_loss_grad(self._branches, logits.detach(), d_qs, sub, self.ensemble_q_sample,
+                                             mu_d_policy_probs, self.log_d_alpha, self.d_policy_entropy_penalty,
+                                             self._stats['loss_policy'], grad_logits, self._stats['d_entropy'])
+            pi_inputs = list(self.model_policy.parameters())
+            with direct_param_grads(only=pi_inputs):
+                torch.autograd.backward([logits], [grad_logits], inputs=pi_inputs)
+            self.optimizer_policy.step()
+            return
         d_policy, c_policy, loc, scale, plain = self._policy(state, obs_list)
         loss_d = loss_c = None
         with torch.no_grad():
@@ -1625,6 +1714,15 @@ class SAC_Base(AuxHeadsMixin):
     def _train_alpha(self, obs_list, state, ls=None, logp=None):
         """`ls`: the (updated) policy's [B, 2A] (loc | scale) output for `state`, if the caller has it;
         `logp`: log pi of an action already drawn from it with `self._eps_alpha`."""
+        if self._discrete_fused(state.shape[0]):
+            # pure-discrete: dL/dlog_d_alpha = mean_b (1/K) sum_j p_j (-cl(p_j) - target_j) straight into its gradient slot
+            # (log_c_alpha's slot keeps the zero the step's prologue wrote, as after the eager backward)
+            with torch.no_grad():
+                seg0 = self._params.segments['alpha'][0]
+                native.discrete_alpha_grad(self._branches, self._discrete_logits(state, obs_list), self.target_d_alpha,
+                                           self._params.grad[seg0:seg0 + 1])
+            self.optimizer_alpha.step()
+            return
         with torch.no_grad():
             if ls is not None:
                 A = self.c_action_size
@@ -1734,6 +1832,14 @@ class SAC_Base(AuxHeadsMixin):
         obs_list = [o[:, 0] for o in nx_obses_list]
         action = nx_actions[:, 0]
         d_action, c_action = action[..., :dsum], action[..., dsum:]
+        if c_q is None and self._discrete_fused(state.shape[0]):
+            # pure-discrete: the return's launch writes mean_e |(1/K) sum_j a_j q_e - y| itself
+            assert not sidecars and pending_alpha is None and td_update is None
+            heads = [q(state, c_action, obs_list)[0] for q in self.model_q_list]
+            self._get_y(n_last_masks, n_padding_masks, nx_obses_list, nx_target_states, nx_actions, n_rewards, n_dones,
+                        n_mu_probs, eps_buf=self._eps_td, subset_prefix='td', y_out=self._y_td_buf, td_out=self._td_error,
+                        d_q_online=heads)
+            return self._td_error, False
         q_list = None
         if c_q is not None:
             pass                  # [E, B] online Q of (s0, a0), already computed by the caller

@@ -1,0 +1,79 @@
+// Per-row pieces of the branched categorical policy (reference nn_models/policy.py: one OneHotCategorical per discrete
+// action branch, concatenated), shared by the four kernels of discrete.hip.  ONE implementation: a value two kernels both
+// form (p at the step's state in the policy step and in the temperature step) has the same bits in both.
+//   p  = softmax(z)           = exp(z - max) / sum_j exp(z_j - max)        (torch softmax)
+//   lp = z - logsumexp(z)     = z - (log(sum_j exp(z_j - max)) + max)      (torch logsumexp)
+//   cl(p) = log(max(p, 1e-8))                                              (sac_base.py: torch.log(probs.clamp(min=1e-8)))
+//   H  = -sum_j p_j lp_j                                                   (torch Categorical.entropy)
+// Sums run over the branch's entries in index order by one lane.  Accurate expf / logf, -ffp-contract=off.
+#pragma once
+#include "asac_common.h"
+#include "asac_vtrace.h"
+
+#include <cmath>
+
+namespace asac {
+
+constexpr float kCatProbFloor = 1e-8f;
+
+// the branch table of a launch: K sizes, D = their sum (by value in the kernel arguments)
+__host__ __device__ __forceinline__ bool cat_branches_ok(const asac_branches_t& br) {
+    if (br.K <= 0 || br.K > ASAC_DISCRETE_MAX_BRANCHES || br.D <= 0 || br.D > ASAC_DISCRETE_MAX_WIDTH) return false;
+    int d = 0;
+    for (int k = 0; k < br.K; ++k) {
+        if (br.size[k] <= 0) return false;
+        d += br.size[k];
+    }
+    return d == br.D;
+}
+
+struct CatStats {
+    float m, sum, lse;       // max_j z_j, sum_j exp(z_j - m), log(sum) + m
+};
+
+// z[0..s): the logits of one branch of one row (stride 1; LDS or global)
+__device__ __forceinline__ CatStats cat_stats(const float* z, int s) {
+    CatStats st;
+    float m = z[0];
+    for (int j = 1; j < s; ++j) m = fmaxf(m, z[j]);
+    float sum = 0.f;
+    for (int j = 0; j < s; ++j) sum += expf(z[j] - m);
+    st.m = m, st.sum = sum, st.lse = logf(sum) + m;
+    return st;
+}
+// ... rebuilt from (m, sum) kept by the caller
+__device__ __forceinline__ CatStats cat_stats_from(float m, float sum) {
+    CatStats st;
+    st.m = m, st.sum = sum, st.lse = logf(sum) + m;
+    return st;
+}
+
+__device__ __forceinline__ float cat_prob(float z, const CatStats& st) { return expf(z - st.m) / st.sum; }
+__device__ __forceinline__ float cat_logp(float z, const CatStats& st) { return z - st.lse; }
+__device__ __forceinline__ float cat_cl(float p) { return logf(fmaxf(p, kCatProbFloor)); }
+// d cl(p) / d p * p: 1 where the clamp passes the gradient (torch: p >= min), else 0
+__device__ __forceinline__ float cat_cl_open(float p) { return p >= kCatProbFloor ? 1.f : 0.f; }
+
+__device__ __forceinline__ float cat_entropy(const float* z, int s, const CatStats& st) {
+    float h = 0.f;
+    for (int j = 0; j < s; ++j) h += cat_prob(z[j], st) * cat_logp(z[j], st);
+    return -h;
+}
+
+// mean over the members of a device-resident subset of element `off` of each member's tensor (the members are separate
+// tensors of one shape: a pointer table instead of a stack).  Every member's load is requested before the first add
+// (members beyond the real ones re-read the last real one: a valid address, the value is not added); sum in subset order,
+// one division (torch mean).  `tab`: the table read in place from the kernel-argument segment.
+__device__ __forceinline__ float cat_member_mean(const ASAC_KARG asac_members_t& tab, const int32_t* subset, int Es,
+                                                 int64_t off) {
+    float v[ASAC_DISCRETE_MAX_MEMBERS];
+#pragma unroll
+    for (int e = 0; e < ASAC_DISCRETE_MAX_MEMBERS; ++e) v[e] = tab.base[member(subset, min(e, Es - 1))][off];
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < ASAC_DISCRETE_MAX_MEMBERS; ++e)
+        if (e < Es) s += v[e];
+    return s / (float)Es;
+}
+
+}  // namespace asac

@@ -14,7 +14,7 @@ PKG_DIR = Path(__file__).resolve().parent
 import os as _os
 
 LIB_PATH = Path(_os.environ.get('ASAC_HIP_LIB', PKG_DIR / 'lib' / 'libasac_hip.so'))   # env override: debugging builds
-ABI_VERSION = 87
+ABI_VERSION = 88
 
 MAX_GATHER_KEYS = 16
 PAD_KEEP, PAD_WORD, PAD_BYTE, PAD_ROW, PAD_EMIT_MASK = 0, 1, 2, 3, 4
@@ -85,6 +85,26 @@ class VtraceArgs(C.Structure):
         ('use_n_step_is', C.c_int32), ('B', C.c_int32), ('n', C.c_int32),
         ('q_online', C.c_void_p), ('E_online', C.c_int32),
         ('td_error_out', C.c_void_p), ('y_out', C.c_void_p)]
+
+
+DISCRETE_MAX_WIDTH, DISCRETE_MAX_BRANCHES, DISCRETE_MAX_MEMBERS, DISCRETE_MAX_STEPS, DISCRETE_MAX_ROWS = 64, 8, 8, 64, 1024
+
+
+class Branches(C.Structure):
+    """asac_branches_t: the sizes of the discrete action branches (K of them, D entries in all)"""
+    _fields_ = [('K', C.c_int32), ('D', C.c_int32), ('size', C.c_int32 * DISCRETE_MAX_BRANCHES)]
+
+
+class Members(C.Structure):
+    """asac_members_t: the ensemble members' head outputs, separate tensors of one shape, as a pointer table"""
+    _fields_ = [('base', C.c_void_p * DISCRETE_MAX_MEMBERS), ('stride_b', C.c_int64), ('stride_t', C.c_int64),
+                ('E', C.c_int32), ('reserved_', C.c_int32)]
+
+
+class DiscreteReturn(C.Structure):
+    _fields_ = [('branches', Branches), ('q_target', Members), ('q_online', Members),
+                ('logits', C.c_void_p), ('logits_stride_b', C.c_int64), ('logits_stride_t', C.c_int64),
+                ('action', C.c_void_p), ('action_stride_b', C.c_int64), ('action_stride_t', C.c_int64)]
 
 
 class MlpDesc(C.Structure):
@@ -484,6 +504,14 @@ _SIGNATURES = {
     'asac_termination_loss_grad': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
                                              C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_int, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_discrete_return': (C.c_int, [C.POINTER(VtraceArgs), C.POINTER(DiscreteReturn), C.c_void_p]),
+    'asac_discrete_q_loss_grad': (C.c_int, [C.POINTER(Branches), C.POINTER(Members), C.c_void_p, C.c_int64, C.c_void_p,
+                                            C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_discrete_policy_loss_grad': (C.c_int, [C.POINTER(Branches), C.c_void_p, C.c_int64, C.POINTER(Members), C.c_void_p,
+                                                 C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_int, C.c_void_p,
+                                                 C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_discrete_alpha_grad': (C.c_int, [C.POINTER(Branches), C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -2618,3 +2646,114 @@ def termination_loss_grad(beta, y, v_options, done, priority_is, terminal_entrop
         _p(beta), col(beta, 'beta'), _p(y), col(y, 'y'), _p(v_options), v_options.stride(0), v_options.stride(1),
         v_options.shape[1], _p(done), _p(priority_is), col(priority_is, 'priority_is') if priority_is is not None else 0,
         float(terminal_entropy), B, _p(loss_out), _p(dbeta), _p(ws), _stream()), 'asac_termination_loss_grad')
+
+
+# ------------------------------------------------------------------------------------------------
+# pure-discrete, policy-based SAC (csrc/discrete.hip)
+# ------------------------------------------------------------------------------------------------
+def discrete_sizes_ok(d_action_sizes, E: int, n: int, B: int) -> bool:
+    """the limits of the `discrete_*` entry points (include/asac_hip.h ASAC_DISCRETE_MAX_*)"""
+    sizes = list(d_action_sizes)
+    return (0 < len(sizes) <= DISCRETE_MAX_BRANCHES and all(s > 0 for s in sizes) and sum(sizes) <= DISCRETE_MAX_WIDTH
+            and 0 < E <= DISCRETE_MAX_MEMBERS and 0 < n <= DISCRETE_MAX_STEPS and 0 < B <= DISCRETE_MAX_ROWS)
+
+
+def branches(d_action_sizes) -> Branches:
+    sizes = [int(s) for s in d_action_sizes]
+    br = Branches()
+    br.K, br.D = len(sizes), sum(sizes)
+    for k, s in enumerate(sizes[:DISCRETE_MAX_BRANCHES]):      # (a longer table is refused by the entry point: K)
+        br.size[k] = s
+    return br
+
+
+def members(tensors, D: int) -> Members:
+    """the members' head outputs ([B, D] or [B, T, D] float32 each, one shape and one set of strides, dense rows) ->
+    `Members`; the tensors must stay alive until the launch that reads the table is issued"""
+    m = Members()
+    m.E = len(tensors)
+    if not tensors:
+        return m
+    t0 = tensors[0]
+    for e, t in enumerate(tensors[:DISCRETE_MAX_MEMBERS]):     # (more members are refused by the entry point: E)
+        assert t.is_cuda and t.dtype == torch.float32 and t.shape == t0.shape and t.stride() == t0.stride()
+        assert t.shape[-1] == D and (t.stride(-1) == 1 or D == 1) and t.dim() in (2, 3)
+        m.base[e] = t.data_ptr()
+    m.stride_b = t0.stride(0)
+    m.stride_t = t0.stride(1) if t0.dim() == 3 else 0
+    return m
+
+
+def _discrete_rows(t, D, name):
+    assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] >= D and (t.stride(1) == 1 or D == 1), name
+    return t.stride(0)
+
+
+@_profiled
+def discrete_return(args: VtraceArgs, br: Branches, q_target, logits, action=None, q_online=None):
+    """`args` (`_vtrace_args` + subset_n / subset_next / E_sample / log_alpha, mu_prob and its strides under importance
+    sampling, td_error_out with `q_online`) -> y_out (and the TD error): one launch.  q_target: the target members' head
+    outputs [B, n+1, D]; logits [B, n+1, D]; action: the stored window [B, >= n, >= D]; q_online: the online members'
+    head outputs [B, D]."""
+    D, B, n = br.D, args.B, args.n
+    job = DiscreteReturn()
+    job.branches = br
+    job.q_target = members(list(q_target), D)
+    assert all(t.shape[:2] == (B, n + 1) for t in q_target)
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.shape == (B, n + 1, D)
+    assert logits.stride(2) == 1 or D == 1
+    job.logits, job.logits_stride_b, job.logits_stride_t = logits.data_ptr(), logits.stride(0), logits.stride(1)
+    if action is not None:
+        assert action.is_cuda and action.dtype == torch.float32 and action.dim() == 3 and action.shape[0] == B
+        assert action.shape[1] >= n and action.shape[2] >= D and (action.stride(2) == 1 or D == 1)
+        job.action, job.action_stride_b, job.action_stride_t = action.data_ptr(), action.stride(0), action.stride(1)
+    if q_online is not None:
+        job.q_online = members(list(q_online), D)
+        assert all(t.shape == (B, D) for t in q_online)
+    _check(load().asac_discrete_return(C.byref(args), C.byref(job), _stream()), 'asac_discrete_return')
+
+
+@_profiled
+def discrete_q_loss_grad(br: Branches, q, action, y, w, loss_out, grad_q):
+    """q: the online members' head outputs [B, D]; action [B, >= D]; y, w (optional): B float32 elements each ([B] or
+    [B, 1]); loss_out [E]; grad_q [E, B, D] contiguous <- d (sum_e loss_e) / d q"""
+    B, D, E = action.shape[0], br.D, len(q)
+
+    def col(t, name):
+        assert t.is_cuda and t.dtype == torch.float32 and t.numel() == B and t.shape[0] == B, name
+        return t.stride(0) if B > 1 else 1
+    if loss_out is not None and grad_q is not None:
+        assert loss_out.dtype == torch.float32 and loss_out.numel() >= E and loss_out.is_contiguous()
+        assert grad_q.dtype == torch.float32 and grad_q.shape == (E, B, D) and grad_q.is_contiguous()
+    _check(load().asac_discrete_q_loss_grad(C.byref(br), C.byref(members(list(q), D)), _p(action),
+                                            _discrete_rows(action, D, 'action'),
+                                            _p(y), col(y, 'y'), _p(w), col(w, 'w') if w is not None else 0, B,
+                                            _p(loss_out), _p(grad_q), _stream()), 'asac_discrete_q_loss_grad')
+
+
+@_profiled
+def discrete_policy_loss_grad(br: Branches, logits, q, subset, E_sample, mu, log_alpha, entropy_penalty, loss_out,
+                              grad_logits, entropy_out, probs_out=None, row_entropy_out=None):
+    """logits [B, D]; q: the online members' head outputs [B, D]; subset: int32 [E_sample] device tensor or None (members
+    0..E_sample-1); mu [B, >= D]; -> loss_out [1], grad_logits [B, D], entropy_out [1] (and, optionally, p [B, D]
+    contiguous and the rows' entropies [B])"""
+    B, D = logits.shape[0], br.D
+    for t in (probs_out, row_entropy_out):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == (B * D if t is probs_out else B))
+    gs = _discrete_rows(grad_logits, D, 'grad_logits') if grad_logits is not None else 0
+    _check(load().asac_discrete_policy_loss_grad(
+        C.byref(br), _p(logits), _discrete_rows(logits, D, 'logits'), C.byref(members(list(q), D)), _p(subset), int(E_sample),
+        _p(mu), _discrete_rows(mu, D, 'mu'), _p(log_alpha), float(entropy_penalty), B, _p(loss_out), _p(grad_logits), gs,
+        _p(entropy_out), _p(probs_out), _p(row_entropy_out), _stream()), 'asac_discrete_policy_loss_grad')
+
+
+@_profiled
+def discrete_alpha_grad(br: Branches, logits, target, grad_slot, probs_out=None, row_entropy_out=None):
+    """*grad_slot <- mean_b (1/K) sum_j p_j (-cl(p_j) - target_j); logits [B, D], target [D] (device)"""
+    B, D = logits.shape[0], br.D
+    assert target.is_cuda and target.dtype == torch.float32 and target.numel() == D and target.is_contiguous()
+    for t in (probs_out, row_entropy_out):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == (B * D if t is probs_out else B))
+    _check(load().asac_discrete_alpha_grad(C.byref(br), _p(logits), _discrete_rows(logits, D, 'logits'), _p(target), B,
+                                           _p(grad_slot), _p(probs_out), _p(row_entropy_out), _stream()),
+           'asac_discrete_alpha_grad')

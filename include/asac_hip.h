@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ASAC_ABI_VERSION 87
+#define ASAC_ABI_VERSION 88
 #define ASAC_MAX_GATHER_KEYS 16
 #define ASAC_MAX_ENSEMBLE 16
 #define ASAC_MAX_ACTION 64
@@ -1500,6 +1500,86 @@ int asac_termination_loss_grad(const float* beta, int64_t beta_stride, const flo
                                const float* v_options, int64_t v_stride_b, int64_t v_stride_o, int num_options,
                                const uint8_t* done, const float* priority_is, int64_t is_stride, float terminal_entropy,
                                int B, float* loss, float* dbeta, float* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Pure-discrete, policy-based SAC (d_action_sizes set, c_action_size == 0, discrete_dqn_like False): the learner's
+ * row-wise arithmetic around the networks as one launch per item (csrc/discrete.hip, csrc/asac_categorical.h).
+ * Notation: logits z[row, j]; K branches of sizes s_k, D = sum s_k; within a branch p = softmax(z),
+ * lp = z - logsumexp(z), cl(p) = log(max(p, 1e-8)); Qbar_j = the mean over the members of a device-resident subset.
+ * The branch table and the ensemble members' base pointers travel by value: the members' head outputs are separate
+ * tensors of one shape.  Nothing allocates or synchronises.  Bad arguments (null outputs, a branch table that does not
+ * add up, E_sample > E, a size over the limits below) return hipErrorInvalidValue without a launch.
+ * ------------------------------------------------------------------------------------------- */
+#define ASAC_DISCRETE_MAX_WIDTH 64      /* D  */
+#define ASAC_DISCRETE_MAX_BRANCHES 8    /* K  */
+#define ASAC_DISCRETE_MAX_MEMBERS 8     /* E  */
+#define ASAC_DISCRETE_MAX_STEPS 64      /* n  */
+#define ASAC_DISCRETE_MAX_ROWS 1024     /* B of the single-workgroup reductions (the two losses, the temperature) */
+typedef struct {
+    int32_t K, D;
+    int32_t size[ASAC_DISCRETE_MAX_BRANCHES];
+} asac_branches_t;
+typedef struct {
+    const float* base[ASAC_DISCRETE_MAX_MEMBERS];  /* member e: element (b, t, j) at base[e] + b*stride_b + t*stride_t + j */
+    int64_t stride_b, stride_t;
+    int32_t E, reserved_;
+} asac_members_t;
+
+/* The return target of SAC_Base._get_y's policy-based discrete branch (sac_base.py:1383-1421 + _v_trace 1244-1295) in
+ * ONE launch (with q_online: _get_td_error's 2219-2244 too).  Per window position u in [0, n]:
+ *   V = (1/K) sum_j p_j (Qbar_j - alpha cl(p_j));  positions 0..n-1 use
+ * subset_n, positions 1..n subset_next.  Under use_n_step_is: pi_t = exp(sum_k lp[argmax of the stored one-hot in
+ * branch k]) (first maximum, as torch), mu_t = prod_j (mu_j a_j, zeros -> 1), ratio pi / max(mu, 1e-8).  Then
+ * asac_vtrace.h's step arithmetic and row scan.
+ *   args      reward / done / masks / ratios / gamma / B / n / y_out as for asac_vtrace_return_min; also read:
+ *             subset_n, subset_next, E_sample, log_alpha (= log_d_alpha), mu_prob + mu_stride_b/t (entries [0, D)),
+ *             td_error_out.  q, logp, pi_prob, A, mu_offset, q_online, E_online are not read.
+ *   q_target  the target members' head outputs [B, n+1, D];  logits [B, n+1, D] (rows logits_stride_b/t floats apart)
+ *   action    the stored actions' window [B, >= n, >= D] (needed under use_n_step_is and for the TD error)
+ *   q_online  optional (E == 0: none) online members' head outputs [B, D] at the step's state (stride_t not read): with
+ *             args->td_error_out the launch writes td[b] = mean_e |(1/K) sum_j a_j q_e[b, j] - y_b|, a = action at t = 0
+ * Many workgroups, no exchange between them.  n <= ASAC_DISCRETE_MAX_STEPS; any B. */
+typedef struct {
+    asac_branches_t branches;
+    asac_members_t q_target;
+    asac_members_t q_online;
+    const float* logits;
+    int64_t logits_stride_b, logits_stride_t;
+    const float* action;
+    int64_t action_stride_b, action_stride_t;
+} asac_discrete_return_t;
+int asac_discrete_return(const asac_vtrace_args_t* args_host, const asac_discrete_return_t* job_host, void* stream);
+
+/* Q loss of the discrete heads and its gradient (sac_base.py:1533-1538, 1563-1568):
+ *   qs[e][b] = (1/K) sum_j a[b][j] q_e[b][j];   loss_out[e] = mean_b w_b (qs - y_b)^2   (w may be NULL)
+ *   grad_q[e][b][j] = 2 w_b (qs - y_b) a[b][j] / (K B)      one contiguous [E, B, D] buffer
+ * One workgroup per member, the batch mean summed in a fixed order.  q: members' head outputs [B, D] (stride_t not read);
+ * action rows action_stride floats apart; y, w: element b at b * stride.  B <= ASAC_DISCRETE_MAX_ROWS. */
+int asac_discrete_q_loss_grad(const asac_branches_t* branches, const asac_members_t* q, const float* action,
+                              int64_t action_stride, const float* y, int64_t y_stride, const float* w, int64_t w_stride,
+                              int B, float* loss_out, float* grad_q, void* stream);
+
+/* Policy objective of the discrete heads, value + gradient with respect to the logits (sac_base.py:1858-1880, 1903):
+ *   L = mean_b [ (1/K) sum_j p_j (alpha cl(p_j) - Qbar_j) + (lambda/2) (H_mu - H_pi)^2 ]
+ *   H_mu = -(1/K) sum_j mu_j cl(mu_j),  H_pi = (1/K) sum_k H_k
+ *   dL_b/dz_i = p_i (g_i - sum_j p_j g_j) + (lambda/K)(H_mu - H_pi) p_i (lp_i + H_k)   per branch, all of it / B
+ *   g_j = (1/K)(alpha cl(p_j) - Qbar_j + alpha [p_j >= 1e-8])
+ * loss_out f32[1]; grad_logits [B, D] rows grad_stride apart; entropy_out f32[1] = mean_b H_pi.  Optional (may be NULL):
+ * probs_out [B, D] contiguous = p, row_entropy_out f32[B] = H_pi per row.  One workgroup;  B <= ASAC_DISCRETE_MAX_ROWS. */
+int asac_discrete_policy_loss_grad(const asac_branches_t* branches, const float* logits, int64_t logits_stride,
+                                   const asac_members_t* q, const int32_t* subset, int E_sample, const float* mu,
+                                   int64_t mu_stride, const float* log_alpha, float entropy_penalty, int B,
+                                   float* loss_out, float* grad_logits, int64_t grad_stride, float* entropy_out,
+                                   float* probs_out, float* row_entropy_out, void* stream);
+
+/* Temperature gradient of the discrete heads (sac_base.py:1924-1929, 1944):
+ *   *grad_slot = mean_b (1/K) sum_j p_j (-cl(p_j) - target[j])       target: DEVICE f32[D]
+ * grad_slot is the flat-gradient element of log_d_alpha.  Optional probs_out / row_entropy_out as above (the same
+ * functions form them: same bits as asac_discrete_policy_loss_grad on the same logits).  One workgroup;
+ * B <= ASAC_DISCRETE_MAX_ROWS. */
+int asac_discrete_alpha_grad(const asac_branches_t* branches, const float* logits, int64_t logits_stride,
+                             const float* target, int B, float* grad_slot, float* probs_out, float* row_entropy_out,
+                             void* stream);
 
 #ifdef __cplusplus
 }

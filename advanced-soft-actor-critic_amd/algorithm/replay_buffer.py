@@ -122,6 +122,7 @@ class PrioritizedReplayBuffer:
         self.sharded = None            # parallel.ShardedParityReplay: sampling / write-backs over all ranks' shards
         self.lookahead, self.next_valid, self.parity, self._alt = False, False, 0, None
         self._gather_sidecar = None
+        self._head_plan = None         # `head_gather`: the step's own gather as a rider, built once per static set
         self._closed = False
 
     # ------------------------------------------------------------------------------------------
@@ -406,6 +407,49 @@ class PrioritizedReplayBuffer:
             self._gather_sidecar = self._make_gather_sidecar()
         self.next_valid = False
 
+    # ------------------------------------------------------------------------------------------
+    # the step's own gather as a rider of its first network launch (hip_config['head_gather_sidecar'])
+    # ------------------------------------------------------------------------------------------
+    def head_gather(self, obs_key: str, build: bool = False, weights: bool = True):
+        """The current static set's window gather in the form the learner's first network launch can carry:
+        dict(sidecar: the gather as a sidecar job, x0 / action: the keys `obs_key` and 'action' as that launch reads them
+        from the ring itself — `native.pi_q_ring_rows`) or None where that form does not apply (a sharded replay, a joint
+        layout, converted or derived keys, a plain gather without padding).  Built once per static set, with `build`
+        (the sidecar's launch description is a blocking copy: host time, never inside a capture); `weights`: the rider
+        also forms the IS weights of a batch the prologue's sampler drew in its partial form (`sidecar_w` instead of
+        `sidecar`: a learner uses one of the two)."""
+        if self._gather_keys is None or self.sharded is not None or self.min_ratio_reducer is not None or self.lookahead:
+            return None
+        plan = self._head_plan
+        if plan is not None and plan['for'] is self._gather_keys and plan['weights'] == weights:
+            return plan['plan']
+        if not build:
+            return None
+        made = None
+        dst = {k: self._batch.get(k) for k in (obs_key, 'action')}
+        specs = {k: next((sp for sp in self._gather_refs if sp.get('dst') is t and not sp.get('derive')), None)
+                 for k, t in dst.items() if t is not None}
+        if (len(specs) == 2 and all(sp is not None and not sp.get('dst_row_pitch') for sp in specs.values())
+                and self._pad_action is not None and self.derived is None and self.joint_pre_action is None):
+            x0, action = native.ring_key(specs[obs_key]), native.ring_key(specs['action'])
+            if x0 is not None and action is not None:
+                with torch.cuda.device(self.device):
+                    made = dict(x0=x0, action=action, index_ring=self._index_ring())
+                    if weights:
+                        made['sidecar_w'] = native.sidecar_window_gather_w(
+                            self._gather_keys, self._ids, self.batch_size, self.prev_n, self.post_n, self.capacity,
+                            self._index_ring(), self._p, self._tree, self._beta, self.beta_increment_per_sampling, self._w,
+                            self._min_p)
+                    else:
+                        made['sidecar'] = self._make_gather_sidecar()
+        self._head_plan = {'for': self._gather_keys, 'weights': weights, 'plan': made}
+        return made
+
+    def gather_now(self, weights: bool = False) -> None:
+        """the window gather of the batch drawn last (`weights`: and its IS weights, left over by the partial sampler), as
+        a launch of its own (a step whose first network launch did not take it as a rider)"""
+        self.sample_into_static(sampled=3 if weights else 1)
+
     def _make_gather_sidecar(self):
         return native.sidecar_window_gather(self._gather_keys, self._ids, self.batch_size, self.prev_n, self.post_n,
                                             self.capacity, self._index_ring())
@@ -471,11 +515,15 @@ class PrioritizedReplayBuffer:
         self.sample_into_static()
         return self._ids, self._batch, self._w.unsqueeze(-1)
 
-    def sample_into_static(self, sampled: int = 0) -> None:
+    def sample_into_static(self, sampled: int = 0, gather: bool = True) -> None:
         """The device part of `sample()` (no host logic; safe inside graph capture).  `sampled`: 1 — the tree walk
         (leaf, p, ids, IS weights) has already been done by the caller's fused prologue launch; 2 — and the window gather
         too (`NoiseSource.begin_step_with_sample(..., gather=True)`); 3 — the tree walk has been done, the IS weights have
-        not: the gather's launch forms them (`asac_window_gather_pad_w`)."""
+        not: the gather's launch forms them (`asac_window_gather_pad_w`).  `gather` False (with `sampled` 1 or 3): the caller
+        issues the gather itself — as a rider of a later launch (`head_gather`) or through `gather_now`."""
+        assert gather or (sampled in (1, 3) and self.sharded is None and self.min_ratio_reducer is None)
+        if not gather:
+            return
         B, C = self.batch_size, self.capacity
         if self.sharded is not None:       # "parity" mode: the batch is drawn over every rank's shard (host logic)
             self.sharded.sample_into(self)

@@ -292,6 +292,12 @@ class SAC_Base(AuxHeadsMixin):
         # slower than the launches in line and are gone: a fork / join inside a replayed hipGraph costs more than the small
         # launches it hides, NOTES.md section 1 rounds 4 / 5)
         self._la_gather_sidecar = bool(hip_config.get('lookahead_gather_sidecar', True)) and self._use_sidecars
+        # the synchronous schedule's own gather as a rider of the step's first network launch, which reads its rows from
+        # the replay ring (`_train_rep_q_stock`); False: the stand-alone gather launch in front of it
+        self._head_gather_sidecar = bool(hip_config.get('head_gather_sidecar', True)) and self._use_sidecars
+        self._head_gather = None      # the pending gather of the step's batch (`rb.head_gather`), until a launch takes it
+        self._head_gather_w = False   # ... and the batch's IS weights are pending with it
+        self._head_plan_cache = None  # (`rb._gather_keys` it was decided for, `rb.head_gather` or None): `_head_gather_plan`
         self._la_gather = None
         self._fuse_prediction_dense = bool(hip_config.get('fuse_prediction_dense', True))
         self._fused_q_loss_with_aux = bool(hip_config.get('fused_q_loss_with_aux', True))
@@ -1333,12 +1339,21 @@ class SAC_Base(AuxHeadsMixin):
                                     a2_out=self._pi_a, logp2_out=self._pi_logp)
             if not native.policy_sample_q_forward_ok(fused):
                 fused = None
+        riders = None
+        if fused is not None and self._head_gather is not None:
+            # the step's gather is still pending: this launch reads its rows (states, stored actions, the stored pair) from
+            # the replay ring and carries the gather for the launches behind it
+            ring = self._head_ring_job(fused, job_tq, self._head_gather, nx_states, nx_actions)
+            if ring is not None:
+                fused, riders = ring, [self._head_gather['sidecar_w' if self._head_gather_w else 'sidecar']]
+                self._head_gather = None
+        self._join_head_gather()
         if fused is not None:
             self.noise.normal_(self._eps_y)
             if policy_sample:
                 self.noise.normal_(self._eps_pi)
                 self._pi_sampled = True
-            native.policy_sample_q_forward(fused, [job_tq], sidecars=self._take_la_gather())
+            native.policy_sample_q_forward(fused, [job_tq], sidecars=riders if riders is not None else self._take_la_gather())
             _, c_y, ret = self._get_y(*window, eps_buf=self._eps_y, subset_prefix='y', y_out=self._y_buf,
                                       ls=ls[0].view(B, T, 2 * A), sample=(a_y, logp_y), stored_pi=c_pi,
                                       q_table=q_tab.view(E, B, T), launch=False)
@@ -1352,6 +1367,22 @@ class SAC_Base(AuxHeadsMixin):
         if not fold:
             self._finish_rep_q(None, None)
 
+    def _head_ring_job(self, fused, job_tq, head, nx_states, nx_actions):
+        """`fused` (the one-launch forward chain over `nx_states` / `nx_actions`, views of the static batch from window row
+        b on) and `job_tq` (the stored pair at row b, riding along) with ring-addressed rows, or None where the views are not
+        the gathered observation / action buffers or the launch refuses the pair of jobs"""
+        rb, b = self.replay_buffer, self.burn_in_step
+        obs, act = rb._batch[f'obs_{self.obs_names[0]}'], rb._batch['action']
+        if b != rb.prev_n or nx_states.shape[1] + b != rb.window:
+            return None
+        for view, whole in ((nx_states, obs), (nx_actions, act)):
+            at = whole[:, b:]
+            if view.data_ptr() != at.data_ptr() or view.stride() != at.stride() or view.shape != at.shape:
+                return None
+        job = native.pi_q_ring_rows(fused, rb._ids, head['index_ring'], rb.capacity, rb.prev_n, rb.window, b, head['x0'],
+                                    head['action'], x_j0=b, x_action_offset=self.d_action_summed_size)
+        return job if native.policy_sample_q_forward_ok(job, [job_tq]) else None
+
     def _train_rep_q(self, n_last_masks, n_padding_masks, nx_obses_list, nx_states, nx_actions, n_rewards,
                      n_dones, n_mu_probs, priority_is, aux=None, policy_sample=False, state_base=None):
         """`policy_sample`: see `_get_y`.  `state_base` = (window states [B, L, S], t) with
@@ -1361,6 +1392,7 @@ class SAC_Base(AuxHeadsMixin):
                 and self.optimizer_rep is None):
             return self._train_rep_q_stock(n_last_masks, n_padding_masks, nx_obses_list, nx_states, nx_actions,
                                            n_rewards, n_dones, n_mu_probs, priority_is, policy_sample)
+        self._join_head_gather()
         dsum = self.d_action_summed_size
         obs_list = [o[:, 0] for o in nx_obses_list]
         state, action = nx_states[:, 0], nx_actions[:, 0]
@@ -1926,6 +1958,7 @@ class SAC_Base(AuxHeadsMixin):
         self._counter_advanced = False
         w = self._step_sample()
         self._step_rep_and_q(w)
+        self._join_head_gather()       # (taken by the first network launch, or issued in front of it: never still pending)
         self._step_policy(w)
         post = _AfterPolicy()
         if not self.use_replay_buffer:
@@ -1950,6 +1983,34 @@ class SAC_Base(AuxHeadsMixin):
         if self._la_gather is not None:      # no launch hosted the next batch's gather: on its own, before any write-back
             self._la_gather = None
             self.replay_buffer.gather_next_now()
+
+    def _head_gather_plan(self, rb, build=False):
+        """-> `rb.head_gather` where the step's first network launch is the stock one-launch forward chain on the gathered
+        vector observation itself (parameter-free representation: the state IS that buffer), else None.  The answer is kept
+        per static set (`rb._gather_keys`): `train()` pays one identity test per call, `build` (host time, a blocking copy)
+        happens where a set is new — never on a replayed step, never inside a capture."""
+        cached = self._head_plan_cache
+        if cached is not None and cached[0] is rb._gather_keys:
+            return cached[1]
+        if not build:
+            return None
+        plan = None
+        # (no burn-in: the window views are then the whole buffers, nothing copies them in front of the launch; a batch of
+        # more than 256 rows with deferred weights keeps `window_gather_pad_w`)
+        weights = self._defer_is_weights
+        if (self._head_gather_sidecar and self._lookahead == 0 and self.burn_in_step == 0 and self._dist is None
+                and self._stock_c_only()
+                and type(self.model_rep) is ModelSimpleRep and self.optimizer_rep is None
+                and self.clip_epsilon > 0 and self.siamese is None and not self.use_prediction
+                and not self._wide_critics and len(self.obs_names) == 1 and not (weights and rb.batch_size > 256)):
+            plan = rb.head_gather(f'obs_{self.obs_names[0]}', build=True, weights=weights)
+        self._head_plan_cache = (rb._gather_keys, plan)
+        return plan
+
+    def _join_head_gather(self) -> None:
+        if self._head_gather is not None:    # no launch took the step's gather as a rider: on its own, before its first reader
+            self._head_gather = None
+            self.replay_buffer.gather_now(weights=self._head_gather_w)
 
     def _take_la_gather(self):
         """-> the pending gather of the NEXT batch as a sidecar list for a launch that reads nothing of it, or None"""
@@ -1995,13 +2056,22 @@ class SAC_Base(AuxHeadsMixin):
                 rb.sample_next_into_static(sampled=sampled)      # same launches, in line
         else:
             # ... and the sampler of the batch it draws: one launch for K1 + K2 + K5
+            # (where the step's first network launch will carry the gather, the IS weights of a one-workgroup batch ride
+            # there too: the sampler leaves them out — `defer_small`)
+            head = self._head_gather_plan(rb)
             sampled = self._use_sidecars and self.noise.begin_step_with_sample(
                 self._opt_steps, rb, self._eps_all, self._subsets_all, self.ensemble_q_num, polyak=polyak, zero=zero,
-                defer_weights=self._defer_is_weights)
+                defer_weights=self._defer_is_weights, defer_small=head is not None)
             if not sampled:
                 self.noise.begin_step(self._opt_steps, rb._u if rb.uniform_source is self.noise else None, self._eps_all,
                                       self._subsets_all, self.ensemble_q_num, polyak=polyak, zero=zero)
-            rb.sample_into_static(sampled=sampled)
+            # the gather rides in the step's first network launch where that launch can read its rows from the ring
+            # (`_train_rep_q_stock` takes it; `_join_head_gather` issues it on its own in front of any other reader)
+            self._head_gather_w = sampled == 3
+            self._head_gather = head if head is not None and ('sidecar_w' if sampled == 3 else 'sidecar') in head else None
+            if not sampled:
+                self._head_gather = None
+            rb.sample_into_static(sampled=sampled, gather=self._head_gather is None)
         derived = rb.derived if rb.derived is not None and rb.sharded is None else None
         return self._window_views(rb._batch, rb._ids, rb._w.unsqueeze(-1) if self.use_priority else None, derived,
                                   rb.joint_pre_action)
@@ -2391,6 +2461,8 @@ class SAC_Base(AuxHeadsMixin):
         elif rb._gather_keys is None:
             rb._build_batch()
             self._drop_graphs()
+        if rb is not None:
+            self._head_gather_plan(rb, build=True)      # (host work, once per static set: before any capture)
 
         if self._lookahead:
             if not rb.lookahead:

@@ -51,11 +51,16 @@ struct GatherLaunch {
 
 __device__ __forceinline__ int64_t load_id(const int64_t* ids, int s) { return ids[s]; }
 
+// window row j belongs to the centre row's episode: the stored step indexes run on from the centre's (the centre itself always)
+__device__ __forceinline__ bool index_run(int idx_j, int idx_c, int j, int prev_n) {
+    return j == prev_n || (idx_j - idx_c) == (j - prev_n);
+}
+
 __device__ __forceinline__ bool row_valid(const GatherArgs& a, int64_t id, int j) {
     if (j == a.prev_n) return true;
     const int idx_j = a.index_ring[ring_slot(id + (j - a.prev_n), a.capacity)];
     const int idx_c = a.index_ring[ring_slot(id, a.capacity)];
-    return (idx_j - idx_c) == (j - a.prev_n);
+    return index_run(idx_j, idx_c, j, a.prev_n);
 }
 
 template <typename Unit>
@@ -80,6 +85,18 @@ __device__ __forceinline__ uint8_t pad_value<uint8_t>(const GatherKeyDev& k, int
     if (k.pad_mode == ASAC_PAD_ROW) return k.pad_row[w];
     if (k.pad_mode == ASAC_PAD_WORD) return (uint8_t)(k.pad_word >> (8 * (w & 3)));
     return (uint8_t)(k.pad_word & 0xff);
+}
+
+// One 4-byte word of window row j of a sample, as copy_units delivers it: word `w` of key `k`'s padded row.  Every load is
+// issued whatever the validity test says (slot and pad addresses are always valid) and the result is SELECTED: a reader
+// that takes its rows straight from the ring (mlp.hip, RING instantiations) pays one round trip behind the id.
+__device__ __forceinline__ uint32_t ring_word(const GatherArgs& a, const GatherKeyDev& k, int64_t id, int j, int w) {
+    const int slot = ring_slot(id + (j - a.prev_n), a.capacity);
+    const uint32_t data = reinterpret_cast<const uint32_t*>(k.src + (int64_t)slot * k.row_bytes)[w];
+    const int idx_j = a.index_ring[slot];
+    const int idx_c = a.index_ring[ring_slot(id, a.capacity)];
+    const uint32_t pad = pad_value<uint32_t>(k, w);
+    return (k.pad_mode == ASAC_PAD_KEEP || index_run(idx_j, idx_c, j, a.prev_n)) ? data : pad;
 }
 
 // Derived keys (ASAC_DERIVE_*): destination row j of the window is the key's padded row `src_row(j)`; the first row of a

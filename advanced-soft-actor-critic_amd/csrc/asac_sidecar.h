@@ -215,6 +215,42 @@ __device__ __forceinline__ void scatter_write_row(const ScatterArgs& a, int flat
 }
 
 // ------------------------------------------------------------------------------------------------
+// The batch's IS weights (K2) as ONE workgroup beside a gather's: the sampler of an earlier launch
+// (asac_step_prologue_sample_partial: a workgroup per 256 samples) left its workgroups' minima in min_p_out[2..]; here they
+// are combined, beta advances, and the weights of all <= 1 024 rows are written — under a gather or a network launch
+// instead of on the sampler workgroup's serial path (the f64 powers) or behind a cross-workgroup exchange inside it.
+struct WeightsJob {
+    const float* p;            // [batch] leaf priorities of the sampled rows
+    const float* tree;         // tree[0] = total
+    double* beta_state;
+    double beta_increment;
+    float* w_out;              // [batch]
+    float* min_p_out;          // [0] <- min p; [2 .. 2 + parts) the sampler workgroups' minima
+    int32_t batch, parts;
+};
+
+__device__ __forceinline__ void weights_job(const WeightsJob& j) {
+    float bm = j.min_p_out[2];
+    for (int k = 1; k < j.parts; ++k) bm = fminf(bm, j.min_p_out[2 + k]);
+    const float root = j.tree[0];
+    const double b = fmin(1.0, *j.beta_state + j.beta_increment);
+    const float min_ratio = bm / root;
+    __syncthreads();               // every lane has read the old beta
+    for (int i = threadIdx.x; i < j.batch; i += kGatherBlock) j.w_out[i] = is_weight(j.p[i], root, min_ratio, b);
+    if (threadIdx.x == 0) {
+        *j.beta_state = b;
+        j.min_p_out[0] = bm;
+    }
+}
+
+// a window gather's launch description in device memory (asac_window_gather_plan), with the weights job of
+// asac_window_gather_plan_w behind it (ASAC_SIDECAR_WINDOW_GATHER_W: its first workgroup)
+struct GatherPlanDev {
+    GatherLaunch<ASAC_MAX_GATHER_KEYS> g;
+    WeightsJob w;
+};
+
+// ------------------------------------------------------------------------------------------------
 struct SidecarDev {
     int32_t kind, first_block;        // first workgroup of this job among the launch's sidecar workgroups
     AlphaAdamArgs alpha;
@@ -243,7 +279,8 @@ constexpr int kSidecarRowsPerWg = 256;        // SCATTER_ELECT, and SCATTER_WRIT
 inline int scatter_write_rows_per_wg(int row_bytes) { return row_bytes <= 32 ? kSidecarRowsPerWg : 4; }
 
 // host: device-side job list + workgroup count from the C structs; 0 = ok
-inline int sidecars_prepare(const asac_sidecar_t* jobs, int n, SidecarsDev& out) {
+// (with_weights: the host carries the code of ASAC_SIDECAR_WINDOW_GATHER_W — asac_policy_sample_q_forward with ring rows)
+inline int sidecars_prepare(const asac_sidecar_t* jobs, int n, SidecarsDev& out, bool with_weights = false) {
     out.n = 0;
     out.blocks = 0;
     if (n < 0 || n > ASAC_MAX_SIDECARS || (n > 0 && !jobs)) return 1;
@@ -266,8 +303,8 @@ inline int sidecars_prepare(const asac_sidecar_t* jobs, int n, SidecarsDev& out)
             const int total = h.batch * h.count;
             const int per = h.kind == ASAC_SIDECAR_SCATTER_ELECT ? kSidecarRowsPerWg : scatter_write_rows_per_wg(h.row_bytes);
             out.blocks += (total + per - 1) / per;
-        } else if (h.kind == ASAC_SIDECAR_WINDOW_GATHER) {
-            if (!h.gather_plan || h.gather_blocks <= 0) return 1;
+        } else if (h.kind == ASAC_SIDECAR_WINDOW_GATHER || h.kind == ASAC_SIDECAR_WINDOW_GATHER_W) {
+            if (!h.gather_plan || h.gather_blocks <= 0 || (h.kind == ASAC_SIDECAR_WINDOW_GATHER_W && !with_weights)) return 1;
             d.gather = h.gather_plan;
             out.blocks += h.gather_blocks;
         } else {
@@ -279,8 +316,9 @@ inline int sidecars_prepare(const asac_sidecar_t* jobs, int n, SidecarsDev& out)
 }
 
 // device: workgroup `block` (0-based among the sidecar workgroups) of a host kernel with >= 256 threads
-// (GATHER: hosts that accept ASAC_SIDECAR_WINDOW_GATHER jobs — the others do not carry the gather's code)
-template <int NSC, bool GATHER = false>
+// (GATHER: hosts that accept ASAC_SIDECAR_WINDOW_GATHER jobs — the others do not carry the gather's code; WEIGHTS: ... and
+// ASAC_SIDECAR_WINDOW_GATHER_W jobs)
+template <int NSC, bool GATHER = false, bool WEIGHTS = false>
 __device__ __forceinline__ void sidecar_run(const SidecarsT<NSC>& sc, int block, float* lds256) {
     int k = 0;
 #pragma unroll
@@ -294,6 +332,12 @@ __device__ __forceinline__ void sidecar_run(const SidecarsT<NSC>& sc, int block,
         if (threadIdx.x < kGatherBlock)
             gather_block<ASAC_MAX_GATHER_KEYS, 1>(*static_cast<const GatherLaunch<ASAC_MAX_GATHER_KEYS>*>(job.gather),
                                                   (unsigned)local);
+    } else if (WEIGHTS && job.kind == ASAC_SIDECAR_WINDOW_GATHER_W) {
+        if (threadIdx.x < kGatherBlock) {       // (only the first 256 threads of a host workgroup get here: their barrier)
+            const GatherPlanDev* plan = static_cast<const GatherPlanDev*>(job.gather);
+            if (local == 0) weights_job(plan->w);
+            else gather_block<ASAC_MAX_GATHER_KEYS, 1>(plan->g, (unsigned)(local - 1));
+        }
     } else if (threadIdx.x < 256) {
         if (job.kind == ASAC_SIDECAR_SCATTER_ELECT) {
             scatter_elect_row(job.scatter, local * kSidecarRowsPerWg + (int)threadIdx.x);

@@ -23,30 +23,7 @@ __global__ __launch_bounds__(kGatherBlock) void k_window_gather_pad(const Gather
 // front (asac_step_prologue_sample_partial: a workgroup per 256 samples) left its workgroups' minima in min_p_out[2..]; here
 // they are combined, beta advances, and the weights of all <= 1 024 rows are written — under a gather of tens of
 // microseconds instead of behind a cross-workgroup exchange inside the sampler (~1.5 us of the step's first launch).
-struct WeightsJob {
-    const float* p;            // [batch] leaf priorities of the sampled rows
-    const float* tree;         // tree[0] = total
-    double* beta_state;
-    double beta_increment;
-    float* w_out;              // [batch]
-    float* min_p_out;          // [0] <- min p; [2 .. 2 + parts) the sampler workgroups' minima
-    int32_t batch, parts;
-};
-
-__device__ __forceinline__ void weights_job(const WeightsJob& j) {
-    float bm = j.min_p_out[2];
-    for (int k = 1; k < j.parts; ++k) bm = fminf(bm, j.min_p_out[2 + k]);
-    const float root = j.tree[0];
-    const double b = fmin(1.0, *j.beta_state + j.beta_increment);
-    const float min_ratio = bm / root;
-    __syncthreads();               // every lane has read the old beta
-    for (int i = threadIdx.x; i < j.batch; i += kGatherBlock) j.w_out[i] = is_weight(j.p[i], root, min_ratio, b);
-    if (threadIdx.x == 0) {
-        *j.beta_state = b;
-        j.min_p_out[0] = bm;
-    }
-}
-
+// (WeightsJob / weights_job: asac_sidecar.h — the same workgroup also rides in the step's first network launch)
 template <int NK, int kUnroll>
 __global__ __launch_bounds__(kGatherBlock) void k_window_gather_pad_w(const GatherLaunch<NK> m, unsigned gather_blocks,
                                                                       const WeightsJob j) {
@@ -225,7 +202,7 @@ int asac_window_gather_pad_w(const asac_gather_key_t* keys_host, int n_keys, con
                              int post_n, int capacity, const int32_t* index_ring, const float* p, const float* tree,
                              double* beta_state, double beta_increment, float* is_weights_out, float* min_p_out,
                              void* stream) {
-    if (!p || !tree || !beta_state || !is_weights_out || !min_p_out || batch <= 256 || batch > 1024)
+    if (!p || !tree || !beta_state || !is_weights_out || !min_p_out || batch <= 0 || batch > 1024)
         return bad_arg("asac_window_gather_pad_w");
     GatherLaunch<ASAC_MAX_GATHER_KEYS> m{};
     uint64_t blocks = 0;
@@ -258,7 +235,7 @@ int asac_window_gather_pad_w(const asac_gather_key_t* keys_host, int n_keys, con
     return finish_launch("asac_window_gather_pad_w");
 }
 
-int64_t asac_window_gather_plan_bytes(void) { return (int64_t)sizeof(GatherLaunch<ASAC_MAX_GATHER_KEYS>); }
+int64_t asac_window_gather_plan_bytes(void) { return (int64_t)sizeof(GatherPlanDev); }
 
 int asac_window_gather_plan(const asac_gather_key_t* keys_host, int n_keys, const int64_t* ids, int batch, int prev_n,
                             int post_n, int capacity, const int32_t* index_ring, void* plan_dev, int* blocks_out) {
@@ -275,6 +252,27 @@ int asac_window_gather_plan(const asac_gather_key_t* keys_host, int n_keys, cons
         return (int)e;
     }
     *blocks_out = (int)blocks;
+    return 0;
+}
+
+int asac_window_gather_plan_w(const asac_gather_key_t* keys_host, int n_keys, const int64_t* ids, int batch, int prev_n,
+                              int post_n, int capacity, const int32_t* index_ring, const float* p, const float* tree,
+                              double* beta_state, double beta_increment, float* is_weights_out, float* min_p_out,
+                              void* plan_dev, int* blocks_out) {
+    if (!plan_dev || !blocks_out || !p || !tree || !beta_state || !is_weights_out || !min_p_out || batch <= 0 || batch > 1024)
+        return bad_arg("asac_window_gather_plan_w");
+    GatherPlanDev plan{};
+    uint64_t blocks = 0;
+    int unroll = 0;
+    if (const int rc = gather_fill(keys_host, n_keys, ids, batch, prev_n, post_n, capacity, index_ring, 1, plan.g, &blocks, &unroll))
+        return rc;
+    plan.w = WeightsJob{p, tree, beta_state, beta_increment, is_weights_out, min_p_out, batch, (batch + 255) / 256};
+    const hipError_t e = hipMemcpy(plan_dev, &plan, sizeof(plan), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        set_error(e, "asac_window_gather_plan_w");
+        return (int)e;
+    }
+    *blocks_out = (int)blocks + 1;
     return 0;
 }
 

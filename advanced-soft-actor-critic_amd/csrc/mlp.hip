@@ -485,6 +485,82 @@ __device__ __forceinline__ void fetch_input_tile_fixed(const StageScalars& q, in
     }
 }
 
+// ---- rows taken straight from the replay ring (RING instantiations): logical row r of the job is window row
+// j0 + r % T of sample r / T; column c < in0 is word c of key k0's padded row, column in0 + d word c1 + d of key k1's
+// (asac_gather.h `ring_word`: the window gather's own slot, validity test and padding — the tile holds what the gathered
+// batch would).  Two phases: the ids are requested FIRST, the weights go out right behind them (net_fetch_fixed), and
+// the rows — one round trip behind the ids, data and index ring together — travel under the weights.
+struct RingKeyArg {
+    const uint8_t *src, *pad_row;
+    int32_t row_bytes;
+    uint32_t pad_word;
+};
+struct RingArg {         // kernel-argument form
+    const int64_t* ids;
+    const int32_t* index_ring;
+    int32_t capacity, prev_n, L, j0, x_j0, x_a_off;
+    int32_t pad_mode0, pad_mode1;
+    RingKeyArg x0, action;
+};
+static_assert(sizeof(RingArg) == 96, "RingArg");
+
+struct RingStage {
+    GatherArgs g;
+    GatherKeyDev k0, k1;
+    int32_t j0, T, c1;
+};
+
+__device__ __forceinline__ GatherKeyDev ring_key(const ASAC_KARG RingKeyArg& k, int pad_mode) {
+    GatherKeyDev d{};
+    d.src = k.src, d.pad_row = k.pad_row, d.row_bytes = k.row_bytes, d.pad_word = k.pad_word, d.pad_mode = pad_mode;
+    return d;
+}
+
+template <bool X1>
+__device__ __forceinline__ RingStage ring_stage(const ASAC_KARG RingArg& r, int j0, int T, int c1) {
+    RingStage R{};
+    R.g.ids = r.ids, R.g.index_ring = r.index_ring, R.g.prev_n = r.prev_n, R.g.L = r.L, R.g.capacity = r.capacity;
+    R.k0 = ring_key(r.x0, r.pad_mode0);
+    if (X1) R.k1 = ring_key(r.action, r.pad_mode1);
+    R.j0 = j0, R.T = T, R.c1 = c1;
+    return R;
+}
+
+template <int THREADS, int SLOTS>
+__device__ __forceinline__ void ring_tile_ids(const StageScalars& q, const RingStage& R, int64_t row0, int64_t (&id)[SLOTS]) {
+#pragma unroll
+    for (int u = 0; u < SLOTS; ++u) {
+        const int r = (threadIdx.x + u * THREADS) >> 6;
+        const uint32_t row = (uint32_t)row0 + (uint32_t)r;
+        const bool live = (int64_t)row0 + r < q.N;
+        id[u] = load_id(R.g.ids, live ? (int)(row / (uint32_t)R.T) : 0);
+    }
+}
+
+template <int THREADS, int SLOTS, bool X1>
+__device__ __forceinline__ void ring_tile_rows(const StageScalars& q, const RingStage& R, int64_t row0,
+                                               const int64_t (&id)[SLOTS], float (&v)[SLOTS]) {
+    const int in0 = q.in0, in1 = X1 ? q.in1 : 0;
+#pragma unroll
+    for (int u = 0; u < SLOTS; ++u) {
+        const int i = threadIdx.x + u * THREADS;
+        const int r = i >> 6, c = i & 63;
+        const uint32_t row = (uint32_t)row0 + (uint32_t)r;
+        const bool live = (int64_t)row0 + r < q.N;
+        const uint32_t smp = row / (uint32_t)R.T;
+        const int j = live ? R.j0 + (int)(row - smp * (uint32_t)R.T) : R.g.prev_n;     // (a dead row: any valid address)
+        const bool first = c < in0;
+        uint32_t x = ring_word(R.g, R.k0, id[u], j, first ? c : 0);
+        x = (live && first) ? x : 0u;
+        if (X1) {
+            const bool second = !first && c < in0 + in1;
+            const uint32_t x1 = ring_word(R.g, R.k1, id[u], j, second ? R.c1 + (c - in0) : R.c1);
+            x = (live && second) ? x1 : x;
+        }
+        v[u] = __builtin_bit_cast(float, x);
+    }
+}
+
 template <int THREADS, int NB>
 __device__ __forceinline__ void net_fetch_fixed(const StageScalars& q, StagedNet<THREADS>& r) {
     constexpr int U = 4096 / THREADS;
@@ -579,9 +655,11 @@ inline size_t mlp_fwd_lds_bytes(int n_blocks, bool wide = false, int TM = 32) {
 // re-staging 36 KB of weights per tile would be most of the traffic).
 // EPI: a Gaussian-head policy job whose rows are sampled from (and whose stored actions are scored) by the lanes that form
 // the head (asac_squash.h `sample_epilogue`: asac_squash_multi's jobs without a launch of their own)
-template <int TM, bool WINDOW, bool WIDE = false, int NB = 0, bool EPI = false>
+// RING: the job's rows are read where they lie in the replay ring (`ring`; ring_tile_rows above)
+template <int TM, bool WINDOW, bool WIDE = false, int NB = 0, bool EPI = false, bool RING = false>
 __device__ __forceinline__ void mlp_fwd_tiles(const MlpFwdArgs& a, const int e, const int tile0, const int tile_stride,
-                                              MlpLds<TM>& L, const SampleEpi* epi = nullptr) {
+                                              MlpLds<TM>& L, const SampleEpi* epi = nullptr, const RingStage* ring = nullptr) {
+    static_assert(!RING || (NB > 0 && !WINDOW && !EPI), "ring-addressed rows: the fixed-shape path");
     constexpr int THREADS = threads_of<TM>();
     constexpr int RT = TM / 16;                               // row tiles of a workgroup tile
     constexpr bool fixed = NB > 0;                            // NB blocks of 64 (see net_fetch_fixed)
@@ -601,9 +679,12 @@ __device__ __forceinline__ void mlp_fwd_tiles(const MlpFwdArgs& a, const int e, 
     if constexpr (fixed) {
         q = stage_scalars<NB>(a, e);
         float in_lo[4];
-        fetch_input_tile_fixed<THREADS, WINDOW>(q, e, (int64_t)tile0 * TM, in_lo);
+        int64_t id_lo[4];
+        if constexpr (RING) ring_tile_ids<THREADS, 4>(q, *ring, (int64_t)tile0 * TM, id_lo);
+        else fetch_input_tile_fixed<THREADS, WINDOW>(q, e, (int64_t)tile0 * TM, in_lo);
         StagedNet<THREADS> regs;
         net_fetch_fixed<THREADS, NB>(q, regs);
+        if constexpr (RING) ring_tile_rows<THREADS, 4, true>(q, *ring, (int64_t)tile0 * TM, id_lo, in_lo);
         put_input_tile<THREADS>(in_lo, L.xs[0]);
         net_put_fixed<THREADS, NB>(regs, L);
     } else {
@@ -631,7 +712,11 @@ __device__ __forceinline__ void mlp_fwd_tiles(const MlpFwdArgs& a, const int e, 
         const bool more = tile + tile_stride < n_tiles;
         float nxt[4], nxt_hi[4];
         if (more) {
-            if constexpr (fixed) fetch_input_tile_fixed<THREADS, WINDOW>(q, e, (int64_t)(tile + tile_stride) * TM, nxt);
+            if constexpr (RING) {
+                int64_t id_nxt[4];
+                ring_tile_ids<THREADS, 4>(q, *ring, (int64_t)(tile + tile_stride) * TM, id_nxt);
+                ring_tile_rows<THREADS, 4, true>(q, *ring, (int64_t)(tile + tile_stride) * TM, id_nxt, nxt);
+            } else if constexpr (fixed) fetch_input_tile_fixed<THREADS, WINDOW>(q, e, (int64_t)(tile + tile_stride) * TM, nxt);
             else fetch_input_tile<THREADS, WINDOW>(a, e, (int64_t)(tile + tile_stride) * TM, nxt);
         }
         if (more && wide) fetch_input_tile<THREADS, WINDOW>(a, e, (int64_t)(tile + tile_stride) * TM, nxt_hi, kMaxW);
@@ -1745,8 +1830,10 @@ __device__ __forceinline__ float gauss_head_value(bool location, float raw) {
     return location ? tanhf(raw / 5.f) * 5.f : expf(fminf(fmaxf(raw, -20.f), 0.5f));
 }
 
-template <bool WINDOW>
-__device__ __forceinline__ void pi_q_tiles(const ASAC_KARG PiQLaunch& a, PiQLds& L) {
+// RING: the rows and the stored actions come from the replay ring (`ring`), not from a gathered batch
+template <bool WINDOW, bool RING = false>
+__device__ __forceinline__ void pi_q_tiles(const ASAC_KARG PiQLaunch& a, PiQLds& L, const ASAC_KARG RingArg* ring = nullptr) {
+    static_assert(!(RING && WINDOW), "ring-addressed rows have their own (sample, row) addressing");
     // eight waves: the staging (loads and LDS writes of two networks and the input tile) is dealt over 512 threads —
     // 1.5 us instead of 2.5; the forward chains have four column tiles: waves 4..7 only keep the barriers company there
     constexpr int THREADS = kPiQThreads;
@@ -1767,10 +1854,18 @@ __device__ __forceinline__ void pi_q_tiles(const ASAC_KARG PiQLaunch& a, PiQLds&
     const StageScalars sp = stage_scalars_stock(a.pi, 0);
     const StageScalars sq = stage_scalars_stock_like(a.q, e, sp);
     float in_lo[SLOTS];
-    fetch_input_tile_fixed<THREADS, WINDOW, SLOTS>(sp, 0, (int64_t)group * 16, in_lo);
+    int64_t id_lo[SLOTS];
+    RingStage R{};
+    if constexpr (RING) {
+        R = ring_stage<false>(*ring, ring->j0, a.T, 0);
+        ring_tile_ids<THREADS, SLOTS>(sp, R, (int64_t)group * 16, id_lo);
+    } else {
+        fetch_input_tile_fixed<THREADS, WINDOW, SLOTS>(sp, 0, (int64_t)group * 16, in_lo);
+    }
     StagedNet<THREADS> rp, rq;
     net_fetch_fixed<THREADS, 3>(sp, rp);
     net_fetch_fixed<THREADS, 3>(sq, rq);
+    if constexpr (RING) ring_tile_rows<THREADS, SLOTS, false>(sp, R, (int64_t)group * 16, id_lo, in_lo);
     put_input_tile<THREADS, SLOTS>(in_lo, L.xs[0]);
     net_put_fixed<THREADS, 3>(rp, L);
     // (critic e's weights stay in registers until the policy has run: its 36 KB are still travelling when the policy's
@@ -1782,10 +1877,31 @@ __device__ __forceinline__ void pi_q_tiles(const ASAC_KARG PiQLaunch& a, PiQLds&
     for (int tile = group; tile < n_tiles; tile += a.tile_groups) {
         const int row0 = tile * 16;
         if (tile != group) {       // (later tiles of a looping workgroup: the first one arrived with the weights)
-            fetch_input_tile_fixed<THREADS, WINDOW, SLOTS>(sp, 0, row0, in_lo);
+            if constexpr (RING) {
+                ring_tile_ids<THREADS, SLOTS>(sp, R, row0, id_lo);
+                ring_tile_rows<THREADS, SLOTS, false>(sp, R, row0, id_lo, in_lo);
+            } else {
+                fetch_input_tile_fixed<THREADS, WINDOW, SLOTS>(sp, 0, row0, in_lo);
+            }
             __syncthreads();
             put_input_tile<THREADS, SLOTS>(in_lo, L.xs[0]);
             __syncthreads();
+        }
+        // (ring-addressed: the stored actions wave 1 will score — 16 A <= 128 items, two per lane — are requested now:
+        // their id -> row chain travels under the policy's layers.  Every wave issues the loads, from addresses that are
+        // always valid: straight-line code — inside a branch the block cost the kernel a private segment)
+        float av_ring[2] = {0.f, 0.f};
+        if constexpr (RING) {
+            const RingStage Ra = ring_stage<true>(*ring, ring->j0, a.sp.T, a.sp.action ? a.sp.a_off : 0);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int it = min(lane + 64 * h, 16 * A - 1);
+                const int lrow = it / A, d = it - lrow * A;
+                const int r = min(row0 + lrow, N - 1);
+                const int sb = (int)((unsigned)r / (unsigned)Ra.T), st = r - sb * Ra.T;
+                av_ring[h] = __builtin_bit_cast(float, ring_word(Ra.g, Ra.k1, load_id(Ra.g.ids, sb), Ra.j0 + st,
+                                                                 a.sp.action ? Ra.c1 + d : 0));
+            }
         }
         // ---- policy forward ----------------------------------------------------------------------------------------
         int cur = 0;
@@ -1847,7 +1963,9 @@ __device__ __forceinline__ void pi_q_tiles(const ASAC_KARG PiQLaunch& a, PiQLds&
                     if (job == 1) {
                         const int spT = a.sp.T;
                         const int sb = (int)((unsigned)r / (unsigned)spT), st = r - sb * spT;
-                        const float av = a.sp.action[sb * a.sp.a_sb + st * a.sp.a_st + a.sp.a_off + d];
+                        float av;
+                        if constexpr (RING) av = it < 64 ? av_ring[0] : av_ring[1];
+                        else av = a.sp.action[sb * a.sp.a_sb + st * a.sp.a_st + a.sp.a_off + d];
                         const float x = atanhf(fminf(fmaxf(av, -0.999f), 0.999f));
                         s0[lrow * 8 + d] = squash_jac(x);
                         s1[lrow * 8 + d] = expf(normal_log_prob(x, l, sc));
@@ -1993,6 +2111,49 @@ __global__ __launch_bounds__(kPiQThreads) void k_pi_sample_q(const PiQLaunch m_b
         mlp_fwd_tiles<16, true, false, 3>(job, local % E, local / E, m.x_tile_stride[k], L);
     else
         mlp_fwd_tiles<16, false, false, 3>(job, local % E, local / E, m.x_tile_stride[k], L);
+}
+
+// ... with ring-addressed rows (asac_ring_rows_t): a kernel of its own — the one above stays what it was.  The ring
+// description follows the launch description in the argument block (+96 bytes).
+struct PiQLaunchRing {
+    PiQLaunch m;
+    RingArg ring;
+};
+static_assert(offsetof(PiQLaunchRing, m) == 0 && sizeof(PiQLaunchRing) <= 768, "kernel arguments of k_pi_sample_q_ring");
+
+template <int NSC>
+__global__ __launch_bounds__(kPiQThreads) void k_pi_sample_q_ring(const PiQLaunchRing m_by_value, const SidecarsT<NSC> sc) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const ASAC_KARG PiQLaunchRing& mr = *static_cast<const ASAC_KARG PiQLaunchRing*>(kernarg_base());
+    const ASAC_KARG PiQLaunch& m = mr.m;
+    const int blk = (int)blockIdx.x;
+    const int fused_blocks = m.blocks;
+    if (blk >= fused_blocks && threadIdx.x >= 256) return;
+    if (blk < fused_blocks) {
+        pi_q_tiles<false, true>(m, *reinterpret_cast<PiQLds*>(smem_raw), &mr.ring);
+        return;
+    }
+    const int xb = blk - fused_blocks;
+    if (xb >= m.x_blocks) {
+        sidecar_run<NSC, true, true>(sc, xb - m.x_blocks, reinterpret_cast<float*>(smem_raw));
+        return;
+    }
+    int k = 0;
+#pragma unroll
+    for (int q = 1; q < ASAC_MLP_MAX_JOBS; ++q)
+        if (q < m.x_n && xb >= m.x_first_block[q]) k = q;
+    const int local = xb - m.x_first_block[k];
+    const int E = m.x_E[k];
+    MlpLds<16>& L = *reinterpret_cast<MlpLds<16>*>(smem_raw);
+    const MlpFwdArgs job = expand_stock(m.x_job[k]);
+    if (k == 0 && mr.ring.x_j0 >= 0) {       // one row per sample, window row x_j0: (state | stored action)
+        const RingStage R = ring_stage<true>(mr.ring, mr.ring.x_j0, 1, mr.ring.x_a_off);
+        mlp_fwd_tiles<16, false, false, 3, false, true>(job, local % E, local / E, m.x_tile_stride[k], L, nullptr, &R);
+    } else if (job.x0_T > 0) {
+        mlp_fwd_tiles<16, true, false, 3>(job, local % E, local / E, m.x_tile_stride[k], L);
+    } else {
+        mlp_fwd_tiles<16, false, false, 3>(job, local % E, local / E, m.x_tile_stride[k], L);
+    }
 }
 
 // grad[e*stride + i] (+)= sum_tiles partial[tile][e][i]   (fixed order: deterministic)
@@ -2534,6 +2695,29 @@ static asac_mlp_job_t pi_rows(const asac_mlp_job_t& p) {
     return r;
 }
 
+// a key the ring-addressed instantiations can read: float32 words, a padding the gather's `pad_value` forms per word
+static bool ring_key_ok(const asac_ring_key_t& k, int first_col, int cols) {
+    if (!k.src || k.row_bytes <= 0 || k.row_bytes % 4 != 0 || k.row_bytes > (1 << 20) ||
+        reinterpret_cast<uintptr_t>(k.src) % 4 != 0)
+        return false;
+    if (first_col < 0 || cols <= 0 || (int64_t)(first_col + cols) * 4 > k.row_bytes) return false;
+    if (k.pad_mode == ASAC_PAD_ROW) return k.pad_row && reinterpret_cast<uintptr_t>(k.pad_row) % 4 == 0;
+    return k.pad_mode == ASAC_PAD_KEEP || k.pad_mode == ASAC_PAD_WORD;
+}
+
+// the ring description of a fused job (asac_ring_rows_t; the extra job's part: asac_policy_sample_q_forward)
+static bool ring_rows_ok(const asac_pi_q_job_t& j) {
+    const asac_ring_rows_t& r = j.ring;
+    const asac_squash_job_t& s = j.sample;
+    if (!r.ids || !r.index_ring || r.capacity <= 0 || r.prev_n < 0 || r.L <= r.prev_n) return false;
+    if (s.T <= 0 || j.pi.N % s.T != 0 || r.j0 < 0 || r.j0 + s.T > r.L) return false;
+    if (j.pi.x0_window_T != 0 && j.pi.x0_window_T != s.T) return false;
+    if (!ring_key_ok(r.x0, 0, j.pi.desc->in0)) return false;
+    if ((s.action || r.x_j0 >= 0) && !ring_key_ok(r.action, 0, 1)) return false;
+    if (s.action && !ring_key_ok(r.action, s.action_offset, s.A)) return false;
+    return r.x_j0 < r.L;
+}
+
 static bool pi_q_job_ok(const asac_pi_q_job_t& j) {
     const asac_mlp_job_t &p = j.pi, &q = j.q;
     if (!p.desc || !q.desc || !desc_ok(*p.desc) || !desc_ok(*q.desc) || p.N <= 0 || q.N != p.N || p.E != 1 || q.E < 1) return false;
@@ -2552,17 +2736,42 @@ static bool pi_q_job_ok(const asac_pi_q_job_t& j) {
     if (s.action && (!fits32((p.N / s.T + 1) * s.action_stride_b) || !fits32((p.N / s.T + 1) * s.prob_stride_b) ||
                      !fits32(s.T * s.action_stride_t) || !fits32(s.T * s.prob_stride_t)))
         return false;
-    return job_fits32(pi_rows(p));
+    return job_fits32(pi_rows(p)) && (!j.ring.ids || ring_rows_ok(j));
+}
+
+// the plain forward jobs riding along, and what the ring description says about the first of them
+static bool pi_q_extras_ok(const asac_pi_q_job_t& job, const asac_mlp_job_t* extra_jobs, int n_extra) {
+    if (n_extra < 0 || n_extra > ASAC_MLP_MAX_JOBS || (n_extra > 0 && !extra_jobs)) return false;
+    for (int k = 0; k < n_extra; ++k) {
+        const asac_mlp_job_t& j = extra_jobs[k];
+        if (!job_ok(j, true) || !stock3(*j.desc, j.params, j.member_stride) || j.x0_window_T < 0 || !job_fits32(j) ||
+            !fits32(j.member_stride) || !fits32(j.x0_member_stride) || !fits32(j.x1_member_stride))
+            return false;
+    }
+    const asac_ring_rows_t& r = job.ring;
+    if (r.ids && r.x_j0 >= 0) {       // extra job 0: one (state | stored action) row per sample, read from the ring
+        if (n_extra < 1) return false;
+        const asac_mlp_job_t& x = extra_jobs[0];
+        if (x.x0_window_T != 0 || x.x0_member_stride != 0 || x.x1_member_stride != 0 || x.N != job.pi.N / job.sample.T ||
+            x.desc->in1 <= 0 || !ring_key_ok(r.x0, 0, x.desc->in0) || !ring_key_ok(r.action, r.x_action_offset, x.desc->in1))
+            return false;
+    }
+    return true;
 }
 
 int asac_policy_sample_q_forward_ok(const asac_pi_q_job_t* job) { return job && pi_q_job_ok(*job) ? 1 : 0; }
 
+int asac_policy_sample_q_forward_jobs_ok(const asac_pi_q_job_t* job, const asac_mlp_job_t* extra_jobs, int n_extra) {
+    return job && pi_q_job_ok(*job) && pi_q_extras_ok(*job, extra_jobs, n_extra) ? 1 : 0;
+}
+
 int asac_policy_sample_q_forward(const asac_pi_q_job_t* job, const asac_mlp_job_t* extra_jobs, int n_extra,
                                  const asac_sidecar_t* sidecars_host, int n_sidecars, void* stream) {
-    if (!job || !pi_q_job_ok(*job) || n_extra < 0 || n_extra > ASAC_MLP_MAX_JOBS || (n_extra > 0 && !extra_jobs))
-        return bad_arg("asac_policy_sample_q_forward");
+    if (!job || !pi_q_job_ok(*job)) return bad_arg("asac_policy_sample_q_forward");
+    if (!pi_q_extras_ok(*job, extra_jobs, n_extra)) return bad_arg("asac_policy_sample_q_forward: extra job");
     SidecarsDev sc{};
-    if (sidecars_prepare(sidecars_host, n_sidecars, sc)) return bad_arg("asac_policy_sample_q_forward: sidecar");
+    if (sidecars_prepare(sidecars_host, n_sidecars, sc, job->ring.ids != nullptr))
+        return bad_arg("asac_policy_sample_q_forward: sidecar");
     PiQLaunch m{};
     const asac_mlp_job_t p = pi_rows(job->pi);
     asac_mlp_job_t q = pi_rows(job->q);         // (its rows are the policy's: pi_q_job_ok)
@@ -2589,9 +2798,6 @@ int asac_policy_sample_q_forward(const asac_pi_q_job_t* job, const asac_mlp_job_
     int blocks = 0;
     for (int k = 0; k < n_extra; ++k) {
         const asac_mlp_job_t& j = extra_jobs[k];
-        if (!job_ok(j, true) || !stock3(*j.desc, j.params, j.member_stride) || j.x0_window_T < 0 || !job_fits32(j) ||
-            !fits32(j.member_stride) || !fits32(j.x0_member_stride) || !fits32(j.x1_member_stride))
-            return bad_arg("asac_policy_sample_q_forward: extra job");
         m.x_job[k] = stock_job_arg(j);
         m.x_E[k] = j.E;
         m.x_first_block[k] = blocks;
@@ -2599,6 +2805,39 @@ int asac_policy_sample_q_forward(const asac_pi_q_job_t* job, const asac_mlp_job_
         blocks += m.x_tile_stride[k] * j.E;
     }
     m.x_blocks = blocks;
+    if (job->ring.ids) {
+        const asac_ring_rows_t& r = job->ring;
+        PiQLaunchRing mr{};
+        mr.m = m;
+        if (sj.action) mr.m.sp.action = static_cast<const float*>(r.action.src);       // (non-NULL: the job is on)
+        // (no action key: the kernel's speculative stored-action loads read word 0 of the observation key's rows)
+        const asac_ring_key_t& ak = (sj.action || r.x_j0 >= 0) ? r.action : r.x0;
+        mr.ring = RingArg{r.ids, r.index_ring, r.capacity, r.prev_n, r.L, r.j0, r.x_j0, r.x_action_offset,
+                          r.x0.pad_mode, ak.pad_mode,
+                          RingKeyArg{static_cast<const uint8_t*>(r.x0.src), static_cast<const uint8_t*>(r.x0.pad_row),
+                                     r.x0.row_bytes, r.x0.pad_word},
+                          RingKeyArg{static_cast<const uint8_t*>(ak.src), static_cast<const uint8_t*>(ak.pad_row), ak.row_bytes,
+                                     ak.pad_word}};
+        static bool ring_attr = false, ring_attr1 = false;
+        if (int rc = set_lds_limit(reinterpret_cast<const void*>(k_pi_sample_q_ring<ASAC_MAX_SIDECARS>), sizeof(PiQLds),
+                                   ring_attr, "asac_policy_sample_q_forward: hipFuncSetAttribute"))
+            return rc;
+        if (int rc = set_lds_limit(reinterpret_cast<const void*>(k_pi_sample_q_ring<1>), sizeof(PiQLds), ring_attr1,
+                                   "asac_policy_sample_q_forward: hipFuncSetAttribute"))
+            return rc;
+        const SidecarsDev no_sc{};
+        for (int rep = 0; rep < g_launch_repeat; ++rep) {
+            const bool last = rep == g_launch_repeat - 1;
+            const dim3 grid((unsigned)(m.blocks + blocks + (last ? sc.blocks : 0)));
+            if (sc.n <= 1)
+                hipLaunchKernelGGL(k_pi_sample_q_ring<1>, grid, dim3(kPiQThreads), sizeof(PiQLds), as_stream(stream), mr,
+                                   sidecars_first<1>(last ? sc : no_sc));
+            else
+                hipLaunchKernelGGL(k_pi_sample_q_ring<ASAC_MAX_SIDECARS>, grid, dim3(kPiQThreads), sizeof(PiQLds),
+                                   as_stream(stream), mr, last ? sc : no_sc);
+        }
+        return finish_launch("asac_policy_sample_q_forward");
+    }
     static bool attr_done = false;
     static bool attr_done1 = false;
     if (int rc = set_lds_limit(reinterpret_cast<const void*>(k_pi_sample_q<ASAC_MAX_SIDECARS>), sizeof(PiQLds), attr_done,

@@ -252,11 +252,12 @@ __device__ __forceinline__ void sumtree_sample_body(
     float m = wave_min(pmin);
     if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = m;
     __syncthreads();
-    SampleSync* const sync = MULTI ? reinterpret_cast<SampleSync*>(min_p_out + 2) : nullptr;
+    SampleSync* const sync = (MULTI || PARTIAL) ? reinterpret_cast<SampleSync*>(min_p_out + 2) : nullptr;
     const unsigned n_wg = MULTI ? (unsigned)((batch + kSampleBlock - 1) / kSampleBlock) : 1u;
     if (PARTIAL) {
-        // the weights are formed by a workgroup of the NEXT launch (asac_window_gather_pad_w, beside the gather): this
-        // workgroup's minimum is all that is left to hand over — no exchange, no power, no beta here
+        // the weights are formed by a workgroup of a LATER launch (asac_window_gather_pad_w, beside the gather; a one-workgroup
+        // batch: a rider of the step's first network launch, ASAC_SIDECAR_WINDOW_GATHER_W): this workgroup's minimum is
+        // all that is left to hand over — no exchange, no power, no beta here
         if (threadIdx.x == 0) {
             float bm = red[0];
             for (int w = 1; w < kSampleBlock / kWave; ++w) bm = fminf(bm, red[w]);
@@ -361,7 +362,7 @@ __global__ __launch_bounds__(kSampleBlock) void k_prologue_sample(
         // (thirteen staged levels, 32 KB: trees of 2^16 / 2^19 leaves keep 3 / 6 levels for memory — one / two round trips
         // of three levels each, one less than with twelve; the launch has a handful of other workgroups, LDS is free)
         if (n_s == 1)
-            sumtree_sample_body<true, true, true, false, 1, false, 13>(
+            sumtree_sample_body<true, true, true, false, 1, false, 13, PARTIAL>(
                 tree, capacity, levels, batch, pa.u, slot_ids, beta_state, beta_increment, leaf_out, p_out, ids_out, w_out,
                 min_p_out, dr);
         else
@@ -758,7 +759,6 @@ int asac_step_prologue_sample_partial(float* target, const float* source, int64_
                                       float* normal_out, int64_t n_normal, int32_t* subsets_out, int n_subsets, int E_sample,
                                       int E, const float* tree, int capacity, int batch, const int64_t* slot_ids,
                                       int32_t* leaf_out, float* p_out, int64_t* ids_out, float* min_p_out, void* stream) {
-    if (batch <= kSampleBlock) return bad_arg("asac_step_prologue_sample_partial: one workgroup samples such a batch whole");
     static double unused_beta = 0.0;      // (never dereferenced in the partial form)
     return prologue_sample_launch(target, source, n_polyak, tau, zero_out, n_zero, seed, step_counter, uniform_out, normal_out,
                                   n_normal, subsets_out, n_subsets, E_sample, E, tree, capacity, batch, slot_ids, &unused_beta,

@@ -14,7 +14,7 @@ PKG_DIR = Path(__file__).resolve().parent
 import os as _os
 
 LIB_PATH = Path(_os.environ.get('ASAC_HIP_LIB', PKG_DIR / 'lib' / 'libasac_hip.so'))   # env override: debugging builds
-ABI_VERSION = 88
+ABI_VERSION = 89
 
 MAX_GATHER_KEYS = 16
 PAD_KEEP, PAD_WORD, PAD_BYTE, PAD_ROW, PAD_EMIT_MASK = 0, 1, 2, 3, 4
@@ -144,6 +144,7 @@ class Sidecar(C.Structure):
 
 
 SIDECAR_ALPHA_ADAM, SIDECAR_SCATTER_ELECT, SIDECAR_SCATTER_WRITE, SIDECAR_WINDOW_GATHER, MAX_SIDECARS = 1, 2, 3, 4, 4
+SIDECAR_WINDOW_GATHER_W = 5
 
 
 class SquashJob(C.Structure):
@@ -158,10 +159,23 @@ class SquashJob(C.Structure):
 SQUASH_MAX_JOBS = 4
 
 
+class RingKey(C.Structure):
+    """asac_ring_key_t: a float32 key of the replay ring as a ring-addressed launch reads it"""
+    _fields_ = [('src', C.c_void_p), ('pad_row', C.c_void_p), ('row_bytes', C.c_int32), ('pad_mode', C.c_int32),
+                ('pad_word', C.c_uint32), ('reserved_', C.c_int32)]
+
+
+class RingRows(C.Structure):
+    """asac_ring_rows_t: `policy_sample_q_forward` takes its rows from the replay ring (ids None: off)"""
+    _fields_ = [('ids', C.c_void_p), ('index_ring', C.c_void_p), ('capacity', C.c_int32), ('prev_n', C.c_int32),
+                ('L', C.c_int32), ('j0', C.c_int32), ('x_j0', C.c_int32), ('x_action_offset', C.c_int32),
+                ('x0', RingKey), ('action', RingKey)]
+
+
 class PiQJob(C.Structure):
     """asac_pi_q_job_t: policy forward -> sampling -> critics forward over the same rows"""
     _fields_ = [('pi', MlpJob), ('sample', SquashJob), ('eps2', C.c_void_p), ('t2', C.c_int32), ('reserved_', C.c_int32),
-                ('a2_out', C.c_void_p), ('logp2_out', C.c_void_p), ('q', MlpJob)]
+                ('a2_out', C.c_void_p), ('logp2_out', C.c_void_p), ('q', MlpJob), ('ring', RingRows)]
 
 
 class SampleEpilogue(C.Structure):
@@ -221,6 +235,9 @@ _SIGNATURES = {
     'asac_window_gather_plan_bytes': (C.c_int64, []),
     'asac_window_gather_plan': (C.c_int, [C.POINTER(GatherKey), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    'asac_window_gather_plan_w': (C.c_int, [C.POINTER(GatherKey), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     'asac_sumtree_descend': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     'asac_gather_rows': (C.c_int, [C.POINTER(GatherKey), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -279,6 +296,7 @@ _SIGNATURES = {
                                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     'asac_struct_size': (C.c_int64, [C.c_char_p]),
     'asac_policy_sample_q_forward_ok': (C.c_int, [C.POINTER(PiQJob)]),
+    'asac_policy_sample_q_forward_jobs_ok': (C.c_int, [C.POINTER(PiQJob), C.POINTER(MlpJob), C.c_int]),
     'asac_policy_sample_q_forward': (C.c_int, [C.POINTER(PiQJob), C.POINTER(MlpJob), C.c_int, C.POINTER(Sidecar), C.c_int,
                                                C.c_void_p]),
     'asac_policy_step_fused_ok': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.POINTER(MlpDesc), C.c_void_p,
@@ -726,6 +744,22 @@ def sidecar_window_gather(keys, ids, batch, prev_n, post_n, capacity, index_ring
     return sc
 
 
+def sidecar_window_gather_w(keys, ids, batch, prev_n, post_n, capacity, index_ring, p, tree, beta_state, beta_increment,
+                            is_weights_out, min_p_out) -> Sidecar:
+    """`window_gather_pad_w` as a sidecar job (hosted by `policy_sample_q_forward` with ring-addressed rows): the gather and,
+    as one more workgroup, the IS weights of the batch `step_prologue_sample_partial` drew.  Build time, as
+    `sidecar_window_gather`."""
+    import torch
+    plan = torch.empty(int(load().asac_window_gather_plan_bytes()), dtype=torch.uint8, device=ids.device)
+    blocks = C.c_int(0)
+    _check(load().asac_window_gather_plan_w(keys, len(keys), _p(ids), batch, prev_n, post_n, capacity, _p(index_ring), _p(p),
+                                            _p(tree), _p(beta_state), float(beta_increment), _p(is_weights_out),
+                                            _p(min_p_out), _p(plan), C.byref(blocks)), 'asac_window_gather_plan_w')
+    sc = Sidecar(kind=SIDECAR_WINDOW_GATHER_W, gather_plan=_p(plan), gather_blocks=blocks.value)
+    sc._keep = (plan, keys, ids, index_ring, p, tree, beta_state, is_weights_out, min_p_out)
+    return sc
+
+
 @_profiled
 def gather_rows(keys, ids, capacity):
     """dst_key[r] = ring_key[ids[r] % capacity] for every key of `keys` (all PAD_KEEP) in one launch"""
@@ -1149,8 +1183,47 @@ def pi_q_job(pi_job: MlpJob, q_job: MlpJob, eps, a_out, logp_out, T, action=None
     return j
 
 
-def policy_sample_q_forward_ok(job: PiQJob) -> bool:
-    return bool(load().asac_policy_sample_q_forward_ok(C.byref(job)))
+def ring_key(spec) -> RingKey | None:
+    """a gather key spec (`make_gather_keys`) as a key of `pi_q_ring_rows`; None: not a plain float32 key (converted,
+    derived, a mask, rows that are no whole words)"""
+    src = spec.get('src')
+    if (src is None or src.dtype != torch.float32 or spec.get('convert', CVT_NONE) != CVT_NONE or spec.get('derive', 0)
+            or spec['pad_mode'] not in (PAD_KEEP, PAD_WORD, PAD_ROW) or int(spec['row_bytes']) % 4):
+        return None
+    k = RingKey()
+    k.src, k.row_bytes, k.pad_mode = src.data_ptr(), int(spec['row_bytes']), int(spec['pad_mode'])
+    k.pad_word = int(spec.get('pad_word', 0)) & 0xffffffff
+    if spec['pad_mode'] == PAD_ROW:
+        k.pad_row = spec['pad_row'].data_ptr()
+    return k
+
+
+def pi_q_ring_rows(job: PiQJob, ids, index_ring, capacity, prev_n, L, j0, x0_key: RingKey, action_key: RingKey | None = None,
+                   x_j0=-1, x_action_offset=0) -> PiQJob:
+    """-> a copy of `job` (from `pi_q_job`) whose rows — the policy's / critics' x0 and, with `action_key`, the stored
+    actions — are read where they lie in the replay ring: row r of the job is window row j0 + r % T of sample r // T, as
+    `window_gather_pad` would have delivered it.  `x_j0 >= 0`: the first extra job of the launch reads (x0 | stored
+    action) of window row x_j0 of every sample the same way.  Raw pointers: keep the tensors alive."""
+    assert ids.dtype == torch.int64 and index_ring.dtype == torch.int32
+    out = PiQJob()
+    C.memmove(C.byref(out), C.byref(job), C.sizeof(PiQJob))
+    r = out.ring
+    r.ids, r.index_ring = ids.data_ptr(), index_ring.data_ptr()
+    r.capacity, r.prev_n, r.L, r.j0, r.x_j0, r.x_action_offset = capacity, prev_n, L, j0, x_j0, x_action_offset
+    r.x0 = x0_key
+    if action_key is not None:
+        r.action = action_key
+    return out
+
+
+def policy_sample_q_forward_ok(job: PiQJob, extra_jobs=None) -> bool:
+    """the launch qualifies; with `extra_jobs` also they, and what `job`'s ring description says about the first of them:
+    exactly what `policy_sample_q_forward(job, extra_jobs)` accepts"""
+    if extra_jobs is None:
+        return bool(load().asac_policy_sample_q_forward_ok(C.byref(job)))
+    extra_jobs = list(extra_jobs)
+    arr = (MlpJob * len(extra_jobs))(*extra_jobs) if extra_jobs else None
+    return bool(load().asac_policy_sample_q_forward_jobs_ok(C.byref(job), arr, len(extra_jobs)))
 
 
 @_profiled
@@ -1937,10 +2010,11 @@ def step_prologue_sample(polyak, zero, seed, step_counter, uniform_out, normal_o
 @_profiled
 def step_prologue_sample_partial(polyak, zero, seed, step_counter, uniform_out, normal_out, subsets_out, ensemble, tree,
                                  capacity, batch, slot_ids, leaf_out, p_out, ids_out, min_p_out):
-    """`step_prologue_sample` for 256 < batch <= 1024 without the weights: the sampler workgroups leave their minima in
-    `min_p_out[2:]`; `window_gather_pad_w` (the next launch) forms the weights and advances beta"""
+    """`step_prologue_sample` without the weights: the sampler workgroups leave their minima in `min_p_out[2:]`;
+    `window_gather_pad_w` (the next launch; 256 < batch <= 1024) or its sidecar form `sidecar_window_gather_w` (a rider of
+    the step's first network launch) forms the weights and advances beta"""
     target_flat, source_flat, tau = polyak if polyak is not None else (None, None, 0.0)
-    assert uniform_out.numel() == batch and uniform_out.dtype == torch.float64 and 256 < batch <= PROLOGUE_SAMPLE_MAX_BATCH
+    assert uniform_out.numel() == batch and uniform_out.dtype == torch.float64 and 0 < batch <= PROLOGUE_SAMPLE_MAX_BATCH
     assert min_p_out.numel() >= 528 and min_p_out.dtype == torch.float32
     assert zero is None or (zero.is_contiguous() and zero.dtype == torch.float32)
     nn_ = 0 if normal_out is None else normal_out.numel()

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ASAC_ABI_VERSION 88
+#define ASAC_ABI_VERSION 89
 #define ASAC_MAX_GATHER_KEYS 16
 #define ASAC_MAX_ENSEMBLE 16
 #define ASAC_MAX_ACTION 64
@@ -203,6 +203,13 @@ int64_t asac_window_gather_plan_bytes(void);
 int asac_window_gather_plan(const asac_gather_key_t* keys_host, int n_keys, const int64_t* ids, int batch, int prev_n,
                             int post_n, int capacity, const int32_t* index_ring, void* plan_dev, int* blocks_out);
 
+/* ... with the batch's IS weights as one more workgroup (the arguments of asac_window_gather_pad_w), for an
+ * ASAC_SIDECAR_WINDOW_GATHER_W job.  plan_dev: asac_window_gather_plan_bytes() bytes. */
+int asac_window_gather_plan_w(const asac_gather_key_t* keys_host, int n_keys, const int64_t* ids, int batch, int prev_n,
+                              int post_n, int capacity, const int32_t* index_ring, const float* p, const float* tree,
+                              double* beta_state, double beta_increment, float* is_weights_out, float* min_p_out,
+                              void* plan_dev, int* blocks_out);
+
 int asac_gather_rows(const asac_gather_key_t* keys_host, int n_keys, const int64_t* ids, int n_rows, int capacity,
                      void* stream);
 
@@ -307,6 +314,10 @@ int asac_squash_sample_bwd(const float* loc, const float* scale, int64_t ls_row_
 #define ASAC_SIDECAR_SCATTER_ELECT 2
 #define ASAC_SIDECAR_SCATTER_WRITE 3
 #define ASAC_SIDECAR_WINDOW_GATHER 4
+/*   ASAC_SIDECAR_WINDOW_GATHER_W a plan made by asac_window_gather_plan_w: the gather and, as its first workgroup, the
+ *                                IS weights of the batch asac_step_prologue_sample_partial drew (asac_window_gather_pad_w
+ *                                as a rider); hosted by asac_policy_sample_q_forward with ring-addressed rows only */
+#define ASAC_SIDECAR_WINDOW_GATHER_W 5
 #define ASAC_MAX_SIDECARS 4
 typedef struct {
     int32_t kind;
@@ -559,7 +570,34 @@ int asac_mlp_forward_multi_sampled(const asac_mlp_job_t* jobs_host, int n_jobs, 
  *           out [E][N]
  * extra_jobs: up to ASAC_MLP_MAX_JOBS plain forward passes (three 64-wide blocks) riding as further workgroups;
  * sidecars as asac_mlp_forward_multi.  asac_policy_sample_q_forward_ok: 1 when `job` qualifies (both networks three
- * 64-wide blocks on <= 64 inputs, 16-byte aligned weights, scalar-head critics on (in0 | A), Gaussian-head policy). */
+ * 64-wide blocks on <= 64 inputs, 16-byte aligned weights, scalar-head critics on (in0 | A), Gaussian-head policy).
+ *
+ * Ring-addressed rows (`ring`, ids != NULL): the launch reads its input rows where they lie in the replay ring instead of
+ * from a gathered batch — the values asac_window_gather_pad would have delivered, bit for bit (same slot, validity test and
+ * padding), so the gather of the very batch the launch works on can ride in it as an ASAC_SIDECAR_WINDOW_GATHER job.
+ * Logical row r of the fused job is window row j0 + r % T of sample r / T (T = sample.T, N = batch * T):
+ *   x0       the key pi.x0 / q.x0 are taken from (float32 rows of >= in0 columns; their x0 addressing is ignored)
+ *   action   the key sample.action is taken from (columns action_offset .. + A), when sample.action is set
+ * x_j0 >= 0: extra_jobs[0] too reads rows of the ring — one per sample, window row x_j0: x0 from key `x0`, x1 from
+ * columns x_action_offset .. + in1 of key `action` (the stored pair of the clipped double-Q loss).  Keys are plain
+ * float32 keys of the gather (no conversion, not derived); pad_mode ASAC_PAD_KEEP, ASAC_PAD_WORD or ASAC_PAD_ROW. */
+typedef struct {
+    const void* src;      /* the key's ring [capacity][row_bytes] */
+    const void* pad_row;  /* ASAC_PAD_ROW only */
+    int32_t row_bytes;
+    int32_t pad_mode;
+    uint32_t pad_word;
+    int32_t reserved_;
+} asac_ring_key_t;
+typedef struct {
+    const int64_t* ids;         /* [batch] sampled ids; NULL: rows are read as the jobs describe them */
+    const int32_t* index_ring;  /* i32[capacity] the stored 'index' column */
+    int32_t capacity, prev_n, L;
+    int32_t j0;                 /* first window row of the fused job's rows */
+    int32_t x_j0;               /* window row of extra_jobs[0]'s rows; < 0: that job reads memory as it says */
+    int32_t x_action_offset;
+    asac_ring_key_t x0, action;
+} asac_ring_rows_t;
 typedef struct {
     asac_mlp_job_t pi;
     asac_squash_job_t sample;
@@ -569,8 +607,12 @@ typedef struct {
     float* a2_out;
     float* logp2_out;
     asac_mlp_job_t q;
+    asac_ring_rows_t ring;
 } asac_pi_q_job_t;
 int asac_policy_sample_q_forward_ok(const asac_pi_q_job_t* job);
+/* ... and the extra jobs with it, the ring description of the first one included (x_j0, x_action_offset, one row per
+ * sample): 1 exactly when asac_policy_sample_q_forward accepts the three arguments. */
+int asac_policy_sample_q_forward_jobs_ok(const asac_pi_q_job_t* job, const asac_mlp_job_t* extra_jobs, int n_extra);
 int asac_policy_sample_q_forward(const asac_pi_q_job_t* job, const asac_mlp_job_t* extra_jobs, int n_extra,
                                  const asac_sidecar_t* sidecars_host, int n_sidecars, void* stream);
 
@@ -1201,7 +1243,8 @@ int asac_step_prologue_sample(float* target, const float* source, int64_t n_poly
                               double* beta_state, double beta_increment, int32_t* leaf_out, float* p_out,
                               int64_t* ids_out, float* is_weights_out, float* min_p_out, void* stream);
 
-/* The pair for batches of 257 .. 1 024 rows on one GPU (hip_config['defer_is_weights']): the sampler's workgroups (256
+/* The pair for batches of 257 .. 1 024 rows on one GPU (hip_config['defer_is_weights']; smaller batches too where the weights
+ * ride in the step's first network launch, ASAC_SIDECAR_WINDOW_GATHER_W): the sampler's workgroups (256
  * samples each) only leave their minima in min_p_out[2 ..] — no exchange between them, no weights, beta untouched —, and
  * asac_window_gather_pad_w, the NEXT launch, forms the weights in one extra workgroup beside the gather's (minimum over the
  * workgroups' minima, beta advanced first, f64 power: replay_buffer.py:352-354), min_p_out[0] = min p.  Same numbers as

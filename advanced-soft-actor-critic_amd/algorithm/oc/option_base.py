@@ -80,6 +80,7 @@ class OptionBase(SAC_Base):
         # the option's discrete branches stay on the eager arithmetic (its own `_get_y` / `_get_td_error` mix the
         # termination in; the parent's one-launch discrete path is the plain learner's)
         self._fused_discrete = False
+        self._fused_dqn = False         # (its own `get_dqn_like_d_y` mixes the termination in as well)
 
     # -- construction (option_base.py:27-86) ----------------------------------------------------------------------------
     def _sample_thread(self):

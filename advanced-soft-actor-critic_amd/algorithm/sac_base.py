@@ -102,6 +102,18 @@ def fused_discrete_applies(*, enabled, plain_learner, d_action_sizes, c_action_s
                 and native.discrete_sizes_ok(d_action_sizes, ensemble_q_num, n_step, batch_size))
 
 
+def fused_dqn_applies(*, enabled, plain_learner, d_action_sizes, c_action_size, discrete_dqn_like, offline_loss, siamese,
+                      use_prediction, curiosity, data_parallel, float32_on_device, ensemble_q_num, n_step, batch_size) -> bool:
+    """Does a step of this configuration run the pure-discrete, DQN-like learner's arithmetic on the `asac_dqn_*`
+    launches (`hip_config['fused_dqn']`)?  Only a plain `SAC_Base` step (`plain_learner`: not an `OptionBase`) with
+    discrete branches alone and `discrete_dqn_like`, without an offline loss, a siamese or a prediction head, curiosity or
+    a data-parallel context, on float32 device tensors, within the entry points' size limits.  Everything else runs the
+    eager code."""
+    return bool(enabled and plain_learner and len(d_action_sizes) > 0 and c_action_size == 0 and discrete_dqn_like
+                and not offline_loss and not siamese and not use_prediction and not curiosity and not data_parallel
+                and float32_on_device and native.discrete_sizes_ok(d_action_sizes, ensemble_q_num, n_step, batch_size))
+
+
 class _Window:
     """views of the step's static batch tensors and what the phases of `_device_step_body` hand to each other"""
 
@@ -279,6 +291,7 @@ class SAC_Base(AuxHeadsMixin):
         self._rep_from_burn_in = bool(hip_config.get('rep_from_burn_in', True))
         self._fused_curiosity = bool(hip_config.get('fused_curiosity', True))
         self._fused_discrete = bool(hip_config.get('fused_discrete', True))     # asac_discrete_* (pure-discrete learner)
+        self._fused_dqn = bool(hip_config.get('fused_dqn', True))               # asac_dqn_* (DQN-like discrete learner)
         self._fused_rpm_loss = bool(hip_config.get('fused_rpm_loss', True))
         # one backward walk per prediction model (gates and model gradients from it): sac_aux._train_rpm
         self._rpm_single_backward = bool(hip_config.get('rpm_single_backward', True))
@@ -798,6 +811,20 @@ class SAC_Base(AuxHeadsMixin):
             win = lambda t: t.as_strided((batch, 1, A), (t.stride(0), t.stride(0), 1))  # noqa: E731
             native.squash_prob(win(loc), win(scale), win(c_action), 0, win(prob), 0)
             return c_action, prob
+        if offline_action is None and not use_rnd and state.dim() == 2 and self._dqn_fused(1, acting=True):
+            # DQN-like, discrete branches only: the first critic's forward, then ONE launch for the greedy one-hot per
+            # branch and (train mode) the epsilon-random rows, their uniforms drawn on the device — instead of ~30 eager
+            # launches and a host-to-device copy of the mask per environment step.  The policy is not evaluated: nothing
+            # of it is read (`prob` is ones).
+            d_qs, _ = self.model_q_list[0](state, None, obs_list)
+            d_action = torch.empty((batch, self.d_action_summed_size), dtype=torch.float32, device=self.device)
+            u = None
+            if self.train_mode:
+                u = torch.empty((batch, 1 + self.d_action_branch_size), dtype=torch.float32, device=self.device)
+                self.noise.uniform_(u)
+            native.dqn_act(self._branches, d_qs, u, self.discrete_dqn_epsilon, d_action)
+            d_action, _ = self._random_action(d_action, torch.zeros(0, device=self.device))
+            return d_action, torch.ones((batch, self.d_action_summed_size), device=self.device)
         d_policy, c_policy = self.model_policy(state, obs_list)
         if offline_action is None:
             if self.d_action_sizes and self.discrete_dqn_like:
@@ -1077,6 +1104,41 @@ class SAC_Base(AuxHeadsMixin):
             use_prediction=self.use_prediction, data_parallel=self._dist is not None,
             float32_on_device=self._params.flat.dtype == torch.float32 and self._params.flat.is_cuda,
             ensemble_q_num=self.ensemble_q_num, n_step=self.n_step, batch_size=B)
+
+    def _dqn_fused(self, B: int, acting: bool = False) -> bool:
+        """the step's DQN-like arithmetic runs on the `asac_dqn_*` launches (`fused_dqn_applies`), B rows a batch; `acting`:
+        the acting launch, where neither the batch nor the window plays a part"""
+        return fused_dqn_applies(
+            enabled=self._fused_dqn, plain_learner=True, d_action_sizes=self.d_action_sizes,
+            c_action_size=self.c_action_size, discrete_dqn_like=self.discrete_dqn_like,
+            offline_loss=self.offline_enabled and self.offline_loss, siamese=self.siamese is not None,
+            use_prediction=self.use_prediction, curiosity=self.curiosity is not None, data_parallel=self._dist is not None,
+            float32_on_device=self._params.flat.dtype == torch.float32 and self._params.flat.is_cuda,
+            ensemble_q_num=self.ensemble_q_num, n_step=1 if acting else self.n_step, batch_size=1 if acting else B)
+
+    @torch.no_grad()
+    def _dqn_target_job(self, n_last_masks, n_padding_masks, nx_obses_list, nx_states, nx_actions, n_rewards, n_dones, *,
+                        subset_prefix, y_out, q_online, td_out=None):
+        """The double-DQN target's inputs (reference `_get_y` 1363-1382 up to the call of `get_dqn_like_d_y`) ->
+        `_Return(args, keep)` for `native.dqn_return` / `native.dqn_q_loss_grad`, `args` = (VtraceArgs, DqnJob) and `keep`
+        the tensors they point into (alive as long as the record is: hold it until the launch is issued).  It runs the
+        target critics over the window and the online critics over its next positions and draws the two subsets (target
+        subset first, eval subset second, as the reference draws them).  The policy is not evaluated over the window: this mode never reads it.  `q_online`: the online critics'
+        head outputs [B, D] at the step's state (detached)."""
+        E = self.ensemble_q_num
+        no_c = torch.zeros(0, device=self.device)
+        target = [q(nx_states, no_c, nx_obses_list)[0] for q in self.model_target_q_list]
+        sub_next, sub_eval = self._subsets[subset_prefix + '_dnext'], self._subsets[subset_prefix + '_dn']
+        self.noise.subset_(sub_next, E)
+        next_obs = [o[:, 1:] for o in nx_obses_list]
+        eval_next = [q(nx_states[:, 1:], no_c, next_obs)[0] for q in self.model_q_list]
+        self.noise.subset_(sub_eval, E)
+        args = self._vtrace_args(n_rewards, n_dones, n_last_masks, n_padding_masks, y_out)
+        args.subset_n, args.subset_next, args.E_sample = sub_eval.data_ptr(), sub_next.data_ptr(), self.ensemble_q_sample
+        if td_out is not None:
+            args.td_error_out = td_out.data_ptr()
+        job = native.dqn_job(self._branches, eval_next, target, action=nx_actions[:, 0], q_online=q_online)
+        return _Return((args, job), (eval_next, target, q_online, sub_next, sub_eval))
 
     def _discrete_logits(self, state, obs_list):
         """the discrete branches' logits [.., D] (the launches normalise them per branch themselves): the stock policy's
@@ -1458,6 +1520,20 @@ class SAC_Base(AuxHeadsMixin):
             c_q = torch.stack([q[1] for q in q_list]).squeeze(-1) if self.c_action_size else None
         else:
             c_q = self._c_q_values(False, state, c_action, obs_list, select=state_base)   # [E, B]
+        if self.d_action_sizes and aux is None and self._dqn_fused(state.shape[0]):
+            # DQN-like: the loss launch forms the double-DQN target itself (row-local, y stays in registers), then loss
+            # values and d(sum_e l_e) / d(head outputs); back-propagation starts at the heads
+            heads = [q[0] for q in q_list]
+            grad_q, _ = self._discrete_grad_buffers(state.shape[0])
+            ret = self._dqn_target_job(n_last_masks, n_padding_masks, nx_obses_list, nx_states.detach(), nx_actions,
+                                       n_rewards, n_dones, subset_prefix='y', y_out=self._y_buf,
+                                       q_online=[h.detach() for h in heads])
+            native.dqn_q_loss_grad(*ret.args, priority_is, self._loss_q_e, grad_q)
+            del ret
+            with direct_param_grads(), DeferredPartialSums() as sums_later:
+                torch.autograd.backward(heads, list(grad_q.unbind(0)))
+            sums_later.flush()
+            return self._finish_rep_q(None, None)
         d_y, c_y = self._get_y(n_last_masks, n_padding_masks, nx_obses_list, nx_states.detach(), nx_actions,
                                n_rewards, n_dones, n_mu_probs if self.use_n_step_is else None,
                                eps_buf=self._eps_y, subset_prefix='y', y_out=self._y_buf,
@@ -1871,6 +1947,16 @@ class SAC_Base(AuxHeadsMixin):
             self._get_y(n_last_masks, n_padding_masks, nx_obses_list, nx_target_states, nx_actions, n_rewards, n_dones,
                         n_mu_probs, eps_buf=self._eps_td, subset_prefix='td', y_out=self._y_td_buf, td_out=self._td_error,
                         d_q_online=heads)
+            return self._td_error, False
+        if c_q is None and self._dqn_fused(state.shape[0]):
+            # DQN-like: the return's launch writes mean_e |(1/K) sum_j a_j q_e - y| itself
+            assert not sidecars and pending_alpha is None and td_update is None
+            heads = [q(state, c_action, obs_list)[0] for q in self.model_q_list]
+            ret = self._dqn_target_job(n_last_masks, n_padding_masks, nx_obses_list, nx_target_states, nx_actions,
+                                       n_rewards, n_dones, subset_prefix='td', y_out=self._y_td_buf, q_online=heads,
+                                       td_out=self._td_error)
+            native.dqn_return(*ret.args)
+            del ret
             return self._td_error, False
         q_list = None
         if c_q is not None:

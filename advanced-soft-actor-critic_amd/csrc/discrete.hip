@@ -23,37 +23,6 @@
 
 namespace asac {
 
-constexpr int kDiscThreads = 256;
-
-// sum_j a[j] * q[j] over a row of D entries: loads in groups of four requested together (indices beyond D re-read the last
-// entry: a valid address, the product is not added), added in index order
-__device__ __forceinline__ float disc_dot(const float* a, const float* q, int D) {
-    float s = 0.f;
-    for (int j0 = 0; j0 < D; j0 += 4) {
-        float av[4], qv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int j = min(j0 + u, D - 1);
-            av[u] = a[j], qv[u] = q[j];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if (j0 + u < D) s += av[u] * qv[u];
-    }
-    return s;
-}
-
-// the fixed-order tree over a workgroup's 256 lane partials (k_q_loss's), valid in lane 0
-__device__ __forceinline__ float disc_tree_sum(float* red, float part) {
-    red[threadIdx.x] = part;
-    __syncthreads();
-    for (int s = kDiscThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 // ------------------------------------------------------------------------------------------------------------------------
 struct DiscReturnDev {
     asac_vtrace_args_t a;
@@ -345,15 +314,6 @@ __global__ __launch_bounds__(kDiscThreads) void k_discrete_alpha_grad(const Disc
     const float total = disc_tree_sum(red, part);
     if (threadIdx.x == 0) *x.slot = total / (float)B;
 }
-
-// the host checks, written once per kind of argument
-static bool members_ok(const asac_members_t* m) {
-    if (!m || m->E <= 0 || m->E > ASAC_DISCRETE_MAX_MEMBERS) return false;
-    for (int e = 0; e < m->E; ++e)
-        if (!m->base[e]) return false;
-    return true;
-}
-static bool reduction_rows_ok(int B) { return B > 0 && B <= ASAC_DISCRETE_MAX_ROWS; }
 
 }  // namespace asac
 

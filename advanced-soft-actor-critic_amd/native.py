@@ -14,7 +14,7 @@ PKG_DIR = Path(__file__).resolve().parent
 import os as _os
 
 LIB_PATH = Path(_os.environ.get('ASAC_HIP_LIB', PKG_DIR / 'lib' / 'libasac_hip.so'))   # env override: debugging builds
-ABI_VERSION = 89
+ABI_VERSION = 90
 
 MAX_GATHER_KEYS = 16
 PAD_KEEP, PAD_WORD, PAD_BYTE, PAD_ROW, PAD_EMIT_MASK = 0, 1, 2, 3, 4
@@ -105,6 +105,13 @@ class DiscreteReturn(C.Structure):
     _fields_ = [('branches', Branches), ('q_target', Members), ('q_online', Members),
                 ('logits', C.c_void_p), ('logits_stride_b', C.c_int64), ('logits_stride_t', C.c_int64),
                 ('action', C.c_void_p), ('action_stride_b', C.c_int64), ('action_stride_t', C.c_int64)]
+
+
+class DqnJob(C.Structure):
+    """asac_dqn_job_t: the DQN-like target's tables (eval [B, n, D], target [B, n+1, D]), the online heads and the stored
+    action at the step's state"""
+    _fields_ = [('branches', Branches), ('q_eval', Members), ('q_target', Members), ('q_online', Members),
+                ('action', C.c_void_p), ('action_stride', C.c_int64)]
 
 
 class MlpDesc(C.Structure):
@@ -530,6 +537,11 @@ _SIGNATURES = {
                                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'asac_discrete_alpha_grad': (C.c_int, [C.POINTER(Branches), C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_dqn_return': (C.c_int, [C.POINTER(VtraceArgs), C.POINTER(DqnJob), C.c_void_p]),
+    'asac_dqn_q_loss_grad': (C.c_int, [C.POINTER(VtraceArgs), C.POINTER(DqnJob), C.c_void_p, C.c_int64, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    'asac_dqn_act': (C.c_int, [C.POINTER(Branches), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p,
+                               C.c_int64, C.c_int, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -2831,3 +2843,63 @@ def discrete_alpha_grad(br: Branches, logits, target, grad_slot, probs_out=None,
     _check(load().asac_discrete_alpha_grad(C.byref(br), _p(logits), _discrete_rows(logits, D, 'logits'), _p(target), B,
                                            _p(grad_slot), _p(probs_out), _p(row_entropy_out), _stream()),
            'asac_discrete_alpha_grad')
+
+
+# ------------------------------------------------------------------------------------------------
+# pure-discrete, DQN-like learner (csrc/dqn.hip)
+# ------------------------------------------------------------------------------------------------
+def dqn_job(br: Branches, q_eval, q_target, action=None, q_online=None) -> DqnJob:
+    """q_eval: the online members' head outputs over the NEXT positions [B, n, D]; q_target: the target members' head
+    outputs [B, n+1, D] (as many); action: the stored action at the step's state [B, >= D]; q_online: the online members'
+    head outputs [B, D] there.  The tensors must stay alive until the launch that reads the job is issued."""
+    D = br.D
+    job = DqnJob()
+    job.branches = br
+    job.q_eval, job.q_target = members(list(q_eval), D), members(list(q_target), D)
+    B, n = q_eval[0].shape[0], q_eval[0].shape[1]
+    assert all(t.shape[:2] == (B, n) for t in q_eval) and all(t.shape[:2] == (B, n + 1) for t in q_target)
+    if action is not None:
+        assert action.shape[0] == B
+        job.action, job.action_stride = action.data_ptr(), _discrete_rows(action, D, 'action')
+    if q_online is not None:
+        job.q_online = members(list(q_online), D)
+        assert all(t.shape == (B, D) for t in q_online)
+    return job
+
+
+@_profiled
+def dqn_return(args: VtraceArgs, job: DqnJob):
+    """`args` (`_vtrace_args` + subset_n = the eval subset / subset_next = the target subset / E_sample; td_error_out with
+    the job's `q_online` and `action`) -> y_out (and the TD error): one launch"""
+    _check(load().asac_dqn_return(C.byref(args), C.byref(job), _stream()), 'asac_dqn_return')
+
+
+@_profiled
+def dqn_q_loss_grad(args: VtraceArgs, job: DqnJob, w, loss_out, grad_q):
+    """The Q step's loss launch, forming the target itself: `job` with `q_online` and `action`; w (optional): B float32
+    elements ([B] or [B, 1]); loss_out [E]; grad_q [E, B, D] contiguous <- d (sum_e loss_e) / d q; `args.y_out`
+    (optional) <- y"""
+    B, D, E = args.B, job.branches.D, job.q_online.E
+    ws = 0
+    if w is not None:
+        assert w.is_cuda and w.dtype == torch.float32 and w.numel() == B and w.shape[0] == B, 'w'
+        ws = w.stride(0) if B > 1 else 1
+    if loss_out is not None and grad_q is not None:
+        assert loss_out.dtype == torch.float32 and loss_out.numel() >= E and loss_out.is_contiguous()
+        assert grad_q.dtype == torch.float32 and grad_q.shape == (E, B, D) and grad_q.is_contiguous()
+    _check(load().asac_dqn_q_loss_grad(C.byref(args), C.byref(job), _p(w), ws, _p(loss_out), _p(grad_q), _stream()),
+           'asac_dqn_q_loss_grad')
+
+
+@_profiled
+def dqn_act(br: Branches, q, u, epsilon: float, action_out):
+    """q: the first critic's head outputs [B, D]; u: [B, 1 + K] uniforms in [0, 1) or None (greedy only);
+    action_out [B, >= D] <- the one-hot action per branch: one launch"""
+    B, D = q.shape[0], br.D
+    us = 0
+    if u is not None:
+        assert u.is_cuda and u.dtype == torch.float32 and u.shape == (B, 1 + br.K) and u.stride(1) == 1, 'u'
+        us = u.stride(0)
+    assert action_out.shape[0] == B
+    _check(load().asac_dqn_act(C.byref(br), _p(q), _discrete_rows(q, D, 'q'), _p(u), us, float(epsilon), _p(action_out),
+                               _discrete_rows(action_out, D, 'action_out'), B, _stream()), 'asac_dqn_act')

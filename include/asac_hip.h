@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ASAC_ABI_VERSION 89
+#define ASAC_ABI_VERSION 90
 #define ASAC_MAX_GATHER_KEYS 16
 #define ASAC_MAX_ENSEMBLE 16
 #define ASAC_MAX_ACTION 64
@@ -1623,6 +1623,55 @@ int asac_discrete_policy_loss_grad(const asac_branches_t* branches, const float*
 int asac_discrete_alpha_grad(const asac_branches_t* branches, const float* logits, int64_t logits_stride,
                              const float* target, int B, float* grad_slot, float* probs_out, float* row_entropy_out,
                              void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Pure-discrete, DQN-like learner (d_action_sizes set, c_action_size == 0, discrete_dqn_like True: critics only): the
+ * arithmetic around the critics as three launches (csrc/dqn.hip; the per-row target is csrc/asac_dqn.h's, one
+ * implementation for both launches that form it).  Branch table, member tables and limits as above.
+ *   eval[e]    online member e's head outputs over the NEXT positions [B, n, D]: position t is window row t + 1
+ *   target[e]  target member e's head outputs [B, n+1, D]
+ * Double-DQN n-step target (sac_base.py get_dqn_like_d_y 1194-1242, called from _get_y 1363-1382), per row b:
+ *   L    = the largest t in [0, n) with !(last[b,t] | pad[b,t]); n - 1 where there is none
+ *   j*_k = the LOWEST index of the maximum of eval[subset_n[i]][b, L, branch k]            (torch.argmax), i < E_sample
+ *   v_i  = (1/K) sum_k target[subset_next[i]][b, L+1, j*_k]        (the two subsets pair by position i)
+ *   y_b  = sum_t gamma_ratio[t] reward[b,t] + gamma^(L+1) min_i v_i (done[b,L] ? 0 : 1)
+ * Inputs are finite; nothing is promised for NaN.
+ *   args  read: reward / done / last_mask / padding_mask and their strides, gamma_ratio, gamma, subset_n (eval subset),
+ *         subset_next (target subset; NULL = 0..E_sample-1 each), E_sample, B, n, y_out, td_error_out.  Nothing else.
+ *   action   the stored action at the step's state [B, >= D], rows action_stride floats apart
+ *   q_online the online members' head outputs [B, D] at the step's state (stride_t not read)
+ * Bad arguments (null outputs, E_sample > E, eval and target tables of different E, D > 64, K > 8, a branch table that
+ * does not add up, n > 64, B > 1024 for the loss) return hipErrorInvalidValue without a launch; B == 0 launches nothing.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    asac_branches_t branches;
+    asac_members_t q_eval;
+    asac_members_t q_target;
+    asac_members_t q_online;
+    const float* action;
+    int64_t action_stride;
+} asac_dqn_job_t;
+
+/* y -> args->y_out.  With args->td_error_out (then job->q_online and job->action are needed) also _get_td_error's
+ * sac_base.py:2219-2244:  td[b] = mean over ALL E online members of |(1/K) sum_j a[b,j] q_e[b,j] - y_b|.
+ * One lane per row, workgroups of 64 rows, no exchange between them.  n <= ASAC_DISCRETE_MAX_STEPS; any B. */
+int asac_dqn_return(const asac_vtrace_args_t* args_host, const asac_dqn_job_t* job_host, void* stream);
+
+/* The Q step's loss launch (sac_base.py:1533-1538, 1563-1568); it forms the target itself:
+ *   qs[e][b] = (1/K) sum_j a[b][j] q_e[b][j];   loss_out[e] = mean_b w_b (qs - y_b)^2   (w may be NULL; element b at b * w_stride)
+ *   grad_q[e][b][j] = 2 w_b (qs - y_b) a[b][j] / (K B)      one contiguous [E, B, D] buffer
+ * One workgroup per online member (job->q_online), each computing its rows' y; workgroup 0 also stores y to
+ * args->y_out when that is non-null (the same bits asac_dqn_return writes).  The batch mean is summed in a fixed order.
+ * B <= ASAC_DISCRETE_MAX_ROWS. */
+int asac_dqn_q_loss_grad(const asac_vtrace_args_t* args_host, const asac_dqn_job_t* job_host, const float* w,
+                         int64_t w_stride, float* loss_out, float* grad_q, void* stream);
+
+/* Epsilon-greedy acting (sac_base.py:904-930 without RND), per row: the greedy one-hot of each branch (lowest index at
+ * ties) from the first critic's heads q [B, D] (rows q_stride apart).  With u ([B, 1+K] uniforms in [0, 1), rows
+ * u_stride apart) and u[b,0] < epsilon, branch k's index is min(floor(u[b,1+k] * s_k), s_k - 1) instead.  u == NULL:
+ * greedy only.  Writes every element of the D columns of action_out (rows action_stride apart).  Any B. */
+int asac_dqn_act(const asac_branches_t* branches, const float* q, int64_t q_stride, const float* u, int64_t u_stride,
+                 float epsilon, float* action_out, int64_t action_stride, int B, void* stream);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,11 @@
           profiler.  With the flag off the step runs exactly the code of the commit before the discrete kernels, so this is
           the A/B against it without a second checkout; bench.py has no discrete configuration.
 
-    python tools/discrete_bench.py [--steps 600] [--fill 16384]
+    python tools/discrete_bench.py [--steps 600] [--fill 16384] [--dqn-like]
+
+`--dqn-like`: the same A/B with `discrete_dqn_like=True` (critics only, double-DQN target; csrc/dqn.hip,
+`hip_config['fused_dqn']`), and — acting is not part of the step's figure — the device kernels of ONE `choose_action` call in
+train mode with the flag off and on, from torch's profiler.
 
 The two ways alternate (off, on, off, on, ...: a drift of the box's clocks hits both) and every timed window ends in a device
 synchronise; the median of the rounds is reported, all rounds are listed.  BOTH captured learners stay alive while the tool
@@ -37,7 +41,7 @@ def count_kernels(fn):
     return sum(e.count for e in prof.key_averages() if e.device_type == torch.autograd.DeviceType.CUDA)
 
 
-def step_row(steps, fill):
+def step_row(steps, fill, dqn_like=False):
     import bench
     from asac_amd import native
     from algorithm.sac_base import SAC_Base
@@ -48,20 +52,22 @@ def step_row(steps, fill):
     episodes = [pu.synthetic_episode(rng, cfg['obs_shapes'], D_ACTION_SIZES, 0, cfg['hidden'], cfg['episode_len'])
                 for _ in range(max(4, fill // cfg['episode_len']))]
 
+    flag, prefix = ('fused_dqn', 'asac_dqn_') if dqn_like else ('fused_discrete', 'asac_discrete_')
+
     def learner(fused, use_graph):
         torch.manual_seed(0)
         agent = SAC_Base(cfg['obs_names'], cfg['obs_shapes'], D_ACTION_SIZES, 0, None, plugin, device='cuda:0',
                          n_step=cfg['n_step'], burn_in_step=cfg['burn_in_step'], batch_size=cfg['batch_size'],
                          ensemble_q_num=cfg['ensemble_q_num'], ensemble_q_sample=cfg['ensemble_q_sample'],
-                         replay_config={'capacity': cfg['capacity']},
-                         hip_config={'use_graph': use_graph, 'fused_discrete': fused})
+                         replay_config={'capacity': cfg['capacity']}, discrete_dqn_like=dqn_like,
+                         hip_config={'use_graph': use_graph, flag: fused})
         for ep in episodes:
             agent.put_episode(**ep)
         return agent
 
     agents = {}
-    row = {'mode': 'step', 'd_action_sizes': D_ACTION_SIZES, 'batch': cfg['batch_size'], 'n_step': cfg['n_step'],
-           'steps': steps, 'rounds': ROUNDS}
+    row = {'mode': 'step', 'dqn_like': dqn_like, 'd_action_sizes': D_ACTION_SIZES, 'batch': cfg['batch_size'],
+           'n_step': cfg['n_step'], 'steps': steps, 'rounds': ROUNDS}
     for fused in (False, True):
         tag = 'fused' if fused else 'eager'
         agent = learner(fused, False)
@@ -71,8 +77,14 @@ def step_row(steps, fill):
         seen = prof.summary()
         row['native_launches_' + tag] = sum(v['calls'] for v in seen.values())
         row['discrete_launches_' + tag] = {k: v['calls'] for k, v in seen.items()
-                                           if k.startswith('asac_discrete_') or k == 'asac_vtrace_return_direct'}
+                                           if k.startswith(prefix) or k == 'asac_vtrace_return_direct'}
         row['device_kernels_' + tag] = count_kernels(agent.train)
+        if dqn_like:                 # one `choose_action` call in train mode, 8 agents
+            obs = [torch.randn(8, *shape, device='cuda') for shape in cfg['obs_shapes']]
+            act_args = (obs, torch.zeros(8, sum(D_ACTION_SIZES), device='cuda'),
+                        torch.zeros(8, *agent.seq_hidden_state_shape, device='cuda'))
+            agent.choose_action_device(*act_args)
+            row['acting_device_kernels_' + tag] = count_kernels(lambda: agent.choose_action_device(*act_args))
         agent.close()
         agent = learner(fused, True)
         for _ in range(20):          # eager warm-up, capture, first replays
@@ -102,10 +114,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=600)
     ap.add_argument('--fill', type=int, default=16384, help='rows put into the replay before the first step')
+    ap.add_argument('--dqn-like', action='store_true', help='discrete_dqn_like=True: the A/B of hip_config[\'fused_dqn\']')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'needs the GPU: nothing is measured without one'
     import asac_amd  # noqa: F401
-    print(json.dumps(step_row(args.steps, args.fill)), flush=True)
+    print(json.dumps(step_row(args.steps, args.fill, args.dqn_like)), flush=True)
 
 
 if __name__ == '__main__':

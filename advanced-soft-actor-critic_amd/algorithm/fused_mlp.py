@@ -174,6 +174,32 @@ def describe_dense(ll, skip: int = 0) -> 'native.MlpDesc | None':
     return desc
 
 
+def describe_rnd_stack(ll, state_size: int, action_size: int) -> 'native.RndDesc | None':
+    """`ModelRND.c_dense` as the `asac_rnd_*` launches take it: `LinearLayers(S + A, 64, 2, None)` — exactly two GELU (erf
+    form) ResBlocks  S + A -> 64 -> 64  with biases, dropout 0 and NO output Linear, S + A <= 128.  The descriptor carries
+    the blocks' residual flags (the first adds its input only where S + A == 64).  Anything else — a plugin's
+    `_build_model` with other widths, depths or activations — is None and keeps the module code."""
+    if not isinstance(ll, LinearLayers):
+        return None
+    parsed = _blocks_of(ll)
+    if parsed is None or parsed[1] is not None or len(parsed[0]) != 2:
+        return None
+    b1, b2 = parsed[0]
+    k0 = state_size + action_size
+    if (state_size <= 0 or action_size <= 0 or ll.input_size != k0 or k0 > native.RND_MAX_IN
+            or b1.linear.in_features != k0 or b1.linear.out_features != native.RND_WIDTH
+            or b2.linear.in_features != native.RND_WIDTH or b2.linear.out_features != native.RND_WIDTH
+            or b1.linear.bias is None or b2.linear.bias is None):
+        return None
+    return native.rnd_desc(state_size, action_size, (b1.residual, b2.residual))
+
+
+def rnd_stack_tensors(ll) -> tuple:
+    """(w1, b1, w2, b2) of a stack `describe_rnd_stack` accepts"""
+    b1, b2 = _blocks_of(ll)[0]
+    return b1.linear.weight, b1.linear.bias, b2.linear.weight, b2.linear.bias
+
+
 def _flat_alias(tensors):
     """-> a 1-D tensor aliasing `tensors` if they sit back to back, in order, in one storage (the learner's flat
     parameter / gradient buffers), else None"""

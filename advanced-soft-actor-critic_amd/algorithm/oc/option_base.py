@@ -68,6 +68,8 @@ def _reject_unsupported(args, kwargs) -> None:
 
 
 class OptionBase(SAC_Base):
+    _plain_learner = False
+
     def __init__(self, option: int, display_name: str, fix_policy: bool, random_q: bool, *args, **kwargs):
         self.option = option
         self.display_name = display_name

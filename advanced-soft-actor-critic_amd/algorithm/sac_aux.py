@@ -538,6 +538,8 @@ class AuxHeadsMixin:
 
     def _train_rnd(self, n_padding_masks, n_states, n_actions):
         """Distil the frozen random target network on visited (state, action) pairs (1978-2025)."""
+        if n_states.dim() == 3 and (rnd := self._rnd_fused(rows=n_states.shape[0] * n_states.shape[1])) is not None:
+            return self._train_rnd_fused(rnd, n_padding_masks, n_states, n_actions)
         dsum = self.d_action_summed_size
         d_act, c_act = n_actions[..., :dsum], n_actions[..., dsum:]
         keep = ~n_padding_masks.unsqueeze(-1)
@@ -569,6 +571,37 @@ class AuxHeadsMixin:
             self._dist.all_reduce_grads(self._params.grad, *self._params.span('rnd'))
         self.optimizer_rnd.step()
         return loss.detach()
+
+    @torch.no_grad()
+    def _train_rnd_fused(self, rnd, n_padding_masks, n_states, n_actions):
+        """`_train_rnd` for continuous actions on the stock stacks (`SAC_Base._rnd_fused`): ONE launch for both stacks
+        over the window, the masked loss and the cotangents at the predictor's pre-activations (`asac_rnd_distill`), ONE
+        `xty_multi` call whose two jobs OVERWRITE the gradient views of `c_dense` (weights = cotangent^T input, biases =
+        its column sums), then the unchanged Adam launch.  No `zero_grad()`: the launch pair overwrites all of `c_dense`'s
+        span, and `s_dense` — which a continuous learner never evaluates (the reference leaves its `.grad` None) — has its
+        span of the flat gradient buffer zeroed once, when the buffers are made, and nothing writes it afterwards: Adam
+        reads zeros there, its moments and weights never move.  Buffers (the learner's own exchange words among them) are
+        made once per (B, n) and reused; the returned loss is the launch's output buffer."""
+        from asac_amd import native
+        desc, pred, targ, tensors = rnd
+        B, n = n_states.shape[:2]
+        buf = self._rnd_buffers.get((B, n))
+        if buf is None:
+            N, dev = B * n, self.device
+            new = lambda w: torch.empty((N, w), dtype=torch.float32, device=dev)        # noqa: E731
+            buf = self._rnd_buffers[(B, n)] = (new(desc.S + desc.A), new(native.RND_WIDTH), new(native.RND_WIDTH),
+                                                new(native.RND_WIDTH), torch.zeros((), dtype=torch.float32, device=dev),
+                                                torch.zeros(native.rnd_distill_workspace_floats(N), dtype=torch.float32, device=dev))
+            for p in self.model_rnd.s_dense.parameters():
+                if p.grad is not None:
+                    p.grad.zero_()
+        x_cat, h1, gz1, gz2, loss, ws = buf
+        mask = n_padding_masks if n_padding_masks.element_size() == 1 else n_padding_masks.to(torch.bool)
+        native.rnd_distill(desc, pred, targ, n_states, n_actions, mask, x_cat, h1, gz1, gz2, loss, ws)
+        w1, b1, w2, b2 = tensors[:4]
+        native.xty_multi([(gz2, h1, w2.grad, b2.grad), (gz1, x_cat, w1.grad, b1.grad)], accumulate=False)
+        self.optimizer_rnd.step()
+        return loss
 
     # ------------------------------------------------------------------------------------------
     # RND-guided action sampling (acting path, 792-856)

@@ -114,6 +114,17 @@ def fused_dqn_applies(*, enabled, plain_learner, d_action_sizes, c_action_size, 
                 and float32_on_device and native.discrete_sizes_ok(d_action_sizes, ensemble_q_num, n_step, batch_size))
 
 
+def fused_rnd_applies(*, enabled, plain_learner, d_action_sizes, c_action_size, data_parallel, float32_on_device, stack_ok,
+                      state_size, n_sample=1, rows=1) -> bool:
+    """Does random network distillation of this configuration run on the `asac_rnd_*` launches (`hip_config['fused_rnd']`)?
+    Only a plain `SAC_Base` (`plain_learner`: not an `OptionBase`) with continuous actions alone, without a data-parallel
+    context, on float32 device tensors, whose `model_rnd.c_dense` and `model_target_rnd.c_dense` are both the stock stack
+    on 16-byte-aligned contiguous parameters (`stack_ok`), within the entry points' limits (`n_sample` candidates an
+    entry when acting, `rows` = batch * window rows when training).  Everything else runs the eager code."""
+    return bool(enabled and plain_learner and len(d_action_sizes) == 0 and c_action_size > 0 and not data_parallel
+                and float32_on_device and stack_ok and native.rnd_sizes_ok(state_size, c_action_size, n_sample, rows))
+
+
 class _Window:
     """views of the step's static batch tensors and what the phases of `_device_step_body` hand to each other"""
 
@@ -133,6 +144,7 @@ class _AfterPolicy:
 
 class SAC_Base(AuxHeadsMixin):
     _closed = False
+    _plain_learner = True        # (OptionBase: False — the one-launch paths of the plain learner's arithmetic stay off)
 
     def __init__(self,
                  obs_names: list[str],
@@ -292,6 +304,9 @@ class SAC_Base(AuxHeadsMixin):
         self._fused_curiosity = bool(hip_config.get('fused_curiosity', True))
         self._fused_discrete = bool(hip_config.get('fused_discrete', True))     # asac_discrete_* (pure-discrete learner)
         self._fused_dqn = bool(hip_config.get('fused_dqn', True))               # asac_dqn_* (DQN-like discrete learner)
+        self._fused_rnd = bool(hip_config.get('fused_rnd', True))               # asac_rnd_* (continuous RND, stock stacks)
+        self._rnd_stacks = None          # (RndDesc, predictor, target, tensors) | False once described (`_rnd_fused`)
+        self._rnd_buffers = {}           # (B, n) -> the distillation launch's dense outputs
         self._fused_rpm_loss = bool(hip_config.get('fused_rpm_loss', True))
         # one backward walk per prediction model (gates and model gradients from it): sac_aux._train_rpm
         self._rpm_single_backward = bool(hip_config.get('rpm_single_backward', True))
@@ -811,6 +826,21 @@ class SAC_Base(AuxHeadsMixin):
             win = lambda t: t.as_strided((batch, 1, A), (t.stride(0), t.stride(0), 1))  # noqa: E731
             native.squash_prob(win(loc), win(scale), win(c_action), 0, win(prob), 0)
             return c_action, prob
+        if (use_rnd and offline_action is None and not disable_sample and self.action_noise is None and self._stock_c_only()
+                and state.dim() == 2 and (rnd := self._rnd_fused(rows=batch * self.rnd_n_sample)) is not None):
+            # novelty-guided acting on the stock networks: the policy's forward, the Gaussian draws of the rnd_n_sample
+            # candidates, then ONE launch for the candidates, both RND stacks on them, the first largest distillation error
+            # per entry and the chosen action's probability — instead of the policy module, `Normal.sample`, two
+            # concatenations, four ResBlocks, pow / sum / argmax, an index and `squash_correction_prob` per environment step
+            A, k = self.c_action_size, self.rnd_n_sample
+            ls = self._fpi._launch_forward(StockMLP._rows(state, self.state_size), None)[0]      # [batch, 2A] (loc | scale)
+            eps = torch.empty((batch, k, A), dtype=torch.float32, device=self.device)
+            self.noise.normal_(eps)
+            c_action = torch.empty((batch, A), dtype=torch.float32, device=self.device)
+            prob = torch.empty((batch, A), dtype=torch.float32, device=self.device)
+            native.rnd_pick(rnd[0], rnd[1], rnd[2], StockMLP._rows(state, self.state_size), ls[:, :A], ls[:, A:], eps,
+                            c_action, prob)
+            return c_action, prob
         if offline_action is None and not use_rnd and state.dim() == 2 and self._dqn_fused(1, acting=True):
             # DQN-like, discrete branches only: the first critic's forward, then ONE launch for the greedy one-hot per
             # branch and (train mode) the epsilon-random rows, their uniforms drawn on the device — instead of ~30 eager
@@ -1115,6 +1145,35 @@ class SAC_Base(AuxHeadsMixin):
             use_prediction=self.use_prediction, curiosity=self.curiosity is not None, data_parallel=self._dist is not None,
             float32_on_device=self._params.flat.dtype == torch.float32 and self._params.flat.is_cuda,
             ensemble_q_num=self.ensemble_q_num, n_step=1 if acting else self.n_step, batch_size=1 if acting else B)
+
+    def _rnd_fused(self, rows: int = 1):
+        """-> (RndDesc, predictor RndStack, target RndStack, tensors) when random network distillation runs on the
+        `asac_rnd_*` launches (`fused_rnd_applies`, with `rnd_n_sample` candidates an entry: a learner whose acting cannot
+        take the path does not train on it either), else None.  The stacks are described once: the parameters are views
+        of the flat buffers (predictor) or the target's own storage and keep their addresses."""
+        if not self.use_rnd or not self._fused_rnd:
+            return None
+        if self._rnd_stacks is None:
+            self._rnd_stacks = False
+            from .fused_mlp import describe_rnd_stack, rnd_stack_tensors
+            A = self.c_action_size
+            if A and not self.d_action_sizes and hasattr(self.model_rnd, 'c_dense'):
+                dp = describe_rnd_stack(self.model_rnd.c_dense, self.state_size, A)
+                dt = describe_rnd_stack(self.model_target_rnd.c_dense, self.state_size, A)
+                if dp is not None and dt is not None and list(dp.residual) == list(dt.residual):
+                    pred, targ = rnd_stack_tensors(self.model_rnd.c_dense), rnd_stack_tensors(self.model_target_rnd.c_dense)
+                    ok = all(x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.data_ptr() % 16 == 0
+                             for x in pred + targ)
+                    ok = ok and all(x.grad is not None and x.grad.is_contiguous() and x.grad.data_ptr() % 16 == 0 for x in pred)
+                    if ok:
+                        self._rnd_stacks = (dp, native.rnd_stack(*pred), native.rnd_stack(*targ), pred + targ)
+        stacks = self._rnd_stacks
+        ok = fused_rnd_applies(
+            enabled=self._fused_rnd, plain_learner=type(self)._plain_learner, d_action_sizes=self.d_action_sizes,
+            c_action_size=self.c_action_size, data_parallel=self._dist is not None,
+            float32_on_device=self._params.flat.dtype == torch.float32 and self._params.flat.is_cuda,
+            stack_ok=bool(stacks), state_size=self.state_size, n_sample=self.rnd_n_sample, rows=rows)
+        return stacks if ok else None
 
     @torch.no_grad()
     def _dqn_target_job(self, n_last_masks, n_padding_masks, nx_obses_list, nx_states, nx_actions, n_rewards, n_dones, *,

@@ -14,7 +14,7 @@ PKG_DIR = Path(__file__).resolve().parent
 import os as _os
 
 LIB_PATH = Path(_os.environ.get('ASAC_HIP_LIB', PKG_DIR / 'lib' / 'libasac_hip.so'))   # env override: debugging builds
-ABI_VERSION = 90
+ABI_VERSION = 91
 
 MAX_GATHER_KEYS = 16
 PAD_KEEP, PAD_WORD, PAD_BYTE, PAD_ROW, PAD_EMIT_MASK = 0, 1, 2, 3, 4
@@ -112,6 +112,16 @@ class DqnJob(C.Structure):
     action at the step's state"""
     _fields_ = [('branches', Branches), ('q_eval', Members), ('q_target', Members), ('q_online', Members),
                 ('action', C.c_void_p), ('action_stride', C.c_int64)]
+
+
+class RndDesc(C.Structure):
+    """asac_rnd_desc_t: state and action widths of an RND stack (in = S + A -> 64 -> 64) and its blocks' residual flags"""
+    _fields_ = [('S', C.c_int32), ('A', C.c_int32), ('residual', C.c_int32 * 2)]
+
+
+class RndStack(C.Structure):
+    """asac_rnd_stack_t: the four parameter pointers of one RND stack"""
+    _fields_ = [('w1', C.c_void_p), ('b1', C.c_void_p), ('w2', C.c_void_p), ('b2', C.c_void_p)]
 
 
 class MlpDesc(C.Structure):
@@ -542,6 +552,15 @@ _SIGNATURES = {
                                        C.c_void_p, C.c_void_p]),
     'asac_dqn_act': (C.c_int, [C.POINTER(Branches), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p,
                                C.c_int64, C.c_int, C.c_void_p]),
+    'asac_rnd_supported': (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    'asac_rnd_distill_workspace': (C.c_int64, [C.c_int64]),
+    'asac_rnd_distill': (C.c_int, [C.POINTER(RndDesc), C.POINTER(RndStack), C.POINTER(RndStack), C.c_void_p, C.c_int64,
+                                   C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
+                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    'asac_rnd_pick': (C.c_int, [C.POINTER(RndDesc), C.POINTER(RndStack), C.POINTER(RndStack), C.c_void_p, C.c_int64,
+                                C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -2903,3 +2922,92 @@ def dqn_act(br: Branches, q, u, epsilon: float, action_out):
     assert action_out.shape[0] == B
     _check(load().asac_dqn_act(C.byref(br), _p(q), _discrete_rows(q, D, 'q'), _p(u), us, float(epsilon), _p(action_out),
                                _discrete_rows(action_out, D, 'action_out'), B, _stream()), 'asac_dqn_act')
+
+
+# ------------------------------------------------------------------------------------------------
+# random network distillation, continuous actions (csrc/rnd.hip)
+# ------------------------------------------------------------------------------------------------
+RND_WIDTH, RND_MAX_IN, RND_MAX_SAMPLES, RND_MAX_ROWS = 64, 128, 64, 1 << 20
+
+
+def rnd_sizes_ok(S: int, A: int, k: int = 1, rows: int = 1) -> bool:
+    """the limits of the `rnd_*` entry points (include/asac_hip.h ASAC_RND_*): k candidates per entry, `rows` = B * n"""
+    return bool(load().asac_rnd_supported(int(S), int(A), int(k))) and 0 <= rows <= RND_MAX_ROWS
+
+
+def rnd_desc(S: int, A: int, residual=(False, True)) -> RndDesc:
+    d = RndDesc()
+    d.S, d.A = int(S), int(A)
+    d.residual[0], d.residual[1] = int(bool(residual[0])), int(bool(residual[1]))
+    return d
+
+
+def rnd_stack(w1, b1, w2, b2) -> RndStack:
+    """the parameters of one stack (float32 device tensors, each contiguous; nn.Linear layout) -> `RndStack`; the tensors
+    must stay alive until the launch that reads the table is issued"""
+    for t in (w1, b1, w2, b2):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    assert w1.shape[0] == RND_WIDTH and w2.shape == (RND_WIDTH, RND_WIDTH) and b1.numel() == b2.numel() == RND_WIDTH
+    s = RndStack()
+    s.w1, s.b1, s.w2, s.b2 = w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
+    return s
+
+
+def rnd_distill_workspace_floats(rows: int) -> int:
+    """floats of a caller-owned workspace of `rnd_distill` over `rows` rows (zero before the first launch)"""
+    return int(load().asac_rnd_distill_workspace(int(rows)))
+
+
+def rnd_distill_workspace(device, rows: int) -> torch.Tensor:
+    """the zeroed exchange words of `rnd_distill` over `rows` rows on `device` (every launch leaves them ready for the next)"""
+    return _exchange_words('asac_rnd_distill', device, int(rows))
+
+
+@_profiled
+def rnd_distill(desc: RndDesc, predictor: RndStack, target: RndStack, state, action, padding_mask, x_cat, h1, gz1, gz2,
+                loss_out, workspace=None):
+    """state [B, n, S] and action [B, n, A]: float32 views with a dense last dim (any batch / time strides); padding_mask
+    [B, n] (one byte an element, any strides) or None -> x_cat [B * n, S + A], h1 / gz1 / gz2 [B * n, 64] (contiguous) and
+    the masked mean squared distillation error in loss_out: one launch (the weight gradients: `xty_multi` on these buffers)"""
+    B, n, S = state.shape
+    A = action.shape[2]
+    N = B * n
+    ps, s_sb, s_st = _window3(state)
+    pa, a_sb, a_st = _window3(action)
+    assert action.shape[:2] == (B, n) and (S, A) == (desc.S, desc.A)
+    pm, m_sb, m_st = None, 0, 0
+    if padding_mask is not None:
+        assert padding_mask.shape == (B, n) and padding_mask.element_size() == 1 and padding_mask.is_cuda
+        pm, m_sb, m_st = _p(padding_mask), padding_mask.stride(0), padding_mask.stride(1)
+    for t, width in ((x_cat, S + A), (h1, RND_WIDTH), (gz1, RND_WIDTH), (gz2, RND_WIDTH)):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == N * width
+    assert loss_out.is_cuda and loss_out.dtype == torch.float32 and loss_out.numel() == 1
+    ws = workspace if workspace is not None else (rnd_distill_workspace(state.device, N) if 0 < N <= RND_MAX_ROWS else loss_out)
+    _check(load().asac_rnd_distill(C.byref(desc), C.byref(predictor), C.byref(target), ps, s_sb, s_st, pa, a_sb, a_st, pm, m_sb,
+                                   m_st, B, n, _p(x_cat), _p(h1), _p(gz1), _p(gz2), _p(loss_out), _p(ws), _stream()),
+           'asac_rnd_distill')
+
+
+@_profiled
+def rnd_pick(desc: RndDesc, predictor: RndStack, target: RndStack, state, loc, scale, eps, action_out, prob_out,
+             err_out=None, index_out=None):
+    """state [batch, S]; loc / scale [batch, A] with one row stride (the halves of the policy's [batch, 2A] output); eps
+    [batch, k, A] contiguous -> action_out [batch, A] <- the candidate tanh(loc + scale * eps_j) of the largest distillation
+    error, prob_out [batch, A] <- its squash-corrected density; optionally err_out [batch, k] and index_out [batch] (int32):
+    one launch"""
+    batch, k, A = eps.shape
+    S = state.shape[1]
+    assert (S, A) == (desc.S, desc.A) and state.shape[0] == batch and loc.shape == scale.shape == (batch, A)
+    for t in (state, loc, scale):
+        assert t.is_cuda and t.dtype == torch.float32 and (t.stride(1) == 1 or t.shape[1] == 1)
+    assert loc.stride(0) == scale.stride(0) or batch <= 1
+    assert eps.is_cuda and eps.dtype == torch.float32 and eps.is_contiguous()
+    for t in (action_out, prob_out):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (batch, A)
+    if err_out is not None:
+        assert err_out.is_cuda and err_out.dtype == torch.float32 and err_out.is_contiguous() and err_out.shape == (batch, k)
+    if index_out is not None:
+        assert index_out.is_cuda and index_out.dtype == torch.int32 and index_out.is_contiguous() and index_out.numel() == batch
+    _check(load().asac_rnd_pick(C.byref(desc), C.byref(predictor), C.byref(target), _p(state), state.stride(0), _p(loc),
+                                _p(scale), loc.stride(0), _p(eps), k, batch, _p(action_out), _p(prob_out), _p(err_out),
+                                _p(index_out), _stream()), 'asac_rnd_pick')

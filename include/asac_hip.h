@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ASAC_ABI_VERSION 90
+#define ASAC_ABI_VERSION 91
 #define ASAC_MAX_GATHER_KEYS 16
 #define ASAC_MAX_ENSEMBLE 16
 #define ASAC_MAX_ACTION 64
@@ -1672,6 +1672,65 @@ int asac_dqn_q_loss_grad(const asac_vtrace_args_t* args_host, const asac_dqn_job
  * greedy only.  Writes every element of the D columns of action_out (rows action_stride apart).  Any B. */
 int asac_dqn_act(const asac_branches_t* branches, const float* q, int64_t q_stride, const float* u, int64_t u_stride,
                  float epsilon, float* action_out, int64_t action_stride, int B, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Random network distillation with continuous actions on the stock stacks (csrc/rnd.hip; shared device code
+ * csrc/asac_rnd.h).  One "RND stack" is ModelRND.c_dense = LinearLayers(S + A, 64, 2, None): two GELU (erf form)
+ * ResBlocks  in -> 64 -> 64,  in = S + A <= ASAC_RND_MAX_IN, biases present, dropout 0, no output Linear
+ * (nn.Linear layout: w1 [64][in], w2 [64][64]):
+ *   x = [state | action],  z1 = W1 x + b1,  h1 = gelu(z1) + r1 x,  z2 = W2 h1 + b2,  p = gelu(z2) + r2 h1
+ * residual[0] = r1 may be 1 only where in == 64 (ResBlock adds its input whenever the widths agree), residual[1] = r2.
+ * The four parameter pointers of a stack and the dense outputs are 16-byte aligned; the rows of states, actions,
+ * locations and scales may lie at any stride.  Products are f32 MFMA: each sum runs over the inputs in two interleaved
+ * blocks-of-16 chains that are added once; GELU is asac_gelu.h's.  No float atomics: equal inputs give equal bits.
+ * Bad arguments (a null required pointer, a misaligned parameter or output, in > 128, A > ASAC_MAX_ACTION, k < 1 or
+ * k > ASAC_RND_MAX_SAMPLES, r1 at another width, more than ASAC_RND_MAX_ROWS rows) return hipErrorInvalidValue without
+ * a launch; B == 0 / batch == 0 launches nothing.
+ * ------------------------------------------------------------------------------------------- */
+#define ASAC_RND_WIDTH 64
+#define ASAC_RND_MAX_IN 128
+#define ASAC_RND_MAX_SAMPLES 64
+#define ASAC_RND_MAX_ROWS (1 << 20)
+typedef struct {
+    int32_t S, A;
+    int32_t residual[2];
+} asac_rnd_desc_t;
+typedef struct {
+    const float *w1, *b1, *w2, *b2;
+} asac_rnd_stack_t;
+
+/* the limits above: 1 where (S, A) and k candidates per entry are within them (k = 1 for the distillation) */
+int asac_rnd_supported(int S, int A, int k);
+
+/* The distillation step without its weight gradients (sac_base.py _train_rnd 1978-2025, continuous branch), ONE launch.
+ * Row (b, t) of N = B n rows reads state[b * state_stride_b + t * state_stride_t + 0..S) and action likewise (strides in
+ * floats: window views of the step's batch); padding_mask (u8, element (b, t) at b * mask_stride_b + t * mask_stride_t)
+ * may be NULL.  With p the predictor's and t the frozen target's output:
+ *   d = (p - t) * !pad,   *loss_out = sum d^2 / (N 64),   g = 2 d / (N 64)
+ *   gz2 = g gelu'(z2),   gh1 = r2 g + gz2 W2,   gz1 = gh1 gelu'(z1)             (the predictor's pre-activations)
+ * Dense outputs: x_cat [N][S + A], h1 [N][64], gz1 [N][64], gz2 [N][64].  The predictor's gradients are products over
+ * the rows, formed by asac_xty_multi:  dW2 = gz2^T h1, db2 = colsum gz2, dW1 = gz1^T x_cat, db1 = colsum gz1.
+ * workspace: asac_rnd_distill_workspace(N) floats, zero before the first launch and left zero (the workgroups' loss sums
+ * are added in workgroup order by the last one to arrive). */
+int64_t asac_rnd_distill_workspace(int64_t n_rows);
+int asac_rnd_distill(const asac_rnd_desc_t* desc, const asac_rnd_stack_t* predictor, const asac_rnd_stack_t* target,
+                     const float* state, int64_t state_stride_b, int64_t state_stride_t, const float* action,
+                     int64_t action_stride_b, int64_t action_stride_t, const uint8_t* padding_mask, int64_t mask_stride_b,
+                     int64_t mask_stride_t, int B, int n, float* x_cat, float* h1, float* gz1, float* gz2, float* loss_out,
+                     float* workspace, void* stream);
+
+/* Novelty-guided acting (sac_base.py rnd_sample_c_action 829-856 and the probability of _choose_action 948-951), ONE
+ * launch behind the policy's forward.  state [batch][S] (rows state_stride apart), loc / scale [batch][A] (rows
+ * ls_row_stride apart: the two halves of the policy launch's [batch][2A] output), eps [batch][k][A] dense.  Candidate j
+ * of an entry is a_j = tanh(loc + scale eps_j) (the bits of asac_squash_sample_fwd), err_j = sum_f (p - t)^2 on
+ * [state | a_j];  action_out [batch][A] <- the candidate of the largest err_j (the lowest j among equal maxima, NaN the
+ * largest: torch.argmax), prob_out [batch][A] <- its squash-corrected density under (loc, scale) (the bits of
+ * asac_squash_prob on that action).  Optional (NULL-able): err_out [batch][k], index_out [batch] (int32).  Whole entries
+ * are mapped to a workgroup: an entry's candidates are compared in one place. */
+int asac_rnd_pick(const asac_rnd_desc_t* desc, const asac_rnd_stack_t* predictor, const asac_rnd_stack_t* target,
+                  const float* state, int64_t state_stride, const float* loc, const float* scale, int64_t ls_row_stride,
+                  const float* eps, int k, int batch, float* action_out, float* prob_out, float* err_out, int32_t* index_out,
+                  void* stream);
 
 #ifdef __cplusplus
 }

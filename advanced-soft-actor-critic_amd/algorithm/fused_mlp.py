@@ -194,6 +194,24 @@ def describe_rnd_stack(ll, state_size: int, action_size: int) -> 'native.RndDesc
     return native.rnd_desc(state_size, action_size, (b1.residual, b2.residual))
 
 
+def describe_drnd_member(ll, state_size: int) -> 'tuple | None':
+    """one member of `ModelRND.d_dense_list` as the `asac_drnd_*` launches take it: `describe_rnd_stack`'s rules at action
+    width 0 — `LinearLayers(S, 64, 2, None)`, exactly two GELU ResBlocks  S -> 64 -> 64  with biases, dropout 0, no output
+    Linear, S <= 128.  -> the blocks' residual flags (the first adds its input only where S == 64), else None."""
+    if not isinstance(ll, LinearLayers):
+        return None
+    parsed = _blocks_of(ll)
+    if parsed is None or parsed[1] is not None or len(parsed[0]) != 2:
+        return None
+    b1, b2 = parsed[0]
+    if (state_size <= 0 or ll.input_size != state_size or state_size > native.RND_MAX_IN
+            or b1.linear.in_features != state_size or b1.linear.out_features != native.RND_WIDTH
+            or b2.linear.in_features != native.RND_WIDTH or b2.linear.out_features != native.RND_WIDTH
+            or b1.linear.bias is None or b2.linear.bias is None):
+        return None
+    return bool(b1.residual), bool(b2.residual)
+
+
 def rnd_stack_tensors(ll) -> tuple:
     """(w1, b1, w2, b2) of a stack `describe_rnd_stack` accepts"""
     b1, b2 = _blocks_of(ll)[0]

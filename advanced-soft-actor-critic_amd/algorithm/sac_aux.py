@@ -540,6 +540,8 @@ class AuxHeadsMixin:
         """Distil the frozen random target network on visited (state, action) pairs (1978-2025)."""
         if n_states.dim() == 3 and (rnd := self._rnd_fused(rows=n_states.shape[0] * n_states.shape[1])) is not None:
             return self._train_rnd_fused(rnd, n_padding_masks, n_states, n_actions)
+        if n_states.dim() == 3 and (drnd := self._drnd_fused(rows=n_states.shape[0] * n_states.shape[1])) is not None:
+            return self._train_drnd_fused(drnd, n_padding_masks, n_states, n_actions)
         dsum = self.d_action_summed_size
         d_act, c_act = n_actions[..., :dsum], n_actions[..., dsum:]
         keep = ~n_padding_masks.unsqueeze(-1)
@@ -600,6 +602,38 @@ class AuxHeadsMixin:
         native.rnd_distill(desc, pred, targ, n_states, n_actions, mask, x_cat, h1, gz1, gz2, loss, ws)
         w1, b1, w2, b2 = tensors[:4]
         native.xty_multi([(gz2, h1, w2.grad, b2.grad), (gz1, x_cat, w1.grad, b1.grad)], accumulate=False)
+        self.optimizer_rnd.step()
+        return loss
+
+    @torch.no_grad()
+    def _train_drnd_fused(self, drnd, n_padding_masks, n_states, n_actions):
+        """`_train_rnd` for a pure-discrete, policy-based learner on the stock stacks (`SAC_Base._drnd_fused`): ONE launch
+        for the selected members of predictor and target over the window, the masked loss and the cotangents at the
+        predictor's pre-activations as compact (row, branch) records (`asac_drnd_distill`), ONE launch that OVERWRITES the
+        gradient views of all D members of `d_dense_list` from those records (`asac_drnd_param_grads`: zeros for a member
+        no row selected, on which Adam still steps), then the unchanged Adam launch.  No `zero_grad()`: `s_dense` — never
+        evaluated by a policy-based learner (the reference leaves its `.grad` None) — has its span of the flat gradient
+        buffer zeroed once, when the buffers are made.  Buffers and exchange words are made once per (B, n) and reused."""
+        from asac_amd import native
+        residual, pred, targ, grads, _ = drnd
+        B, n = n_states.shape[:2]
+        br, S = self._branches, self.state_size
+        buf = self._drnd_buffers.get((B, n))
+        if buf is None:
+            N, dev, W = B * n, self.device, native.RND_WIDTH
+            rec = lambda: torch.empty((N, br.K, W), dtype=torch.float32, device=dev)        # noqa: E731
+            zeros = lambda words: torch.zeros(words, dtype=torch.float32, device=dev)       # noqa: E731
+            buf = self._drnd_buffers[(B, n)] = (
+                torch.empty((N, br.K), dtype=torch.int32, device=dev), torch.empty((N, S), dtype=torch.float32, device=dev),
+                rec(), rec(), rec(), torch.zeros((), dtype=torch.float32, device=dev),
+                zeros(native.drnd_distill_workspace_floats(N)), zeros(native.drnd_param_grads_workspace_floats(N, S, br.D)))
+            for p in self.model_rnd.s_dense.parameters():
+                if p.grad is not None:
+                    p.grad.zero_()
+        sel, x, h1, gz1, gz2, loss, ws_d, ws_g = buf
+        mask = n_padding_masks if n_padding_masks.element_size() == 1 else n_padding_masks.to(torch.bool)
+        native.drnd_distill(br, residual, pred, targ, n_states, n_actions, mask, sel, x, h1, gz1, gz2, loss, ws_d)
+        native.drnd_param_grads(br, S, sel, x, h1, gz1, gz2, grads, ws_g)
         self.optimizer_rnd.step()
         return loss
 

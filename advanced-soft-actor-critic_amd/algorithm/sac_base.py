@@ -125,6 +125,19 @@ def fused_rnd_applies(*, enabled, plain_learner, d_action_sizes, c_action_size, 
                 and float32_on_device and stack_ok and native.rnd_sizes_ok(state_size, c_action_size, n_sample, rows))
 
 
+def fused_rnd_discrete_applies(*, enabled, plain_learner, d_action_sizes, c_action_size, discrete_dqn_like, data_parallel,
+                               float32_on_device, stack_ok, state_size, n_sample=1, rows=1) -> bool:
+    """Does random network distillation of this configuration run on the `asac_drnd_*` launches
+    (`hip_config['fused_rnd_discrete']`)?  Only a plain `SAC_Base` (`plain_learner`: not an `OptionBase`) with discrete
+    branches alone and a policy (`discrete_dqn_like=False`), without a data-parallel context, on float32 device tensors,
+    whose `model_rnd.d_dense_list` and `model_target_rnd.d_dense_list` are all the stock stack on 16-byte-aligned contiguous
+    parameters (`stack_ok`), within the entry points' limits (`n_sample` candidates an entry when acting, `rows` = batch *
+    window rows when training).  Everything else — hybrid spaces, the DQN-like `s_dense` form — runs the eager code."""
+    return bool(enabled and plain_learner and len(d_action_sizes) > 0 and c_action_size == 0 and not discrete_dqn_like
+                and not data_parallel and float32_on_device and stack_ok
+                and native.drnd_sizes_ok(state_size, d_action_sizes, n_sample, rows))
+
+
 class _Window:
     """views of the step's static batch tensors and what the phases of `_device_step_body` hand to each other"""
 
@@ -307,6 +320,10 @@ class SAC_Base(AuxHeadsMixin):
         self._fused_rnd = bool(hip_config.get('fused_rnd', True))               # asac_rnd_* (continuous RND, stock stacks)
         self._rnd_stacks = None          # (RndDesc, predictor, target, tensors) | False once described (`_rnd_fused`)
         self._rnd_buffers = {}           # (B, n) -> the distillation launch's dense outputs
+        # asac_drnd_* (pure-discrete RND with a policy, stock stacks): NOTES.md, "discrete RND"
+        self._fused_rnd_discrete = bool(hip_config.get('fused_rnd_discrete', True))
+        self._drnd_stacks = None         # (residual, predictor table, target table, gradient table, tensors) | False (`_drnd_fused`)
+        self._drnd_buffers = {}          # (B, n) -> the distillation launch's records and both launches' exchange words
         self._fused_rpm_loss = bool(hip_config.get('fused_rpm_loss', True))
         # one backward walk per prediction model (gates and model gradients from it): sac_aux._train_rpm
         self._rpm_single_backward = bool(hip_config.get('rpm_single_backward', True))
@@ -841,6 +858,23 @@ class SAC_Base(AuxHeadsMixin):
             native.rnd_pick(rnd[0], rnd[1], rnd[2], StockMLP._rows(state, self.state_size), ls[:, :A], ls[:, A:], eps,
                             c_action, prob)
             return c_action, prob
+        if (use_rnd and offline_action is None and not disable_sample and self.action_noise is None and state.dim() == 2
+                and (drnd := self._drnd_fused(rows=batch * self.rnd_n_sample)) is not None):
+            # novelty-guided acting, discrete branches with a policy: the policy's logits (`_discrete_logits`: the stock
+            # policy's raw head outputs, the distribution logits of a plugin policy that has its own `forward`), the
+            # uniforms of the rnd_n_sample candidates, then ONE launch for the branch softmax, the candidates (inverse CDF),
+            # both stacks of all D members of `d_dense_list`, the first largest distillation error per entry and the
+            # one-hot action — instead of 2 D two-block stacks, two `torch.stack`, `OneHotCategorical.sample((k,))` per
+            # branch, two [batch, k, D, 64] broadcast products and pow / sum / argmax / index per environment step
+            D = self.d_action_summed_size
+            logits = self._discrete_logits(state, obs_list)
+            u = torch.empty((batch, self.rnd_n_sample, self.d_action_branch_size), dtype=torch.float32, device=self.device)
+            self.noise.uniform_(u)
+            d_action = torch.empty((batch, D), dtype=torch.float32, device=self.device)
+            prob = torch.empty((batch, D), dtype=torch.float32, device=self.device)
+            native.drnd_pick(self._branches, drnd[0], drnd[1], drnd[2], StockMLP._rows(state, self.state_size), logits, u,
+                             d_action, prob)
+            return d_action, prob
         if offline_action is None and not use_rnd and state.dim() == 2 and self._dqn_fused(1, acting=True):
             # DQN-like, discrete branches only: the first critic's forward, then ONE launch for the greedy one-hot per
             # branch and (train mode) the epsilon-random rows, their uniforms drawn on the device — instead of ~30 eager
@@ -1171,6 +1205,39 @@ class SAC_Base(AuxHeadsMixin):
         ok = fused_rnd_applies(
             enabled=self._fused_rnd, plain_learner=type(self)._plain_learner, d_action_sizes=self.d_action_sizes,
             c_action_size=self.c_action_size, data_parallel=self._dist is not None,
+            float32_on_device=self._params.flat.dtype == torch.float32 and self._params.flat.is_cuda,
+            stack_ok=bool(stacks), state_size=self.state_size, n_sample=self.rnd_n_sample, rows=rows)
+        return stacks if ok else None
+
+    def _drnd_fused(self, rows: int = 1):
+        """-> (residual flags, predictor table, target table, gradient table, tensors) when random network distillation of a
+        pure-discrete, policy-based learner runs on the `asac_drnd_*` launches (`fused_rnd_discrete_applies`, with
+        `rnd_n_sample` candidates an entry: a learner whose acting cannot take the path does not train on it either), else
+        None.  The members are described and the device tables built once: the parameters are views of the flat buffers
+        (predictor, and its gradients) or the target's own storage and keep their addresses."""
+        if not self.use_rnd or not self._fused_rnd_discrete:
+            return None
+        if self._drnd_stacks is None:
+            self._drnd_stacks = False
+            from .fused_mlp import describe_drnd_member, rnd_stack_tensors
+            pl, tl = getattr(self.model_rnd, 'd_dense_list', None), getattr(self.model_target_rnd, 'd_dense_list', None)
+            D = self.d_action_summed_size
+            if (self.d_action_sizes and not self.c_action_size and pl is not None and tl is not None
+                    and len(pl) == len(tl) == D <= native.DRND_MAX_MEMBERS):
+                flags = {describe_drnd_member(m, self.state_size) for m in list(pl) + list(tl)}
+                if len(flags) == 1 and None not in flags:
+                    pred, targ = [rnd_stack_tensors(m) for m in pl], [rnd_stack_tensors(m) for m in tl]
+                    every = [x for m in pred + targ for x in m]
+                    ok = all(x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.data_ptr() % 16 == 0 for x in every)
+                    ok = ok and all(x.grad is not None and x.grad.is_contiguous() and x.grad.data_ptr() % 16 == 0
+                                    for m in pred for x in m)
+                    if ok:
+                        self._drnd_stacks = (flags.pop(), native.drnd_table(pred), native.drnd_table(targ),
+                                             native.drnd_table([[x.grad for x in m] for m in pred]), every)
+        stacks = self._drnd_stacks
+        ok = fused_rnd_discrete_applies(
+            enabled=self._fused_rnd_discrete, plain_learner=type(self)._plain_learner, d_action_sizes=self.d_action_sizes,
+            c_action_size=self.c_action_size, discrete_dqn_like=self.discrete_dqn_like, data_parallel=self._dist is not None,
             float32_on_device=self._params.flat.dtype == torch.float32 and self._params.flat.is_cuda,
             stack_ok=bool(stacks), state_size=self.state_size, n_sample=self.rnd_n_sample, rows=rows)
         return stacks if ok else None

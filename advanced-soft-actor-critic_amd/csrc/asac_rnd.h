@@ -163,5 +163,19 @@ __device__ __forceinline__ float squashed_action(float loc, float scale, float e
     return tanhf(x);
 }
 
+// host side, shared by rnd.hip and drnd.hip: raise a kernel's dynamic LDS limit once; the alignment the 16-byte accesses need
+inline int set_lds_limit(const void* fn, size_t bytes, bool& done, const char* where) {
+    if (done) return 0;
+    hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (err != hipSuccess) {
+        set_error(err, where);
+        return (int)err;
+    }
+    done = true;
+    return 0;
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 }  // namespace rnd
 }  // namespace asac

@@ -176,19 +176,6 @@ static size_t pick_lds(int in, int A) {
     return sizeof(float) * (2 * stack_floats(in) + kTile * (pad16(in) + 4) + kTile * kPitch + kPickRows * A + kPickRows + 256);
 }
 
-static int set_lds_limit(const void* fn, size_t bytes, bool& done, const char* where) {
-    if (done) return 0;
-    hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (err != hipSuccess) {
-        set_error(err, where);
-        return (int)err;
-    }
-    done = true;
-    return 0;
-}
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 static bool stack_ok(const asac_rnd_stack_t* s) {
     return s && s->w1 && s->b1 && s->w2 && s->b2 && aligned16(s->w1) && aligned16(s->b1) && aligned16(s->w2) && aligned16(s->b2);
 }

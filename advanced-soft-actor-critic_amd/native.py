@@ -561,6 +561,18 @@ _SIGNATURES = {
     'asac_rnd_pick': (C.c_int, [C.POINTER(RndDesc), C.POINTER(RndStack), C.POINTER(RndStack), C.c_void_p, C.c_int64,
                                 C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_drnd_supported': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'asac_drnd_distill_workspace': (C.c_int64, [C.c_int64]),
+    'asac_drnd_distill': (C.c_int, [C.POINTER(Branches), C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    'asac_drnd_param_grads_workspace': (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    'asac_drnd_param_grads': (C.c_int, [C.POINTER(Branches), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_drnd_pick': (C.c_int, [C.POINTER(Branches), C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -3011,3 +3023,126 @@ def rnd_pick(desc: RndDesc, predictor: RndStack, target: RndStack, state, loc, s
     _check(load().asac_rnd_pick(C.byref(desc), C.byref(predictor), C.byref(target), _p(state), state.stride(0), _p(loc),
                                 _p(scale), loc.stride(0), _p(eps), k, batch, _p(action_out), _p(prob_out), _p(err_out),
                                 _p(index_out), _stream()), 'asac_rnd_pick')
+
+
+# ------------------------------------------------------------------------------------------------
+# random network distillation, pure-discrete policy-based learner (csrc/drnd.hip)
+# ------------------------------------------------------------------------------------------------
+DRND_MAX_MEMBERS = 16
+
+
+def drnd_sizes_ok(S: int, d_action_sizes, k: int = 1, rows: int = 1) -> bool:
+    """the limits of the `drnd_*` entry points (include/asac_hip.h): S, D = sum of the branch sizes, K branches, k candidates
+    per entry, `rows` = B * n"""
+    sizes = [int(s) for s in d_action_sizes]
+    return (len(sizes) > 0 and all(s > 0 for s in sizes)
+            and bool(load().asac_drnd_supported(int(S), sum(sizes), len(sizes), int(k))) and 0 <= rows <= RND_MAX_ROWS)
+
+
+def drnd_table(members, device=None) -> torch.Tensor:
+    """the members' tensors ((w1, b1, w2, b2) each: parameters, or their gradient views) -> the DEVICE table the `drnd_*`
+    launches read (`asac_rnd_stack_t` / `asac_rnd_grads_t` x D, int64 [D, 4]).  Every tensor is float32, contiguous, on the
+    device and 16-byte aligned (the entry points cannot see the members: this is their check); the tensors must stay alive
+    and keep their addresses as long as the table is used."""
+    members = [tuple(m) for m in members]
+    if not 0 < len(members) <= DRND_MAX_MEMBERS:
+        raise AsacNativeError(f'drnd_table: {len(members)} members (1..{DRND_MAX_MEMBERS})')
+    for w1, b1, w2, b2 in members:
+        for t in (w1, b1, w2, b2):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0):
+                raise AsacNativeError('drnd_table: a member tensor is not a contiguous, 16-byte-aligned float32 device tensor')
+        if not (w1.shape[0] == RND_WIDTH and tuple(w2.shape) == (RND_WIDTH, RND_WIDTH)
+                and b1.numel() == b2.numel() == RND_WIDTH and w1.shape[1] == members[0][0].shape[1]):
+            raise AsacNativeError('drnd_table: a member is not a  S -> 64 -> 64  stack')
+    dev = members[0][0].device if device is None else device
+    return torch.tensor([[t.data_ptr() for t in m] for m in members], dtype=torch.int64).to(dev)
+
+
+def _residual2(residual):
+    return (C.c_int32 * 2)(int(bool(residual[0])), int(bool(residual[1])))
+
+
+def drnd_distill_workspace_floats(rows: int) -> int:
+    return int(load().asac_drnd_distill_workspace(int(rows)))
+
+
+def drnd_param_grads_workspace_floats(rows: int, S: int, D: int) -> int:
+    return int(load().asac_drnd_param_grads_workspace(int(rows), int(S), int(D)))
+
+
+def drnd_distill_workspace(device, rows: int) -> torch.Tensor:
+    """the zeroed exchange words of `drnd_distill` over `rows` rows on `device` (every launch leaves them ready for the next)"""
+    return _exchange_words('asac_drnd_distill', device, int(rows))
+
+
+def drnd_param_grads_workspace(device, rows: int, S: int, D: int) -> torch.Tensor:
+    return _exchange_words('asac_drnd_param_grads', device, int(rows), int(S), int(D))
+
+
+@_profiled
+def drnd_distill(br: Branches, residual, predictors, targets, state, action, padding_mask, sel, x, h1, gz1, gz2, loss_out,
+                 workspace=None):
+    """state [B, n, S] and action [B, n, >= D]: float32 views with a dense last dim (any batch / time strides); padding_mask
+    [B, n] (one byte an element) or None; predictors / targets: `drnd_table`s of the D members -> sel int32 [B * n, K], the
+    records h1 / gz1 / gz2 [B * n, K, 64], x [B * n, S] (contiguous) and the masked mean squared distillation error in
+    loss_out: one launch (the parameter gradients: `drnd_param_grads` on these buffers)"""
+    B, n, S = state.shape
+    N, K, D = B * n, br.K, br.D
+    ps, s_sb, s_st = _window3(state)
+    pa, a_sb, a_st = _window3(action)
+    assert action.shape[:2] == (B, n) and action.shape[2] >= D
+    pm, m_sb, m_st = None, 0, 0
+    if padding_mask is not None:
+        assert padding_mask.shape == (B, n) and padding_mask.element_size() == 1 and padding_mask.is_cuda
+        pm, m_sb, m_st = _p(padding_mask), padding_mask.stride(0), padding_mask.stride(1)
+    for t, width in ((x, S), (h1, K * RND_WIDTH), (gz1, K * RND_WIDTH), (gz2, K * RND_WIDTH)):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == N * width
+    assert sel.is_cuda and sel.dtype == torch.int32 and sel.is_contiguous() and sel.numel() == N * K
+    assert loss_out.is_cuda and loss_out.dtype == torch.float32 and loss_out.numel() == 1
+    for tab in (predictors, targets):
+        assert tab is None or (tab.is_cuda and tab.dtype == torch.int64 and tab.is_contiguous() and tab.shape == (D, 4))
+    ws = workspace if workspace is not None else (drnd_distill_workspace(state.device, N) if 0 < N <= RND_MAX_ROWS else loss_out)
+    _check(load().asac_drnd_distill(C.byref(br), S, _residual2(residual), _p(predictors), _p(targets), ps, s_sb, s_st, pa, a_sb,
+                                    a_st, pm, m_sb, m_st, B, n, _p(sel), _p(x), _p(h1), _p(gz1), _p(gz2), _p(loss_out), _p(ws),
+                                    _stream()), 'asac_drnd_distill')
+
+
+@_profiled
+def drnd_param_grads(br: Branches, S: int, sel, x, h1, gz1, gz2, grads, workspace=None):
+    """the records of `drnd_distill` -> every element of the D members' gradient views (`grads`: the `drnd_table` of
+    (w1.grad, b1.grad, w2.grad, b2.grad) per member), rows in ascending order: one launch"""
+    N, K, D = sel.numel() // br.K, br.K, br.D
+    for t, width in ((x, S), (h1, K * RND_WIDTH), (gz1, K * RND_WIDTH), (gz2, K * RND_WIDTH)):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == N * width
+    assert sel.is_cuda and sel.dtype == torch.int32 and sel.is_contiguous()
+    assert grads is None or (grads.is_cuda and grads.dtype == torch.int64 and grads.is_contiguous() and grads.shape == (D, 4))
+    ws = workspace if workspace is not None else (drnd_param_grads_workspace(x.device, N, S, D) if 0 < N <= RND_MAX_ROWS else x)
+    _check(load().asac_drnd_param_grads(C.byref(br), int(S), _p(sel), _p(x), _p(h1), _p(gz1), _p(gz2), N, _p(grads), _p(ws),
+                                        _stream()), 'asac_drnd_param_grads')
+
+
+@_profiled
+def drnd_pick(br: Branches, residual, predictors, targets, state, logits, u, action_out, prob_out, err_out=None,
+              cand_out=None, index_out=None):
+    """state [batch, S]; logits [batch, D] (the policy's branch head outputs); u [batch, k, K] contiguous uniforms in [0, 1)
+    -> action_out [batch, D] <- the one-hot candidate of the largest distillation error, prob_out [batch, D] <- the branch
+    softmax; optionally err_out [batch, k], cand_out [batch, k, K] (int32) and index_out [batch] (int32): one launch"""
+    batch, k, K = u.shape
+    S, D = state.shape[1], br.D
+    assert K == br.K and state.shape[0] == batch and logits.shape == (batch, D)
+    for t in (state, logits):
+        assert t.is_cuda and t.dtype == torch.float32 and (t.stride(1) == 1 or t.shape[1] == 1)
+    assert u.is_cuda and u.dtype == torch.float32 and u.is_contiguous()
+    for t in (action_out, prob_out):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (batch, D)
+    if err_out is not None:
+        assert err_out.is_cuda and err_out.dtype == torch.float32 and err_out.is_contiguous() and err_out.shape == (batch, k)
+    if cand_out is not None:
+        assert cand_out.is_cuda and cand_out.dtype == torch.int32 and cand_out.is_contiguous() and cand_out.shape == (batch, k, K)
+    if index_out is not None:
+        assert index_out.is_cuda and index_out.dtype == torch.int32 and index_out.is_contiguous() and index_out.numel() == batch
+    for tab in (predictors, targets):
+        assert tab is None or (tab.is_cuda and tab.dtype == torch.int64 and tab.is_contiguous() and tab.shape == (D, 4))
+    _check(load().asac_drnd_pick(C.byref(br), S, _residual2(residual), _p(predictors), _p(targets), _p(state), state.stride(0),
+                                 _p(logits), logits.stride(0), _p(u), k, batch, _p(action_out), _p(prob_out), _p(err_out),
+                                 _p(cand_out), _p(index_out), _stream()), 'asac_drnd_pick')

@@ -1732,6 +1732,72 @@ int asac_rnd_pick(const asac_rnd_desc_t* desc, const asac_rnd_stack_t* predictor
                   const float* eps, int k, int batch, float* action_out, float* prob_out, float* err_out, int32_t* index_out,
                   void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Random network distillation for a pure-discrete, policy-based learner (csrc/drnd.hip; device code shared with the block
+ * above: csrc/asac_rnd.h, and csrc/asac_categorical.h).  ModelRND.d_dense_list holds D = sum of the branch sizes
+ * independent stacks LinearLayers(S, 64, 2, None) (the stack of the block above with in = S and no action columns; r1 may
+ * be 1 only where S == 64).  A row's action is K concatenated one-hot vectors; per (row, branch) it SELECTS the member at
+ * the first non-zero element of the branch, and that element's value is the weight w (1 for every stored action).  A branch
+ * without a non-zero element selects nothing.  Rows that are not one-hot per branch are outside the contract.  A member a
+ * row did not select is not evaluated for it (the reference multiplies its output by 0, which turns an infinite output
+ * into NaN; this path does not).
+ * predictors / targets: DEVICE tables of D asac_rnd_stack_t (member m's four parameter pointers, each 16-byte aligned —
+ * the caller checks the members when it fills the table; the host side checks the table pointers); residual: HOST int32[2]
+ * (r1, r2), the same for all members.  Limits (asac_drnd_supported): S <= ASAC_RND_MAX_IN, D <= ASAC_DRND_MAX_MEMBERS,
+ * K <= ASAC_DISCRETE_MAX_BRANCHES, k <= ASAC_RND_MAX_SAMPLES, rows <= ASAC_RND_MAX_ROWS, tables and records 16-byte aligned.
+ * Anything outside returns hipErrorInvalidValue without a launch; B == 0 / n_rows == 0 / batch == 0 launches nothing.
+ * No float atomics: equal inputs give equal bits.
+ * ------------------------------------------------------------------------------------------- */
+#define ASAC_DRND_MAX_MEMBERS 16
+typedef struct {
+    float *w1, *b1, *w2, *b2;
+} asac_rnd_grads_t;
+
+int asac_drnd_supported(int S, int D, int K, int k);
+
+/* The distillation step without its parameter gradients (sac_base.py _train_rnd 1997-2010), ONE launch.  Row (b, t) of
+ * N = B n rows reads state and action as asac_rnd_distill does (strides in floats); padding_mask may be NULL.  With P_m,
+ * T_m member m of the predictor and of the frozen target and (m_j, w_j) the selection of branch j:
+ *   d = sum_j w_j (P_{m_j}(x) - T_{m_j}(x))      (members in ascending order; padded rows select nothing: d = 0)
+ *   *loss_out = sum d^2 / (N 64)                 (lanes -> waves -> workgroup in a fixed order; the workgroups' sums are
+ *                                                 added in workgroup order by the last one to arrive)
+ *   g_j = w_j (2 d / (N 64)),  gz2_j = g_j gelu'(z2),  gh1_j = r2 g_j + gz2_j W2,  gz1_j = gh1_j gelu'(z1)    (of P_{m_j})
+ * Outputs: sel i32 [N][K] (m_j or -1), the records h1 / gz1 / gz2 f32 [N][K][64] (zeros where sel is -1), x [N][S].
+ * workspace: asac_drnd_distill_workspace(N) floats (the workgroups' sums, then the arrival counter), zero before the first
+ * launch; every launch leaves the COUNTER zero — the sums stay in their slots and are rewritten by the next launch. */
+int64_t asac_drnd_distill_workspace(int64_t n_rows);
+int asac_drnd_distill(const asac_branches_t* branches, int S, const int32_t* residual, const asac_rnd_stack_t* predictors,
+                      const asac_rnd_stack_t* targets, const float* state, int64_t state_stride_b, int64_t state_stride_t,
+                      const float* action, int64_t action_stride_b, int64_t action_stride_t, const uint8_t* padding_mask,
+                      int64_t mask_stride_b, int64_t mask_stride_t, int B, int n, int32_t* sel, float* x, float* h1, float* gz1,
+                      float* gz2, float* loss_out, float* workspace, void* stream);
+
+/* The predictor's parameter gradients from those records (autograd's walk through the D stacks), ONE launch.  For member
+ * m of branch j, over the rows r with sel[r][j] == m in ASCENDING order (fmaf chains, float32):
+ *   dW2_m = sum gz2[r][j]^T h1[r][j],  db2_m = sum gz2[r][j],  dW1_m = sum gz1[r][j]^T x[r],  db1_m = sum gz1[r][j]
+ * grads: DEVICE table of D asac_rnd_grads_t (member m's four gradient views, nn.Linear layout).  Every element of all D
+ * members' views is overwritten (zeros for a member nobody selected).  Rows are split in at most 64 chunks; the chunks'
+ * sums are added in chunk order by the member's last arriver.  workspace: asac_drnd_param_grads_workspace(N, S, D)
+ * floats (the chunks' sums, then one arrival counter a member), zero before the first launch; every launch leaves the
+ * counters zero. */
+int64_t asac_drnd_param_grads_workspace(int64_t n_rows, int S, int D);
+int asac_drnd_param_grads(const asac_branches_t* branches, int S, const int32_t* sel, const float* x, const float* h1,
+                          const float* gz1, const float* gz2, int64_t n_rows, const asac_rnd_grads_t* grads, float* workspace,
+                          void* stream);
+
+/* Novelty-guided acting (sac_base.py rnd_sample_d_action 793-826 and the probability of _choose_action 957-961), ONE
+ * launch behind the policy's logits.  state [batch][S] (rows state_stride apart), logits [batch][D] (rows logits_stride
+ * apart), u [batch][k][K] dense uniforms in [0, 1).  p = the branch softmax (the bits of asac_discrete_policy_loss_grad's
+ * probs_out).  Candidate c's index in a branch of s entries is #{i < s - 1 : c_i <= u}, c_i the running float32 sum of p in
+ * index order;  err_c = sum_f (sum_j E_{m_j}[f])^2 with E_m = P_m(x) - T_m(x), j and then f in ascending order.
+ * action_out [batch][D] <- the one-hot candidate of the largest err (the lowest c among equal maxima, NaN the largest:
+ * torch.argmax), every element written; prob_out [batch][D] <- p.  Optional (NULL-able): err_out [batch][k], cand_out i32
+ * [batch][k][K], index_out i32 [batch].  An entry is decided inside one workgroup. */
+int asac_drnd_pick(const asac_branches_t* branches, int S, const int32_t* residual, const asac_rnd_stack_t* predictors,
+                   const asac_rnd_stack_t* targets, const float* state, int64_t state_stride, const float* logits,
+                   int64_t logits_stride, const float* u, int k, int batch, float* action_out, float* prob_out, float* err_out,
+                   int32_t* cand_out, int32_t* index_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

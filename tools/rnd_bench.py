@@ -10,7 +10,11 @@ two launches (csrc/rnd.hip, `hip_config['fused_rnd']`) and as today's eager chai
 With the flag off both run exactly the code of the commit before the kernels, so this is the A/B against it without a second
 checkout; bench.py has no `use_rnd` configuration.
 
-    python tools/rnd_bench.py [--steps 600] [--calls 300] [--fill 16384]
+    python tools/rnd_bench.py [--steps 600] [--calls 300] [--fill 16384] [--discrete 3[,2,..]]
+
+`--discrete SIZES` measures the pure-discrete, policy-based learner instead (csrc/drnd.hip, `hip_config['fused_rnd_discrete']`:
+branches of these sizes, no continuous action, the plugin `nn_vec_full` — the mountain-car shape is `--discrete 3`), acting at
+(batch, rnd_n_sample) = (10, 10) and (100, 50); flag off is again the code of the commit before.
 
 The two ways alternate (off, on, off, on, ...: a drift of the box's clocks hits both) and every timed window ends in a device
 synchronise; the median of the rounds is reported, all rounds are listed.  BOTH learners stay alive while the tool alternates
@@ -50,14 +54,26 @@ def plugin_with_rnd(base):
     return ns
 
 
-def learner(cfg, plugin, fused, use_graph, episodes=(), **kw):
+def mode_of(sizes):
+    """what a run measures: the branch sizes (--discrete; then no continuous action), the switch and its launches' prefix"""
+    if sizes:
+        return types.SimpleNamespace(sizes=list(sizes), flag='fused_rnd_discrete', prefix='asac_drnd_')
+    return types.SimpleNamespace(sizes=[], flag='fused_rnd', prefix='asac_rnd_')
+
+
+def action_sizes(cfg, mode):
+    return (list(mode.sizes), 0) if mode.sizes else ([], cfg['c_action_size'])
+
+
+def learner(cfg, plugin, mode, fused, use_graph, episodes=(), **kw):
     from algorithm.sac_base import SAC_Base
     torch.manual_seed(0)
-    agent = SAC_Base(cfg['obs_names'], cfg['obs_shapes'], [], cfg['c_action_size'], None, plugin, device='cuda:0',
+    d_sizes, c_size = action_sizes(cfg, mode)
+    agent = SAC_Base(cfg['obs_names'], cfg['obs_shapes'], d_sizes, c_size, None, plugin, device='cuda:0',
                      n_step=cfg['n_step'], burn_in_step=cfg['burn_in_step'], batch_size=cfg['batch_size'],
                      ensemble_q_num=cfg['ensemble_q_num'], ensemble_q_sample=cfg['ensemble_q_sample'],
                      replay_config={'capacity': cfg['capacity']}, use_rnd=True,
-                     hip_config={'use_graph': use_graph, 'fused_rnd': fused}, **kw)
+                     hip_config={'use_graph': use_graph, mode.flag: fused}, **kw)
     for ep in episodes:
         agent.put_episode(**ep)
     return agent
@@ -72,26 +88,27 @@ def alternate(run, rounds=ROUNDS):
     return runs
 
 
-def step_row(cfg, plugin, steps, fill):
+def step_row(cfg, plugin, mode, steps, fill):
     from asac_amd import native
     from tests import parity_utils as pu
     rng = np.random.default_rng(1)
-    episodes = [pu.synthetic_episode(rng, cfg['obs_shapes'], [], cfg['c_action_size'], cfg['hidden'], cfg['episode_len'])
+    episodes = [pu.synthetic_episode(rng, cfg['obs_shapes'], *action_sizes(cfg, mode), cfg['hidden'], cfg['episode_len'])
                 for _ in range(max(4, fill // cfg['episode_len']))]
     agents = {}
-    row = {'mode': 'step', 'batch': cfg['batch_size'], 'n_step': cfg['n_step'], 'steps': steps, 'rounds': ROUNDS}
+    row = {'mode': 'step', 'discrete': list(mode.sizes), 'batch': cfg['batch_size'], 'n_step': cfg['n_step'], 'steps': steps,
+           'rounds': ROUNDS}
     for fused in (False, True):
         tag = 'fused' if fused else 'eager'
-        agent = learner(cfg, plugin, fused, False, episodes)
+        agent = learner(cfg, plugin, mode, fused, False, episodes)
         agent.train()                # the eager step, counted
         with native.LaunchProfiler(repeat=1) as prof:
             agent.train()
         seen = prof.summary()
         row['native_launches_' + tag] = sum(v['calls'] for v in seen.values())
-        row['rnd_launches_' + tag] = {k: v['calls'] for k, v in seen.items() if k.startswith('asac_rnd_')}
+        row['rnd_launches_' + tag] = {k: v['calls'] for k, v in seen.items() if k.startswith(mode.prefix)}
         row['device_kernels_' + tag] = count_kernels(agent.train)
         agent.close()
-        agent = learner(cfg, plugin, fused, True, episodes)
+        agent = learner(cfg, plugin, mode, fused, True, episodes)
         for _ in range(20):          # eager warm-up, capture, first replays
             agent.train()
         torch.cuda.synchronize()
@@ -116,10 +133,10 @@ def step_row(cfg, plugin, steps, fill):
     return row
 
 
-def acting_row(cfg, plugin, batch, k, calls):
-    agents = {fused: learner(cfg, plugin, fused, False, rnd_n_sample=k) for fused in (False, True)}
+def acting_row(cfg, plugin, mode, batch, k, calls):
+    agents = {fused: learner(cfg, plugin, mode, fused, False, rnd_n_sample=k) for fused in (False, True)}
     obs = [torch.randn(batch, *shape, device='cuda') for shape in cfg['obs_shapes']]
-    args = (obs, torch.zeros(batch, cfg['c_action_size'], device='cuda'),
+    args = (obs, torch.zeros(batch, sum(mode.sizes) if mode.sizes else cfg['c_action_size'], device='cuda'),
             torch.zeros(batch, *agents[True].seq_hidden_state_shape, device='cuda'))
     row = {'mode': 'acting', 'batch': batch, 'rnd_n_sample': k, 'calls': calls, 'rounds': ROUNDS}
     for fused, agent in agents.items():
@@ -150,16 +167,18 @@ def main():
     ap.add_argument('--steps', type=int, default=600)
     ap.add_argument('--calls', type=int, default=300)
     ap.add_argument('--fill', type=int, default=16384, help='rows put into the replay before the first step')
+    ap.add_argument('--discrete', default='', help='branch sizes, e.g. 3 or 3,2: the pure-discrete learner (csrc/drnd.hip)')
     args = ap.parse_args()
+    mode = mode_of([int(v) for v in args.discrete.split(',')] if args.discrete else [])
     assert torch.cuda.is_available(), 'needs the GPU: nothing is measured without one'
     import asac_amd  # noqa: F401
     import bench
     from tests import parity_utils as pu
     cfg = bench.CONFIGS['cfg2']
-    plugin = plugin_with_rnd(pu.plugin(cfg['plugin']))
-    print(json.dumps(step_row(cfg, plugin, args.steps, args.fill)), flush=True)
-    for batch, k in ACTING:
-        print(json.dumps(acting_row(cfg, plugin, batch, k, args.calls)), flush=True)
+    plugin = plugin_with_rnd(pu.plugin('nn_vec_full' if mode.sizes else cfg['plugin']))
+    print(json.dumps(step_row(cfg, plugin, mode, args.steps, args.fill)), flush=True)
+    for batch, k in ([(10, 10), (100, 50)] if mode.sizes else ACTING):
+        print(json.dumps(acting_row(cfg, plugin, mode, batch, k, args.calls)), flush=True)
 
 
 if __name__ == '__main__':

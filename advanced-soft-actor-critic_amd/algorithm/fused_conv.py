@@ -16,7 +16,7 @@ from asac_amd import native
 
 from .fused_mlp import _flat_alias, direct_enabled
 
-__all__ = ['fused_conv_stack', 'conv_stack_desc', 'DeferredConvBackward']
+__all__ = ['fused_conv_stack', 'conv_stack_desc', 'DeferredConvBackward', 'fused_conv1d_stack', 'conv1d_stack_desc']
 
 # add the parameter gradients into existing consecutive `.grad` views from the reduction kernel itself
 DIRECT_PARAM_GRADS = True
@@ -158,34 +158,42 @@ class _ConvStackFn(torch.autograd.Function):
         n_frames = x.shape[0] * x.shape[1] if ctx.windows else x.shape[0]
         run = native.conv2_backward_windows if ctx.windows else native.conv2_backward
         ws = torch.empty(native.conv2_backward_workspace(desc, n_frames), dtype=x.dtype, device=x.device)
-        params = ctx.params
-        # the four gradients as one packed block: inside the learner they are consecutive views of the flat
-        # gradient buffer, and the reduction kernel adds into them directly (no AccumulateGrad launches)
-        flat = None
-        if DIRECT_PARAM_GRADS and direct_enabled() and all(p.requires_grad and p.grad is not None for p in params):
-            flat = _flat_alias([p.grad for p in params])
-        from .fused_mlp import DeferredPartialSums
-        later = DeferredPartialSums.active()          # (the slab sums as one launch with the walk's other second launches)
-        n = native.conv2_param_count(desc)
-        if flat is not None:
-            run(desc, x, w2.detach().contiguous(), z1, z2, grad_y.contiguous(), flat, ws,
-                native.SUM_DEFER if later is not None else True)
-            if later is not None:
-                later.add(ws, native.conv2_backward_slabs(desc, n_frames), 16, n, n, flat, accumulate=True)
-            return (None, None, None, None, None, None, None, None)
-        g = torch.empty(n, dtype=x.dtype, device=x.device)
-        run(desc, x, w2.detach().contiguous(), z1, z2, grad_y.contiguous(), g, ws,
-            native.SUM_DEFER if later is not None else False)
-        grads, off = [], 0
-        for p in params:
-            k = p.numel()
-            grads.append(g[off:off + k].view(p.shape) if p.requires_grad else None)
-            off += k
-        if later is not None:           # (the gradients reach the caller through `later.flush()`)
-            later.add(ws, native.conv2_backward_slabs(desc, n_frames), 16, n, n, g)
-            later.record(params, grads)
-            grads = [None] * 4
+        w2d, gy = w2.detach().contiguous(), grad_y.contiguous()
+        grads = _packed_param_grads(ctx.params, native.conv2_param_count(desc), ws,
+                                    lambda: native.conv2_backward_slabs(desc, n_frames),
+                                    lambda out, mode: run(desc, x, w2d, z1, z2, gy, out, ws, mode))
         return (None, None, *grads, None, None)
+
+
+def _packed_param_grads(params, n, ws, slabs, launch):
+    """The tail both stacks' backward share.  `launch(out, mode)` runs the backward kernel whose slabs of `n` packed floats
+    land in `ws` and whose slab sum goes to `out` (mode False: written, True: added, `native.SUM_DEFER`: left to the walk's
+    `DeferredPartialSums`, `slabs()` slabs).  -> the gradients autograd receives, one per parameter (None where the kernel
+    already added them, or where `DeferredPartialSums.flush()` delivers them)"""
+    # the gradients as one packed block: inside the learner they are consecutive views of the flat
+    # gradient buffer, and the reduction kernel adds into them directly (no AccumulateGrad launches)
+    flat = None
+    if DIRECT_PARAM_GRADS and direct_enabled() and all(p.requires_grad and p.grad is not None for p in params):
+        flat = _flat_alias([p.grad for p in params])
+    from .fused_mlp import DeferredPartialSums
+    later = DeferredPartialSums.active()          # (the slab sums as one launch with the walk's other second launches)
+    if flat is not None:
+        launch(flat, native.SUM_DEFER if later is not None else True)
+        if later is not None:
+            later.add(ws, slabs(), 16, n, n, flat, accumulate=True)
+        return [None] * len(params)
+    g = torch.empty(n, dtype=ws.dtype, device=ws.device)
+    launch(g, native.SUM_DEFER if later is not None else False)
+    grads, off = [], 0
+    for p in params:
+        k = p.numel()
+        grads.append(g[off:off + k].view(p.shape) if p.requires_grad else None)
+        off += k
+    if later is not None:           # (the gradients reach the caller through `later.flush()`)
+        later.add(ws, slabs(), 16, n, n, g)
+        later.record(params, grads)
+        grads = [None] * len(params)
+    return grads
 
 
 def _out_width(desc):
@@ -208,3 +216,68 @@ def fused_conv_stack(x, desc, conv_layers, windows=None):
     (then x may be a non-materialised stand-in of the right shape)"""
     c1, _, c2, _ = list(conv_layers)
     return _ConvStackFn.apply(x, desc, c1.weight, c1.bias, c2.weight, c2.bias, windows, torch.is_grad_enabled())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The ray-sensor encoder: `Conv1dLayers`' Conv1d LeakyReLU Conv1d LeakyReLU stack (`asac_conv1_forward` / `_backward`,
+# csrc/conv1d.hip).  Rays are data: parameter gradients only.  The backward recomputes the first layer from the rays, so the
+# forward saves nothing but its own output.
+# ---------------------------------------------------------------------------------------------------------------------
+def conv1d_stack_desc(conv_layers, x):
+    """-> the kernel descriptor if `conv_layers` applied to `x.permute(0, 2, 1)`, x [N, L, C] as stored, fits
+    `csrc/conv1d.hip`, else None"""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and not x.requires_grad):
+        return None
+    mods = list(conv_layers) if isinstance(conv_layers, nn.Sequential) else None
+    if mods is None or len(mods) != 4:
+        return None
+    c1, g1, c2, g2 = mods
+    if not (type(c1) is nn.Conv1d and type(c2) is nn.Conv1d and type(g1) is nn.LeakyReLU and type(g2) is nn.LeakyReLU):
+        return None
+    if g1.negative_slope != g2.negative_slope:
+        return None
+    for c in (c1, c2):
+        if (c.padding not in ((0,), 0) or c.dilation != (1,) or c.groups != 1 or c.bias is None
+                or c.padding_mode != 'zeros'):
+            return None
+    if x.shape[0] < 1 or c1.in_channels != x.shape[2] or c2.in_channels != c1.out_channels:
+        return None
+    desc = native.conv1_desc(x.shape[1], x.shape[2], c1.out_channels, c1.kernel_size[0], c1.stride[0],
+                             c2.out_channels, c2.kernel_size[0], c2.stride[0], g1.negative_slope)
+    return desc if native.conv1_supported(desc) else None
+
+
+class _Conv1dStackFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, desc, w1, b1, w2, b2, grad_mode=True):
+        N = x.shape[0]
+        # (the caller's grad mode is handed in: see `_ConvStackFn.forward`)
+        train = grad_mode and any(ctx.needs_input_grad[2:6])
+        x = x.contiguous()
+        y = torch.empty(N, desc.out2 * native.conv1_out_shape(desc)[1], dtype=x.dtype, device=x.device)
+        wd = [t.detach().contiguous() for t in (w1, b1, w2, b2)]
+        native.conv1_forward(desc, x, *wd, y)
+        if train:
+            ctx.desc = desc
+            ctx.save_for_backward(x, w1, b1, w2, y)      # (y itself: its sign is the second pre-activation's)
+            ctx.params = (w1, b1, w2, b2)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        desc = ctx.desc
+        x, w1, b1, w2, y = ctx.saved_tensors
+        N = x.shape[0]
+        ws = torch.empty(native.conv1_backward_workspace(desc, N), dtype=x.dtype, device=x.device)
+        wd = [t.detach().contiguous() for t in (w1, b1, w2)]
+        gy = grad_y.contiguous()
+        grads = _packed_param_grads(ctx.params, native.conv1_param_count(desc), ws,
+                                    lambda: native.conv1_backward_slabs(desc, N),
+                                    lambda out, mode: native.conv1_backward(desc, x, *wd, y, gy, out, ws, mode))
+        return (None, None, *grads, None)
+
+
+def fused_conv1d_stack(x, desc, conv_layers):
+    """x [N, L, C] -> [N, out2*L2]: what `conv_layers(x.permute(0, 2, 1)).reshape(N, -1)` returns"""
+    c1, _, c2, _ = list(conv_layers)
+    return _Conv1dStackFn.apply(x, desc, c1.weight, c1.bias, c2.weight, c2.bias, torch.is_grad_enabled())

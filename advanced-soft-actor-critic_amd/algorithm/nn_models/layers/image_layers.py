@@ -2,7 +2,8 @@
 `algorithm/nn_models/layers/image_layers.py:12-256,360-377`: same constructor arguments, attribute
 names (`conv_layers`, `dense`, `conv_transpose`) and pre-defined stacks `small` / `simple` / `nature`,
 so `state_dict`s interchange).  Two-layer Conv2d-GELU stacks on small frames (the `simple` preset) run as
-one fused launch per pass (`algorithm/fused_conv.py`, `csrc/conv.hip`); other stacks run on MIOpen.  The replay
+one fused launch per pass (`algorithm/fused_conv.py`, `csrc/conv.hip`), and so do Conv1d-LeakyReLU stacks over rays
+(`Conv1dLayers`' `default`, `csrc/conv1d.hip`, switch `FUSED_CONV1D`); other stacks run on MIOpen.  The replay
 side feeds them straight from HBM (uint8 frames are widened to float32 / 255 inside the gather kernel).
 `VisionTransformer` needs torchvision's encoder, which this image does not ship: importing the name
 works, constructing it raises with that explanation.
@@ -18,6 +19,11 @@ from .linear_layers import LinearLayers
 __all__ = ['conv1d_output_size', 'conv2d_output_shape', 'pool_out_shape', 'convtranspose_output_shape',
            'default_conv1d', 'small_visual', 'simple_visual', 'nature_visual',
            'Conv1dLayers', 'ConvLayers', 'ConvTransposeLayers', 'VisionTransformer', 'Transform']
+
+
+# route `Conv1dLayers`' convolution stack through the one-launch kernels where they take it (algorithm/fused_conv.py,
+# csrc/conv1d.hip); False: always the module path
+FUSED_CONV1D = True
 
 
 def conv1d_output_size(l, kernel_size=1, stride=1, padding=0, dilation=1) -> int:
@@ -102,6 +108,12 @@ class Conv1dLayers(nn.Module):
     def forward(self, x):
         assert x.dim() >= 3, 'The dimension of input should be greater than or equal to 3'
         lead, x = _flatten_lead(x, 2)
+        if FUSED_CONV1D and x.is_cuda:
+            from algorithm import fused_conv      # lazy: avoids an import cycle
+            desc = fused_conv.conv1d_stack_desc(self.conv_layers, x)
+            if desc is not None:      # Conv1d LeakyReLU Conv1d LeakyReLU over rays as stored: one launch (csrc/conv1d.hip)
+                h = fused_conv.fused_conv1d_stack(x, desc, self.conv_layers)
+                return self.dense(h.reshape(*lead, self.conv_output_size))
         h = self.conv_layers(x.permute(0, 2, 1))
         return self.dense(h.reshape(*lead, self.conv_output_size))
 

@@ -1588,7 +1588,8 @@ class SAC_Base(AuxHeadsMixin):
             state = state_base[0][:, state_base[1]]     # (`_step_rep_and_q`: the differentiable pass covered this position only)
         d_action, c_action = action[..., :dsum], action[..., dsum:]
 
-        if (self._fused_q_state_grads and self._fq is not None and self._ftq is not None and not self.d_action_sizes
+        if (self._fused_q_state_grads and self._fq is not None and self._ftq is not None and self._fpi is not None
+                and not self.d_action_sizes
                 and self.c_action_size and self.clip_epsilon > 0 and aux is None and state_base is not None
                 and state_base[0].dim() == 3 and state.requires_grad):
             # stock critics behind a trainable representation: target Q of the stored pair -> return target -> ONE

@@ -606,6 +606,7 @@ int64_t asac_struct_size(const char* name) {
     ASAC_SZ(asac_mlp_sample_epilogue_t);
     ASAC_SZ(asac_gru_desc_t);
     ASAC_SZ(asac_conv2_desc_t);
+    ASAC_SZ(asac_conv1_desc_t);
     ASAC_SZ(asac_obs_decoder_params_t);
     ASAC_SZ(asac_branches_t);
     ASAC_SZ(asac_members_t);

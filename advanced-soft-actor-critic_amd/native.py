@@ -216,6 +216,12 @@ class Conv2Desc(C.Structure):
                                          'out2', 'kernel2', 'stride2')]
 
 
+class Conv1Desc(C.Structure):
+    """`asac_conv1_desc_t`: the ray encoder's Conv1d LeakyReLU Conv1d LeakyReLU stack (csrc/conv1d.hip)"""
+    _fields_ = [(n, C.c_int32) for n in ('length', 'channels', 'out1', 'kernel1', 'stride1',
+                                         'out2', 'kernel2', 'stride2')] + [('negative_slope', C.c_float)]
+
+
 GRU_MAX_LAYERS, GRU_MAX_DIM = 2, 16
 _PtrArray = C.c_void_p * GRU_MAX_LAYERS
 
@@ -413,6 +419,14 @@ _SIGNATURES = {
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'asac_conv2_backward': (C.c_int, [C.POINTER(Conv2Desc), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'asac_conv1_supported': (C.c_int, [C.POINTER(Conv1Desc)]),
+    'asac_conv1_param_count': (C.c_int64, [C.POINTER(Conv1Desc)]),
+    'asac_conv1_backward_workspace': (C.c_int64, [C.POINTER(Conv1Desc), C.c_int64]),
+    'asac_conv1_backward_slabs': (C.c_int, [C.POINTER(Conv1Desc), C.c_int64]),
+    'asac_conv1_forward': (C.c_int, [C.POINTER(Conv1Desc), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_conv1_backward': (C.c_int, [C.POINTER(Conv1Desc), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     'asac_gru_param_count': (C.c_int64, [C.POINTER(GruDesc)]),
     'asac_gru_backward_workspace': (C.c_int64, [C.POINTER(GruDesc), C.c_int]),
     'asac_gru_forward': (C.c_int, [C.POINTER(GruDesc), _PtrArray, _PtrArray, _PtrArray, _PtrArray, C.c_void_p,
@@ -1822,6 +1836,63 @@ def conv2_backward(desc, x, w2, z1, z2, grad_y, grad_params, workspace, accumula
     _check(load().asac_conv2_backward(C.byref(desc), _p(x), x.shape[0], _p(w2), _p(z1), _p(z2), _p(grad_y),
                                       _p(grad_params), _sum_mode(accumulate), _p(workspace), _stream()),
            'asac_conv2_backward')
+
+
+def conv1_desc(length, channels, out1, kernel1, stride1, out2, kernel2, stride2, negative_slope=0.01) -> Conv1Desc:
+    return Conv1Desc(length, channels, out1, kernel1, stride1, out2, kernel2, stride2, negative_slope)
+
+
+def conv1_supported(desc) -> bool:
+    return bool(load().asac_conv1_supported(C.byref(desc)))
+
+
+def conv1_param_count(desc) -> int:
+    return int(load().asac_conv1_param_count(C.byref(desc)))
+
+
+def conv1_backward_workspace(desc, N) -> int:
+    return int(load().asac_conv1_backward_workspace(C.byref(desc), N))
+
+
+def conv1_backward_slabs(desc, N) -> int:
+    """partial slabs a backward launch over N rays leaves in its workspace (`SUM_DEFER`)"""
+    return int(load().asac_conv1_backward_slabs(C.byref(desc), N))
+
+
+def conv1_out_shape(desc):
+    """-> (L1, L2): positions of the two maps"""
+    l1 = (desc.length - desc.kernel1) // desc.stride1 + 1
+    return l1, (l1 - desc.kernel2) // desc.stride2 + 1
+
+
+def conv1_flops(desc, N, backward=False) -> float:
+    """multiply-adds x 2 of the two products (backward: layer 1 again, both weight-gradient products and W2^T dz2)"""
+    l1, l2 = conv1_out_shape(desc)
+    g1 = l1 * desc.channels * desc.kernel1 * desc.out1
+    g2 = l2 * desc.out1 * desc.kernel2 * desc.out2
+    return 2.0 * N * ((2 * g1 + 2 * g2) if backward else (g1 + g2))
+
+
+@_profiled
+def conv1_forward(desc, x, w1, b1, w2, b2, y, a1_out=None):
+    """x [N, L, C] (channels last, as stored) -> y [N, out2*L2] (Conv1d LeakyReLU Conv1d LeakyReLU, flattened
+    channel-major).  `a1_out`: reserved (a form that saves the layer-1 activations); None."""
+    global _last_work
+    _last_work = conv1_flops(desc, x.shape[0])
+    _dense_f32(x, w1, b1, w2, b2, y, a1_out)
+    _check(load().asac_conv1_forward(C.byref(desc), _p(x), x.shape[0], _p(w1), _p(b1), _p(w2), _p(b2), _p(y), _p(a1_out),
+                                     _stream()), 'asac_conv1_forward')
+
+
+@_profiled
+def conv1_backward(desc, x, w1, b1, w2, y, grad_y, grad_params, workspace, accumulate=False, a1=None):
+    """-> grad_params (packed w1 | b1 | w2 | b2: written, added with `accumulate`, or left as slabs with `SUM_DEFER`)."""
+    global _last_work
+    _last_work = conv1_flops(desc, x.shape[0], backward=True)
+    _dense_f32(x, w1, b1, w2, y, a1, grad_y, grad_params, workspace)
+    _check(load().asac_conv1_backward(C.byref(desc), _p(x), x.shape[0], _p(w1), _p(b1), _p(w2), _p(y), _p(a1), _p(grad_y),
+                                      _p(grad_params), _sum_mode(accumulate), _p(workspace), _stream()),
+           'asac_conv1_backward')
 
 
 def gru_desc(input_size: int, hidden: int, layers: int) -> GruDesc:

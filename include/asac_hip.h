@@ -905,6 +905,40 @@ int asac_conv2_backward(const asac_conv2_desc_t* desc_host, const float* x, int6
                         const float* z1, const float* z2, const float* grad_y, float* grad_params, int accumulate,
                         float* workspace, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * One-launch 1-D convolution stack over rays: Conv1d(C -> out1, k1, s1) LeakyReLU Conv1d(out1 -> out2, k2, s2) LeakyReLU,
+ * no padding, dilation 1, groups 1 — the `default` stack of `Conv1dLayers` (nn_models/layers/image_layers.py; the
+ * reference's ray-sensor encoders with 400 and 61 rays of 2 channels).  csrc/conv1d.hip, f32 MFMA 16x16x4.
+ *   x  [N][L][C]              rays as stored, channels LAST (the module's permute(0, 2, 1) is folded in)
+ *   w1 [out1][C][k1], b1 [out1], w2 [out2][out1][k2], b2 [out2]     nn.Conv1d layouts
+ *   y  [N][out2 * L2]         channel-major: `.reshape(N, -1)` of the [N, out2, L2] map
+ * A workgroup stages a group of rays once; the layer-1 activations stay in LDS; position tiles span the rays of the group.
+ * a1_out / a1: reserved for a form that saves the layer-1 activations; this library recomputes them and takes NULL only.
+ * Backward: gradients of the four parameter tensors only (rays are data), packed w1 | b1 | w2 | b2 into grad_params
+ * (asac_conv1_param_count floats), from x, w1, b1, w2, y (the sign of y is the sign of the second pre-activation) and grad_y.
+ * One slab of partial sums per workgroup in `workspace` (asac_conv1_backward_workspace floats), asac_conv1_backward_slabs(desc, N)
+ * of them, summed in a fixed order by a second launch: accumulate == 0 writes grad_params, 1 adds to it, ASAC_CONV_SUM_DEFER
+ * leaves the slabs to asac_sum_partials_multi (16 slices).  Equal inputs give equal bits.
+ * Limits (asac_conv1_supported): out1 <= 16, out2 <= 32, C*k1 and out1*k2 multiples of 4, C*k1 <= 64, out1*k2 <= 256,
+ * L2 >= 1, negative_slope > 0 and finite, one ray within the LDS budget (L = 802, C = 2 is); anything else returns
+ * ASAC_ERR_BAD_ARG before any launch and callers keep the module path.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t length, channels;
+    int32_t out1, kernel1, stride1;
+    int32_t out2, kernel2, stride2;
+    float negative_slope;
+} asac_conv1_desc_t;
+int asac_conv1_supported(const asac_conv1_desc_t* desc_host);
+int64_t asac_conv1_param_count(const asac_conv1_desc_t* desc_host);
+int64_t asac_conv1_backward_workspace(const asac_conv1_desc_t* desc_host, int64_t N);
+int asac_conv1_backward_slabs(const asac_conv1_desc_t* desc_host, int64_t N);
+int asac_conv1_forward(const asac_conv1_desc_t* desc_host, const float* x, int64_t N, const float* w1, const float* b1,
+                       const float* w2, const float* b2, float* y, float* a1_out, void* stream);
+int asac_conv1_backward(const asac_conv1_desc_t* desc_host, const float* x, int64_t N, const float* w1, const float* b1,
+                        const float* w2, const float* y, const float* a1, const float* grad_y, float* grad_params,
+                        int accumulate, float* workspace, void* stream);
+
 /* Cosine-sign gating of auxiliary gradients: `calculate_adaptive_weights` (sac_base.py:1607-1631) after its autograd
  * calls.  main / aux_k / grad: flat f32[n] (the representation's gradient segment and K <= 4 auxiliary gradients of the
  * same layout; aux_host = host array of K device pointers):  gate_k = clamp(sign(cos(main, aux_k)), min = 0)  — the sign

@@ -41,10 +41,36 @@ inline int ilog2(int v) {
     return l;
 }
 
-// ring slot of a (possibly negative) id, NumPy `%` semantics
+// ring slot of a (possibly negative) id, NumPy `%` semantics.  A power-of-two capacity (every ring behind a sum tree:
+// PrioritizedReplayBuffer rounds it down, the tree's entry points refuse anything else) makes the slot the id's low bits —
+// two's complement: also for negative ids and ids >= 2^32 — instead of an expanded signed 64-bit division (both its
+// slow path and its 32-bit bypass, a divergent branch around them) on the address chain id -> slot -> row.
+//   kSlotMask  the capacity IS a power of two (the host has checked): kernels on the step's critical path
+//   kSlotDiv   any positive capacity: the stand-alone gather / scatter launches the host found no power of two for
+//   kSlotAuto  decided per call from the capacity (a scalar: wave-uniform) — sidecar jobs, off the critical path
+enum : int { kSlotDiv = 0, kSlotMask = 1, kSlotAuto = 2 };
+
+inline bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+
+template <int SLOT>
 __device__ __forceinline__ int ring_slot(int64_t id, int capacity) {
+    if (SLOT == kSlotMask || (SLOT == kSlotAuto && (capacity & (capacity - 1)) == 0))
+        return (int)((uint32_t)id & (uint32_t)(capacity - 1));
     int64_t m = id % capacity;
     return (int)(m < 0 ? m + capacity : m);
+}
+
+// Division by a divisor the host knows when it builds a launch's arguments (k_td_update: the n-step count) and the
+// address chains wait for: q = mulhi(x, M) with M = floor(2^32 / d) + 1 instead of an expanded 32-bit division.
+// M d = 2^32 + e with 0 < e <= d, so x M / 2^32 = x / d + x e / (d 2^32): the floor is floor(x / d) as long as the second
+// term stays below 1 / d, i.e. x e < 2^32 — guaranteed for every x <= x_max when x_max d < 2^32.  Outside that range,
+// and for d = 1 (no 32-bit M), the magic is 0 and the kernel keeps its division.
+inline uint32_t fastdiv_magic(uint32_t d, uint64_t x_max) {
+    if (d < 2 || (uint64_t)d * x_max >= (1ull << 32)) return 0;
+    return (uint32_t)((1ull << 32) / d) + 1u;
+}
+__device__ __forceinline__ uint32_t fastdiv(uint32_t x, uint32_t d, uint32_t magic) {
+    return magic ? __umulhi(x, magic) : x / d;
 }
 
 // K5 Polyak, reference algorithm/sac_base.py:761-764:  t.copy_(t * (1 - tau) + p * tau)

@@ -56,10 +56,12 @@ __device__ __forceinline__ bool index_run(int idx_j, int idx_c, int j, int prev_
     return j == prev_n || (idx_j - idx_c) == (j - prev_n);
 }
 
+// (SLOT: how a ring slot is formed from an id — asac_common.h `ring_slot`)
+template <int SLOT>
 __device__ __forceinline__ bool row_valid(const GatherArgs& a, int64_t id, int j) {
     if (j == a.prev_n) return true;
-    const int idx_j = a.index_ring[ring_slot(id + (j - a.prev_n), a.capacity)];
-    const int idx_c = a.index_ring[ring_slot(id, a.capacity)];
+    const int idx_j = a.index_ring[ring_slot<SLOT>(id + (j - a.prev_n), a.capacity)];
+    const int idx_c = a.index_ring[ring_slot<SLOT>(id, a.capacity)];
     return index_run(idx_j, idx_c, j, a.prev_n);
 }
 
@@ -90,11 +92,12 @@ __device__ __forceinline__ uint8_t pad_value<uint8_t>(const GatherKeyDev& k, int
 // One 4-byte word of window row j of a sample, as copy_units delivers it: word `w` of key `k`'s padded row.  Every load is
 // issued whatever the validity test says (slot and pad addresses are always valid) and the result is SELECTED: a reader
 // that takes its rows straight from the ring (mlp.hip, RING instantiations) pays one round trip behind the id.
+template <int SLOT>
 __device__ __forceinline__ uint32_t ring_word(const GatherArgs& a, const GatherKeyDev& k, int64_t id, int j, int w) {
-    const int slot = ring_slot(id + (j - a.prev_n), a.capacity);
+    const int slot = ring_slot<SLOT>(id + (j - a.prev_n), a.capacity);
     const uint32_t data = reinterpret_cast<const uint32_t*>(k.src + (int64_t)slot * k.row_bytes)[w];
     const int idx_j = a.index_ring[slot];
-    const int idx_c = a.index_ring[ring_slot(id, a.capacity)];
+    const int idx_c = a.index_ring[ring_slot<SLOT>(id, a.capacity)];
     const uint32_t pad = pad_value<uint32_t>(k, w);
     return (k.pad_mode == ASAC_PAD_KEEP || index_run(idx_j, idx_c, j, a.prev_n)) ? data : pad;
 }
@@ -112,7 +115,7 @@ template <> __device__ __forceinline__ uint4 zero_unit<uint4>() { return make_ui
 template <typename Unit> __device__ __forceinline__ Unit next_index(Unit v) { return v; }
 template <> __device__ __forceinline__ uint32_t next_index<uint32_t>(uint32_t v) { return v + (v != 0xffffffffu ? 1u : 0u); }
 
-template <typename Unit, int kUnroll>
+template <typename Unit, int kUnroll, int SLOT>
 __device__ __forceinline__ void copy_units(const GatherArgs& a, const GatherKeyDev& k, int64_t g0,
                                            int64_t total_units) {
     // g indexes units of the dense destination [B, L, units_per_row]
@@ -134,9 +137,9 @@ __device__ __forceinline__ void copy_units(const GatherArgs& a, const GatherKeyD
         // valid address): the validity test's own loads — random reads of the index ring — travel WITH the data
         // instead of in front of it
         const int js = derived_row(k.derive, j, a.L);
-        const int slot = ring_slot(id + (js - a.prev_n), a.capacity);
+        const int slot = ring_slot<SLOT>(id + (js - a.prev_n), a.capacity);
         const Unit data = reinterpret_cast<const Unit*>(k.src + (int64_t)slot * k.row_bytes)[w];
-        const bool valid = (k.pad_mode == ASAC_PAD_KEEP) || row_valid(a, id, js);
+        const bool valid = (k.pad_mode == ASAC_PAD_KEEP) || row_valid<SLOT>(a, id, js);
         val[r] = valid ? data : pad_value<Unit>(k, w);
         if (k.derive == ASAC_DERIVE_PREVIOUS && j == 0) val[r] = zero_unit<Unit>();
         if (k.derive == ASAC_DERIVE_HOLD_LAST_NEXT && j == a.L - 1) val[r] = next_index<Unit>(val[r]);
@@ -147,7 +150,7 @@ __device__ __forceinline__ void copy_units(const GatherArgs& a, const GatherKeyD
 }
 
 // conversion path: 4 source bytes -> 4 floats (uint8/255 or bool)
-template <int kUnroll>
+template <int kUnroll, int SLOT>
 __device__ __forceinline__ void convert_units(const GatherArgs& a, const GatherKeyDev& k, int64_t g0,
                                               int64_t total_units) {
 #pragma unroll
@@ -159,7 +162,7 @@ __device__ __forceinline__ void convert_units(const GatherArgs& a, const GatherK
         const int sample = (int)(row / a.L);
         const int j = (int)(row - (int64_t)sample * a.L);
         const int64_t id = load_id(a.ids, sample);
-        const int slot = ring_slot(id + (j - a.prev_n), a.capacity);
+        const int slot = ring_slot<SLOT>(id + (j - a.prev_n), a.capacity);
         const uint8_t* srow = k.src + (int64_t)slot * k.row_bytes;
         float* drow = reinterpret_cast<float*>(k.dst + row * k.dst_pitch);
         if (k.unit_log2 == 2) {
@@ -181,7 +184,7 @@ __device__ __forceinline__ void convert_units(const GatherArgs& a, const GatherK
 }
 
 // workgroup `block` of a gather launch: its key `k` and the shared arguments `a`
-template <int kUnroll>
+template <int kUnroll, int SLOT>
 __device__ __forceinline__ void gather_work(const GatherArgs& a, const GatherKeyDev& k, unsigned block) {
     const int64_t rows = (int64_t)a.batch * a.L;
     const int64_t total_units = rows * k.units_per_row;
@@ -194,28 +197,28 @@ __device__ __forceinline__ void gather_work(const GatherArgs& a, const GatherKey
             if (g >= rows) continue;
             const int sample = (int)(g / a.L);
             const int j = (int)(g - (int64_t)sample * a.L);
-            k.dst[g] = row_valid(a, load_id(a.ids, sample), derived_row(k.derive, j, a.L)) ? 0 : 1;
+            k.dst[g] = row_valid<SLOT>(a, load_id(a.ids, sample), derived_row(k.derive, j, a.L)) ? 0 : 1;
         }
         return;
     }
     if (k.convert != ASAC_CVT_NONE) {
-        convert_units<kUnroll>(a, k, g0, total_units);
+        convert_units<kUnroll, SLOT>(a, k, g0, total_units);
         return;
     }
-    if (k.unit_log2 == 4) copy_units<uint4, kUnroll>(a, k, g0, total_units);
-    else if (k.unit_log2 == 2) copy_units<uint32_t, kUnroll>(a, k, g0, total_units);
-    else copy_units<uint8_t, kUnroll>(a, k, g0, total_units);
+    if (k.unit_log2 == 4) copy_units<uint4, kUnroll, SLOT>(a, k, g0, total_units);
+    else if (k.unit_log2 == 2) copy_units<uint32_t, kUnroll, SLOT>(a, k, g0, total_units);
+    else copy_units<uint8_t, kUnroll, SLOT>(a, k, g0, total_units);
 }
 
 // workgroup `block` of a gather launch described by `m` (read from the kernel arguments or from device memory)
-template <int NK, int kUnroll>
+template <int NK, int kUnroll, int SLOT>
 __device__ __forceinline__ void gather_block(const GatherLaunch<NK>& m, unsigned block) {
     // which key does this block belong to?  (<= 16 entries, wave-uniform scan)
     int ki = 0;
 #pragma unroll 1
     for (int q = 1; q < m.c.n_keys; ++q)
         if (block >= m.key[q].first_block) ki = q;
-    gather_work<kUnroll>(m.c, m.key[ki], block);
+    gather_work<kUnroll, SLOT>(m.c, m.key[ki], block);
 }
 
 // host: the launch description of a window gather (key table, shared arguments, workgroups per key); force_unroll 0:

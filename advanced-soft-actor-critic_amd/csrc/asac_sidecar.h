@@ -175,6 +175,8 @@ struct ScatterArgs {
     int32_t* winner;
 };
 
+// (SLOT: asac_common.h `ring_slot` — the stand-alone launches know their capacity's kind, a sidecar job looks)
+template <int SLOT>
 __device__ __forceinline__ bool scatter_target(const ScatterArgs& a, int flat, int* slot_out) {
     const int s = flat / a.count;
     const int j = flat - s * a.count;
@@ -183,22 +185,24 @@ __device__ __forceinline__ bool scatter_target(const ScatterArgs& a, int flat, i
     // none of its window rows is this shard's to write, whatever id + offset comes to
     if (a.ids[s] < 0) return false;
     const int64_t tid = a.ids[s] + a.first_off + j;
-    const int slot = ring_slot(tid, a.capacity);
+    const int slot = ring_slot<SLOT>(tid, a.capacity);
     *slot_out = slot;
     return a.slot_ids[slot] == tid;
 }
 
+template <int SLOT>
 __device__ __forceinline__ void scatter_elect_row(const ScatterArgs& a, int flat) {
     if (flat >= a.batch * a.count) return;
     int slot;
-    if (scatter_target(a, flat, &slot)) atomicMax(&a.winner[slot], flat);
+    if (scatter_target<SLOT>(a, flat, &slot)) atomicMax(&a.winner[slot], flat);
 }
 
 // the elected row `flat` copies its payload with `lanes` lanes (lane index `lane`), then hands the slot back
+template <int SLOT>
 __device__ __forceinline__ void scatter_write_row(const ScatterArgs& a, int flat, int lane, int lanes) {
     if (flat >= a.batch * a.count) return;
     int slot;
-    if (!scatter_target(a, flat, &slot)) return;
+    if (!scatter_target<SLOT>(a, flat, &slot)) return;
     if (__hip_atomic_load(&a.winner[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != flat) return;
     const int s = flat / a.count;
     const int j = flat - s * a.count;
@@ -330,21 +334,21 @@ __device__ __forceinline__ void sidecar_run(const SidecarsT<NSC>& sc, int block,
         alpha_adam_block(job.alpha, lds256);
     } else if (GATHER && job.kind == ASAC_SIDECAR_WINDOW_GATHER) {
         if (threadIdx.x < kGatherBlock)
-            gather_block<ASAC_MAX_GATHER_KEYS, 1>(*static_cast<const GatherLaunch<ASAC_MAX_GATHER_KEYS>*>(job.gather),
+            gather_block<ASAC_MAX_GATHER_KEYS, 1, kSlotAuto>(*static_cast<const GatherLaunch<ASAC_MAX_GATHER_KEYS>*>(job.gather),
                                                   (unsigned)local);
     } else if (WEIGHTS && job.kind == ASAC_SIDECAR_WINDOW_GATHER_W) {
         if (threadIdx.x < kGatherBlock) {       // (only the first 256 threads of a host workgroup get here: their barrier)
             const GatherPlanDev* plan = static_cast<const GatherPlanDev*>(job.gather);
             if (local == 0) weights_job(plan->w);
-            else gather_block<ASAC_MAX_GATHER_KEYS, 1>(plan->g, (unsigned)(local - 1));
+            else gather_block<ASAC_MAX_GATHER_KEYS, 1, kSlotAuto>(plan->g, (unsigned)(local - 1));
         }
     } else if (threadIdx.x < 256) {
         if (job.kind == ASAC_SIDECAR_SCATTER_ELECT) {
-            scatter_elect_row(job.scatter, local * kSidecarRowsPerWg + (int)threadIdx.x);
+            scatter_elect_row<kSlotAuto>(job.scatter, local * kSidecarRowsPerWg + (int)threadIdx.x);
         } else if (job.scatter.row_bytes <= 32) {
-            scatter_write_row(job.scatter, local * kSidecarRowsPerWg + (int)threadIdx.x, 0, 1);
+            scatter_write_row<kSlotAuto>(job.scatter, local * kSidecarRowsPerWg + (int)threadIdx.x, 0, 1);
         } else {
-            scatter_write_row(job.scatter, local * 4 + (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63), kWave);
+            scatter_write_row<kSlotAuto>(job.scatter, local * 4 + (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63), kWave);
         }
     }
 }

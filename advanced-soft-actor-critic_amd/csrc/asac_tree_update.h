@@ -83,7 +83,7 @@ __device__ __forceinline__ void sumtree_update_wg(
     float own_p = 0.f;
     for (int i = threadIdx.x; i < k; i += blockDim.x) {
         const int64_t id = ids[i];
-        const int slot = ring_slot(id, capacity);
+        const int slot = ring_slot<kSlotMask>(id, capacity);      // (a sum tree: the capacity is a power of two)
         const bool live = (slot_ids == nullptr) || (slot_ids[slot] == id);
         float p = td[i];
         if (mode == 0) {

@@ -14,9 +14,10 @@
 
 namespace asac {
 
-template <int NK, int kUnroll>
+// (SLOT: kSlotMask where the entry point found the capacity a power of two — the replay's rings always — else kSlotDiv)
+template <int NK, int kUnroll, int SLOT>
 __global__ __launch_bounds__(kGatherBlock) void k_window_gather_pad(const GatherLaunch<NK> m) {
-    gather_block<NK, kUnroll>(m, blockIdx.x);
+    gather_block<NK, kUnroll, SLOT>(m, blockIdx.x);
 }
 
 // ... with the batch's IS weights (K2) formed by ONE extra workgroup beside the gather's: the sampler of the launch in
@@ -24,24 +25,26 @@ __global__ __launch_bounds__(kGatherBlock) void k_window_gather_pad(const Gather
 // they are combined, beta advances, and the weights of all <= 1 024 rows are written — under a gather of tens of
 // microseconds instead of behind a cross-workgroup exchange inside the sampler (~1.5 us of the step's first launch).
 // (WeightsJob / weights_job: asac_sidecar.h — the same workgroup also rides in the step's first network launch)
-template <int NK, int kUnroll>
+template <int NK, int kUnroll, int SLOT>
 __global__ __launch_bounds__(kGatherBlock) void k_window_gather_pad_w(const GatherLaunch<NK> m, unsigned gather_blocks,
                                                                       const WeightsJob j) {
     if (blockIdx.x == 0) {         // (first in the grid: dispatched at once — as the LAST workgroup it started when the
         weights_job(j);            //  gather was nearly through and its f64 powers stuck out of the launch by ~1.2 us)
         return;
     }
-    gather_block<NK, kUnroll>(m, blockIdx.x - 1);
+    gather_block<NK, kUnroll, SLOT>(m, blockIdx.x - 1);
 }
 
 // K7 (asac_sidecar.h: ScatterArgs, scatter_elect_row, scatter_write_row)
+template <int SLOT>
 __global__ __launch_bounds__(256) void k_scatter_elect(const ScatterArgs a) {
-    scatter_elect_row(a, blockIdx.x * blockDim.x + threadIdx.x);
+    scatter_elect_row<SLOT>(a, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // one wave per target row; lanes stride over the payload in 4-byte (or 1-byte) units
+template <int SLOT>
 __global__ __launch_bounds__(256) void k_scatter_write(const ScatterArgs a) {
-    scatter_write_row(a, blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave, threadIdx.x & (kWave - 1), kWave);
+    scatter_write_row<SLOT>(a, blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave, threadIdx.x & (kWave - 1), kWave);
 }
 
 // The representation's window inputs that are pure functions of the sampled window (reference
@@ -152,6 +155,54 @@ int gather_fill(const asac_gather_key_t* keys_host, int n_keys, const int64_t* i
     return 0;
 }
 
+// the stand-alone launch of a filled description: sized key table, units per thread
+template <int SLOT>
+static void gather_launch(const GatherLaunch<ASAC_MAX_GATHER_KEYS>& m, int n_keys, int unroll, uint64_t blocks, hipStream_t stream) {
+    if (n_keys <= 8) {
+        GatherLaunch<8> m8{};
+        for (int q = 0; q < n_keys; ++q) m8.key[q] = m.key[q];
+        m8.c = m.c;
+        if (unroll == 1)
+            ASAC_LAUNCH((k_window_gather_pad<8, 1, SLOT>), dim3((unsigned)blocks), dim3(kGatherBlock), 0, stream, m8);
+        else
+            ASAC_LAUNCH((k_window_gather_pad<8, kUnrollLarge, SLOT>), dim3((unsigned)blocks), dim3(kGatherBlock), 0, stream, m8);
+    } else if (unroll == 1) {
+        ASAC_LAUNCH((k_window_gather_pad<ASAC_MAX_GATHER_KEYS, 1, SLOT>), dim3((unsigned)blocks), dim3(kGatherBlock), 0,
+                    stream, m);
+    } else {
+        ASAC_LAUNCH((k_window_gather_pad<ASAC_MAX_GATHER_KEYS, kUnrollLarge, SLOT>), dim3((unsigned)blocks), dim3(kGatherBlock), 0,
+                    stream, m);
+    }
+}
+
+template <int SLOT>
+static void gather_launch_w(const GatherLaunch<ASAC_MAX_GATHER_KEYS>& m, int n_keys, int unroll, uint64_t blocks, const WeightsJob& job,
+                            hipStream_t stream) {
+    const dim3 grid((unsigned)blocks + 1u);
+    // (under the measurement repeat knob beta advances in the first repetition only)
+    for (int rep = 0; rep < g_launch_repeat; ++rep) {
+        WeightsJob j = job;
+        if (rep > 0) j.beta_increment = 0.0;
+        if (n_keys <= 8) {
+            GatherLaunch<8> m8{};
+            for (int q = 0; q < n_keys; ++q) m8.key[q] = m.key[q];
+            m8.c = m.c;
+            if (unroll == 1)
+                hipLaunchKernelGGL((k_window_gather_pad_w<8, 1, SLOT>), grid, dim3(kGatherBlock), 0, stream, m8,
+                                   (unsigned)blocks, j);
+            else
+                hipLaunchKernelGGL((k_window_gather_pad_w<8, kUnrollLarge, SLOT>), grid, dim3(kGatherBlock), 0, stream,
+                                   m8, (unsigned)blocks, j);
+        } else if (unroll == 1) {
+            hipLaunchKernelGGL((k_window_gather_pad_w<ASAC_MAX_GATHER_KEYS, 1, SLOT>), grid, dim3(kGatherBlock), 0,
+                               stream, m, (unsigned)blocks, j);
+        } else {
+            hipLaunchKernelGGL((k_window_gather_pad_w<ASAC_MAX_GATHER_KEYS, kUnrollLarge, SLOT>), grid, dim3(kGatherBlock), 0,
+                               stream, m, (unsigned)blocks, j);
+        }
+    }
+}
+
 }  // namespace asac
 
 using namespace asac;
@@ -180,21 +231,8 @@ int asac_window_gather_pad(const asac_gather_key_t* keys_host, int n_keys, const
     int unroll = 0;
     if (const int rc = gather_fill(keys_host, n_keys, ids, batch, prev_n, post_n, capacity, index_ring, 0, m, &blocks, &unroll))
         return rc;
-    if (n_keys <= 8) {
-        GatherLaunch<8> m8{};
-        for (int q = 0; q < n_keys; ++q) m8.key[q] = m.key[q];
-        m8.c = m.c;
-        if (unroll == 1)
-            ASAC_LAUNCH((k_window_gather_pad<8, 1>), dim3((unsigned)blocks), dim3(kGatherBlock), 0, as_stream(stream), m8);
-        else
-            ASAC_LAUNCH((k_window_gather_pad<8, kUnrollLarge>), dim3((unsigned)blocks), dim3(kGatherBlock), 0, as_stream(stream), m8);
-    } else if (unroll == 1) {
-        ASAC_LAUNCH((k_window_gather_pad<ASAC_MAX_GATHER_KEYS, 1>), dim3((unsigned)blocks), dim3(kGatherBlock), 0,
-                    as_stream(stream), m);
-    } else {
-        ASAC_LAUNCH((k_window_gather_pad<ASAC_MAX_GATHER_KEYS, kUnrollLarge>), dim3((unsigned)blocks), dim3(kGatherBlock), 0,
-                    as_stream(stream), m);
-    }
+    if (is_pow2(capacity)) gather_launch<kSlotMask>(m, n_keys, unroll, blocks, as_stream(stream));
+    else gather_launch<kSlotDiv>(m, n_keys, unroll, blocks, as_stream(stream));
     return finish_launch("asac_window_gather_pad");
 }
 
@@ -209,29 +247,9 @@ int asac_window_gather_pad_w(const asac_gather_key_t* keys_host, int n_keys, con
     int unroll = 0;
     if (const int rc = gather_fill(keys_host, n_keys, ids, batch, prev_n, post_n, capacity, index_ring, 0, m, &blocks, &unroll))
         return rc;
-    const dim3 grid((unsigned)blocks + 1u);
-    // (under the measurement repeat knob beta advances in the first repetition only)
-    for (int rep = 0; rep < g_launch_repeat; ++rep) {
-        const WeightsJob j{p, tree, beta_state, rep == 0 ? beta_increment : 0.0, is_weights_out, min_p_out, batch,
-                           (batch + 255) / 256};
-        if (n_keys <= 8) {
-            GatherLaunch<8> m8{};
-            for (int q = 0; q < n_keys; ++q) m8.key[q] = m.key[q];
-            m8.c = m.c;
-            if (unroll == 1)
-                hipLaunchKernelGGL((k_window_gather_pad_w<8, 1>), grid, dim3(kGatherBlock), 0, as_stream(stream), m8,
-                                   (unsigned)blocks, j);
-            else
-                hipLaunchKernelGGL((k_window_gather_pad_w<8, kUnrollLarge>), grid, dim3(kGatherBlock), 0, as_stream(stream),
-                                   m8, (unsigned)blocks, j);
-        } else if (unroll == 1) {
-            hipLaunchKernelGGL((k_window_gather_pad_w<ASAC_MAX_GATHER_KEYS, 1>), grid, dim3(kGatherBlock), 0,
-                               as_stream(stream), m, (unsigned)blocks, j);
-        } else {
-            hipLaunchKernelGGL((k_window_gather_pad_w<ASAC_MAX_GATHER_KEYS, kUnrollLarge>), grid, dim3(kGatherBlock), 0,
-                               as_stream(stream), m, (unsigned)blocks, j);
-        }
-    }
+    const WeightsJob j{p, tree, beta_state, beta_increment, is_weights_out, min_p_out, batch, (batch + 255) / 256};
+    if (is_pow2(capacity)) gather_launch_w<kSlotMask>(m, n_keys, unroll, blocks, j, as_stream(stream));
+    else gather_launch_w<kSlotDiv>(m, n_keys, unroll, blocks, j, as_stream(stream));
     return finish_launch("asac_window_gather_pad_w");
 }
 
@@ -297,8 +315,13 @@ int asac_scatter_rows_if_id_match(void* ring, int row_bytes, int capacity, const
                   rows_sample_stride_bytes, rows_row_stride_bytes, winner};
     const int total = batch * count;
     hipStream_t s = as_stream(stream);
-    ASAC_LAUNCH(k_scatter_elect, dim3((total + 255) / 256), dim3(256), 0, s, a);
-    ASAC_LAUNCH(k_scatter_write, dim3((total + 3) / 4), dim3(256), 0, s, a);
+    if (is_pow2(capacity)) {
+        ASAC_LAUNCH(k_scatter_elect<kSlotMask>, dim3((total + 255) / 256), dim3(256), 0, s, a);
+        ASAC_LAUNCH(k_scatter_write<kSlotMask>, dim3((total + 3) / 4), dim3(256), 0, s, a);
+    } else {
+        ASAC_LAUNCH(k_scatter_elect<kSlotDiv>, dim3((total + 255) / 256), dim3(256), 0, s, a);
+        ASAC_LAUNCH(k_scatter_write<kSlotDiv>, dim3((total + 3) / 4), dim3(256), 0, s, a);
+    }
     return finish_launch("asac_scatter_rows_if_id_match");
 }
 

@@ -550,11 +550,11 @@ __device__ __forceinline__ void ring_tile_rows(const StageScalars& q, const Ring
         const uint32_t smp = row / (uint32_t)R.T;
         const int j = live ? R.j0 + (int)(row - smp * (uint32_t)R.T) : R.g.prev_n;     // (a dead row: any valid address)
         const bool first = c < in0;
-        uint32_t x = ring_word(R.g, R.k0, id[u], j, first ? c : 0);
+        uint32_t x = ring_word<kSlotMask>(R.g, R.k0, id[u], j, first ? c : 0);
         x = (live && first) ? x : 0u;
         if (X1) {
             const bool second = !first && c < in0 + in1;
-            const uint32_t x1 = ring_word(R.g, R.k1, id[u], j, second ? R.c1 + (c - in0) : R.c1);
+            const uint32_t x1 = ring_word<kSlotMask>(R.g, R.k1, id[u], j, second ? R.c1 + (c - in0) : R.c1);
             x = (live && second) ? x1 : x;
         }
         v[u] = __builtin_bit_cast(float, x);
@@ -1899,7 +1899,7 @@ __device__ __forceinline__ void pi_q_tiles(const ASAC_KARG PiQLaunch& a, PiQLds&
                 const int lrow = it / A, d = it - lrow * A;
                 const int r = min(row0 + lrow, N - 1);
                 const int sb = (int)((unsigned)r / (unsigned)Ra.T), st = r - sb * Ra.T;
-                av_ring[h] = __builtin_bit_cast(float, ring_word(Ra.g, Ra.k1, load_id(Ra.g.ids, sb), Ra.j0 + st,
+                av_ring[h] = __builtin_bit_cast(float, ring_word<kSlotMask>(Ra.g, Ra.k1, load_id(Ra.g.ids, sb), Ra.j0 + st,
                                                                  a.sp.action ? Ra.c1 + d : 0));
             }
         }
@@ -2709,7 +2709,7 @@ static bool ring_key_ok(const asac_ring_key_t& k, int first_col, int cols) {
 static bool ring_rows_ok(const asac_pi_q_job_t& j) {
     const asac_ring_rows_t& r = j.ring;
     const asac_squash_job_t& s = j.sample;
-    if (!r.ids || !r.index_ring || r.capacity <= 0 || r.prev_n < 0 || r.L <= r.prev_n) return false;
+    if (!r.ids || !r.index_ring || !is_pow2(r.capacity) || r.prev_n < 0 || r.L <= r.prev_n) return false;
     if (s.T <= 0 || j.pi.N % s.T != 0 || r.j0 < 0 || r.j0 + s.T > r.L) return false;
     if (j.pi.x0_window_T != 0 && j.pi.x0_window_T != s.T) return false;
     if (!ring_key_ok(r.x0, 0, j.pi.desc->in0)) return false;

@@ -281,6 +281,7 @@ struct TdUpdateArgs {
     int32_t* winner;
     int32_t* nan_flag;
     int32_t capacity, levels, seg, has_alpha;
+    uint32_t n_magic;                // fastdiv_magic(n, B n): the items' f -> (row, step) split
     float alpha_pow, td_min, td_max;
     AlphaAdamArgs alpha;
 };
@@ -307,7 +308,8 @@ __global__ __launch_bounds__(kUpdateBlock) void k_td_update(const TdUpdateArgs u
     const int f0 = threadIdx.x;
     const bool have0 = f0 < B * n;
     VtraceStepRaw raw0{};
-    if (have0) raw0 = vtrace_step_load(a, f0 / n, f0 - (f0 / n) * n);
+    const int r0 = (int)fastdiv((uint32_t)f0, (uint32_t)n, u.n_magic);
+    if (have0) raw0 = vtrace_step_load(a, r0, f0 - r0 * n);
     float q_on[4] = {0.f, 0.f, 0.f, 0.f};
     if (row < B) {
 #pragma unroll
@@ -326,12 +328,12 @@ __global__ __launch_bounds__(kUpdateBlock) void k_td_update(const TdUpdateArgs u
     int slot = 0;
     int64_t resident = 0;
     if (row < B) {
-        slot = ring_slot(id, u.capacity);
+        slot = ring_slot<kSlotMask>(id, u.capacity);          // (asac_td_update refuses any other capacity)
         resident = u.slot_ids ? u.slot_ids[slot] : id;
     }
     const float alpha = expf(log_alpha);
     for (int f = threadIdx.x; f < B * n; f += blockDim.x) {
-        const int r = f / n, t = f - r * n;
+        const int r = (int)fastdiv((uint32_t)f, (uint32_t)n, u.n_magic), t = f - r * n;
         float d, c;
         const float v_t = f == f0 ? vtrace_step_finish(a, raw0, alpha, &d, &c) : vtrace_step_terms(a, r, t, alpha, &d, &c);
         if (t == 0) s_v0[r] = v_t;
@@ -701,6 +703,7 @@ int asac_td_update(const asac_vtrace_args_t* args_host, float* tree, int capacit
     u.tree = tree; u.ids = ids; u.slot_ids = slot_ids; u.winner = winner; u.nan_flag = nan_flag;
     u.capacity = capacity; u.levels = ilog2(capacity); u.seg = vtrace_scan_lanes(h.B, h.n);
     u.alpha_pow = alpha; u.td_min = td_min; u.td_max = td_max;
+    u.n_magic = fastdiv_magic((uint32_t)h.n, (uint64_t)h.B * h.n + kUpdateBlock);      // (B n <= 2^14: the LDS check above)
     u.has_alpha = alpha_step ? 1 : 0;
     if (alpha_step) u.alpha = al.j[0].alpha;
     static bool attr1 = false, attr4 = false;

@@ -61,9 +61,23 @@ __device__ unsigned long long g_mlp_stamps[32];
     do {                                                                                         \
         if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) g_mlp_stamps[i] = wall_clock64(); \
     } while (0)
+#define MLP_STAMP_AT(i, t)                                                                       \
+    do {                                                                                         \
+        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == (t)) g_mlp_stamps[i] = wall_clock64(); \
+    } while (0)
 #else
 #define MLP_STAMP(i)
+#define MLP_STAMP_AT(i, t)
 #endif
+
+// A workgroup barrier that orders LDS traffic only: `s_waitcnt lgkmcnt(0)` + `s_barrier`.  __syncthreads() fences every
+// address space, which on gfx950 drains vmcnt — a wave with a global store or load in flight waits for its round trip
+// at the barrier, and every other wave of the workgroup with it.  For barriers that publish LDS data alone.
+__device__ __forceinline__ void lds_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
 
 __device__ __forceinline__ int round4(int v) { return (v + 3) & ~3; }
 
@@ -1831,11 +1845,17 @@ __device__ __forceinline__ float gauss_head_value(bool location, float raw) {
 }
 
 // RING: the rows and the stored actions come from the replay ring (`ring`), not from a gathered batch
-template <bool WINDOW, bool RING = false>
+// SINGLE: every workgroup of the launch has one tile (n_tiles <= tile_groups: the train step's launches).  The two paths
+// are two instantiations chosen by ONE branch in the kernel, not branches along the way: with the paths interleaved in
+// one body the launches ran 0.3 - 0.5 us LONGER in the step than before the split, while workgroup 0's own stamps in
+// a loop of the same launch had dropped — a step runs eight different kernels, each from a cold instruction cache, and
+// every jump over the other path's code was a miss on the chain (NOTES.md section 2)
+template <bool WINDOW, bool RING = false, bool SINGLE = false>
 __device__ __forceinline__ void pi_q_tiles(const ASAC_KARG PiQLaunch& a, PiQLds& L, const ASAC_KARG RingArg* ring = nullptr) {
     static_assert(!(RING && WINDOW), "ring-addressed rows have their own (sample, row) addressing");
     // eight waves: the staging (loads and LDS writes of two networks and the input tile) is dealt over 512 threads —
     // 1.5 us instead of 2.5; the forward chains have four column tiles: waves 4..7 only keep the barriers company there
+    // (looping workgroups) or form the side outputs beside the critic (SINGLE)
     constexpr int THREADS = kPiQThreads;
     constexpr int SLOTS = 1024 / kPiQThreads;      // of the 16 x 64 input tile per thread
     const bool comp = (threadIdx.x >> 6) < 4;
@@ -1862,21 +1882,48 @@ __device__ __forceinline__ void pi_q_tiles(const ASAC_KARG PiQLaunch& a, PiQLds&
     } else {
         fetch_input_tile_fixed<THREADS, WINDOW, SLOTS>(sp, 0, (int64_t)group * 16, in_lo);
     }
+    // (the main sample's noise for the first tile's items — 16 A <= 128 (row, d) pairs, two per lane, item `it` of the
+    // tile is element row0 A + it of eps — goes out with the input tile: its address is known here, and asked for after
+    // the policy head it was one dependent L2 round trip on the chain.  A clamped index: every load is issued, none
+    // branches)
+    float ev_pre[2];
+    {
+        const float* e1 = a.eps;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) ev_pre[h] = e1[min(group * 16 * A + lane + 64 * h, N * A - 1)];
+    }
     StagedNet<THREADS> rp, rq;
     net_fetch_fixed<THREADS, 3>(sp, rp);
     net_fetch_fixed<THREADS, 3>(sq, rq);
     if constexpr (RING) ring_tile_rows<THREADS, SLOTS, false>(sp, R, (int64_t)group * 16, id_lo, in_lo);
     put_input_tile<THREADS, SLOTS>(in_lo, L.xs[0]);
     net_put_fixed<THREADS, 3>(rp, L);
-    // (critic e's weights stay in registers until the policy has run: its 36 KB are still travelling when the policy's
-    // have landed — memory returns in order — and nothing needs them before the first critic layer)
+    // (looping workgroups: critic e's weights stay in registers until the policy has run and are written beside the
+    // sampling phase; the barrier below waits for them all the same — its fence drains vmcnt)
     PiQCritic C{L.qw, L.qhead, L.qbias, L.qhead_bias};
     __syncthreads();
     MLP_STAMP(1);
 
+    // SINGLE takes everything the critic does not wait for off its chain.  Five places differ from the looping
+    // workgroups' path, which stays what it was:
+    //   (0) above: the main sample's noise is requested with the input tile;
+    //   (1) critic e's weights go to LDS here, at once (the barrier above has drained every wave's loads), and after
+    //       the policy's first layer waves 4..7 — idle under the other two — request what the side outputs read from
+    //       memory: the second sample's noise and the stored actions (ring-addressed rows: requested by every wave at
+    //       the head of the tile, as before);
+    //   (2) under the policy head: the state tile goes back into xs[0], dead since the third layer's barrier;
+    //   (3) after the head's barrier: waves 0..3 form the action only and enter the critic's first layer WITHOUT a
+    //       barrier; waves 4..6 form the side outputs (log-probabilities, stored-action probabilities, second sample)
+    //       beside them;
+    //   (4) every barrier after the staging is LDS-only: no wave waits there for a store to be acknowledged or for a
+    //       side output's operand that is still travelling.
+    constexpr bool single = SINGLE;
+    float av_pre[2] = {0.f, 0.f}, ev2_pre[2] = {0.f, 0.f};
+    if (single) net_put_fixed<THREADS, 3>(rq, C);
+
     for (int tile = group; tile < n_tiles; tile += a.tile_groups) {
         const int row0 = tile * 16;
-        if (tile != group) {       // (later tiles of a looping workgroup: the first one arrived with the weights)
+        if (!single && tile != group) {       // (later tiles of a looping workgroup: the first one arrived with the weights)
             if constexpr (RING) {
                 ring_tile_ids<THREADS, SLOTS>(sp, R, row0, id_lo);
                 ring_tile_rows<THREADS, SLOTS, false>(sp, R, row0, id_lo, in_lo);
@@ -1925,10 +1972,28 @@ __device__ __forceinline__ void pi_q_tiles(const ASAC_KARG PiQLaunch& a, PiQLds&
                     xout[row * kP + col] = y;
                 }
             }
-            __syncthreads();
+            if (single) lds_barrier();
+            else __syncthreads();
+            if (single && l == 0 && !comp) {        // (1): clamped, always valid addresses — an absent job reads eps[0]
+                const float* e2 = a.eps2 ? a.eps2 : a.eps;
+                const float* ap = a.sp.action ? a.sp.action : a.eps;
+                const unsigned sT = (unsigned)a.T, spT = a.sp.action ? (unsigned)a.sp.T : 1u;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int it = min(lane + 64 * h, 16 * A - 1);
+                    const int lrow = it / A, d = it - lrow * A;
+                    const int r = min(row0 + lrow, N - 1);
+                    ev2_pre[h] = e2[a.eps2 ? (int)((unsigned)r / sT) * A + d : 0];
+                    if constexpr (!RING) {
+                        const int sb = (int)((unsigned)r / spT), st = r - sb * (int)spT;
+                        av_pre[h] = ap[a.sp.action ? sb * a.sp.a_sb + st * a.sp.a_st + a.sp.a_off + d : 0];
+                    }
+                }
+            }
             cur ^= 1;
         }
         MLP_STAMP(2);
+        if (single) put_input_tile<THREADS, SLOTS>(in_lo, L.xs[0]);    // (2): the states again (columns >= S are zero)
         if (comp) {
             // the head tile is 16 x 16: every wave forms it (the same MFMA chain: the same values) and finishes ONE of
             // the four rows a lane holds — the head transform (tanh on the location columns, exp on the scale columns,
@@ -1941,14 +2006,120 @@ __device__ __forceinline__ void pi_q_tiles(const ASAC_KARG PiQLaunch& a, PiQLds&
             L.ls[lrow * 2 * kHeadPad + hc] = v;
             if (writer && a.pi.out && row0 + lrow < N && hc < 2 * A) a.pi.out[(row0 + lrow) * (2 * A) + hc] = v;
         }
-        __syncthreads();
+        if (single) lds_barrier();
+        else __syncthreads();
         MLP_STAMP(3);
         // ---- sampling: the elementwise launches' arithmetic (asac_squash.h), spread over lanes ---------------------------
         // Their one-lane-per-row loops cost ~4 us of dependent tanh / log / atanh / exp chains here (16 rows = 16 lanes).
         // Same values, same summation order: the per-(row, d) transcendentals run on 16 A lanes — main sample on wave
         // 0, stored-action probabilities on wave 1, the second sample on wave 2 — and land in LDS; one lane per row
         // then forms the sums / products over d in d order.
-        {
+        if (single) {
+            // (3) The critic's first layer needs t = tanh(loc + eps scale) in xs[0] and nothing else of this phase.
+            // Everything else it reads is already published: the state tile and critic e's weights were written
+            // before the head's barrier.  Each of waves 0..3 forms ALL 16 A actions itself (the same instruction
+            // sequence on the same operands: the same bits, so the four waves store identical words) and reads them
+            // back as the first layer's A operand: LDS serves a wave's requests in order, so no barrier stands
+            // between the action and the layer.
+            // Waves 4..6 form the side outputs from L.ls and their own copy of the noise — the same x / tanh, the
+            // same terms, the same order of the sums over d — in two steps, the per-element terms beside the
+            // critic's first layer and the per-row sums and the stores beside its second, and meet the critic's
+            // three layer barriers in between.  Nothing but those barriers orders them against the critic, and
+            // nothing needs to: L.ls is not written again (one tile), L.xs and the critic's weights are not theirs,
+            // their scratch is the policy's first weight tile (dead after the head; the critic's layers write
+            // xs[1], the scratch of the looping path), and their stores go to global memory: complete when the
+            // kernel is.  The barriers are LDS-only, so a side wave's stores in flight hold nobody up.
+            // A wave without a job (wave 7; an absent job; every side wave of a non-writer workgroup) retires: a
+            // finished wave no longer counts at S_BARRIER ("if some waves of the workgroup have already
+            // terminated, the barrier waits for the surviving waves only", CDNA3 / CDNA4 ISA guide) — a rule of the
+            // target, not of the HIP model; the condition is wave-uniform, and the file refuses to build for any
+            // other target.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
+#error "pi_q_tiles retires whole waves ahead of workgroup barriers: valid on gfx950 (CDNA S_BARRIER semantics) only"
+#endif
+            if (wave >= 4) {
+                const int job = wave - 4;              // 0 main sample's log-probability, 1 stored actions, 2 second sample
+                const bool job_on = writer && (job == 0 || (job == 1 && a.sp.action) || (job == 2 && a.eps2));
+                if (job >= 3 || !job_on) return;
+                float* s0 = L.w[0] + job * 256;        // [16][8] per-element term 0 | [16][8] term 1
+                float* s1 = s0 + 128;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int it = lane + 64 * h;
+                    if (it >= 16 * A) continue;
+                    const int lrow = it / A, d = it - lrow * A;
+                    const int r = row0 + lrow;
+                    if (r >= N) continue;
+                    const float l = L.ls[lrow * 2 * kHeadPad + d], sc = L.ls[lrow * 2 * kHeadPad + A + d];
+                    if (job == 1) {
+                        const float av = RING ? av_ring[h] : av_pre[h];
+                        const float x = atanhf(fminf(fmaxf(av, -0.999f), 0.999f));
+                        s0[lrow * 8 + d] = squash_jac(x);
+                        s1[lrow * 8 + d] = expf(normal_log_prob(x, l, sc));
+                    } else {
+                        const int smp = (int)((unsigned)r / (unsigned)a.T);
+                        if (job == 2 && r - smp * a.T != a.t2) continue;
+                        const float ev = job == 0 ? ev_pre[h] : ev2_pre[h];
+                        const float x = l + ev * sc;
+                        const float t = tanhf(x);
+                        s0[lrow * 8 + d] = logf(fmaxf(1.f - t * t, kSquashFloor));
+                        s1[lrow * 8 + d] = normal_log_prob(x, l, sc);
+                        if (job == 0) a.a_out[r * A + d] = t;
+                        else a.a2_out[smp * A + d] = t;
+                    }
+                }
+                MLP_STAMP_AT(9 + job, 256 + 64 * job);
+                lds_barrier();                          // (the critic's first layer's; it orders the terms above too)
+                const int r = row0 + lane;
+                if (lane < 16 && r < N) {
+                    const int lrow = lane;
+                    if (job == 1) {
+                        float jac = 1.f;
+                        for (int d = 0; d < A; ++d) jac *= s0[lrow * 8 + d];
+                        const int spT = a.sp.T;
+                        const int sb = (int)((unsigned)r / (unsigned)spT), st = r - sb * spT;
+                        float* out = a.sp.out + (sb * a.sp.p_sb + st * a.sp.p_st + a.sp.p_off);
+                        for (int d = 0; d < A; ++d) out[d] = s1[lrow * 8 + d] / jac;
+                    } else {
+                        const int smp = (int)((unsigned)r / (unsigned)a.T);
+                        if (job == 0 || r - smp * a.T == a.t2) {
+                            float corr = 0.f;
+                            for (int d = 0; d < A; ++d) corr += s0[lrow * 8 + d];
+                            float lp = 0.f;
+                            for (int d = 0; d < A; ++d) {
+                                float v = s1[lrow * 8 + d] - corr;
+                                if (v == INFINITY) v = 0.f;
+                                lp += v;
+                            }
+                            if (job == 2) a.logp2_out[smp] = lp;
+                            else a.logp_out[r] = lp;
+                        }
+                    }
+                }
+                MLP_STAMP_AT(12 + job, 256 + 64 * job);
+                lds_barrier();                          // (the second layer's)
+                lds_barrier();                          // (the third's)
+                return;
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int it = lane + 64 * h;
+                if (it >= 16 * A) continue;
+                const int lrow = it / A, d = it - lrow * A;
+                float t = 0.f;                         // (a dead row's action is zero)
+                if (row0 + lrow < N) {
+                    const float l = L.ls[lrow * 2 * kHeadPad + d], sc = L.ls[lrow * 2 * kHeadPad + A + d];
+                    const float x = l + ev_pre[h] * sc;
+                    t = tanhf(x);
+                }
+                L.xs[0][lrow * kP + S + d] = t;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            MLP_STAMP(4);
+            MLP_STAMP(5);
+        } else {
             float* scr = L.xs[1];                  // (the policy's last activations are dead; xs[0] is being refilled)
             const int job = wave;                  // 0 main, 1 stored-action probabilities, 2 second sample
             const bool job_on = job == 0 || (writer && ((job == 1 && a.sp.action) || (job == 2 && a.eps2)));
@@ -2024,18 +2195,18 @@ __device__ __forceinline__ void pi_q_tiles(const ASAC_KARG PiQLaunch& a, PiQLds&
             }
             if (job == 0 && lane < 16 && row0 + lane >= N)
                 for (int d = 0; d < A; ++d) L.act[lane * kHeadPad + d] = 0.f;
+            if (tile == group) net_put_fixed<THREADS, 3>(rq, C);
+            put_input_tile<THREADS, SLOTS>(in_lo, L.xs[0]);         // the states again (columns >= S are zero)
+            __syncthreads();
+            MLP_STAMP(4);
+            if ((int)threadIdx.x < 16 * A) {
+                const int lrow = threadIdx.x / A, d = threadIdx.x - lrow * A;
+                L.xs[0][lrow * kP + S + d] = L.act[lrow * kHeadPad + d];
+            }
+            __syncthreads();
+            MLP_STAMP(5);
         }
         // ---- critic e on (state, sampled action) ---------------------------------------------------------------------
-        if (tile == group) net_put_fixed<THREADS, 3>(rq, C);
-        put_input_tile<THREADS, SLOTS>(in_lo, L.xs[0]);         // the states again (columns >= S are zero)
-        __syncthreads();
-        MLP_STAMP(4);
-        if ((int)threadIdx.x < 16 * A) {
-            const int lrow = threadIdx.x / A, d = threadIdx.x - lrow * A;
-            L.xs[0][lrow * kP + S + d] = L.act[lrow * kHeadPad + d];
-        }
-        __syncthreads();
-        MLP_STAMP(5);
         cur = 0;
 #pragma unroll
         for (int l = 0; l < 3; ++l) {
@@ -2057,7 +2228,9 @@ __device__ __forceinline__ void pi_q_tiles(const ASAC_KARG PiQLaunch& a, PiQLds&
                     xout[row * kP + col] = y;
                 }
             }
-            __syncthreads();
+            if (single) lds_barrier();
+            else __syncthreads();
+            if (l == 0) MLP_STAMP(8);
             cur ^= 1;
         }
         MLP_STAMP(6);
@@ -2072,6 +2245,7 @@ __device__ __forceinline__ void pi_q_tiles(const ASAC_KARG PiQLaunch& a, PiQLds&
             }
         }
         MLP_STAMP(7);
+        if (single) break;
     }
 }
 
@@ -2090,8 +2264,14 @@ __global__ __launch_bounds__(kPiQThreads) void k_pi_sample_q(const PiQLaunch m_b
     if (blk >= fused_blocks && threadIdx.x >= 256) return;
     if (blk < fused_blocks) {
         PiQLds& L = *reinterpret_cast<PiQLds*>(smem_raw);
-        if (m.pi.x0_T > 0) pi_q_tiles<true>(m, L);
-        else pi_q_tiles<false>(m, L);
+        const bool single = (m.pi.N + 15) / 16 <= m.tile_groups;
+        if (m.pi.x0_T > 0) {
+            if (single) pi_q_tiles<true, false, true>(m, L);
+            else pi_q_tiles<true>(m, L);
+        } else {
+            if (single) pi_q_tiles<false, false, true>(m, L);
+            else pi_q_tiles<false>(m, L);
+        }
         return;
     }
     const int xb = blk - fused_blocks;
@@ -2130,7 +2310,9 @@ __global__ __launch_bounds__(kPiQThreads) void k_pi_sample_q_ring(const PiQLaunc
     const int fused_blocks = m.blocks;
     if (blk >= fused_blocks && threadIdx.x >= 256) return;
     if (blk < fused_blocks) {
-        pi_q_tiles<false, true>(m, *reinterpret_cast<PiQLds*>(smem_raw), &mr.ring);
+        PiQLds& L = *reinterpret_cast<PiQLds*>(smem_raw);
+        if ((m.pi.N + 15) / 16 <= m.tile_groups) pi_q_tiles<false, true, true>(m, L, &mr.ring);
+        else pi_q_tiles<false, true>(m, L, &mr.ring);
         return;
     }
     const int xb = blk - fused_blocks;

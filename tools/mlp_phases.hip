@@ -1,6 +1,8 @@
 // Phase timeline of the fused MLP backward (workgroup (0,0), 100 MHz wall clock): includes the library source with
 // ASAC_MLP_STAMPS, drives it through its C ABI at the train step's shapes (N = 256 rows, E = 2 stock Q networks /
-// the stock policy) and prints the time between stamps, averaged over launches.
+// the stock policy) and prints the time between stamps, averaged over launches.  The policy -> sample -> critics forward
+// runs at the step's N = 1 280 rows, E = 2, A = 2, S = 6 with all three side jobs on, on plain rows and on ring-addressed
+// rows; its side waves (threads 256, 320, 384) stamp the end of their two steps.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Iinclude -Iadvanced-soft-actor-critic_amd/csrc \
 //         tools/mlp_phases.hip -o tools/mlp_phases
 #define ASAC_MLP_STAMPS 1
@@ -114,19 +116,50 @@ int main() {
         job.sample.T = T; job.sample.action = aout; job.sample.action_stride_b = T * A; job.sample.action_stride_t = A;
         job.sample.prob_out = prob; job.sample.prob_stride_b = T * A; job.sample.prob_stride_t = A;
         job.eps2 = eps; job.t2 = 0; job.a2_out = a2; job.logp2_out = lp2;
-        double acc2[10] = {0};
-        for (int r = 0; r < reps; ++r) {
-            asac_policy_sample_q_forward(&job, nullptr, 0, nullptr, 0, nullptr);
-            hipDeviceSynchronize();
-            unsigned long long st[32];
-            hipMemcpyFromSymbol(st, HIP_SYMBOL(asac::g_mlp_stamps), sizeof st);
-            for (int i = 1; i <= 7; ++i) acc2[i] += (double)(st[i] - st[i - 1]) / 100.0;
-            acc2[0] += (double)(st[7] - st[0]) / 100.0;
+        // ... and the same launch with ring-addressed rows (k_pi_sample_q_ring): a full ring of one long episode, the
+        // batch's ids spread over it (every window row valid: the addressing is what is timed, not the padding)
+        const int C = 4096;
+        std::vector<int64_t> h_ids(N);
+        std::vector<int32_t> h_index(C);
+        for (int i = 0; i < N; ++i) h_ids[i] = (int64_t)((i * 2654435761u) % (unsigned)(C - T)) + C;
+        for (int i = 0; i < C; ++i) h_index[i] = i;
+        int64_t* ids;
+        int32_t* index_ring;
+        float *obs_ring, *act_ring;
+        hipMalloc(&ids, N * 8); hipMemcpy(ids, h_ids.data(), N * 8, hipMemcpyHostToDevice);
+        hipMalloc(&index_ring, C * 4); hipMemcpy(index_ring, h_index.data(), C * 4, hipMemcpyHostToDevice);
+        hipMalloc(&obs_ring, C * S * 4); hipMemset(obs_ring, 0, C * S * 4);
+        hipMalloc(&act_ring, C * A * 4); hipMemset(act_ring, 0, C * A * 4);
+        asac_pi_q_job_t rjob = job;
+        rjob.ring.ids = ids; rjob.ring.index_ring = index_ring; rjob.ring.capacity = C; rjob.ring.prev_n = 0; rjob.ring.L = T;
+        rjob.ring.j0 = 0; rjob.ring.x_j0 = -1;
+        rjob.ring.x0.src = obs_ring; rjob.ring.x0.row_bytes = S * 4; rjob.ring.x0.pad_mode = ASAC_PAD_KEEP;
+        rjob.ring.action.src = act_ring; rjob.ring.action.row_bytes = A * 4; rjob.ring.action.pad_mode = ASAC_PAD_WORD;
+        for (int form = 0; form < 2; ++form) {
+            double acc2[10] = {0}, side[6] = {0};
+            int bad = 0;
+            for (int r = 0; r < reps; ++r) {
+                bad |= asac_policy_sample_q_forward(form ? &rjob : &job, nullptr, 0, nullptr, 0, nullptr);
+                hipDeviceSynchronize();
+                unsigned long long st[32];
+                hipMemcpyFromSymbol(st, HIP_SYMBOL(asac::g_mlp_stamps), sizeof st);
+                for (int i = 1; i <= 7; ++i) acc2[i] += (double)(st[i] - st[i - 1]) / 100.0;
+                acc2[0] += (double)(st[7] - st[0]) / 100.0;
+                acc2[8] += (double)(st[8] - st[5]) / 100.0;
+                for (int i = 0; i < 6; ++i) side[i] += (double)((long long)(st[9 + i] - st[3])) / 100.0;
+            }
+            // (a single-tile workgroup: "sampling" is the action alone, "actions -> tile" is empty, and the critic's first
+            // layer ends at the barrier that also waits for the side waves to retire)
+            static const char* names2[] = {"", "staging", "policy forward", "policy head", "sampling", "actions -> tile",
+                                           "critic forward", "critic head"};
+            printf("policy_sample_q_forward%s: workgroup 0 total %.2f us%s\n", form ? " (ring rows)" : "", acc2[0] / reps,
+                   bad ? "  [the launch was refused]" : "");
+            for (int i = 1; i <= 7; ++i) printf("   %-18s %6.2f us\n", names2[i], acc2[i] / reps);
+            printf("   critic forward, first layer up to its barrier: %.2f us\n", acc2[8] / reps);
+            printf("   side waves after the head's barrier (log-probability | stored actions | second sample): terms by"
+                   " %.2f | %.2f | %.2f us, sums and stores by %.2f | %.2f | %.2f us\n", side[0] / reps, side[1] / reps,
+                   side[2] / reps, side[3] / reps, side[4] / reps, side[5] / reps);
         }
-        static const char* names2[] = {"", "staging", "policy forward", "policy head", "sampling", "actions -> tile",
-                                       "critic forward", "critic head"};
-        printf("policy_sample_q_forward: workgroup 0 total %.2f us\n", acc2[0] / reps);
-        for (int i = 1; i <= 7; ++i) printf("   %-18s %6.2f us\n", names2[i], acc2[i] / reps);
     }
     return 0;
 }

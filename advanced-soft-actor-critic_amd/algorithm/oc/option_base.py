@@ -8,8 +8,15 @@ What runs where:
     (`asac_squash_sample_fwd`: the parent's `_window_sample`), the target critics, the return's arguments assembled by
     the parent's `_c_return`, then ONE launch for subset minimum, termination mix, mean over the
     options, ratios and the V-trace scan (`asac_option_return`, csrc/option.hip); with the online critics' values handed
-    in (`_get_td_error`, continuous-only action spaces) the same launch writes mean_e |q_e - y|.  The discrete branches
-    are torch compositions that end in `asac_vtrace_return_direct` / `get_dqn_like_d_y`, as the parent's.
+    in (`_get_td_error`, continuous-only action spaces) the same launch writes mean_e |q_e - y|.
+  * `_get_y`, discrete branches alone with a policy (`fused_option_discrete_applies`, `hip_config['fused_option_discrete']`):
+    the policy's logits and the target critics' head outputs over the window, then ONE launch for the subset minimum per
+    action entry, branch softmax, the termination mix with the mean over the options, ratios and the V-trace scan
+    (`asac_option_discrete_return`, csrc/discrete.hip); `_get_td_error` hands the online heads at t = 0 to the same launch
+    and takes mean_e |q_e - y| from it; `compute_rep_q_grads` forms the Q loss and its gradient at the heads with
+    `asac_discrete_q_loss_grad` and back-propagates from there.  Hybrid and DQN-like options, sizes over the launches'
+    limits and the switch off run torch compositions that end in `asac_vtrace_return_direct` / `get_dqn_like_d_y`, as
+    the parent's.
   * `compute_rep_q_grads` leaves gradients in the flat gradient buffer (clipped double-Q loss and d loss / d q from
     `asac_q_loss_fwd_bwd` for continuous-only action spaces), `train_rep_q` applies Adam to the [rep | q_0 .. q_E-1] span in
     one launch (`asac_adam_step`).  `train_policy_alpha` is the parent's `_train_policy`, `_train_alpha`, `_train_curiosity`,
@@ -67,6 +74,17 @@ def _reject_unsupported(args, kwargs) -> None:
             what='SEQ_ENCODER.ATTN', why='seq_encoder in option cannot be ATTN (option_base.py:180-181)'))
 
 
+def fused_option_discrete_applies(*, enabled, d_action_sizes, c_action_size, discrete_dqn_like, float32_on_device,
+                                  ensemble_q_num, n_step, batch_size, num_options) -> bool:
+    """Do the return, the TD error and the Q loss of an option of this configuration run on `asac_option_discrete_return`
+    / `asac_discrete_q_loss_grad` (`hip_config['fused_option_discrete']`)?  Only with discrete branches alone and a policy
+    (no DQN-like target), on float32 device tensors, within the entry points' size limits, `batch_size` rows a batch
+    and `num_options` options' values a step.  Everything else runs the eager code."""
+    return bool(enabled and len(d_action_sizes) > 0 and c_action_size == 0 and not discrete_dqn_like and float32_on_device
+                and native.discrete_sizes_ok(d_action_sizes, ensemble_q_num, n_step, batch_size)
+                and 0 < num_options <= native.OPTION_MAX_OPTIONS)
+
+
 class OptionBase(SAC_Base):
     _plain_learner = False
 
@@ -79,10 +97,12 @@ class OptionBase(SAC_Base):
         self.random_q = random_q
         _reject_unsupported(args, kwargs)
         super().__init__(*args, **kwargs)
-        # the option's discrete branches stay on the eager arithmetic (its own `_get_y` / `_get_td_error` mix the
-        # termination in; the parent's one-launch discrete path is the plain learner's)
+        # the parent's one-launch discrete path is the plain learner's (the option's own `_get_y` / `_get_td_error` mix
+        # the termination in and take the minimum over the critics): off; the option's own launch has its own switch
         self._fused_discrete = False
         self._fused_dqn = False         # (its own `get_dqn_like_d_y` mixes the termination in as well)
+        hip_config = inspect.signature(SAC_Base.__init__).bind_partial(None, *args, **kwargs).arguments.get('hip_config')
+        self._fused_option_discrete = bool((hip_config or {}).get('fused_option_discrete', True))
 
     # -- construction (option_base.py:27-86) ----------------------------------------------------------------------------
     def _sample_thread(self):
@@ -229,16 +249,56 @@ class OptionBase(SAC_Base):
         self.noise.subset_(sub, self.ensemble_q_num)
         return sub
 
+    def _option_discrete_fused(self, B: int, num_options: int) -> bool:
+        """this call's discrete arithmetic runs on the option's launches (`fused_option_discrete_applies`)"""
+        return fused_option_discrete_applies(
+            enabled=self._fused_option_discrete, d_action_sizes=self.d_action_sizes, c_action_size=self.c_action_size,
+            discrete_dqn_like=self.discrete_dqn_like,
+            float32_on_device=self._params.flat.dtype == torch.float32 and self._params.flat.is_cuda,
+            ensemble_q_num=self.ensemble_q_num, n_step=self.n_step, batch_size=B, num_options=num_options)
+
+    def _get_d_y_fused(self, next_n_vs_over_options, n_terminations, n_last_masks, n_padding_masks, nx_obses_list,
+                       nx_states, n_actions, n_rewards, n_dones, n_mu_probs, subset_prefix, d_q_online, td_out):
+        """option_base.py:287, 333-373 (and, with `d_q_online`, the TD error) as ONE launch -> d_y [batch, 1]: no
+        distribution objects, no stack of the members' head outputs; the subsets are drawn in the eager branch's order"""
+        B = n_rewards.shape[0]
+        no_c = torch.zeros(0, device=self.device)
+        logits = self._discrete_logits(nx_states, nx_obses_list)
+        heads = [q(nx_states, no_c, nx_obses_list)[0] for q in self.model_target_q_list]       # [B, n+1, D] each
+        sub_next, sub_n = self._draw_subset(subset_prefix + '_dnext'), self._draw_subset(subset_prefix + '_dn')
+        # (a fresh tensor per call: the selector keeps the returned y for the termination step)
+        d_y = torch.empty(B, dtype=torch.float32, device=self.device)
+        args = self._vtrace_args(n_rewards, n_dones, n_last_masks, n_padding_masks, d_y)
+        args.subset_n, args.subset_next, args.E_sample = sub_n.data_ptr(), sub_next.data_ptr(), self.ensemble_q_sample
+        args.log_alpha = self.log_d_alpha.data_ptr()
+        if self.use_n_step_is:
+            if n_mu_probs.stride(-1) != 1:
+                n_mu_probs = n_mu_probs.contiguous()
+            args.mu_prob, args.mu_stride_b, args.mu_stride_t = n_mu_probs.data_ptr(), n_mu_probs.stride(0), n_mu_probs.stride(1)
+        if d_q_online is not None:
+            args.td_error_out = td_out.data_ptr()
+        if n_actions.stride(-1) != 1:
+            n_actions = n_actions.contiguous()
+        native.option_discrete_return(args, self._branches, heads, logits, n_terminations, next_n_vs_over_options,
+                                      action=n_actions, q_online=d_q_online)
+        return d_y.unsqueeze(-1)
+
     @torch.no_grad()
     def _get_y(self, next_n_vs_over_options, n_terminations, n_last_masks, n_padding_masks, nx_obses_list, nx_states,
                n_actions, n_rewards, n_dones, n_mu_probs, *, eps_buf=None, subset_prefix='y', y_out=None, q_online=None,
-               td_out=None):
+               td_out=None, d_q_online=None):
         """option_base.py:249-429 -> (d_y [batch, 1] | None, c_y [batch, 1] | None).  The keyword-only arguments are
         this class's: the noise buffer and the ensemble subsets to draw into, where the continuous return goes, and the
-        online critics' values [E, batch] whose TD error the return's launch forms as well."""
+        online critics' values [E, batch] (`d_q_online`: their discrete head outputs [batch, D] each, pure-discrete
+        option on its own launch) whose TD error the return's launch forms as well."""
         B, n = n_rewards.shape
         A = self.c_action_size
         f32 = dict(dtype=torch.float32, device=self.device)
+        if self._option_discrete_fused(B, next_n_vs_over_options.shape[-1]):
+            n_last_masks, n_padding_masks, n_dones = (m.contiguous() for m in (n_last_masks, n_padding_masks, n_dones))
+            return self._get_d_y_fused(next_n_vs_over_options, n_terminations, n_last_masks, n_padding_masks,
+                                       nx_obses_list, nx_states, n_actions, n_rewards, n_dones, n_mu_probs, subset_prefix,
+                                       d_q_online, td_out), None
         if y_out is None:       # (a fresh tensor per call: the selector keeps the returned y for the termination step)
             y_out = torch.empty(B, **f32)
         nx_actions = torch.cat([n_actions, torch.zeros_like(n_actions[:, :1])], dim=1)
@@ -329,7 +389,14 @@ class OptionBase(SAC_Base):
         start, stop = self._params.span('rep', f'q_{E - 1}')
         self._params.grad[start:stop].zero_()                   # optimizer_rep / optimizer_q zero_grad (534-538)
         losses = roots = None
-        if self.d_action_sizes:
+        if self._option_discrete_fused(B, next_n_vs_over_options.shape[-1]):
+            # loss values and d (sum_e l_e) / d (head outputs) from one launch; back-propagation starts at the heads
+            heads = [q[0] for q in q_list]
+            grad_q, _ = self._discrete_grad_buffers(B)
+            native.discrete_q_loss_grad(self._branches, [h.detach() for h in heads], d_action, d_y, priority_is,
+                                        self._loss_q_e, grad_q)
+            roots = (heads, list(grad_q.unbind(0)))
+        elif self.d_action_sizes:
             qs = torch.stack([torch.sum(d_action * q[0], dim=-1, keepdim=True) / self.d_action_branch_size
                               for q in q_list])                                             # [E, B, 1]
             losses = functional.mse_loss(qs, d_y.expand_as(qs), reduction='none')
@@ -450,13 +517,15 @@ class OptionBase(SAC_Base):
             c_q = torch.stack([q[1] for q in q_list]).squeeze(-1).contiguous() if self.c_action_size else None
         else:
             c_q = self._c_q_values(False, state, c_action, obs_list).contiguous()
-        fused_td = bool(self.c_action_size) and not self.d_action_sizes
+        fused_d = self._option_discrete_fused(B, next_n_vs_over_options.shape[-1])
+        fused_td = fused_d or (bool(self.c_action_size) and not self.d_action_sizes)
         td = torch.empty(B, dtype=torch.float32, device=self.device)
         d_y, c_y = self._get_y(next_n_vs_over_options, n_target_terminations, n_last_masks, n_padding_masks,
                                nx_obses_list, nx_target_states, n_actions, n_rewards, n_dones,
                                n_mu_probs if self.use_n_step_is else None,
                                eps_buf=self._eps_td, subset_prefix='td',
-                               q_online=c_q if fused_td else None, td_out=td)
+                               q_online=c_q if fused_td and not fused_d else None, td_out=td,
+                               d_q_online=[q[0] for q in q_list] if fused_d else None)
         if fused_td:
             return td.unsqueeze(-1)
         err = torch.zeros((self.ensemble_q_num, B, 1), device=self.device)

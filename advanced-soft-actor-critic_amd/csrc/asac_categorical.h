@@ -76,6 +76,20 @@ __device__ __forceinline__ float cat_member_mean(const ASAC_KARG asac_members_t&
     return s / (float)Es;
 }
 
+// ... the minimum over the subset instead (the option's target, option_base.py:337-338): the same loads, fminf in subset
+// order (torch min(0)); of one member it is that member's value, as the mean is
+__device__ __forceinline__ float cat_member_min(const ASAC_KARG asac_members_t& tab, const int32_t* subset, int Es,
+                                                int64_t off) {
+    float v[ASAC_DISCRETE_MAX_MEMBERS];
+#pragma unroll
+    for (int e = 0; e < ASAC_DISCRETE_MAX_MEMBERS; ++e) v[e] = tab.base[member(subset, min(e, Es - 1))][off];
+    float m = v[0];
+#pragma unroll
+    for (int e = 1; e < ASAC_DISCRETE_MAX_MEMBERS; ++e)
+        if (e < Es) m = fminf(m, v[e]);
+    return m;
+}
+
 constexpr int kDiscThreads = 256;
 
 // sum_j a[j] * q[j] over a row of D entries: loads in groups of four requested together (indices beyond D re-read the last

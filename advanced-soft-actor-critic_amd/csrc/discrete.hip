@@ -10,6 +10,11 @@
 //       phase 1  one lane per window position: branch softmax, V with subset_n and with subset_next, log pi(stored action),
 //                prod mu
 //       phase 2  one lane per step: ratio, vtrace_step_finish_v;   phase 3  one lane per row: vtrace_scan_row, y, TD error
+//   asac_option_discrete_return     the same kernel's second instantiation (OptionBase._get_y's policy-based discrete
+//       branch, option_base.py:287, 333-373): the MINIMUM over each subset instead of the mean, and per entry of positions
+//       1..n the termination mix (1 - beta_t) (Qx_j - c_j) + beta_t vbar_t, vbar = asac_option.h's option_mean.  A step's
+//       beta and its options' values are requested with the step's reward and masks (at clamped indexes, by every lane)
+//       and handed to position t + 1 through LDS.  The plain instantiation's arithmetic and order are what they were
 //   asac_discrete_q_loss_grad       one workgroup per member
 //   asac_discrete_policy_loss_grad  one workgroup; a lane keeps its row's per-branch (max, sum, sum p g, H) in LDS between
 //                                   the pass that forms the row's loss and entropies and the pass that writes its gradient
@@ -20,6 +25,7 @@
 #include "asac_common.h"
 #include "asac_vtrace.h"
 #include "asac_categorical.h"
+#include "asac_option.h"
 
 namespace asac {
 
@@ -28,16 +34,23 @@ struct DiscReturnDev {
     asac_vtrace_args_t a;
     asac_discrete_return_t x;
     int32_t R, Dp, pitch, seg;       // rows per workgroup, LDS pitch of a position's entries, of a row's steps, scan lanes
+    // the option's termination mix (kOption only): beta [B, n], the options' values [B, n, O], strides in floats
+    const float *beta, *v_options;
+    int64_t beta_sb, beta_st, v_sb, v_st, v_so;
+    int32_t O;
 };
 
 __host__ __device__ __forceinline__ int disc_round4(int v) { return (v + 3) & ~3; }
 // LDS floats of a workgroup of R rows (every part a multiple of four floats)
-__host__ __device__ __forceinline__ int disc_return_lds_floats(int R, int T, int Dp, int pitch, bool is) {
+// (`option`: plus the two [P] arrays of the termination mix)
+__host__ __device__ __forceinline__ int disc_return_lds_floats(int R, int T, int Dp, int pitch, bool is,
+                                                               bool option = false) {
     const int P = R * T;
-    return (is ? 5 : 3) * disc_round4(P * Dp) + 4 * disc_round4(P) + 2 * disc_round4(R * pitch) +
+    return (is ? 5 : 3) * disc_round4(P * Dp) + (option ? 6 : 4) * disc_round4(P) + 2 * disc_round4(R * pitch) +
            disc_round4(R * ASAC_DISCRETE_MAX_MEMBERS);
 }
 
+template <bool kOption>
 __global__ __launch_bounds__(kDiscThreads) void k_discrete_return(const DiscReturnDev by_value) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const ASAC_KARG DiscReturnDev& v = *static_cast<const ASAC_KARG DiscReturnDev*>(kernarg_base());
@@ -59,6 +72,8 @@ __global__ __launch_bounds__(kDiscThreads) void k_discrete_return(const DiscRetu
     float* s_d = s_mup + NP;             // [R][pitch] per-step term d_t
     float* s_c = s_d + NS;               // [R][pitch] trace-cutting factor c_t
     float* s_qs = s_c + NS;              // [R][8] the online members' value of the stored action at t = 0
+    float* s_beta = s_qs + disc_round4(R * ASAC_DISCRETE_MAX_MEMBERS);   // [P] beta of the step INTO the position (kOption)
+    float* s_vbar = s_beta + NP;         // [P] mean over the options at that step                                 (kOption)
     const int row0 = blockIdx.x * R;
     const int tid = threadIdx.x;
 
@@ -78,6 +93,18 @@ __global__ __launch_bounds__(kDiscThreads) void k_discrete_return(const DiscRetu
         raw.keep = gone ? 0.f : 1.f;                       // ~(last | pad)
         raw.ratio = 1.f;
     }
+    if (kOption) {
+        // the step's beta and option values: loaded by EVERY lane at clamped indexes, kept by the lanes that have a step;
+        // step t mixes into position t + 1 (position 0 of a row is never a next position: an exact 0 there)
+        const int b = min(row0 + sr, B - 1);
+        const float beta = v.beta[(int64_t)b * v.beta_sb + (int64_t)st * v.beta_st];
+        const float vbar = option_mean(v.v_options + (int64_t)b * v.v_sb + (int64_t)st * v.v_st, v.v_so, v.O);
+        if (have_step) {
+            const int pos = sr * T + st;
+            s_beta[pos + 1] = beta, s_vbar[pos + 1] = vbar;
+            if (st == 0) s_beta[pos] = 0.f, s_vbar[pos] = 0.f;
+        }
+    }
 
     // phase 0
     const int Es = a.E_sample;
@@ -93,8 +120,10 @@ __global__ __launch_bounds__(kDiscThreads) void k_discrete_return(const DiscRetu
             av = x.action[(int64_t)b * x.action_stride_b + (int64_t)t * x.action_stride_t + j];
             mv = a.mu_prob[(int64_t)b * a.mu_stride_b + (int64_t)t * a.mu_stride_t + j];
         }
-        const float qn = cat_member_mean(x.q_target, a.subset_n, Es, qoff);
-        const float qx = cat_member_mean(x.q_target, a.subset_next, Es, qoff);
+        const float qn = kOption ? cat_member_min(x.q_target, a.subset_n, Es, qoff)
+                                 : cat_member_mean(x.q_target, a.subset_n, Es, qoff);
+        const float qx = kOption ? cat_member_min(x.q_target, a.subset_next, Es, qoff)
+                                 : cat_member_mean(x.q_target, a.subset_next, Es, qoff);
         const int o = pos * Dp + j;
         s_z[o] = z, s_qn[o] = qn, s_qx[o] = qx;
         if (is) s_a[o] = av, s_mu[o] = mv * av;
@@ -106,6 +135,7 @@ __global__ __launch_bounds__(kDiscThreads) void k_discrete_return(const DiscRetu
     if (tid < P && row0 + tid / T < B) {
         const int pos = tid;
         float vn = 0.f, vx = 0.f, lpa = 0.f, mu = 1.f;
+        const float beta = kOption ? s_beta[pos] : 0.f, vbar = kOption ? s_vbar[pos] : 0.f;
         int j0 = 0;
         for (int k = 0; k < K; ++k) {
             const int s = x.branches.size[k];
@@ -117,7 +147,10 @@ __global__ __launch_bounds__(kDiscThreads) void k_discrete_return(const DiscRetu
                 const float p = cat_prob(s_z[o0 + j], cs);
                 const float c = alpha * cat_cl(p);
                 vn += p * (s_qn[o0 + j] - c);
-                vx += p * (s_qx[o0 + j] - c);
+                if (kOption)
+                    vx += p * ((1.f - beta) * (s_qx[o0 + j] - c) + beta * vbar);      // option_base.py:349-351
+                else
+                    vx += p * (s_qx[o0 + j] - c);
                 if (is) {
                     const float av = s_a[o0 + j];
                     if (av > amax) amax = av, arg = j;             // the first maximum (torch max(-1)[1])
@@ -163,6 +196,58 @@ __global__ __launch_bounds__(kDiscThreads) void k_discrete_return(const DiscRetu
         for (int e = 0; e < Eon; ++e) s += fabsf(s_qs[tid * ASAC_DISCRETE_MAX_MEMBERS + e] - y);
         a.td_error_out[b] = s / (float)Eon;
     }
+}
+
+// the host side both instantiations share: the checks (everything but the sign of B) ...
+static bool discrete_return_args_ok(const asac_vtrace_args_t* args_host, const asac_discrete_return_t* job_host) {
+    if (!args_host || !job_host) return false;
+    const asac_vtrace_args_t& h = *args_host;
+    const asac_discrete_return_t& x = *job_host;
+    if (h.n <= 0 || h.n > ASAC_DISCRETE_MAX_STEPS || !h.y_out || !h.reward || !h.done || !h.last_mask ||
+        !h.padding_mask || !h.gamma_ratio || !h.log_alpha || !x.logits || !cat_branches_ok(x.branches) ||
+        !members_ok(&x.q_target) || h.E_sample <= 0 || h.E_sample > x.q_target.E)
+        return false;
+    if (h.use_n_step_is && (!h.mu_prob || !h.lambda_ratio || !x.action)) return false;
+    if (h.td_error_out && (!members_ok(&x.q_online) || !x.action)) return false;
+    return true;
+}
+
+// ... and the launch geometry (`v`: the option's fields already set, the rest filled here)
+template <bool kOption>
+static int discrete_return_launch(const asac_vtrace_args_t& h, const asac_discrete_return_t& x, DiscReturnDev& v,
+                                  const char* where, void* stream) {
+    v.a = h;
+    v.x = x;
+    if (!h.td_error_out) v.x.q_online.E = 0;
+    const int T = h.n + 1, D = x.branches.D;
+    const bool is = h.use_n_step_is != 0;
+    v.Dp = D | 1;                                 // odd pitches: conflict-free position-per-lane / row-per-lane reads
+    v.pitch = (h.n + 1) | 1;
+    // rows per workgroup: one lane per window position, a few rounds of phase 0 at most, and the LDS they need
+    int R = kDiscThreads / T;
+    if (R > 2048 / (T * D)) R = 2048 / (T * D);
+    if (R > h.B) R = h.B;
+    if (R < 1) R = 1;
+    while (R > 1 && (size_t)disc_return_lds_floats(R, T, v.Dp, v.pitch, is, kOption) * sizeof(float) > 64 * 1024) --R;
+    v.R = R;
+    v.seg = vtrace_scan_lanes(h.B, h.n);
+    const size_t lds = (size_t)disc_return_lds_floats(R, T, v.Dp, v.pitch, is, kOption) * sizeof(float);
+    if (lds > 64 * 1024) {                        // one row of a long, wide window under importance sampling (<= 88 KB)
+        static bool raised = false;               // (one flag per instantiation)
+        if (!raised) {
+            hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_discrete_return<kOption>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+            if (err != hipSuccess) {
+                set_error(err, where);
+                return (int)err;
+            }
+            raised = true;
+        }
+        if (lds > 96 * 1024) return bad_arg(where);
+    }
+    const int blocks = (h.B + R - 1) / R;
+    ASAC_LAUNCH(k_discrete_return<kOption>, dim3((unsigned)blocks), dim3(kDiscThreads), lds, as_stream(stream), v);
+    return finish_launch(where);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -322,48 +407,26 @@ using namespace asac;
 extern "C" {
 
 int asac_discrete_return(const asac_vtrace_args_t* args_host, const asac_discrete_return_t* job_host, void* stream) {
-    if (!args_host || !job_host) return bad_arg("asac_discrete_return");
-    const asac_vtrace_args_t& h = *args_host;
-    const asac_discrete_return_t& x = *job_host;
-    if (h.B <= 0 || h.n <= 0 || h.n > ASAC_DISCRETE_MAX_STEPS || !h.y_out || !h.reward || !h.done || !h.last_mask ||
-        !h.padding_mask || !h.gamma_ratio || !h.log_alpha || !x.logits || !cat_branches_ok(x.branches) ||
-        !members_ok(&x.q_target) || h.E_sample <= 0 || h.E_sample > x.q_target.E)
+    if (!discrete_return_args_ok(args_host, job_host) || args_host->B <= 0)
         return bad_arg("asac_discrete_return");
-    if (h.use_n_step_is && (!h.mu_prob || !h.lambda_ratio || !x.action)) return bad_arg("asac_discrete_return: is");
-    if (h.td_error_out && (!members_ok(&x.q_online) || !x.action)) return bad_arg("asac_discrete_return: td error");
     DiscReturnDev v{};
-    v.a = h;
-    v.x = x;
-    if (!h.td_error_out) v.x.q_online.E = 0;
-    const int T = h.n + 1, D = x.branches.D;
-    const bool is = h.use_n_step_is != 0;
-    v.Dp = D | 1;                                 // odd pitches: conflict-free position-per-lane / row-per-lane reads
-    v.pitch = (h.n + 1) | 1;
-    // rows per workgroup: one lane per window position, a few rounds of phase 0 at most, and the LDS they need
-    int R = kDiscThreads / T;
-    if (R > 2048 / (T * D)) R = 2048 / (T * D);
-    if (R > h.B) R = h.B;
-    if (R < 1) R = 1;
-    while (R > 1 && (size_t)disc_return_lds_floats(R, T, v.Dp, v.pitch, is) * sizeof(float) > 64 * 1024) --R;
-    v.R = R;
-    v.seg = vtrace_scan_lanes(h.B, h.n);
-    const size_t lds = (size_t)disc_return_lds_floats(R, T, v.Dp, v.pitch, is) * sizeof(float);
-    if (lds > 64 * 1024) {                        // one row of a long, wide window under importance sampling (<= 87 KB)
-        static bool raised = false;
-        if (!raised) {
-            hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_discrete_return),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            if (err != hipSuccess) {
-                set_error(err, "asac_discrete_return: LDS limit");
-                return (int)err;
-            }
-            raised = true;
-        }
-        if (lds > 96 * 1024) return bad_arg("asac_discrete_return: LDS");
-    }
-    const int blocks = (h.B + R - 1) / R;
-    ASAC_LAUNCH(k_discrete_return, dim3((unsigned)blocks), dim3(kDiscThreads), lds, as_stream(stream), v);
-    return finish_launch("asac_discrete_return");
+    return discrete_return_launch<false>(*args_host, *job_host, v, "asac_discrete_return", stream);
+}
+
+int asac_option_discrete_return(const asac_vtrace_args_t* args_host, const asac_discrete_return_t* job_host,
+                                const float* beta, int64_t beta_stride_b, int64_t beta_stride_t,
+                                const float* v_options, int64_t v_stride_b, int64_t v_stride_t, int64_t v_stride_o,
+                                int num_options, void* stream) {
+    if (!discrete_return_args_ok(args_host, job_host) || args_host->B < 0 || !beta ||
+        !v_options || num_options <= 0 || num_options > ASAC_OPTION_MAX_OPTIONS)
+        return bad_arg("asac_option_discrete_return");
+    if (args_host->B == 0) return 0;
+    DiscReturnDev v{};
+    v.beta = beta, v.v_options = v_options;
+    v.beta_sb = beta_stride_b, v.beta_st = beta_stride_t;
+    v.v_sb = v_stride_b, v.v_st = v_stride_t, v.v_so = v_stride_o;
+    v.O = num_options;
+    return discrete_return_launch<true>(*args_host, *job_host, v, "asac_option_discrete_return", stream);
 }
 
 int asac_discrete_q_loss_grad(const asac_branches_t* branches, const asac_members_t* q, const float* action,

@@ -17,6 +17,7 @@
 // order) -> the last workgroup to arrive adds the workgroups' sums in workgroup order (asac_ordered_finish.h).  The
 // arrival counter is an integer; no float atomics: equal inputs give equal bits.  -ffp-contract=off.
 #include "asac_common.h"
+#include "asac_option.h"
 #include "asac_ordered_finish.h"
 #include "asac_vtrace.h"
 
@@ -29,21 +30,6 @@ struct OptionReturnDev {
     int64_t beta_sb, beta_st, v_sb, v_st, v_so;
     int32_t O, R, pitch, seg;
 };
-
-// mean_o V[b, t, o]: loads in groups of four requested together (indices beyond O re-read the last option: a valid
-// address, the value is not added), added in option order
-__device__ __forceinline__ float option_mean(const float* v, int64_t so, int O) {
-    float s = 0.f;
-    for (int o0 = 0; o0 < O; o0 += 4) {
-        float x[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) x[j] = v[(int64_t)min(o0 + j, O - 1) * so];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (o0 + j < O) s += x[j];
-    }
-    return s / (float)O;
-}
 
 __global__ __launch_bounds__(256) void k_option_return(const OptionReturnDev by_value) {
     extern __shared__ __attribute__((aligned(16))) float lds[];

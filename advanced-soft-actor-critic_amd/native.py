@@ -554,6 +554,8 @@ _SIGNATURES = {
                                              C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_int, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p]),
     'asac_discrete_return': (C.c_int, [C.POINTER(VtraceArgs), C.POINTER(DiscreteReturn), C.c_void_p]),
+    'asac_option_discrete_return': (C.c_int, [C.POINTER(VtraceArgs), C.POINTER(DiscreteReturn), C.c_void_p, C.c_int64,
+                                              C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
     'asac_discrete_q_loss_grad': (C.c_int, [C.POINTER(Branches), C.POINTER(Members), C.c_void_p, C.c_int64, C.c_void_p,
                                             C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'asac_discrete_policy_loss_grad': (C.c_int, [C.POINTER(Branches), C.c_void_p, C.c_int64, C.POINTER(Members), C.c_void_p,
@@ -2877,12 +2879,7 @@ def _discrete_rows(t, D, name):
     return t.stride(0)
 
 
-@_profiled
-def discrete_return(args: VtraceArgs, br: Branches, q_target, logits, action=None, q_online=None):
-    """`args` (`_vtrace_args` + subset_n / subset_next / E_sample / log_alpha, mu_prob and its strides under importance
-    sampling, td_error_out with `q_online`) -> y_out (and the TD error): one launch.  q_target: the target members' head
-    outputs [B, n+1, D]; logits [B, n+1, D]; action: the stored window [B, >= n, >= D]; q_online: the online members'
-    head outputs [B, D]."""
+def _discrete_return_job(args: VtraceArgs, br: Branches, q_target, logits, action, q_online) -> DiscreteReturn:
     D, B, n = br.D, args.B, args.n
     job = DiscreteReturn()
     job.branches = br
@@ -2898,7 +2895,36 @@ def discrete_return(args: VtraceArgs, br: Branches, q_target, logits, action=Non
     if q_online is not None:
         job.q_online = members(list(q_online), D)
         assert all(t.shape == (B, D) for t in q_online)
+    return job
+
+
+@_profiled
+def discrete_return(args: VtraceArgs, br: Branches, q_target, logits, action=None, q_online=None):
+    """`args` (`_vtrace_args` + subset_n / subset_next / E_sample / log_alpha, mu_prob and its strides under importance
+    sampling, td_error_out with `q_online`) -> y_out (and the TD error): one launch.  q_target: the target members' head
+    outputs [B, n+1, D]; logits [B, n+1, D]; action: the stored window [B, >= n, >= D]; q_online: the online members'
+    head outputs [B, D]."""
+    job = _discrete_return_job(args, br, q_target, logits, action, q_online)
     _check(load().asac_discrete_return(C.byref(args), C.byref(job), _stream()), 'asac_discrete_return')
+
+
+@_profiled
+def option_discrete_return(args: VtraceArgs, br: Branches, q_target, logits, beta, v_options, action=None, q_online=None):
+    """`discrete_return` with the option's arithmetic (csrc/discrete.hip, second instantiation): the minimum over each
+    subset instead of the mean, and the termination mix on the next positions' entries, (1 - beta) * (min Q - alpha
+    log p) + beta * mean_o v_options.  beta [B, n] and v_options [B, n, O] float32 views (any strides); everything else
+    as for `discrete_return`."""
+    job = _discrete_return_job(args, br, q_target, logits, action, q_online)
+    if beta is not None:
+        assert beta.is_cuda and beta.dtype == torch.float32 and beta.shape == (args.B, args.n)
+    if v_options is not None:
+        assert v_options.is_cuda and v_options.dtype == torch.float32 and v_options.dim() == 3
+        assert v_options.shape[:2] == (args.B, args.n)
+    bs = (beta.stride(0), beta.stride(1)) if beta is not None else (0, 0)
+    vs = tuple(v_options.stride()) if v_options is not None else (0, 0, 0)
+    O = v_options.shape[2] if v_options is not None else 0
+    _check(load().asac_option_discrete_return(C.byref(args), C.byref(job), _p(beta), bs[0], bs[1], _p(v_options), vs[0],
+                                              vs[1], vs[2], O, _stream()), 'asac_option_discrete_return')
 
 
 @_profiled

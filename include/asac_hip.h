@@ -1627,6 +1627,26 @@ typedef struct {
 } asac_discrete_return_t;
 int asac_discrete_return(const asac_vtrace_args_t* args_host, const asac_discrete_return_t* job_host, void* stream);
 
+/* The return target of OptionBase._get_y's policy-based discrete branch (oc/option_base.py:287, 333-373 + sac_base.py
+ * _v_trace 1244-1295) in ONE launch (with q_online: the option's _get_td_error too).  asac_discrete_return's launch with
+ * the option's two differences, per window position u in [0, n], c_j = alpha cl(p_j):
+ *   Qn_j = min over subset_n of q_target[e][b, u, j],  Qx_j = min over subset_next        (the MINIMUM, not the mean)
+ *   Vn[u] = (1/K) sum_j p_j (Qn_j - c_j)                                                               u < n
+ *   Vx[u] = (1/K) sum_j p_j ((1 - beta[b, u-1]) (Qx_j - c_j) + beta[b, u-1] vbar[b, u-1])              u >= 1
+ *   vbar[b, t] = mean_o v_options[b, t, o]: the sum in option order by one lane, divided by num_options (the bits of
+ *   asac_option_return's and asac_termination_loss_grad's)
+ * Step t takes Vn[t] and Vx[t+1]; ratios, step arithmetic, row scan and the TD error are asac_discrete_return's: with
+ * beta == 0 and E_sample == 1 the two launches give the same y and TD error.  `args` and `job` as for
+ * asac_discrete_return; beta [B, n] and v_options [B, n, num_options] with their strides in floats.  No float atomics:
+ * equal inputs give equal bits.  Inputs are finite.
+ * n <= ASAC_DISCRETE_MAX_STEPS, num_options <= ASAC_OPTION_MAX_OPTIONS, any B; B == 0 launches nothing.  Bad arguments
+ * (asac_discrete_return's, a null beta or v_options, num_options out of range) return hipErrorInvalidValue without a
+ * launch. */
+int asac_option_discrete_return(const asac_vtrace_args_t* args_host, const asac_discrete_return_t* job_host,
+                                const float* beta, int64_t beta_stride_b, int64_t beta_stride_t,
+                                const float* v_options, int64_t v_stride_b, int64_t v_stride_t, int64_t v_stride_o,
+                                int num_options, void* stream);
+
 /* Q loss of the discrete heads and its gradient (sac_base.py:1533-1538, 1563-1568):
  *   qs[e][b] = (1/K) sum_j a[b][j] q_e[b][j];   loss_out[e] = mean_b w_b (qs - y_b)^2   (w may be NULL)
  *   grad_q[e][b][j] = 2 w_b (qs - y_b) a[b][j] / (K B)      one contiguous [E, B, D] buffer

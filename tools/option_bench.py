@@ -8,6 +8,13 @@ on a continuous action space with the stock networks, two ways in one process, s
 
     python tools/option_bench.py [--sequences 300] [--batch 256] [--n-step 4] [--options 3]
 
+With `--discrete 3,2` (branch sizes) the option is pure-discrete with a policy, on tests/plugins/nn_oc_small.py — the shape
+of the reference's option-critic configurations (`--batch 1024 --n-step 5 --options 3`) — and the two ways are this class
+with `hip_config['fused_option_discrete']` on and off: sequences/s and launches per sequence of the whole sequence, and
+the HIP-event time of `compute_rep_q_grads + _get_td_error` alone, three runs each in alternating order.
+`on_faster_in_every_run` says whether every on-run of that pair was faster than every off-run (the rule the switch's
+default follows).
+
 Every timed window ends in a device synchronise.  Launches per sequence are counted with torch's profiler over three
 sequences outside the timing.  No ratio is promised: the numbers are what this run measures."""
 import argparse
@@ -139,6 +146,87 @@ def torch_sequence(opt, d):
     return run
 
 
+def make_discrete(batch, n_step, sizes, fused):
+    import asac_amd  # noqa: F401
+    from algorithm.oc import OptionBase
+    from tests import parity_utils as pu
+    torch.manual_seed(0)
+    return OptionBase(0, 'option_0', False, False, ['vector'], [(6,)], list(sizes), 0, None, pu.plugin('nn_oc_small'),
+                      device='cuda:0', batch_size=batch, n_step=n_step, summary_path=None, write_summary_per_step=1e9,
+                      hip_config={'fused_option_discrete': fused})
+
+
+def discrete_inputs(B, n, O, sizes):
+    d = inputs(B, n, O, A=sum(sizes))
+    rng = np.random.default_rng(B + n + 1)
+    onehot = np.concatenate([np.eye(s, dtype=np.float32)[rng.integers(0, s, (B, n))] for s in sizes], -1)
+    d['n_actions'] = torch.from_numpy(onehot).cuda()
+    return d
+
+
+def discrete_sequence(opt, d):
+    def run():
+        obs = [d['nx_obs']]
+        d_y, _ = opt.compute_rep_q_grads(d['v_next'], None, d['n_last'], d['n_pad'], obs, obs, d['nx_states'], d['nx_states'],
+                                         d['n_actions'], None, d['n_rewards'], d['n_dones'], d['n_mu'], d['hidden'])
+        opt.train_rep_q()
+        opt.train_policy_alpha(d['n_pad'], [d['nx_obs'][:, :-1]], d['nx_states'], d['n_actions'], d['n_mu'])
+        opt.compute_termination_grads(0.05, [d['nx_obs'][:, 0]], d['nx_states'][:, 0], d_y, d['v'], d['done'], None)
+        opt.train_termination()
+        return opt._get_td_error(d['v_next'], d['n_last'], d['n_pad'], obs, obs, d['nx_states'][:, 0], d['nx_states'],
+                                 d['n_actions'], d['n_rewards'], d['n_dones'], d['n_mu'])
+    return run
+
+
+def discrete_pair(opt, d):
+    """`compute_rep_q_grads` and `_get_td_error` alone: the two calls the switch changes"""
+    def run():
+        obs = [d['nx_obs']]
+        opt.compute_rep_q_grads(d['v_next'], None, d['n_last'], d['n_pad'], obs, obs, d['nx_states'], d['nx_states'],
+                                d['n_actions'], None, d['n_rewards'], d['n_dones'], d['n_mu'], d['hidden'])
+        return opt._get_td_error(d['v_next'], d['n_last'], d['n_pad'], obs, obs, d['nx_states'][:, 0], d['nx_states'],
+                                 d['n_actions'], d['n_rewards'], d['n_dones'], d['n_mu'])
+    return run
+
+
+def event_us(fn, reps):
+    """HIP-event time of one call of `fn`, microseconds, over `reps` back-to-back calls"""
+    for _ in range(10):
+        fn()
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    start.record()
+    for _ in range(reps):
+        fn()
+    stop.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(stop) * 1e3 / reps
+
+
+def discrete_main(args):
+    sizes = tuple(int(x) for x in args.discrete.split(','))
+    d = discrete_inputs(args.batch, args.n_step, args.options, sizes)
+    row = {'discrete': list(sizes), 'batch': args.batch, 'n_step': args.n_step, 'options': args.options}
+    rates, pair = {'on': [], 'off': []}, {'on': [], 'off': []}
+    for rep in range(3):        # alternating order: on/off, off/on, on/off
+        for name in (('on', 'off') if rep % 2 == 0 else ('off', 'on')):
+            opt = make_discrete(args.batch, args.n_step, sizes, name == 'on')
+            fn = discrete_sequence(opt, d)
+            rates[name].append(round(timed(fn, args.sequences), 1))
+            pair[name].append(round(event_us(discrete_pair(opt, d), args.sequences), 1))
+            if rep == 0:
+                row[f'{name}_launches'] = round(count_launches(fn), 1)
+                row[f'{name}_pair_launches'] = round(count_launches(discrete_pair(opt, d)), 1)
+            opt.close()
+    for name in ('on', 'off'):
+        row[f'{name}_sequences_per_s'] = sorted(rates[name])[1]
+        row[f'{name}_runs'] = rates[name]
+        row[f'{name}_rep_q_plus_td_us'] = sorted(pair[name])[1]
+        row[f'{name}_rep_q_plus_td_us_runs'] = pair[name]
+    row['on_faster_in_every_run'] = max(pair['on']) < min(pair['off'])
+    print(json.dumps(row), flush=True)
+
+
 def count_launches(fn):
     from torch.profiler import ProfilerActivity, profile
     torch.cuda.synchronize()
@@ -166,8 +254,11 @@ def main():
     ap.add_argument('--batch', type=int, default=256)
     ap.add_argument('--n-step', type=int, default=4)
     ap.add_argument('--options', type=int, default=3)
+    ap.add_argument('--discrete', default=None, help='branch sizes, e.g. 3,2: a pure-discrete option, switch on against off')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'needs the GPU: nothing is measured without one'
+    if args.discrete:
+        return discrete_main(args)
     d = inputs(args.batch, args.n_step, args.options)
     row = {'batch': args.batch, 'n_step': args.n_step, 'options': args.options}
     # each way is timed three times, the two ways interleaved (a drift of the box's clocks hits both); the median is reported

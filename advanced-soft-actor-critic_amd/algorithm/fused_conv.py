@@ -76,7 +76,9 @@ class DeferredConvBackward:
         return True
 
     def flush(self) -> dict:
-        """-> {walk: {id(param): gradient tensor}} (gradients of a parameter reached through several forward passes summed)"""
+        """-> {walk: {id(param): gradient tensor}} (gradients of a parameter reached through several forward passes summed).
+        Inside an active `DeferredPartialSums` the gradients are views of buffers its `flush()` has yet to write: they hold
+        their values — the sums over forward passes included — once that `flush()` has run; nothing may read them before."""
         out = {}
         for ctx, by_walk in self._pending.values():
             desc = ctx.desc
@@ -102,7 +104,12 @@ class DeferredConvBackward:
                         cnt = p_.numel()
                         if p_.requires_grad:
                             piece = g[row, off:off + cnt].view(p_.shape)
-                            grads[id(p_)] = piece if id(p_) not in grads else grads[id(p_)] + piece
+                            if id(p_) not in grads:
+                                grads[id(p_)] = piece
+                            elif later is None:
+                                grads[id(p_)] = grads[id(p_)] + piece
+                            else:      # (neither piece is written before `later.flush()`: the sum is formed there, in place)
+                                later.add_after(grads[id(p_)], piece)
                         off += cnt
         self._pending = {}
         return out

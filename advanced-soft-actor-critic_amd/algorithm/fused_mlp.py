@@ -339,6 +339,7 @@ class DeferredPartialSums:
 
     def __init__(self):
         self.jobs, self.grads, self.walk, self._outer = [], {}, 0, None
+        self.sums_after = []
 
     @classmethod
     def active(cls):
@@ -355,6 +356,11 @@ class DeferredPartialSums:
     def add(self, partial, slabs, slices, slab_stride, n, out, accumulate=False):
         self.jobs.append((partial, slabs, slices, slab_stride, n, out, bool(accumulate)))
 
+    def add_after(self, into, piece):
+        """`into += piece` once the sums have run (both views of buffers `add`ed above, `into` the caller's own): what a
+        caller that hands its gradients out itself owes a parameter it reached twice (fused_conv.DeferredConvBackward)"""
+        self.sums_after.append((into, piece))
+
     def record(self, params, grads):
         """the gradients (views of buffers `add`ed above) this walk owes `params`"""
         mine = self.grads.setdefault(self.walk, {})
@@ -362,11 +368,33 @@ class DeferredPartialSums:
             if g is not None:
                 mine.setdefault(id(p), []).append(g)
 
+    @staticmethod
+    def _launches(jobs):
+        """`jobs` in the order queued, cut into launches: a launch ends where it holds sixteen jobs or where the next job's
+        output floats [out, out + n) overlap those of a job it already holds.  The jobs of one launch run on workgroups of
+        their own in no order, so two of them on one output (a module reached twice in a direct-mode backward: both ADD into
+        its span of the flat gradient buffer) would race; launch after launch they are stream-ordered, as the reductions they
+        stand for were.  (`n` floats, not `out.numel()`: an ensemble member's `out` is a view that runs on over the next's.)"""
+        launches, spans = [], []
+        for job in jobs:
+            lo = job[5].data_ptr()
+            hi = lo + 4 * job[4]
+            if (not launches or len(launches[-1]) == native.SUM_PARTIALS_MAX_JOBS
+                    or any(lo < b and a < hi for a, b in spans)):
+                launches.append([])
+                spans = []
+            launches[-1].append(job)
+            spans.append((lo, hi))
+        return launches
+
     def flush(self):
-        """-> {walk: {id(parameter): gradient}}; the sums run here (one launch per sixteen recorded backwards)"""
+        """-> {walk: {id(parameter): gradient}}; the sums run here (one launch per sixteen recorded backwards, see `_launches`)"""
         jobs, self.jobs = self.jobs, []
-        for k in range(0, len(jobs), native.SUM_PARTIALS_MAX_JOBS):
-            native.sum_partials_multi(jobs[k:k + native.SUM_PARTIALS_MAX_JOBS])
+        for launch in self._launches(jobs):
+            native.sum_partials_multi(launch)
+        after, self.sums_after = self.sums_after, []
+        for into, piece in after:
+            into.add_(piece)
         taken, self.grads = self.grads, {}
         # (a parameter two recorded nodes of one walk share: their gradients added, as autograd would have)
         return {walk: {pid: gl[0] if len(gl) == 1 else sum(gl[1:], gl[0]) for pid, gl in mine.items()}

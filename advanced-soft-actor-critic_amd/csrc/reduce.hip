@@ -66,6 +66,10 @@ int asac_sum_partials_multi(int n_jobs, const asac_partial_sum_t* jobs_host, voi
         const asac_partial_sum_t& j = jobs_host[k];
         if (!j.partial || !j.out || j.slabs < 1 || j.n < 1 || (j.slices != 1 && j.slices != kSumSlices) || j.slab_stride < j.n)
             return bad_arg("asac_sum_partials_multi: job");
+        // (the jobs' workgroups run in no order: two jobs on one output would race — the caller puts them in two launches)
+        for (int i = 0; i < k; ++i)
+            if (j.out < jobs_host[i].out + jobs_host[i].n && jobs_host[i].out < j.out + j.n)
+                return bad_arg("asac_sum_partials_multi: one output twice");
         J.job[k] = j;
         J.first_block[k] = blocks;
         blocks += (int)((j.n + 63) / 64);

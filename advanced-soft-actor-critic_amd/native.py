@@ -1524,7 +1524,8 @@ def attention_proj_partials(workspace, E: int, output_block: bool):
 def sum_partials_multi(jobs):
     """jobs: [(partial, slabs, slices, slab_stride, n, out, accumulate), ...] (at most SUM_PARTIALS_MAX_JOBS) — out[:n]
     (+)= the slabs of `partial` in the fixed order of the launch each job stands for (slices 16: the sliced reductions of
-    `mlp_backward` with >= 64 tiles and of `attention_proj_backward`; 1: slab order), as ONE launch"""
+    `mlp_backward` with >= 64 tiles and of `attention_proj_backward`; 1: slab order), as ONE launch.  The jobs run side by
+    side: no two of them may name overlapping `out[:n]` (RuntimeError, "one output twice")"""
     assert 1 <= len(jobs) <= SUM_PARTIALS_MAX_JOBS
     arr = (PartialSum * len(jobs))()
     for k, (partial, slabs, slices, slab_stride, n, out, accumulate) in enumerate(jobs):

@@ -1461,7 +1461,8 @@ int asac_rows_wide_backward_params(const float* dpre, const float* x, int64_t x_
  *   asac_linear_tanh_backward*    (accumulate == ASAC_LINEAR_SUM_DEFER)  [blocks = ceil(N / 64)][n = O K + O]; 16 slices
  *   asac_conv2_backward(_windows / _multi)  (accumulate == ASAC_CONV_SUM_DEFER)  [blocks][n], n = n_cot x the packed parameter
  *                                 count, blocks = asac_conv2_backward_slabs(desc, N, n_cot); 16 slices
- * jobs_host: a HOST array. */
+ * jobs_host: a HOST array.  The jobs run side by side in no order: two jobs of one launch whose [out, out + n) overlap are
+ * refused ("one output twice") — such sums go into consecutive launches. */
 #define ASAC_SUM_PARTIALS_MAX_JOBS 16
 #define ASAC_ATTN_SUM_DEFER 2
 #define ASAC_CONV_SUM_DEFER 2

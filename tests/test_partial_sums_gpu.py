@@ -50,6 +50,27 @@ def test_sum_partials_multi_is_the_single_reductions_bit_for_bit():
         assert torch.equal(out, w)
 
 
+def test_sum_partials_multi_refuses_one_output_twice():
+    """the jobs of a launch run side by side: two that write the same floats — equal outputs, or ranges [out, out + n) that
+    only partly overlap, adding or overwriting — are refused before anything is launched; ranges that merely touch are not"""
+    import asac_amd  # noqa: F401
+    from asac_amd import native
+    partial = torch.randn(3 * 100, device='cuda')
+    out = torch.zeros(100, device='cuda')
+    for acc in (True, False):
+        with pytest.raises(RuntimeError, match='one output twice'):
+            native.sum_partials_multi([(partial, 3, 1, 100, 100, out, acc), (partial, 3, 1, 100, 100, out, True)])
+        with pytest.raises(RuntimeError, match='one output twice'):
+            native.sum_partials_multi([(partial, 3, 1, 100, 60, out, acc), (partial, 3, 1, 100, 41, out[59:], True)])
+        with pytest.raises(RuntimeError, match='one output twice'):      # (a view at an offset, inside the other's range)
+            native.sum_partials_multi([(partial, 3, 1, 100, 7, out[20:], True), (partial, 3, 1, 100, 100, out, acc)])
+    assert not out.any()
+    native.sum_partials_multi([(partial, 3, 1, 100, 60, out, True), (partial, 3, 1, 100, 40, out[60:], False)])
+    rows = partial.view(3, 100)
+    s = rows[0] + rows[1] + rows[2]
+    assert torch.equal(out[:60], s[:60]) and torch.equal(out[60:], s[:40])
+
+
 @pytest.mark.parametrize('N', [4608, 300])          # 144 / 10 row tiles: the sliced and the sequential reduction
 def test_deferred_sums_of_dense_stack_and_attention_are_the_undeferred_gradients(N):
     """three `autograd.grad` walks through a fused dense stack and an attention block with their second launches deferred:

@@ -14,7 +14,7 @@ from torch import nn
 
 from asac_amd import native
 
-from .fused_mlp import _flat_alias, direct_enabled
+from .param_grads import DeferredPartialSums, deliver_packed, direct_enabled, flat_grad_alias
 
 __all__ = ['fused_conv_stack', 'conv_stack_desc', 'DeferredConvBackward', 'fused_conv1d_stack', 'conv1d_stack_desc']
 
@@ -85,7 +85,6 @@ class DeferredConvBackward:
             x, z1, z2, w2 = ctx.saved_tensors
             n_frames = x.shape[0] * x.shape[1] if ctx.windows else x.shape[0]
             walks = sorted(by_walk)
-            from .fused_mlp import DeferredPartialSums
             later = DeferredPartialSums.active()      # (the launch's own second launch — the slab sums — may wait as well)
             most = native.conv2_backward_multi_max(desc) if later is not None else native.CONV2_MAX_COTANGENTS
             for lo in range(0, len(walks), most):
@@ -173,34 +172,12 @@ class _ConvStackFn(torch.autograd.Function):
 
 
 def _packed_param_grads(params, n, ws, slabs, launch):
-    """The tail both stacks' backward share.  `launch(out, mode)` runs the backward kernel whose slabs of `n` packed floats
-    land in `ws` and whose slab sum goes to `out` (mode False: written, True: added, `native.SUM_DEFER`: left to the walk's
-    `DeferredPartialSums`, `slabs()` slabs).  -> the gradients autograd receives, one per parameter (None where the kernel
-    already added them, or where `DeferredPartialSums.flush()` delivers them)"""
+    """The tail both stacks' backward share (`param_grads.deliver_packed`).  `launch(out, mode)` runs the backward kernel
+    whose slabs of `n` packed floats land in `ws` (`slabs()` of them) and whose slab sum goes to `out`"""
     # the gradients as one packed block: inside the learner they are consecutive views of the flat
     # gradient buffer, and the reduction kernel adds into them directly (no AccumulateGrad launches)
-    flat = None
-    if DIRECT_PARAM_GRADS and direct_enabled() and all(p.requires_grad and p.grad is not None for p in params):
-        flat = _flat_alias([p.grad for p in params])
-    from .fused_mlp import DeferredPartialSums
-    later = DeferredPartialSums.active()          # (the slab sums as one launch with the walk's other second launches)
-    if flat is not None:
-        launch(flat, native.SUM_DEFER if later is not None else True)
-        if later is not None:
-            later.add(ws, slabs(), 16, n, n, flat, accumulate=True)
-        return [None] * len(params)
-    g = torch.empty(n, dtype=ws.dtype, device=ws.device)
-    launch(g, native.SUM_DEFER if later is not None else False)
-    grads, off = [], 0
-    for p in params:
-        k = p.numel()
-        grads.append(g[off:off + k].view(p.shape) if p.requires_grad else None)
-        off += k
-    if later is not None:           # (the gradients reach the caller through `later.flush()`)
-        later.add(ws, slabs(), 16, n, n, g)
-        later.record(params, grads)
-        grads = [None] * len(params)
-    return grads
+    flat = flat_grad_alias(params) if DIRECT_PARAM_GRADS and direct_enabled() else None
+    return deliver_packed(params, flat, n, launch, lambda: (ws, slabs(), 16, n, n))
 
 
 def _out_width(desc):

@@ -7,14 +7,14 @@ ConvTranspose2d(32, 32, 4, 2) / (32, 16, 8, 4) / (16, 3, 3, 1), each followed by
 loss (`sac_base.py:1798-1839`) then costs three launches forward and four backward instead of MIOpen's transposed
 convolutions, their layout transposes and one elementwise launch per bias / activation.  Plain autograd semantics: the
 Function returns the frames, its backward takes their gradient and returns the gradients of the state and of the ten
-parameters (or adds the latter straight into consecutive `.grad` views inside `fused_mlp.direct_param_grads()`).
+parameters (or adds the latter straight into consecutive `.grad` views inside `param_grads.direct_param_grads()`).
 """
 import torch
 from torch import nn
 
 from asac_amd import native
 
-from .fused_mlp import direct_enabled, direct_skips
+from .param_grads import direct_enabled, direct_skips
 
 __all__ = ['decoder_params', 'fused_obs_decoder']
 

@@ -15,12 +15,12 @@ import torch
 
 from asac_amd import native
 
-from .fused_mlp import direct_enabled
+from .param_grads import direct_enabled
 
 __all__ = ['fused_gru', 'fused_gru_supported', 'TwinPass']
 
 # accumulate parameter gradients into existing dense `.grad` tensors from the kernel (see above), inside the
-# learner's `fused_mlp.direct_param_grads()` regions
+# learner's `param_grads.direct_param_grads()` regions
 DIRECT_PARAM_GRADS = True
 
 

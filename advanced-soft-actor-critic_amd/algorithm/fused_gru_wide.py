@@ -13,6 +13,8 @@ import torch
 
 from asac_amd import native
 
+from .param_grads import direct_enabled, direct_skips, queue_param_grads
+
 __all__ = ['fused_gru_wide', 'fused_gru_wide_supported']
 
 ENABLED = os.environ.get('ASAC_GRU_WIDE', '1') != '0'      # (0: keep the module path — A/B runs)
@@ -135,8 +137,6 @@ class _GruWideFn(torch.autograd.Function):
             if native.xty_supported(B * L, 3 * H, max(inp2.shape[1], H)):
                 # weight and bias gradients as products over the B * L rows on MFMA, both in one launch pair (`asac_xty_multi`);
                 # under the learner's direct mode added straight into the `.grad` views (no accumulation launches)
-                from .fused_mlp import direct_enabled, direct_skips
-                from .fused_rows_linear import queue_param_grads
                 params = weights[4 * l:4 * l + 4]
                 direct = (direct_enabled() and not direct_skips(*params)
                           and all(p_.requires_grad and p_.grad is not None and p_.grad.is_contiguous() for p_ in params))

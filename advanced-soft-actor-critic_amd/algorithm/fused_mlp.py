@@ -5,8 +5,6 @@ pass of the network — or of all E ensemble members at once — is ONE `asac_ml
 Anything else (user-defined models, discrete heads, other activations, widths > 64) keeps the
 generic module path; `describe_*` returns None and the caller falls back.
 """
-import contextlib
-import os
 import weakref
 
 import torch
@@ -15,52 +13,14 @@ from torch import nn
 from asac_amd import native
 
 from .nn_models.layers.linear_layers import LinearLayers, ResBlock
+from .param_grads import (SUM_PARTIALS_LATER, DeferredPartialSums, direct_enabled, direct_param_grads,  # noqa: F401  (re-exports)
+                          direct_skips, flat_alias)
 
 __all__ = ['StockMLP', 'describe_q', 'describe_policy', 'describe_dense', 'fused_dense', 'gauss_head']
 
 MAX_WIDTH, MAX_HEAD = 64, 16
 MAX_INPUT = 128         # a first layer may be up to 128 inputs wide when the stack has <= 3 blocks (two K halves)
 FUSED_DENSE = True      # `LinearLayers` stacks that opt in (`fuse = True`: the conv encoders' heads) run fused
-
-# How the fused autograd Functions (this module, fused_conv, fused_gru, fused_linear, layers.seq_layers) deliver
-# PARAMETER gradients.  Default: they are returned to autograd like any op's, so `autograd.grad`, `backward(inputs=
-# ...)` and gradient gating (`sac_aux.calculate_adaptive_weights`) see exactly what PyTorch semantics promise.
-# Inside `direct_param_grads()` the backward kernels instead ADD them straight into the parameters' `.grad` views of
-# the learner's flat gradient buffer (no per-parameter AccumulateGrad launches) and hand autograd nothing: only valid
-# around a backward pass that is meant to accumulate into every parameter it reaches — the learner wraps exactly
-# those (the Q loss, the policy objective, the curiosity loss).  A plain global: the autograd engine runs backward
-# nodes on its own device thread while the caller blocks inside the `with`.
-# `only`: the backward is restricted to these tensors (`backward(inputs=...)`): `ctx.needs_input_grad` is fixed at
-# forward time and does not know about that restriction, so a direct-mode backward consults `direct_skips` and leaves
-# the parameters outside the set alone (no launch, no accumulation) — what autograd does with their gradients anyway.
-_direct_depth = 0
-_direct_only = []
-
-
-@contextlib.contextmanager
-def direct_param_grads(only=None):
-    global _direct_depth
-    if _direct_depth == 0:
-        # (a backward pass that raised may have left queued products and an armed end-of-backward callback behind)
-        from .fused_rows_linear import reset_queue
-        reset_queue()
-    _direct_depth += 1
-    _direct_only.append(None if only is None else {id(t) for t in only})
-    try:
-        yield
-    finally:
-        _direct_only.pop()
-        _direct_depth -= 1
-
-
-def direct_enabled() -> bool:
-    return _direct_depth > 0
-
-
-def direct_skips(*params) -> bool:
-    """inside a restricted direct-mode backward: none of `params` is among the tensors the backward may reach"""
-    only = _direct_only[-1] if _direct_only else None
-    return only is not None and not any(id(p) in only for p in params)
 
 
 def _blocks_of(ll: LinearLayers):
@@ -218,20 +178,6 @@ def rnd_stack_tensors(ll) -> tuple:
     return b1.linear.weight, b1.linear.bias, b2.linear.weight, b2.linear.bias
 
 
-def _flat_alias(tensors):
-    """-> a 1-D tensor aliasing `tensors` if they sit back to back, in order, in one storage (the learner's flat
-    parameter / gradient buffers), else None"""
-    t0 = tensors[0]
-    base, pos = t0.untyped_storage().data_ptr(), t0.storage_offset()
-    first = pos
-    for t in tensors:
-        if (t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
-                or t.untyped_storage().data_ptr() != base or t.storage_offset() != pos):
-            return None
-        pos += t.numel()
-    return torch.empty(0, dtype=torch.float32, device=t0.device).set_(t0.untyped_storage(), first, (pos - first,))
-
-
 _DENSE_LAUNCHERS = weakref.WeakKeyDictionary()
 
 
@@ -263,8 +209,8 @@ def fused_dense(ll, x, skip: int = 0):
         if len(cache) > 8:
             cache.clear()
         desc = describe_dense(ll, skip)
-        flat = _flat_alias([p.data for p in params]) if desc is not None else None
-        gflat = _flat_alias([p.grad for p in params]) if (flat is not None and train) else None
+        flat = flat_alias([p.data for p in params]) if desc is not None else None
+        gflat = flat_alias([p.grad for p in params]) if (flat is not None and train) else None
         ok = flat is not None and (gflat is not None or not train) and flat.data_ptr() % 16 == 0
         cache[key] = StockMLP(desc, flat, gflat, 0, flat.numel(), 1, x.device, params) if ok else None
     mlp = cache[key]
@@ -325,95 +271,24 @@ def describe_policy(pi) -> 'native.MlpDesc | None':
     return desc
 
 
-class DeferredPartialSums:
-    """While active, the backward launches below (and the attention blocks', seq_layers._AttnProjFn) that would hand
-    parameter gradients BACK to autograd — `autograd.grad` walks, not the learner's direct mode — return None for them and
-    leave the second launch of each (the per-workgroup partials summed in workgroup order) to `flush()`, which runs up to
-    sixteen of them as ONE launch (`native.sum_partials_multi`; per job the order, hence the bits, of the launch it stands
-    for) and returns {walk: {id(parameter): gradient}} for the caller to put where autograd left None — like
-    fused_conv.DeferredConvBackward, and for the same walks: those of `calculate_adaptive_weights` / `_train_rpm` (reference
-    sac_base.py:1607-1631, 1798-1839), which only collect their parameter gradients.  `walk`: set by the caller in front of
-    each `autograd.grad`.  A parameter other nodes of the graph use as well still gets those nodes' contributions from
-    autograd; the caller adds."""
-    _active = None
-
-    def __init__(self):
-        self.jobs, self.grads, self.walk, self._outer = [], {}, 0, None
-        self.sums_after = []
-
-    @classmethod
-    def active(cls):
-        return cls._active if SUM_PARTIALS_LATER else None
-
-    def __enter__(self):
-        self._outer, DeferredPartialSums._active = DeferredPartialSums._active, self
-        return self
-
-    def __exit__(self, exc_type, exc, tb):
-        DeferredPartialSums._active = self._outer
-        return False
-
-    def add(self, partial, slabs, slices, slab_stride, n, out, accumulate=False):
-        self.jobs.append((partial, slabs, slices, slab_stride, n, out, bool(accumulate)))
-
-    def add_after(self, into, piece):
-        """`into += piece` once the sums have run (both views of buffers `add`ed above, `into` the caller's own): what a
-        caller that hands its gradients out itself owes a parameter it reached twice (fused_conv.DeferredConvBackward)"""
-        self.sums_after.append((into, piece))
-
-    def record(self, params, grads):
-        """the gradients (views of buffers `add`ed above) this walk owes `params`"""
-        mine = self.grads.setdefault(self.walk, {})
-        for p, g in zip(params, grads):
-            if g is not None:
-                mine.setdefault(id(p), []).append(g)
-
-    @staticmethod
-    def _launches(jobs):
-        """`jobs` in the order queued, cut into launches: a launch ends where it holds sixteen jobs or where the next job's
-        output floats [out, out + n) overlap those of a job it already holds.  The jobs of one launch run on workgroups of
-        their own in no order, so two of them on one output (a module reached twice in a direct-mode backward: both ADD into
-        its span of the flat gradient buffer) would race; launch after launch they are stream-ordered, as the reductions they
-        stand for were.  (`n` floats, not `out.numel()`: an ensemble member's `out` is a view that runs on over the next's.)"""
-        launches, spans = [], []
-        for job in jobs:
-            lo = job[5].data_ptr()
-            hi = lo + 4 * job[4]
-            if (not launches or len(launches[-1]) == native.SUM_PARTIALS_MAX_JOBS
-                    or any(lo < b and a < hi for a, b in spans)):
-                launches.append([])
-                spans = []
-            launches[-1].append(job)
-            spans.append((lo, hi))
-        return launches
-
-    def flush(self):
-        """-> {walk: {id(parameter): gradient}}; the sums run here (one launch per sixteen recorded backwards, see `_launches`)"""
-        jobs, self.jobs = self.jobs, []
-        for launch in self._launches(jobs):
-            native.sum_partials_multi(launch)
-        after, self.sums_after = self.sums_after, []
-        for into, piece in after:
-            into.add_(piece)
-        taken, self.grads = self.grads, {}
-        # (a parameter two recorded nodes of one walk share: their gradients added, as autograd would have)
-        return {walk: {pid: gl[0] if len(gl) == 1 else sum(gl[1:], gl[0]) for pid, gl in mine.items()}
-                for walk, mine in taken.items()}
-
-
-SUM_PARTIALS_LATER = os.environ.get('ASAC_SUM_PARTIALS_LATER', '1') != '0'    # (A/B switch)
-
-
-def _param_grad_target(mlp, param_grads, n_params):
-    """-> (kernel target | None, gradients to return to autograd): the flat `.grad` views in direct mode, else a
-    scratch buffer with the parameters' layout, returned as one view per parameter"""
-    if not param_grads or direct_enabled() or n_params == 0:
-        return None, [None] * n_params
-    scratch = torch.empty_like(mlp.grad_params)      # (every parameter's span is overwritten: MLP_REDUCE_OVERWRITE)
-    base = mlp.params.storage_offset()
-    views = [scratch[p.data.storage_offset() - base:p.data.storage_offset() - base + p.numel()].view(p.shape)
-             for p in mlp.param_tensors]
-    return scratch, views
+def _backward_delivering(ctx, x0, x1, grad_out, need0, need1, **kw):
+    """`ctx.mlp._launch_backward` with the parameter gradients delivered -> (grad_x0, grad_x1, the gradients autograd
+    receives): in direct mode the launch adds them into the flat `.grad` views; else it overwrites a scratch buffer with
+    the parameters' layout, returned as one view per parameter — or, inside `DeferredPartialSums`, through its `flush()`"""
+    mlp = ctx.mlp
+    target, pg = None, [None] * ctx.n_params
+    if ctx.param_grads and not direct_enabled() and ctx.n_params:
+        target = torch.empty_like(mlp.grad_params)      # (every parameter's span is overwritten: MLP_REDUCE_OVERWRITE)
+        base = mlp.params.storage_offset()
+        pg = [target[p.data.storage_offset() - base:p.data.storage_offset() - base + p.numel()].view(p.shape)
+              for p in mlp.param_tensors]
+    later = DeferredPartialSums.active() if ctx.param_grads else None
+    g0, g1 = mlp._launch_backward(x0, x1, grad_out.contiguous(), need0, need1, ctx.param_grads, grad_target=target,
+                                  later=later, **kw)
+    if later is not None and target is not None:       # (the gradients reach the caller through `later.flush()`)
+        later.record(mlp.param_tensors, pg)
+        pg = [None] * ctx.n_params
+    return g0, g1, pg
 
 
 class _MlpFn(torch.autograd.Function):
@@ -432,15 +307,8 @@ class _MlpFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         x0, x1 = ctx.saved_tensors
         x1 = x1 if ctx.has_x1 else None
-        mlp = ctx.mlp
         need0, need1 = ctx.needs_input_grad[1], ctx.has_x1 and ctx.needs_input_grad[2]
-        target, pg = _param_grad_target(mlp, ctx.param_grads, ctx.n_params)
-        later = DeferredPartialSums.active() if ctx.param_grads else None
-        g0, g1 = mlp._launch_backward(x0, x1, grad_out.contiguous(), need0, need1, ctx.param_grads,
-                                      grad_target=target, later=later)
-        if later is not None and target is not None:       # (the gradients reach the caller through `later.flush()`)
-            later.record(mlp.param_tensors, pg)
-            pg = [None] * ctx.n_params
+        g0, g1, pg = _backward_delivering(ctx, x0, x1, grad_out, need0, need1)
         return (None, g0, g1, None, None, *pg)
 
 
@@ -465,13 +333,7 @@ class _MlpSelectFn(torch.autograd.Function):
         x1 = x1 if ctx.has_x1 else None
         mlp, t = ctx.mlp, ctx.t
         need0, need1 = ctx.needs_input_grad[1], ctx.has_x1 and ctx.needs_input_grad[3]
-        target, pg = _param_grad_target(mlp, ctx.param_grads, ctx.n_params)
-        later = DeferredPartialSums.active() if ctx.param_grads else None
-        g0, g1 = mlp._launch_backward(base[:, t], x1, grad_out.contiguous(), need0, need1, ctx.param_grads,
-                                      reduce_members=False, grad_target=target, later=later)
-        if later is not None and target is not None:       # (the gradients reach the caller through `later.flush()`)
-            later.record(mlp.param_tensors, pg)
-            pg = [None] * ctx.n_params
+        g0, g1, pg = _backward_delivering(ctx, base[:, t], x1, grad_out, need0, need1, reduce_members=False)
         g_base = None
         if g0 is not None:
             # (a window gradient that is zero outside position t: the zeros are kept between calls — only the slice is written,

@@ -12,58 +12,12 @@ import os
 
 import torch
 
+from .param_grads import (QUEUE, direct_enabled, direct_skips, flush_param_grads, queue_param_grads,  # noqa: F401  (re-exports)
+                          reset_queue)
+
 ENABLED = os.environ.get('ASAC_ROWS_LINEAR', '1') != '0'      # (0: plain nn.Linear — A/B runs)
 MIN_ROWS = 2048
 WIDE = os.environ.get('ASAC_ROWS_WIDE', '1') != '0'          # (0: the library's GEMMs for wide first layers — A/B runs)
-QUEUE = os.environ.get('ASAC_XTY_QUEUE', '1') != '0'      # (0: one launch pair per product — A/B runs)
-
-
-# Direct mode (the learner's `loss.backward()`: gradients are ADDED into the `.grad` views of the flat buffer, nobody reads them
-# before the optimizer): the products are not launched one by one but queued and issued four at a time as one launch pair
-# (`asac_xty_multi` — the four Linears of an attention block make exactly one), the rest when the backward pass ends.
-_pending = []
-_armed = False
-
-
-def flush_param_grads():
-    from asac_amd import native
-    jobs = list(_pending)
-    del _pending[:]
-    if len(jobs) == 1:
-        native.xty(*jobs[0], accumulate=True)
-    elif jobs:
-        native.xty_multi(jobs, accumulate=True)
-
-
-def reset_queue():
-    """drop what a failed backward pass left behind (called when the learner opens a direct-mode backward)"""
-    global _armed
-    del _pending[:]
-    _armed = False
-
-
-def _end_of_backward():
-    global _armed
-    _armed = False
-    flush_param_grads()
-
-
-def queue_param_grads(g2, x2, w_grad, b_grad):
-    """w_grad += g2^T x2, b_grad += column sums of g2 — some time before this backward pass returns"""
-    global _armed
-    if not QUEUE:
-        from asac_amd import native
-        native.xty(g2, x2, w_grad, b_grad, accumulate=True)
-        return
-    if any(j[2].data_ptr() == w_grad.data_ptr() or (b_grad is not None and j[3] is not None and j[3].data_ptr() == b_grad.data_ptr())
-           for j in _pending):
-        flush_param_grads()      # (a layer applied twice: its two products add to one gradient, one after the other)
-    _pending.append((g2, x2, w_grad, b_grad))
-    if len(_pending) == 4:
-        flush_param_grads()
-    elif not _armed:
-        _armed = True
-        torch.autograd.Variable._execution_engine.queue_callback(_end_of_backward)
 
 
 class _RowsLinearFn(torch.autograd.Function):
@@ -84,7 +38,6 @@ class _RowsLinearFn(torch.autograd.Function):
             g2 = g2.contiguous()
         gx = (g2 @ weight).view(*ctx.lead, weight.shape[1]) if ctx.needs_input_grad[0] else None
         gw = gb = None
-        from algorithm.fused_mlp import direct_enabled, direct_skips
         if (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) and not direct_skips(ctx.weight_param, ctx.bias_param):
             w_grad, b_grad = ctx.weight_param.grad, ctx.bias_param.grad
             if (direct_enabled() and w_grad is not None and b_grad is not None and w_grad.is_contiguous()
@@ -131,7 +84,6 @@ class _AffineGeluFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         from asac_amd import native
-        from algorithm.fused_mlp import direct_enabled, direct_skips
         x2, pre, weight = ctx.saved_tensors
         gpre = torch.ops.aten.gelu_backward(gy.reshape(pre.shape).contiguous(), pre, approximate='none')
         gx = (gpre @ weight.detach()).view(*ctx.lead, weight.shape[1]) if ctx.needs_input_grad[0] else None
@@ -178,7 +130,6 @@ class _WideAffineGeluFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         from asac_amd import native
-        from algorithm.fused_mlp import direct_enabled, direct_skips
         x2, pre, weight = ctx.saved_tensors
         R, K = x2.shape
         g2 = gy.reshape(pre.shape)

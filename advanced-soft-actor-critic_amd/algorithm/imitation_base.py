@@ -24,6 +24,7 @@ import torch
 from asac_amd import native
 
 from .captured_step import CapturedStep
+from .param_grads import learner_backward
 
 
 ENTROPY_COEF = 0.1      # imitation_base.py:58
@@ -246,7 +247,7 @@ class ImitationBase:
 
     def _device_step(self, bk) -> torch.Tensor:
         """Everything one imitation step does on the device, on the bucket's static buffers: no host synchronisation"""
-        from .fused_mlp import DeferredPartialSums, StockMLP, direct_param_grads
+        from .fused_mlp import StockMLP
         from .nn_models.layers.seq_layers import step_mask_cache
         from .utils.enums import SEQ_ENCODER
         sac = self._sac
@@ -270,9 +271,8 @@ class ImitationBase:
                     raise TypeError('ImitationBase needs a policy whose continuous head is a torch.distributions.Normal, '
                                     f'got {type(c_policy).__name__}')
                 loss = bc_loss(loc, scale, bk.action, dsum, bk.t_valid, ENTROPY_COEF)
-            with direct_param_grads(), DeferredPartialSums() as sums_later:
+            with learner_backward():
                 loss.backward(self._unit)
-            sums_later.flush()
         self.opt.step()
         return loss.detach()
 

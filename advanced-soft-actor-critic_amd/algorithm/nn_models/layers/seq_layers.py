@@ -42,6 +42,8 @@ from enum import Enum
 import torch
 from torch import nn
 
+from algorithm.param_grads import deliver_packed, direct_enabled, direct_skips, flat_grad_alias, queue_param_grads
+
 from .linear_layers import LinearLayers
 
 __all__ = ['GRU', 'step_mask_cache', 'POSITIONAL_ENCODING', 'GATE', 'MultiheadAttention', 'GatedResidualLayer', 'GatedOutputLayer',
@@ -303,7 +305,6 @@ class _AttnProjFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_out, g_w, _g_keep):
         from asac_amd import native
-        from algorithm.fused_mlp import _flat_alias, direct_enabled
         xq, xk, weights, keep, *rest = ctx.saved_tensors
         attn_out = rest[0] if rest else None
         params, tail = ctx.params, ctx.tail
@@ -323,32 +324,12 @@ class _AttnProjFn(torch.autograd.Function):
         ws = torch.empty(native.attention_proj_workspace(B, Lq, Lk, E), dtype=xq.dtype, device=xq.device)
         pd = [t.detach().contiguous() for t in params]
         gw = None if g_w is None else g_w.contiguous()
-        flat = None
-        if direct_enabled() and all(p.requires_grad and p.grad is not None for p in params):
-            flat = _flat_alias([p.grad for p in params])
-        from algorithm.fused_mlp import DeferredPartialSums
-        later = DeferredPartialSums.active()
-        if flat is not None:
-            native.attention_proj_backward(xq, xk, pd, weights, g_out, gw, g_xq, g_xk, flat,
-                                           native.SUM_DEFER if later is not None else True, ws, keep, attn_out, ctx.row_zero)
-            if later is not None:
-                slabs, n = native.attention_proj_partials(ws, E, len(params) == 8)
-                later.add(ws, slabs, 16, n, n, flat, accumulate=True)
-            return (g_xq, g_xk, None, None, *([None] * len(params)))
-        g = torch.empty(sum(p.numel() for p in params), dtype=xq.dtype, device=xq.device)
-        native.attention_proj_backward(xq, xk, pd, weights, g_out, gw, g_xq, g_xk, g,
-                                       native.ATTN_SUM_DEFER if later is not None else False, ws, keep, attn_out, ctx.row_zero)
-        if later is not None:       # (the workgroups' partials are summed into g with the other walks', one launch)
-            slabs, n = native.attention_proj_partials(ws, E, len(params) == 8)
-            later.add(ws, slabs, 16, n, n, g)
-        grads, off = [], 0
-        for p_ in params:
-            k = p_.numel()
-            grads.append(g[off:off + k].view(p_.shape) if p_.requires_grad else None)
-            off += k
-        if later is not None:       # (the gradients reach the caller through `later.flush()`)
-            later.record(params, grads)
-            grads = [None] * len(params)
+        slabs, n = native.attention_proj_partials(ws, E, len(params) == 8)
+        grads = deliver_packed(
+            params, flat_grad_alias(params) if direct_enabled() else None, n,
+            lambda out, mode: native.attention_proj_backward(xq, xk, pd, weights, g_out, gw, g_xq, g_xk, out, mode, ws, keep,
+                                                             attn_out, ctx.row_zero),
+            lambda: (ws, slabs, 16, n, n))
         return (g_xq, g_xk, None, None, *grads)
 
 
@@ -357,13 +338,11 @@ def _rows_param_grads(ctx_needs, params, g2, x2, jobs=None):
     (`asac_xty`): added straight into the `.grad` views under the learner's direct mode, else returned.  With a list `jobs` the
     returned product is not launched but appended to it: the caller has several and runs them together (`_run_xty_jobs`)"""
     from asac_amd import native
-    from algorithm.fused_mlp import direct_enabled, direct_skips
     weight, bias = params
     held = [p for p in params if p is not None]
     if not any(ctx_needs) or direct_skips(*held):
         return None, None
     if direct_enabled() and all(p.grad is not None and p.grad.is_contiguous() for p in held):
-        from algorithm.fused_rows_linear import queue_param_grads
         queue_param_grads(g2, x2, weight.grad, None if bias is None else bias.grad)
         return None, None
     gw, gb = torch.empty_like(weight), None if bias is None else torch.empty_like(bias)

@@ -48,8 +48,8 @@ from torch.nn import functional
 from asac_amd import native
 
 from ..fused import FlatParamGroup
-from ..fused_mlp import DeferredPartialSums, direct_param_grads
 from ..imitation_base import SpanAdam
+from ..param_grads import learner_backward
 from ..sac_base import SAC_Base
 from ..utils.enums import SEQ_ENCODER
 from ..utils.operators import get_last_false_indexes
@@ -424,9 +424,8 @@ class OptionBase(SAC_Base):
             loss_q_list = losses.mean(dim=(1, 2))
             self._loss_q_e.copy_(loss_q_list.detach())
             roots = ([loss_q_list.sum()], [None])
-        with direct_param_grads(), DeferredPartialSums() as sums_later:
+        with learner_backward():
             torch.autograd.backward(*roots, retain_graph=True)
-        sums_later.flush()
         self._write_option_summary({'loss/q': self._stats['loss_q']})
         return d_y, c_y
 
@@ -488,9 +487,8 @@ class OptionBase(SAC_Base):
                                          priority_is, terminal_entropy, self._loss_termination, dbeta,
                                          workspace=self._termination_ws)
         self.optimizer_termination.zero_grad()
-        with direct_param_grads(), DeferredPartialSums() as sums_later:
+        with learner_backward():
             torch.autograd.backward([termination], [dbeta.view_as(termination)])
-        sums_later.flush()
         if self._summary_due():
             self._stats['termination'].copy_(torch.mean(termination.detach()))
             self._write_option_summary({'loss/termination': self._stats['loss_termination'],

@@ -15,6 +15,7 @@ import torch
 from torch import autograd, distributions, nn
 from torch.nn import functional
 
+from .param_grads import DeferredPartialSums, flat_alias
 from .utils.enums import SEQ_ENCODER, SIAMESE
 from .utils.operators import get_last_false_indexes
 
@@ -282,8 +283,7 @@ class AuxHeadsMixin:
         # loss over that buffer instead of two per parameter tensor (same products, same sums, entry by entry)
         flat_grad = None
         if all(p.grad is not None for p in params) and params[0].is_cuda:
-            from .fused_mlp import _flat_alias
-            flat_grad = _flat_alias([p.grad for p in params])
+            flat_grad = flat_alias([p.grad for p in params])
         if (flat_grad is not None and self._fused_gating and flat_main.numel() == flat_grad.numel()
                 and len(aux) <= 4 and flat_grad.numel() <= (1 << 20)):
             # the K cosines' signs and the gated additions, loss by loss, as ONE launch (csrc/optim.hip k_cosine_gate_add)
@@ -450,8 +450,7 @@ class AuxHeadsMixin:
             conv_later = DeferredConvBackward() if self._rpm_conv_one_launch else None
             # ... and none of the walks' parameter gradients is read before all walks are done: the fixed-order sums of the
             # backward launches' per-workgroup partials (twelve second launches) wait too and run as one launch
-            # (fused_mlp.DeferredPartialSums; walk ('m', k): through model k down to `nx_states`, ('r', k): the representation)
-            from .fused_mlp import DeferredPartialSums
+            # (param_grads.DeferredPartialSums; walk ('m', k): through model k down to `nx_states`, ('r', k): the representation)
             with DeferredPartialSums() as sums_later:
                 for k, (loss_i, params_i) in enumerate(zip(losses, model_params)):
                     sums_later.walk = ('m', k)
@@ -494,8 +493,7 @@ class AuxHeadsMixin:
         loss = loss_transition + loss_reward + loss_obs
         flat_grad = None
         if pred_params and pred_params[0].is_cuda and all(p.grad is not None for p in pred_params):
-            from .fused_mlp import _flat_alias
-            flat_grad = _flat_alias([p.grad for p in pred_params])
+            flat_grad = flat_alias([p.grad for p in pred_params])
         if flat_grad is not None:
             # the models' gradients are consecutive views of one buffer: written there by ONE concatenation instead of a
             # zero fill and an accumulation launch per parameter tensor (0 + g = g)

@@ -38,10 +38,11 @@ from asac_amd import native
 
 from . import fused_gru, fused_linear
 from .fused import DeviceNoise, FlatAdam, FlatParamGroup, squash_sample, squash_sample_ls, time_slice
-from .fused_mlp import DeferredPartialSums, StockMLP, describe_policy, describe_q, direct_param_grads
+from .fused_mlp import StockMLP, describe_policy, describe_q
 from .nn_models import *  # noqa: F401,F403
 from .nn_models.layers.seq_layers import step_mask_cache
 from .nn_models.representation import ModelSimpleRep
+from .param_grads import direct_param_grads, learner_backward
 from .batch_buffer import BatchBuffer
 from .captured_step import CapturedStep
 from .replay_buffer import PrioritizedReplayBuffer
@@ -1622,8 +1623,8 @@ class SAC_Base(AuxHeadsMixin):
                     torch.sum(g0, dim=0, out=g_base[:, t])
             rep_stepped = False
             # (the backward launches' second launches — per-workgroup partials summed into the flat gradient — run as one
-            # launch when the walk is done, in front of the optimizer step: fused_mlp.DeferredPartialSums)
-            with direct_param_grads(), DeferredPartialSums() as sums_later:
+            # launch when the walk is done, in front of the optimizer step: param_grads.learner_backward)
+            with learner_backward():
                 if at_position:
                     # the window IS a fused GRU's output: its backward sums the members' gradients itself and starts at
                     # position t (the steps behind it only feed detached targets) — no member-sum launch in between;
@@ -1635,7 +1636,6 @@ class SAC_Base(AuxHeadsMixin):
                     fused_linear.backward_from_members(base, g0, t, g_base)
                 else:
                     torch.autograd.backward([base], [g_base])
-            sums_later.flush()
             if fold:
                 if not rep_stepped:
                     self.optimizer_q_list[0].step(*self._params.span('rep'))
@@ -1657,9 +1657,8 @@ class SAC_Base(AuxHeadsMixin):
                                        q_online=[h.detach() for h in heads])
             native.dqn_q_loss_grad(*ret.args, priority_is, self._loss_q_e, grad_q)
             del ret
-            with direct_param_grads(), DeferredPartialSums() as sums_later:
+            with learner_backward():
                 torch.autograd.backward(heads, list(grad_q.unbind(0)))
-            sums_later.flush()
             return self._finish_rep_q(None, None)
         d_y, c_y = self._get_y(n_last_masks, n_padding_masks, nx_obses_list, nx_states.detach(), nx_actions,
                                n_rewards, n_dones, n_mu_probs if self.use_n_step_is else None,
@@ -1673,9 +1672,8 @@ class SAC_Base(AuxHeadsMixin):
             grad_q, _ = self._discrete_grad_buffers(state.shape[0])
             native.discrete_q_loss_grad(self._branches, [h.detach() for h in heads], d_action, d_y, priority_is,
                                         self._loss_q_e, grad_q)
-            with direct_param_grads(), DeferredPartialSums() as sums_later:
+            with learner_backward():
                 torch.autograd.backward(heads, list(grad_q.unbind(0)))
-            sums_later.flush()
             return self._finish_rep_q(None, None)
         if self.d_action_sizes:
             qs = torch.stack([torch.sum(d_action * q[0], dim=-1, keepdim=True) / self.d_action_branch_size
@@ -1692,10 +1690,9 @@ class SAC_Base(AuxHeadsMixin):
                     w = priority_is.reshape(-1).contiguous() if priority_is is not None else None
                     native.q_loss_fwd_bwd(c_q.detach().contiguous(), t_q.contiguous(), c_y.reshape(-1), w,
                                           self.clip_epsilon, self._loss_q_e, self._grad_q)
-                    with direct_param_grads(), DeferredPartialSums() as sums_later:
+                    with learner_backward():
                         torch.autograd.backward([c_q], [self._grad_q],
                                                 retain_graph=aux is not None and self.use_prediction)
-                    sums_later.flush()
                     if aux is None:
                         return self._finish_rep_q(None, None)
                     return self._finish_rep_q(None, None, aux,
@@ -1743,9 +1740,8 @@ class SAC_Base(AuxHeadsMixin):
             # the prediction heads differentiate the representation graph again (sac_aux._train_rpm)
             # the main loss accumulates into every parameter it reaches (representation + Q ensemble): the fused
             # layers add their parameter gradients in place
-            with direct_param_grads(), DeferredPartialSums() as sums_later:
+            with learner_backward():
                 total_loss.backward(retain_graph=aux is not None and self.use_prediction)
-            sums_later.flush()
             self._stats['loss_q'].copy_(loss_q0.detach())
         start, stop = self._params.span('rep', f'q_{self.ensemble_q_num - 1}')
         if aux is None:

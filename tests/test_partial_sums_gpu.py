@@ -1,4 +1,4 @@
-"""GPU: `asac_sum_partials_multi` / `fused_mlp.DeferredPartialSums` — the second launches of several backwards (per-workgroup
+"""GPU: `asac_sum_partials_multi` / `param_grads.DeferredPartialSums` — the second launches of several backwards (per-workgroup
 parameter-gradient partials summed in workgroup order) as ONE launch: per job the bits of the launch it stands for."""
 import copy
 
@@ -118,7 +118,7 @@ def test_deferred_sums_of_dense_stack_and_attention_are_the_undeferred_gradients
         for p, g in zip(dp + ap, want[k]):
             assert torch.equal(late[k][id(p)], g), (k, tuple(p.shape))
     # the switch off: the walks return their gradients themselves
-    import algorithm.fused_mlp as fm
+    import algorithm.param_grads as fm
     fm.SUM_PARTIALS_LATER = False
     try:
         with DeferredPartialSums() as later:

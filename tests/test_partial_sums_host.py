@@ -1,4 +1,4 @@
-"""Host logic of the deferred partial sums (`fused_mlp.DeferredPartialSums`): `flush()` hands the queued reductions to
+"""Host logic of the deferred partial sums (`param_grads.DeferredPartialSums`): `flush()` hands the queued reductions to
 `native.sum_partials_multi` sixteen at a time, and the jobs of one launch run side by side in no order — so two jobs whose
 output floats overlap (a fused module reached twice in a direct-mode backward: both ADD into its span of the flat gradient
 buffer) must never share a launch, and must keep the order they were queued in.  CPU: the launch is replaced by a recorder;
@@ -11,7 +11,7 @@ import torch
 def recorder(monkeypatch):
     import asac_amd  # noqa: F401
     from asac_amd import native
-    from algorithm.fused_mlp import DeferredPartialSums
+    from algorithm.param_grads import DeferredPartialSums
     launches = []
     monkeypatch.setattr(native, 'sum_partials_multi', lambda jobs: launches.append(list(jobs)))
     return DeferredPartialSums(), launches

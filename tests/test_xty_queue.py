@@ -1,4 +1,4 @@
-"""Host logic of the parameter-gradient queue (`algorithm/fused_rows_linear.py`): under the learner's direct mode the `x^T y`
+"""Host logic of the parameter-gradient queue (`algorithm/param_grads.py`): under the learner's direct mode the `x^T y`
 products of a backward pass are issued four at a time (`asac_xty_multi`) and the rest when the backward pass ends.  CPU: the
 launches are replaced by recorders; what is checked is WHEN and in which groups they are issued."""
 import pytest
@@ -9,7 +9,7 @@ import torch
 def recorder(monkeypatch):
     import asac_amd  # noqa: F401
     from asac_amd import native
-    from algorithm import fused_rows_linear as frl
+    from algorithm import param_grads as frl
     calls = []
     monkeypatch.setattr(native, 'xty', lambda g, x, w, b, accumulate=False: calls.append(('one', [w], accumulate)))
     monkeypatch.setattr(native, 'xty_multi', lambda jobs, accumulate=False: calls.append(('multi', [j[2] for j in jobs], accumulate)))
@@ -69,7 +69,7 @@ def test_a_failed_backward_does_not_strand_the_next_one(recorder):
     frl, calls = recorder
     frl._pending.append(('stale',) * 4)          # what an exception between two enqueues leaves behind
     frl._armed = True
-    from algorithm.fused_mlp import direct_param_grads
+    from algorithm.param_grads import direct_param_grads
     with direct_param_grads():
         assert not frl._pending and not frl._armed
         x = torch.ones(2, requires_grad=True)

@@ -65,6 +65,54 @@ class _NormalNllKlLogstdFn(autograd.Function):
         return (g_raw if _is_unit(g_loss) else g_loss * g_raw), None, None, None, None
 
 
+class _SiameseAtcFn(autograd.Function):
+    """mean(BCE-with-logits((e W) te^T, block-diagonal labels) * pad) for one encoder as ONE launch that also leaves
+    d loss / d e and d loss / d W (`asac_siamese_atc_loss_grad`: no N x N logits, labels or cotangent in memory); the
+    backward scales them — every time it is asked, the saved gradients are only read."""
+
+    @staticmethod
+    def forward(ctx, e, w, te, pad, n, workspace):
+        from asac_amd import native
+        g_e, g_w = torch.empty_like(e), torch.empty_like(w)
+        loss = torch.empty((), dtype=torch.float32, device=e.device)
+        native.siamese_atc_loss_grad(e.detach(), te.detach(), w.detach(), pad, n, loss, g_e, g_w, workspace)
+        ctx.save_for_backward(g_e, g_w)
+        ctx.set_materialize_grads(False)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        if g_loss is None:
+            return None, None, None, None, None, None
+        g_e, g_w = ctx.saved_tensors
+        if _is_unit(g_loss):
+            return g_e, g_w, None, None, None, None
+        return (g_loss * g_e if ctx.needs_input_grad[0] else None, g_loss * g_w if ctx.needs_input_grad[1] else None,
+                None, None, None, None)
+
+
+class _SiameseByolFn(autograd.Function):
+    """mean(cosine_similarity(pred, t_proj) * pad) for one encoder as ONE launch that also leaves d loss / d pred
+    (`asac_siamese_byol_loss_grad`); the backward scales it and only reads what was saved."""
+
+    @staticmethod
+    def forward(ctx, pred, t_proj, pad, workspace):
+        from asac_amd import native
+        g_pred = torch.empty_like(pred)
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+        native.siamese_byol_loss_grad(pred.detach(), t_proj.detach(), pad, loss, g_pred, workspace)
+        ctx.save_for_backward(g_pred)
+        ctx.set_materialize_grads(False)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        if g_loss is None:
+            return None, None, None, None
+        (g_pred,) = ctx.saved_tensors
+        return (g_pred if _is_unit(g_loss) else g_loss * g_pred), None, None, None
+
+
 _UNIT = {}
 
 
@@ -314,7 +362,13 @@ class AuxHeadsMixin:
         batch, n = enc[0].shape[:2]
         flat = lambda xs: [x.reshape(batch * n, -1) for x in xs]  # noqa: E731
 
-        if self.siamese == SIAMESE.ATC:
+        if self.siamese == SIAMESE.ATC and self._siamese_fused(batch * n, n, flat(enc), flat(t_enc), t_enc):
+            # loss and gradients of each encoder as one launch: no logits, no labels (`_SiameseAtcFn`)
+            pad = n_padding_masks.reshape(batch * n).to(torch.float32)
+            loss_siamese_list = [
+                _SiameseAtcFn.apply(e, w, te, pad, n, self._siamese_workspace((batch * n, e.shape[1])))
+                for e, w, te in zip(flat(enc), self.contrastive_weight_list, flat(t_enc))]
+        elif self.siamese == SIAMESE.ATC:
             logits = [torch.mm(torch.mm(e, w), te.t())
                       for e, w, te in zip(flat(enc), self.contrastive_weight_list, flat(t_enc))]
             labels = torch.block_diag(*torch.ones(batch, n, n, device=self.device))
@@ -327,7 +381,12 @@ class AuxHeadsMixin:
             pred = [p(x) for p, x in zip(self.model_rep_prediction_list, proj)]
             t_proj = [p(e) for p, e in zip(self.model_target_rep_projection_list, flat(t_enc))]
             pad = n_padding_masks.reshape(batch * n)
-            loss_siamese_list = [(functional.cosine_similarity(a, b) * pad).mean() for a, b in zip(pred, t_proj)]
+            if self._siamese_fused(batch * n, n, pred, t_proj, t_enc):
+                pad = pad.to(torch.float32)
+                loss_siamese_list = [_SiameseByolFn.apply(a, b, pad, self._siamese_workspace(('byol', i)))
+                                     for i, (a, b) in enumerate(zip(pred, t_proj))]
+            else:
+                loss_siamese_list = [(functional.cosine_similarity(a, b) * pad).mean() for a, b in zip(pred, t_proj)]
 
         q_loss_list = []
         if self.siamese_use_q:
@@ -383,6 +442,32 @@ class AuxHeadsMixin:
             self._dist.all_reduce_grads(self._params.grad, *self._params.span('siamese'))
         self.optimizer_siamese.step()
         return sum(loss_siamese_list), (sum(q_loss_list) if self.siamese_use_q else None)
+
+    def _siamese_fused(self, N, n, online, target, t_enc) -> bool:
+        """`online` / `target`: per encoder the two [N, width] operands of the loss (ATC: the encoders; BYOL: prediction
+        and target projection), `t_enc` the target encoders.  True: `hip_config['fused_siamese']` is on and they fit the
+        launches (`fused_siamese_applies`).  The launches hand no gradient to the target side: nothing in this step asks
+        for one (the backward passes name the representation's and the head's own parameters; the target projections of
+        BYOL belong to no optimizer's segment); a target ENCODER that requires grad keeps the eager code."""
+        if not self._fused_siamese:
+            return False
+        from .sac_base import fused_siamese_applies
+        ok = all(x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous() for x in chain(online, target)) \
+            and all(x.shape == t.shape for x, t in zip(online, target))
+        return fused_siamese_applies(enabled=True, siamese=self.siamese, float32_on_device=ok, N=N, n=n,
+                                     widths=[x.shape[1] for x in online],
+                                     target_requires_grad=any(t.requires_grad for t in t_enc))
+
+    def _siamese_workspace(self, key):
+        """the zeroed exchange words of one siamese launch, made once: key (N, E) for `asac_siamese_atc_loss_grad` (launches
+        on one stream run one after the other, so encoders of one shape share them), ('byol', i) for encoder i's
+        `asac_siamese_byol_loss_grad`"""
+        ws = self._siamese_ws.get(key)
+        if ws is None:
+            from asac_amd import native
+            words = native.SIAMESE_BYOL_WORKSPACE_FLOATS if key[0] == 'byol' else native.siamese_atc_workspace_floats(*key)
+            ws = self._siamese_ws[key] = torch.zeros(words, dtype=torch.float32, device=self.device)
+        return ws
 
     def _train_rpm(self, grads_rep_main, nx_obses_list, nx_states, nx_target_states, n_actions, n_rewards):
         """Transition / reward / observation models on the step's states (reference 1798-1839).

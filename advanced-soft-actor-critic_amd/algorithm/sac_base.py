@@ -139,6 +139,22 @@ def fused_rnd_discrete_applies(*, enabled, plain_learner, d_action_sizes, c_acti
                 and native.drnd_sizes_ok(state_size, d_action_sizes, n_sample, rows))
 
 
+def fused_siamese_applies(*, enabled, siamese, float32_on_device, N, n, widths, target_requires_grad) -> bool:
+    """Do the siamese losses of this step run on the `asac_siamese_*` launches (`hip_config['fused_siamese']`, default off)?
+    Only float32 device tensors whose target side carries no gradient, within the entry points' limits: ATC — every
+    encoder width E in 1 .. 128, block length n in 1 .. 64 dividing the N = batch * n rows, N <= 16 384; BYOL — every
+    prediction width P in 1 .. 256, N <= 2^20 (`widths`: the E of each encoder, or the P of each prediction).  Everything
+    else runs the eager code."""
+    if not (enabled and siamese is not None and float32_on_device and not target_requires_grad and len(widths) > 0):
+        return False
+    if siamese == SIAMESE.ATC:
+        return bool(all(1 <= w <= native.SIAMESE_MAX_WIDTH for w in widths) and 1 <= n <= native.SIAMESE_MAX_BLOCK
+                    and 1 <= N <= native.SIAMESE_MAX_ROWS and N % n == 0)
+    if siamese == SIAMESE.BYOL:
+        return bool(all(1 <= w <= native.SIAMESE_BYOL_MAX_WIDTH for w in widths) and 1 <= N <= native.SIAMESE_BYOL_MAX_ROWS)
+    return False
+
+
 class _Window:
     """views of the step's static batch tensors and what the phases of `_device_step_body` hand to each other"""
 
@@ -325,6 +341,9 @@ class SAC_Base(AuxHeadsMixin):
         self._fused_rnd_discrete = bool(hip_config.get('fused_rnd_discrete', True))
         self._drnd_stacks = None         # (residual, predictor table, target table, gradient table, tensors) | False (`_drnd_fused`)
         self._drnd_buffers = {}          # (B, n) -> the distillation launch's records and both launches' exchange words
+        # asac_siamese_* (ATC / BYOL loss and gradients as one launch an encoder); off by default: NOTES.md, "siamese losses"
+        self._fused_siamese = bool(hip_config.get('fused_siamese', False))
+        self._siamese_ws = {}            # (N, E) / ('byol', encoder index) -> the launch's zeroed exchange words
         self._fused_rpm_loss = bool(hip_config.get('fused_rpm_loss', True))
         # one backward walk per prediction model (gates and model gradients from it): sac_aux._train_rpm
         self._rpm_single_backward = bool(hip_config.get('rpm_single_backward', True))

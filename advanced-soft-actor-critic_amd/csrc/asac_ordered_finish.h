@@ -35,14 +35,16 @@ __device__ __forceinline__ float finish_load(float* slot) { return __hip_atomic_
 __device__ __forceinline__ void finish_reset(unsigned int* counter) { __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // arrive: called by EVERY thread of the workgroup after its finish_publish calls; true in every thread of the last workgroup
-__device__ __forceinline__ bool finish_arrive(unsigned int* counter) {
+// (`expected`: how many workgroups arrive at this counter — the grid's x extent unless the caller says otherwise)
+__device__ __forceinline__ bool finish_arrive(unsigned int* counter, unsigned int expected) {
     __shared__ bool last;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // every wave: its own stores have arrived
     __syncthreads();
-    if (threadIdx.x == 0) last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+    if (threadIdx.x == 0) last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == expected - 1;
     __syncthreads();
     return last;
 }
+__device__ __forceinline__ bool finish_arrive(unsigned int* counter) { return finish_arrive(counter, gridDim.x); }
 
 // collect: base[0] + base[stride] + .. + base[(count - 1) * stride], added in that order by the calling lane; sixteen loads
 // requested at a time (one by one, each add waits for its own trip to memory; indices beyond `count` re-read the last slot: a

@@ -589,6 +589,11 @@ _SIGNATURES = {
     'asac_drnd_pick': (C.c_int, [C.POINTER(Branches), C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_siamese_atc_workspace_floats': (C.c_int64, [C.c_int64, C.c_int]),
+    'asac_siamese_atc_loss_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_siamese_byol_loss_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -3244,3 +3249,45 @@ def drnd_pick(br: Branches, residual, predictors, targets, state, logits, u, act
     _check(load().asac_drnd_pick(C.byref(br), S, _residual2(residual), _p(predictors), _p(targets), _p(state), state.stride(0),
                                  _p(logits), logits.stride(0), _p(u), k, batch, _p(action_out), _p(prob_out), _p(err_out),
                                  _p(cand_out), _p(index_out), _stream()), 'asac_drnd_pick')
+
+
+# ------------------------------------------------------------------------------------------------
+# siamese representation losses (csrc/siamese.hip)
+# ------------------------------------------------------------------------------------------------
+SIAMESE_MAX_WIDTH, SIAMESE_MAX_BLOCK, SIAMESE_MAX_ROWS = 128, 64, 16384
+SIAMESE_BYOL_MAX_WIDTH, SIAMESE_BYOL_MAX_ROWS, SIAMESE_BYOL_WORKSPACE_FLOATS = 256, 1 << 20, 257
+
+
+def siamese_atc_workspace_floats(N: int, E: int) -> int:
+    """floats of the caller-owned workspace of `siamese_atc_loss_grad` (zero before the first launch); -1 outside the limits"""
+    return int(load().asac_siamese_atc_workspace_floats(int(N), int(E)))
+
+
+def _dense_rows(t, rows, width):
+    return t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == rows * width
+
+
+@_profiled
+def siamese_atc_loss_grad(e, te, w, pad, n, loss_out, g_e, g_w, workspace):
+    """e / te [N, E], w [E, E], pad [N] float row weights, n the block length -> loss_out (one float) <- the mean over the
+    N x N logits (e w) te^T of pad_i * BCE-with-logits against the block-diagonal labels, g_e [N, E] and g_w [E, E] <- its
+    gradients: one launch, no N x N buffer.  workspace: `siamese_atc_workspace_floats(N, E)` zeroed floats, kept by the caller"""
+    N, E = e.shape
+    assert _dense_rows(e, N, E) and _dense_rows(te, N, E) and _dense_rows(w, E, E) and _dense_rows(pad, N, 1)
+    assert _dense_rows(g_e, N, E) and _dense_rows(g_w, E, E) and _dense_rows(loss_out, 1, 1)
+    assert workspace.is_cuda and workspace.dtype == torch.float32 and workspace.is_contiguous()
+    assert workspace.numel() >= max(1, siamese_atc_workspace_floats(N, E))
+    _check(load().asac_siamese_atc_loss_grad(_p(e), _p(te), _p(w), _p(pad), N, E, int(n), _p(loss_out), _p(g_e), _p(g_w),
+                                             _p(workspace), _stream()), 'asac_siamese_atc_loss_grad')
+
+
+@_profiled
+def siamese_byol_loss_grad(pred, t_proj, pad, loss_out, g_pred, workspace):
+    """pred / t_proj [N, P], pad [N] float row weights -> loss_out (one float) <- mean_i(pad_i * cosine_similarity(pred_i,
+    t_proj_i)), g_pred [N, P] <- its gradient: one launch.  workspace: SIAMESE_BYOL_WORKSPACE_FLOATS zeroed floats"""
+    N, P = pred.shape
+    assert _dense_rows(pred, N, P) and _dense_rows(t_proj, N, P) and _dense_rows(pad, N, 1)
+    assert _dense_rows(g_pred, N, P) and _dense_rows(loss_out, 1, 1)
+    assert workspace.is_cuda and workspace.dtype == torch.float32 and workspace.numel() >= SIAMESE_BYOL_WORKSPACE_FLOATS
+    _check(load().asac_siamese_byol_loss_grad(_p(pred), _p(t_proj), _p(pad), N, P, _p(loss_out), _p(g_pred), _p(workspace),
+                                              _stream()), 'asac_siamese_byol_loss_grad')

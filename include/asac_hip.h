@@ -1853,6 +1853,39 @@ int asac_drnd_pick(const asac_branches_t* branches, int S, const int32_t* residu
                    int64_t logits_stride, const float* u, int k, int batch, float* action_out, float* prob_out, float* err_out,
                    int32_t* cand_out, int32_t* index_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Siamese representation losses (csrc/siamese.hip; sac_base.py _train_siamese_representation_learning 1633-1796), loss
+ * and gradients in ONE launch each.  All tensors float32 with dense rows.  No float atomics: equal inputs give equal bits.
+ * Anything outside the limits, a NULL pointer or N == 0 returns hipErrorInvalidValue without a launch.
+ * ------------------------------------------------------------------------------------------- */
+#define ASAC_SIAMESE_MAX_WIDTH 128
+#define ASAC_SIAMESE_MAX_BLOCK 64
+#define ASAC_SIAMESE_MAX_ROWS 16384
+#define ASAC_SIAMESE_BYOL_MAX_WIDTH 256
+#define ASAC_SIAMESE_BYOL_MAX_ROWS (1 << 20)
+#define ASAC_SIAMESE_BYOL_WORKSPACE_FLOATS 257
+
+/* ATC.  e [N][E] online and te [N][E] target encoders, w [E][E], pad [N] row weights, n the block length (n divides N):
+ *   z = e w,  l_ij = z_i . te_j,  y_ij = (i / n == j / n)
+ *   *loss_out = (1 / N^2) sum_ij pad_i (max(l, 0) - l y + log1p(exp(-|l|)))
+ *   dl_ij = pad_i (sigmoid(l_ij) - y_ij) / N^2,  dz = dl te,  g_w [E][E] = e^T dz,  g_e [N][E] = dz w^T
+ * l, y and dl stay in registers; the products over te are v_mfma_f32_16x16x4_f32.  Limits: 1 <= E <= ASAC_SIAMESE_MAX_WIDTH,
+ * 1 <= n <= ASAC_SIAMESE_MAX_BLOCK, 1 <= N <= ASAC_SIAMESE_MAX_ROWS.  Every element of the three outputs is written.
+ * workspace: asac_siamese_atc_workspace_floats(N, E) floats (-1 outside the limits), zero before the first launch; every
+ * launch leaves its counters zero and rewrites the partial sums it reads (added in workgroup order by the last to arrive). */
+int64_t asac_siamese_atc_workspace_floats(int64_t N, int E);
+int asac_siamese_atc_loss_grad(const float* e, const float* te, const float* w, const float* pad, int64_t N, int E, int n,
+                               float* loss_out, float* g_e, float* g_w, float* workspace, void* stream);
+
+/* BYOL.  pred [N][P], t_proj [N][P], pad [N]:
+ *   c_i = (pred_i / max(|pred_i|, 1e-8)) . (t_proj_i / max(|t_proj_i|, 1e-8))     (torch's cosine_similarity, whose clamp
+ *                                                  is outside autograd: the gradient runs through |pred_i| either way)
+ *   *loss_out = (1 / N) sum_i pad_i c_i,   g_pred [N][P] = d loss / d pred
+ * Limits: 1 <= P <= ASAC_SIAMESE_BYOL_MAX_WIDTH, 1 <= N <= ASAC_SIAMESE_BYOL_MAX_ROWS.
+ * workspace: ASAC_SIAMESE_BYOL_WORKSPACE_FLOATS floats, zero before the first launch and left ready by every launch. */
+int asac_siamese_byol_loss_grad(const float* pred, const float* t_proj, const float* pad, int64_t N, int P, float* loss_out,
+                                float* g_pred, float* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

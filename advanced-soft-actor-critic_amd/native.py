@@ -231,6 +231,13 @@ class ObsDecoderParams(C.Structure):
                                           'ct2_b', 'ct3_w', 'ct3_b')]
 
 
+class ImageOp(C.Structure):
+    """asac_image_op_t: one member of an `image_augment` table"""
+    _fields_ = [('kind', C.c_int32), ('kx', C.c_int32), ('ky', C.c_int32), ('crop_h', C.c_int32), ('crop_w', C.c_int32),
+                ('top', C.c_int32), ('left', C.c_int32), ('lo', C.c_float), ('hi', C.c_float), ('a', C.c_float),
+                ('b', C.c_float), ('c', C.c_float)]
+
+
 _SIGNATURES = {
     'asac_version': (C.c_int, []),
     'asac_last_error': (C.c_char_p, []),
@@ -594,6 +601,8 @@ _SIGNATURES = {
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'asac_siamese_byol_loss_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),
+    'asac_image_augment': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.POINTER(ImageOp), C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -3291,3 +3300,38 @@ def siamese_byol_loss_grad(pred, t_proj, pad, loss_out, g_pred, workspace):
     assert workspace.is_cuda and workspace.dtype == torch.float32 and workspace.numel() >= SIAMESE_BYOL_WORKSPACE_FLOATS
     _check(load().asac_siamese_byol_loss_grad(_p(pred), _p(t_proj), _p(pad), N, P, _p(loss_out), _p(g_pred), _p(workspace),
                                               _stream()), 'asac_siamese_byol_loss_grad')
+
+
+# ------------------------------------------------------------------------------------------------
+# image augmentations (csrc/image.hip)
+# ------------------------------------------------------------------------------------------------
+IMAGE_MAX_OPS, IMAGE_MAX_PLANE, IMAGE_MAX_KERNEL = 8, 9216, 31
+IMAGE_COPY, IMAGE_BLUR, IMAGE_BRIGHTNESS, IMAGE_CROP_RESIZE, IMAGE_SALT_PEPPER, IMAGE_UNIFORM_NOISE = range(6)
+IMAGE_STATE_WORDS = 2          # int64: the draw counter, the arrival word
+IMAGE_DRAWN = ('counter', 'choice', 'top', 'left', 'sigma', 'factor')     # the f64 record of a call's draws
+
+
+def image_ops(ops):
+    """a host table (ctypes array of `ImageOp`) from dicts of its fields; kept by the caller for as long as it launches"""
+    assert 1 <= len(ops) <= IMAGE_MAX_OPS
+    arr = (ImageOp * len(ops))()
+    for slot, fields in zip(arr, ops):
+        slot.top = slot.left = -1
+        for k, v in fields.items():
+            setattr(slot, k, v)
+    return arr
+
+
+@_profiled
+def image_augment(x, y, ops, seed=0, instance=0, state=None, drawn=None):
+    """x [N, C, H, W] -> y [N, C, Ho, Wo] (float32, contiguous) through the op of the table `ops` (`image_ops`), or through
+    one member per call picked on the device where it has several: one launch.  state: int64 [2] zeros (draw counter, arrival
+    word) owned by the drawing module — None only where nothing is drawn; drawn: float64 [6] | None, see `IMAGE_DRAWN`"""
+    N, Cc, H, W = x.shape
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+    assert y.is_cuda and y.dtype == torch.float32 and y.is_contiguous() and y.dim() == 4 and y.shape[:2] == x.shape[:2]
+    assert state is None or (state.is_cuda and state.dtype == torch.int64 and state.numel() == IMAGE_STATE_WORDS)
+    assert drawn is None or (drawn.is_cuda and drawn.dtype == torch.float64 and drawn.numel() == len(IMAGE_DRAWN))
+    _check(load().asac_image_augment(_p(x), _p(y), N * Cc, Cc, H, W, y.shape[2], y.shape[3], ops, len(ops),
+                                     C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint32(int(instance) & 0x0FFFFFFF), _p(state),
+                                     _p(drawn), _stream()), 'asac_image_augment')

@@ -1886,6 +1886,54 @@ int asac_siamese_atc_loss_grad(const float* e, const float* te, const float* w, 
 int asac_siamese_byol_loss_grad(const float* pred, const float* t_proj, const float* pad, int64_t N, int P, float* loss_out,
                                 float* g_pred, float* workspace, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Image augmentations (csrc/image.hip; algorithm/utils/image_transforms.py), ONE launch per call, one 256-thread workgroup
+ * per plane (a grid of at most 512: beyond that a workgroup takes several planes in turn).
+ * x [planes][H][W] -> y [planes][Ho][Wo], float32, contiguous; planes = frames * C.  The plane is staged in LDS,
+ * so H * W <= ASAC_IMAGE_MAX_PLANE (two planes and the taps of two workgroups fit a CU's 160 KiB).
+ *
+ * `ops`: a HOST table of 1 .. ASAC_IMAGE_MAX_OPS descriptors, copied into the launch.  One entry: that op.  Several: one is
+ * picked per call, uniformly, ON THE DEVICE.  Every op but CROP_RESIZE needs Ho == H and Wo == W.
+ *   COPY           y = x
+ *   BLUR           separable Gaussian, kx / ky taps (odd, <= ASAC_IMAGE_MAX_KERNEL, k / 2 < the plane's extent), reflect
+ *                  indexing; sigma = lo, or uniform in [lo, hi) per call; w = exp(-0.5 (x / sigma)^2) over
+ *                  x = linspace(-(k - 1) / 2, (k - 1) / 2, k), normalised, computed in the kernel
+ *   BRIGHTNESS     y = clamp(x * f, 0, 1), f = lo or uniform in [lo, hi) per call
+ *   CROP_RESIZE    the window [top, top + crop_h) x [left, left + crop_w) resampled to Ho x Wo, bilinear, align_corners =
+ *                  False; Ho >= crop_h and Wo >= crop_w only (no antialiasing is needed then); equal sizes copy the
+ *                  window's bits.  top / left >= 0: fixed; -1: uniform over the valid offsets per call
+ *   SALT_PEPPER    one draw r per (frame, pixel), shared by the frame's C planes: r < b adds a, r > c subtracts a, clamped
+ *   UNIFORM_NOISE  y = clamp(x + r * b + a, 0, 1), one draw per element
+ *
+ * Draws.  `state`: 16 bytes owned by the caller, zero-initialised: an int64 draw counter, then the arrival word.  Every
+ * workgroup reads the counter and derives the call's choice, offsets, sigma / factor and its pixels' noise from
+ * Philox4x32-10(seed, instance (28 bits), counter); the last workgroup to arrive stores counter + 1 and leaves the arrival
+ * word zero.  No host value is involved: a captured launch draws afresh on every replay.  `state` may be NULL only for a
+ * table that draws nothing.  `drawn` (NULL or 6 doubles) receives counter, choice, top, left, sigma, factor of this call
+ * (-1 / NaN where the chosen op has none).  Anything outside the limits returns hipErrorInvalidValue without a launch.
+ * ------------------------------------------------------------------------------------------- */
+#define ASAC_IMAGE_MAX_OPS 8
+#define ASAC_IMAGE_MAX_PLANE 9216
+#define ASAC_IMAGE_MAX_KERNEL 31
+#define ASAC_IMAGE_COPY 0
+#define ASAC_IMAGE_BLUR 1
+#define ASAC_IMAGE_BRIGHTNESS 2
+#define ASAC_IMAGE_CROP_RESIZE 3
+#define ASAC_IMAGE_SALT_PEPPER 4
+#define ASAC_IMAGE_UNIFORM_NOISE 5
+
+typedef struct {
+    int32_t kind;
+    int32_t kx, ky;            /* BLUR */
+    int32_t crop_h, crop_w;    /* CROP_RESIZE */
+    int32_t top, left;         /* CROP_RESIZE: fixed offsets, -1: drawn */
+    float lo, hi;              /* BLUR: sigma range; BRIGHTNESS: factor range (lo == hi: fixed) */
+    float a, b, c;             /* SALT_PEPPER: amount, lower and upper threshold; UNIFORM_NOISE: mean, std */
+} asac_image_op_t;
+
+int asac_image_augment(const float* x, float* y, int64_t planes, int C, int H, int W, int Ho, int Wo, const asac_image_op_t* ops,
+                       int n_ops, uint64_t seed, uint32_t instance, int64_t* state, double* drawn, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

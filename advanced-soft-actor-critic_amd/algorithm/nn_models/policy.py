@@ -132,6 +132,16 @@ class ModelPolicy(ModelBasePolicy):
         h = self.dense(state)
         return torch.cat([head(h) for head in self.d_dense_list], dim=-1)
 
+    def heads_raw(self, state):
+        """(`d_head_raw`, *`c_head_raw`) with the trunk evaluated once; None for a part the action space does not have.
+        The acting kernel (`native.act_policy`) forms the branch softmax and the bounding itself."""
+        h = self.dense(state)
+        logits = torch.cat([head(h) for head in self.d_dense_list], dim=-1) if self.d_action_sizes else None
+        if not self.c_action_size:
+            return logits, None, None
+        z = self.c_dense(h)
+        return logits, self.mean_dense(z), self.logstd_dense(z)
+
     def forward(self, state, obs_list):
         h = self.dense(state)
         d_policy = c_policy = None

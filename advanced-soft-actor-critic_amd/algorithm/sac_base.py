@@ -139,6 +139,19 @@ def fused_rnd_discrete_applies(*, enabled, plain_learner, d_action_sizes, c_acti
                 and native.drnd_sizes_ok(state_size, d_action_sizes, n_sample, rows))
 
 
+def fused_act_applies(*, enabled, plain_learner, d_action_sizes, c_action_size, discrete_dqn_like, rnd_in_effect,
+                      offline_action, float32_on_device, state_dim) -> bool:
+    """Does `_choose_action` of this configuration and this call turn the policy's head outputs into (action, prob) with
+    the one `asac_act_policy` launch (`hip_config['fused_act']`)?  Only a plain `SAC_Base` (`plain_learner`: not an
+    `OptionBase`) that acts on its policy (no DQN-like greedy acting), in a call where RND plays no part (`rnd_in_effect`:
+    `use_rnd and (train_mode or force_rnd_if_available)`) and no `offline_action` is given, on float32 device parameters
+    and a 2-D state, within the entry point's limits (`native.act_sizes_ok`).  Everything else runs the eager code.
+    `_choose_action` asks this AFTER its four earlier one-launch branches: a stock continuous-only policy without
+    `action_noise` satisfies this predicate too and is still served by the branch in front of it."""
+    return bool(enabled and plain_learner and not discrete_dqn_like and not rnd_in_effect and not offline_action
+                and float32_on_device and state_dim == 2 and native.act_sizes_ok(d_action_sizes, c_action_size))
+
+
 def fused_siamese_applies(*, enabled, siamese, float32_on_device, N, n, widths, target_requires_grad) -> bool:
     """Do the siamese losses of this step run on the `asac_siamese_*` launches (`hip_config['fused_siamese']`, default off)?
     Only float32 device tensors whose target side carries no gradient, within the entry points' limits: ATC — every
@@ -341,6 +354,7 @@ class SAC_Base(AuxHeadsMixin):
         self._fused_rnd_discrete = bool(hip_config.get('fused_rnd_discrete', True))
         self._drnd_stacks = None         # (residual, predictor table, target table, gradient table, tensors) | False (`_drnd_fused`)
         self._drnd_buffers = {}          # (B, n) -> the distillation launch's records and both launches' exchange words
+        self._fused_act = bool(hip_config.get('fused_act', True))               # asac_act_policy (policy-based acting)
         # asac_siamese_* (ATC / BYOL loss and gradients as one launch an encoder); off by default: NOTES.md, "siamese losses"
         self._fused_siamese = bool(hip_config.get('fused_siamese', False))
         self._siamese_ws = {}            # (N, E) / ('byol', encoder index) -> the launch's zeroed exchange words
@@ -909,6 +923,45 @@ class SAC_Base(AuxHeadsMixin):
             native.dqn_act(self._branches, d_qs, u, self.discrete_dqn_epsilon, d_action)
             d_action, _ = self._random_action(d_action, torch.zeros(0, device=self.device))
             return d_action, torch.ones((batch, self.d_action_summed_size), device=self.device)
+        if fused_act_applies(
+                enabled=self._fused_act, plain_learner=type(self)._plain_learner, d_action_sizes=self.d_action_sizes,
+                c_action_size=self.c_action_size, discrete_dqn_like=bool(self.d_action_sizes) and self.discrete_dqn_like,
+                rnd_in_effect=use_rnd, offline_action=offline_action is not None,
+                float32_on_device=self._params.flat.dtype == torch.float32 and self._params.flat.is_cuda,
+                state_dim=state.dim()):
+            # every other policy-based case — discrete branches, hybrid spaces, `action_noise`, `disable_sample`, a plugin
+            # policy: the policy's head outputs (the stock policy's raw heads, the distribution parameters of a policy that
+            # has its own `forward`), at most one uniform and one Gaussian draw buffer, then ONE launch for the branch
+            # softmax, the sampled / greatest / noise-random one-hots, the squashed Gaussian action, its noise and the
+            # probabilities — instead of the distribution objects, `OneHotCategorical.sample()` per branch,
+            # `_random_action` and the ones / slice / `squash_correction_prob` / concatenation tail below
+            K, D, A = self.d_action_branch_size, self.d_action_summed_size, self.c_action_size
+            f32 = dict(dtype=torch.float32, device=self.device)
+            logits = loc = scale = None
+            stock = type(self.model_policy).forward is ModelPolicy.forward
+            if stock and self._stock_c_only():       # (`action_noise`: the fused forward's [batch, 2A] (loc | scale) rows)
+                ls = self._fpi._launch_forward(StockMLP._rows(state, self.state_size), None)[0]
+                loc, scale, stock = ls[:, :A], ls[:, A:], False
+            elif stock:
+                logits, loc, scale = self.model_policy.heads_raw(state)
+            else:
+                d_policy, c_policy = self.model_policy(state, obs_list)
+                if D:
+                    logits = d_policy.logits
+                if A:
+                    loc, scale = c_policy.loc.contiguous(), c_policy.scale.contiguous()
+            nu, ne = native.act_draw_columns(K, A, bool(disable_sample), self.action_noise is not None)
+            u = eps = None
+            if nu:
+                u = torch.empty((batch, nu), **f32)
+                self.noise.uniform_(u)
+            if ne:
+                eps = torch.empty((batch, ne), **f32)
+                self.noise.normal_(eps)
+            action, prob = torch.empty((batch, D + A), **f32), torch.empty((batch, D + A), **f32)
+            native.act_policy(native.act_job(self._branches, logits, loc, scale, u, eps, action, prob, head_raw=stock,
+                                             deterministic=disable_sample, action_noise=self.action_noise))
+            return action, prob
         d_policy, c_policy = self.model_policy(state, obs_list)
         if offline_action is None:
             if self.d_action_sizes and self.discrete_dqn_like:

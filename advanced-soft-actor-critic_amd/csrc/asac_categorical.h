@@ -60,6 +60,18 @@ __device__ __forceinline__ float cat_entropy(const float* z, int s, const CatSta
     return -h;
 }
 
+// index drawn from a branch of s entries with probabilities p[0..s) by the inverse CDF on one uniform u in [0, 1):
+// #{i < s - 1 : c_i <= u}, c the running float32 sum in index order (drnd.hip's candidates, act.hip's sampled action)
+__device__ __forceinline__ int inverse_cdf(const float* p, int s, float u) {
+    float c = 0.f;
+    int idx = 0;
+    for (int i = 0; i < s - 1; ++i) {
+        c += p[i];
+        idx += c <= u ? 1 : 0;
+    }
+    return idx;
+}
+
 // mean over the members of a device-resident subset of element `off` of each member's tensor (the members are separate
 // tensors of one shape: a pointer table instead of a stack).  Every member's load is requested before the first add
 // (members beyond the real ones re-read the last real one: a valid address, the value is not added); sum in subset order,

@@ -11,6 +11,11 @@ namespace asac {
 constexpr float kSquashFloor = 1e-2f;
 constexpr float kLogSqrt2Pi = 0.91893853320467274178f;   // math.log(math.sqrt(2*math.pi))
 
+// the Gaussian policy head (policy.py:170-172): location columns 5 tanh(x / 5), scale columns exp(clamp(x, -20, 0.5))
+__device__ __forceinline__ float gauss_head_value(bool location, float raw) {
+    return location ? tanhf(raw / 5.f) * 5.f : expf(fminf(fmaxf(raw, -20.f), 0.5f));
+}
+
 // torch.distributions.Normal.log_prob:  -((x-loc)^2)/(2*scale^2) - log(scale) - log(sqrt(2pi))
 __device__ __forceinline__ float normal_log_prob(float x, float loc, float scale) {
     const float d = x - loc;

@@ -287,17 +287,6 @@ struct PickDev {
     int32_t *cand, *index;
 };
 
-// candidate index in a branch of s entries with probabilities p[0..s): #{i < s - 1 : c_i <= u}, c the running float32 sum
-__device__ __forceinline__ int inverse_cdf(const float* p, int s, float u) {
-    float c = 0.f;
-    int idx = 0;
-    for (int i = 0; i < s - 1; ++i) {
-        c += p[i];
-        idx += c <= u ? 1 : 0;
-    }
-    return idx;
-}
-
 __global__ __launch_bounds__(kThreads) void k_drnd_pick(const PickDev v) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ float s_p[kTile * kMaxD];               // the branch softmax of the tile's entries

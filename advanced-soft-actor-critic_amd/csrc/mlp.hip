@@ -1839,11 +1839,6 @@ __device__ __forceinline__ StageScalars stage_scalars_stock_like(const ASAC_KARG
     return q;
 }
 
-// the Gaussian policy head (policy.py:170-172): location columns 5 tanh(x / 5), scale columns exp(clamp(x, -20, 0.5))
-__device__ __forceinline__ float gauss_head_value(bool location, float raw) {
-    return location ? tanhf(raw / 5.f) * 5.f : expf(fminf(fmaxf(raw, -20.f), 0.5f));
-}
-
 // RING: the rows and the stored actions come from the replay ring (`ring`), not from a gathered batch
 // SINGLE: every workgroup of the launch has one tile (n_tiles <= tile_groups: the train step's launches).  The two paths
 // are two instantiations chosen by ONE branch in the kernel, not branches along the way: with the paths interleaved in

@@ -114,6 +114,20 @@ class DqnJob(C.Structure):
                 ('action', C.c_void_p), ('action_stride', C.c_int64)]
 
 
+ACT_MAX_CONT = 8
+
+
+class ActJob(C.Structure):
+    """asac_act_job_t: the policy's head outputs, the caller's draws and the outputs of the acting launch (csrc/act.hip)"""
+    _fields_ = [('branches', Branches), ('logits', C.c_void_p), ('logits_stride', C.c_int64),
+                ('loc', C.c_void_p), ('scale', C.c_void_p), ('ls_row_stride', C.c_int64),
+                ('A', C.c_int32), ('head_raw', C.c_int32),
+                ('u', C.c_void_p), ('u_stride', C.c_int64), ('eps', C.c_void_p), ('eps_stride', C.c_int64),
+                ('deterministic', C.c_int32), ('use_noise', C.c_int32), ('noise_lo', C.c_float), ('noise_hi', C.c_float),
+                ('action_out', C.c_void_p), ('action_stride', C.c_int64), ('prob_out', C.c_void_p), ('prob_stride', C.c_int64),
+                ('B', C.c_int32), ('reserved_', C.c_int32)]
+
+
 class RndDesc(C.Structure):
     """asac_rnd_desc_t: state and action widths of an RND stack (in = S + A -> 64 -> 64) and its blocks' residual flags"""
     _fields_ = [('S', C.c_int32), ('A', C.c_int32), ('residual', C.c_int32 * 2)]
@@ -575,6 +589,8 @@ _SIGNATURES = {
                                        C.c_void_p, C.c_void_p]),
     'asac_dqn_act': (C.c_int, [C.POINTER(Branches), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p,
                                C.c_int64, C.c_int, C.c_void_p]),
+    'asac_act_sizes_ok': (C.c_int, [C.POINTER(Branches), C.c_int]),
+    'asac_act_policy': (C.c_int, [C.POINTER(ActJob), C.c_void_p]),
     'asac_rnd_supported': (C.c_int, [C.c_int, C.c_int, C.c_int]),
     'asac_rnd_distill_workspace': (C.c_int64, [C.c_int64]),
     'asac_rnd_distill': (C.c_int, [C.POINTER(RndDesc), C.POINTER(RndStack), C.POINTER(RndStack), C.c_void_p, C.c_int64,
@@ -3046,6 +3062,70 @@ def dqn_act(br: Branches, q, u, epsilon: float, action_out):
     assert action_out.shape[0] == B
     _check(load().asac_dqn_act(C.byref(br), _p(q), _discrete_rows(q, D, 'q'), _p(u), us, float(epsilon), _p(action_out),
                                _discrete_rows(action_out, D, 'action_out'), B, _stream()), 'asac_dqn_act')
+
+
+# ------------------------------------------------------------------------------------------------
+# acting of a policy-based learner (csrc/act.hip)
+# ------------------------------------------------------------------------------------------------
+def act_sizes_ok(d_action_sizes, c_action_size: int) -> bool:
+    """the limits of `act_policy` (include/asac_hip.h: K <= 8, D <= 64, A <= ASAC_ACT_MAX_CONT, at least one part present):
+    what `asac_act_sizes_ok` answers, decided on the host (it is asked once per environment step)"""
+    sizes, A = list(d_action_sizes), int(c_action_size)
+    if sizes and not (len(sizes) <= DISCRETE_MAX_BRANCHES and all(s > 0 for s in sizes) and sum(sizes) <= DISCRETE_MAX_WIDTH):
+        return False
+    return 0 <= A <= ACT_MAX_CONT and (bool(sizes) or A > 0)
+
+
+def act_draw_columns(K: int, A: int, deterministic: bool, use_noise: bool):
+    """-> (columns of `u`, columns of `eps`) of `act_policy` (the layout of include/asac_hip.h):
+    u   = [K sampling columns: not deterministic] [1 gate column, K index columns: use_noise], none without branches;
+    eps = [A sampling columns: not deterministic] [A noise columns: use_noise]"""
+    nu = ((0 if deterministic else K) + ((1 + K) if use_noise else 0)) if K else 0
+    ne = (0 if deterministic else A) + (A if use_noise else 0)
+    return nu, ne
+
+
+def act_job(br, logits, loc, scale, u, eps, action_out, prob_out, *, head_raw=False, deterministic=False,
+            action_noise=None) -> ActJob:
+    """The arguments of `act_policy`.  br: `Branches` or None (no discrete part) with logits [B, D]; loc, scale: [B, A]
+    views of one row stride (the two halves of a [B, 2A] row) or None (no continuous part), with `head_raw` the stock
+    policy's (mean, logstd) before the bounding; u / eps: the draws in the column layout of `act_draw_columns` (None where
+    that is no column); action_noise: None or (lo, hi); action_out, prob_out: [B, D + A].  The tensors must stay alive
+    until the launch is issued."""
+    K, D = (br.K, br.D) if br is not None else (0, 0)
+    A = loc.shape[1] if loc is not None else 0
+    B = action_out.shape[0]
+    job = ActJob()
+    if K:
+        assert logits.shape[0] == B
+        job.branches = br
+        job.logits, job.logits_stride = logits.data_ptr(), _discrete_rows(logits, D, 'logits')
+    if A:
+        for t, name in ((loc, 'loc'), (scale, 'scale')):
+            assert t.is_cuda and t.dtype == torch.float32 and t.shape == (B, A) and (t.stride(1) == 1 or A == 1), name
+        assert B <= 1 or loc.stride(0) == scale.stride(0), 'loc and scale rows at one stride'
+        job.loc, job.scale, job.ls_row_stride = loc.data_ptr(), scale.data_ptr(), loc.stride(0)
+    job.A, job.head_raw, job.deterministic = A, int(bool(head_raw)), int(bool(deterministic))
+    if action_noise is not None:
+        job.use_noise, job.noise_lo, job.noise_hi = 1, float(action_noise[0]), float(action_noise[1])
+    nu, ne = act_draw_columns(K, A, bool(deterministic), action_noise is not None)
+    for t, n, name in ((u, nu, 'u'), (eps, ne, 'eps')):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.shape == (B, n) and (t.stride(1) == 1 or n == 1)), name
+    if u is not None and nu:
+        job.u, job.u_stride = u.data_ptr(), u.stride(0)
+    if eps is not None and ne:
+        job.eps, job.eps_stride = eps.data_ptr(), eps.stride(0)
+    assert prob_out.shape[0] == B
+    job.action_out, job.action_stride = action_out.data_ptr(), _discrete_rows(action_out, D + A, 'action_out')
+    job.prob_out, job.prob_stride = prob_out.data_ptr(), _discrete_rows(prob_out, D + A, 'prob_out')
+    job.B = B
+    return job
+
+
+@_profiled
+def act_policy(job: ActJob):
+    """One launch: the policy's head outputs and the draws -> (action, prob) (`act_job`)"""
+    _check(load().asac_act_policy(C.byref(job), _stream()), 'asac_act_policy')
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1854,6 +1854,70 @@ int asac_drnd_pick(const asac_branches_t* branches, int S, const int32_t* residu
                    int32_t* cand_out, int32_t* index_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Acting of a policy-based learner on the policy's head outputs (csrc/act.hip; sac_base.py _choose_action 931-966 and
+ * _random_action 858-880, operators.py squash_correction_prob 17-19): discrete branches, continuous actions or both, sampled
+ * or deterministic, with or without action_noise, as ONE launch.  One lane per row, workgroups of 64 rows, no exchange
+ * between them; any B, B == 0 launches nothing.  It allocates nothing and synchronises nothing.
+ *
+ * Row b of B, branches (K, D) and A continuous actions (either part may be absent, not both):
+ *   noise_b  = torch.linspace(noise_lo, noise_hi, B)[b] in float32: step = (hi - lo) / (B - 1),
+ *              b < B / 2 ? fma(step, b, lo) : fma(-step, B - 1 - b, hi);  lo at B == 1
+ *   branch k (s_k entries, logits z):  p = softmax(z) (the bits of asac_discrete_policy_loss_grad's probs_out)
+ *     sampled        index = #{i < s_k - 1 : c_i <= u[b, k]}, c the running float32 sum of p in index order (asac_drnd_pick's
+ *                    rule), then lowered to the last entry with p > 0: an entry of probability zero is never returned
+ *     deterministic  index = the first maximum of z
+ *     with noise     u[b, gate] < noise_b: every branch's index becomes min(floor(u[b, idx_k] * s_k), s_k - 1) (asac_dqn_act's
+ *                    rule for its random rows)
+ *   continuous  (loc, scale) as given, or with head_raw = 1 loc = tanh(mean / 5) * 5, scale = exp(clamp(logstd, -20, 0.5))
+ *     sampled        a = tanh(loc + eps[b, d] * scale)         (the bits of asac_squash_sample_fwd's a_tanh)
+ *     deterministic  a = tanh(loc)
+ *     with noise     a = tanh(atanh(a) + eps[b, noise_d] * noise_b), infinities included
+ *   action_out[b] = (one-hot per branch | a)                            D + A floats, every one written
+ *   prob_out[b]   = (p | exp(N(loc, scale).log_prob(x_d)) / prod_e max(1 - tanh(x_e)^2, 1e-2)), x = atanh(clamp(a, +-0.999))
+ *                   (the bits of asac_squash_prob on the returned action)
+ *
+ * Draw buffers, float32, rows u_stride / eps_stride floats apart; the caller fills them (uniforms in [0, 1), standard
+ * normals).  Columns, in this order, a group being ABSENT (not skipped) when its condition fails:
+ *   u    [K sampling columns: !deterministic] [1 gate column, K index columns: use_noise]         (none without branches)
+ *   eps  [A sampling columns: !deterministic] [A noise columns: use_noise]                       (none when A == 0)
+ * A buffer of no columns may be NULL.
+ *
+ * Limits: K <= ASAC_DISCRETE_MAX_BRANCHES, D <= ASAC_DISCRETE_MAX_WIDTH, A <= ASAC_ACT_MAX_CONT.  branches.K == 0: no
+ * discrete part (logits not read); A == 0: no continuous part (loc / scale not read).  Bad arguments (null outputs, a branch
+ * table that does not add up, sizes over the limits, neither part present, a missing input or draw buffer the mode needs,
+ * noise_lo > noise_hi, negative or NaN noise, B < 0) return hipErrorInvalidValue without a launch.
+ * ------------------------------------------------------------------------------------------- */
+#define ASAC_ACT_MAX_CONT 8
+
+typedef struct {
+    asac_branches_t branches;      /* K == 0: no discrete part */
+    const float* logits;           /* [B, D], rows logits_stride floats apart */
+    int64_t logits_stride;
+    const float* loc;              /* [B, A] each, rows ls_row_stride floats apart: two pointers, so that they may be the */
+    const float* scale;            /* two halves of a [B, 2A] row */
+    int64_t ls_row_stride;
+    int32_t A;
+    int32_t head_raw;              /* 1: loc / scale hold the stock policy's (mean, logstd) before the bounding */
+    const float* u;
+    int64_t u_stride;
+    const float* eps;
+    int64_t eps_stride;
+    int32_t deterministic;
+    int32_t use_noise;
+    float noise_lo, noise_hi;
+    float* action_out;             /* [B, D + A], rows action_stride floats apart */
+    int64_t action_stride;
+    float* prob_out;               /* [B, D + A], rows prob_stride floats apart */
+    int64_t prob_stride;
+    int32_t B;
+    int32_t reserved_;
+} asac_act_job_t;
+
+/* 1 when (branches, A) is within the limits above (branches NULL or K == 0: no discrete part), else 0 */
+int asac_act_sizes_ok(const asac_branches_t* branches, int A);
+int asac_act_policy(const asac_act_job_t* job_host, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Siamese representation losses (csrc/siamese.hip; sac_base.py _train_siamese_representation_learning 1633-1796), loss
  * and gradients in ONE launch each.  All tensors float32 with dense rows.  No float atomics: equal inputs give equal bits.
  * Anything outside the limits, a NULL pointer or N == 0 returns hipErrorInvalidValue without a launch.

@@ -439,12 +439,13 @@ class StockMLP:
         native.mlp_backward_policy_q(self._pass(x0, x1), q_table, subset, E_sample, g1)
         return g1
 
-    def backward_policy_sample(self, x0, eps, grad_a, log_alpha, defer=False):
+    def backward_policy_sample(self, x0, eps, grad_a, log_alpha, defer=False, offline=None):
         """Gaussian-head policy (E = 1): sampling backward + network backward in one launch; `grad_a`
-        [members, N, A] are the action gradients of the ensemble members."""
+        [members, N, A] are the action gradients of the ensemble members.  `offline`: the stored actions ([N, A], rows
+        may be strided) of the offline loss, whose term on the pre-tanh sample then joins the objective."""
         N = x0.shape[-2]
         native.mlp_backward_policy_sample(self._pass(x0, None), eps, grad_a, log_alpha, self.grad_params,
-                                          self._workspace_for(N), self._reduce_mode(defer))
+                                          self._workspace_for(N), self._reduce_mode(defer), offline=offline)
         self._deferred_rows = N if defer else None
 
     def policy_step_fused_ok(self, critics: 'StockMLP', N: int) -> bool:
@@ -454,19 +455,19 @@ class StockMLP:
                                             self.member_stride, N))
 
     def policy_step_fused(self, critics: 'StockMLP', x0, action, eps, log_alpha, q_out=None, defer=False, subset=None,
-                          sample_out=None):
+                          sample_out=None, offline=None):
         """Gaussian-head policy (E = 1) against the TWO critics the objective samples (`subset`: device i32[2], None =
         members 0 and 1 of a two-member ensemble): the whole policy step in one launch (`asac_policy_step_fused`);
         `q_out` [E, N, 1] receives those critics' values of (x0, action).  `action` None: the action is sampled inside
         the launch (no policy-forward / sampling launch in front of it) and lands in `sample_out` = (a_tanh [N, A],
-        logp [N], ls [N, 2A] | None)."""
+        logp [N], ls [N, 2A] | None).  `offline`: as in `backward_policy_sample`."""
         N = x0.shape[-2]
         assert subset is not None or critics.E == 2
         a_out, logp_out, ls_out = sample_out if action is None else (None, None, None)
         native.policy_step_fused(critics.desc, critics.params, critics.member_stride, self.desc, self.params,
                                  self.member_stride, x0, N, action, eps, log_alpha, q_out, self.grad_params,
                                  self._workspace_for(N), self._reduce_mode(defer), subset=subset, a_out=a_out,
-                                 logp_out=logp_out, ls_out=ls_out)
+                                 logp_out=logp_out, ls_out=ls_out, offline=offline)
         self._deferred_rows = N if defer else None
 
     def adam_partials(self, opt, loss_out=None):

@@ -115,6 +115,17 @@ def fused_dqn_applies(*, enabled, plain_learner, d_action_sizes, c_action_size, 
                 and float32_on_device and native.discrete_sizes_ok(d_action_sizes, ensemble_q_num, n_step, batch_size))
 
 
+def fused_offline_applies(*, enabled, plain_learner, offline_loss, c_action_size, d_action_sizes, stock_networks,
+                          data_parallel, float32_on_device) -> bool:
+    """Does a continuous learner with the offline loss (`offline_enabled and offline_loss`: reference sac_base.py:1899-1900)
+    keep the native continuous path, the loss' term riding in the policy-step launches
+    (`hip_config['fused_offline']`)?  Only a plain `SAC_Base` (`plain_learner`: not an `OptionBase`) with continuous
+    actions alone, stock Q and policy networks (`stock_networks`), without a data-parallel context, on float32 device
+    parameters.  Everything else runs the eager code."""
+    return bool(enabled and plain_learner and offline_loss and c_action_size > 0 and len(d_action_sizes) == 0
+                and stock_networks and not data_parallel and float32_on_device)
+
+
 def fused_rnd_applies(*, enabled, plain_learner, d_action_sizes, c_action_size, data_parallel, float32_on_device, stack_ok,
                       state_size, n_sample=1, rows=1) -> bool:
     """Does random network distillation of this configuration run on the `asac_rnd_*` launches (`hip_config['fused_rnd']`)?
@@ -348,6 +359,7 @@ class SAC_Base(AuxHeadsMixin):
         self._fused_discrete = bool(hip_config.get('fused_discrete', True))     # asac_discrete_* (pure-discrete learner)
         self._fused_dqn = bool(hip_config.get('fused_dqn', True))               # asac_dqn_* (DQN-like discrete learner)
         self._fused_rnd = bool(hip_config.get('fused_rnd', True))               # asac_rnd_* (continuous RND, stock stacks)
+        self._fused_offline = bool(hip_config.get('fused_offline', True))       # the offline loss inside the policy-step launches
         self._rnd_stacks = None          # (RndDesc, predictor, target, tensors) | False once described (`_rnd_fused`)
         self._rnd_buffers = {}           # (B, n) -> the distillation launch's dense outputs
         # asac_drnd_* (pure-discrete RND with a policy, stock stacks): NOTES.md, "discrete RND"
@@ -1848,15 +1860,31 @@ class SAC_Base(AuxHeadsMixin):
         """Stock Q ensemble and stock policy on a continuous-only action space: the whole policy / alpha
         / write-back chain runs on libasac_hip kernels without autograd."""
         return (self._fpi is not None and self._fq is not None and bool(self.c_action_size)
-                and not self.d_action_sizes and not (self.offline_enabled and self.offline_loss))
+                and not self.d_action_sizes and (not (self.offline_enabled and self.offline_loss) or self._offline_fused()))
+
+    def _offline_fused(self) -> bool:
+        """the offline loss' term rides in the stock policy step's launches (`fused_offline_applies`)"""
+        return fused_offline_applies(
+            enabled=self._fused_offline, plain_learner=type(self)._plain_learner,
+            offline_loss=self.offline_enabled and self.offline_loss, c_action_size=self.c_action_size,
+            d_action_sizes=self.d_action_sizes, stock_networks=self._fq is not None and self._fpi is not None,
+            data_parallel=self._dist is not None,
+            float32_on_device=self._params.flat.dtype == torch.float32 and self._params.flat.is_cuda)
+
+    def _offline_plain(self) -> bool:
+        """the offline loss' term joins the plain-Gaussian autograd path of `_train_policy` (plugin critics) through
+        `asac_policy_offline_term`; an `OptionBase`, a data-parallel context or the switch off keep the eager tail"""
+        return bool(self._fused_offline and type(self)._plain_learner and self._dist is None
+                    and self._params.flat.dtype == torch.float32 and self._params.flat.is_cuda)
 
     @torch.no_grad()
-    def _train_policy_stock(self, state, ls=None):
+    def _train_policy_stock(self, state, ls=None, offline=None):
         """Policy step (reference 1841-1911) for the stock networks as an explicit kernel chain:
         [policy forward] -> rsample/tanh/log-prob -> Q ensemble forward -> objective + its gradients
         -> Q backward (input gradients only) -> sampling backward (sums the members' action gradients)
         -> policy backward -> Adam.  `ls` = the policy's [B, 2A] (loc | scale) output for `state` if
-        the caller already has it (same parameters, same input)."""
+        the caller already has it (same parameters, same input).  `offline`: the stored actions [B, A] (a strided view of
+        the window) when the offline loss is on — its term is formed inside the sampling backward of either route."""
         A, E = self.c_action_size, self.ensemble_q_num
         x = StockMLP._rows(state, self.state_size)
         B = x.shape[0]
@@ -1882,7 +1910,9 @@ class SAC_Base(AuxHeadsMixin):
                 native.squash_sample_fwd(loc, scale, self._eps_pi, a_tanh, logp)
         sub = self._subsets['pi_c']
         self.noise.subset_(sub, E)
-        self._pi_stats_src = (logp, scale)
+        # (with the offline loss the logged objective also needs the (loc | scale) rows, the noise and the stored actions)
+        self._pi_stats_src = (logp, scale) if offline is None else (
+            logp, scale, sample_out[2] if sample_out is not None else ls, self._eps_pi, offline)
         opt = self.optimizer_policy
         fold = self._dist is None and (opt.start, opt.stop) == (self._fpi._start, self._fpi._start + self._fpi.member_stride)
         if fusable and a_tanh.is_contiguous():
@@ -1890,7 +1920,7 @@ class SAC_Base(AuxHeadsMixin):
             # sampling backward and policy backward in ONE launch (bit-identical to the chain below)
             self._fpi.policy_step_fused(self._fq, x, None if sample_out is not None else a_tanh, self._eps_pi,
                                         self.log_c_alpha, q_out=self._pi_q, defer=fold, subset=sub if E != 2 else None,
-                                        sample_out=sample_out)
+                                        sample_out=sample_out, offline=offline)
         else:
             c_qs = self._fq._launch_forward(x, a_tanh, out=self._pi_q)                   # [E, B, 1]
             # objective gradients formed on chip: dL/dq inside the Q backward (from the value table), dL/dlogp =
@@ -1898,7 +1928,7 @@ class SAC_Base(AuxHeadsMixin):
             g_a = self._fq.backward_policy_q(x, a_tanh, c_qs.view(E, B), sub if self.ensemble_q_sample != E else None,
                                              self.ensemble_q_sample)                    # [E, B, A]
             # sampling backward (sums the members' action gradients) + policy backward in one launch
-            self._fpi.backward_policy_sample(x, self._eps_pi, g_a, self.log_c_alpha, defer=fold)
+            self._fpi.backward_policy_sample(x, self._eps_pi, g_a, self.log_c_alpha, defer=fold, offline=offline)
         if fold:
             self._fpi.adam_partials(opt)
             return
@@ -1907,9 +1937,10 @@ class SAC_Base(AuxHeadsMixin):
         opt.step()
 
     def _train_policy(self, obs_list, state, action, mu_d_policy_probs, ls=None):
-        if self._stock_c_only():
-            return self._train_policy_stock(state, ls)
         dsum, E = self.d_action_summed_size, self.ensemble_q_num
+        offline = self.offline_enabled and self.offline_loss
+        if self._stock_c_only():
+            return self._train_policy_stock(state, ls, offline=action[..., dsum:] if offline else None)
         if self._discrete_fused(state.shape[0]):
             # pure-discrete: the critics only supply values; objective, entropy statistic and d loss / d logits from one
             # launch; back-propagation starts at the logits
@@ -1954,7 +1985,7 @@ class SAC_Base(AuxHeadsMixin):
         # restricted to the policy: its parameters (and the fused policy's anchor); the Q ensemble only passes the
         # action gradient through (param_grads=False), so the direct accumulation reaches the policy alone
         pi_inputs = list(self.model_policy.parameters()) + ([self._fpi._anchor] if self._fpi is not None else [])
-        if self.c_action_size and not self.d_action_sizes and plain and not (self.offline_enabled and self.offline_loss):
+        if self.c_action_size and not self.d_action_sizes and plain and (not offline or self._offline_plain()):
             # continuous-only fast path: objective, its gradients and the entropy statistic from one
             # launch; back-propagation starts at (logp, q) with the kernel-produced gradients
             self.noise.normal_(self._eps_pi)
@@ -1969,8 +2000,17 @@ class SAC_Base(AuxHeadsMixin):
                                        sub if self.ensemble_q_sample != E else None, self.ensemble_q_sample,
                                        self.log_c_alpha, scale.detach(), self._stats['loss_policy'],
                                        self._grad_logp, self._grad_q, self._stats['c_entropy'])
+            heads, grads = [logp, c_qs], [self._grad_logp, self._grad_q]
+            if offline:
+                # the offline loss: + mean_b sum_d (u - stored action)^2 on the pre-tanh sample u (reference 1899-1900),
+                # value into the logged objective and gradient at u from one more launch
+                u = loc + scale * self._eps_pi
+                ls_rows = (self._ls if self._ls is not None else torch.cat([loc, scale], -1)).detach()
+                grad_u = torch.empty_like(self._eps_pi)
+                native.policy_offline_term(ls_rows, self._eps_pi, action[..., dsum:], self._stats['loss_policy'], grad_u)
+                heads, grads = heads + [u], grads + [grad_u]
             with direct_param_grads(only=pi_inputs):
-                torch.autograd.backward([logp, c_qs], [self._grad_logp, self._grad_q], inputs=pi_inputs)
+                torch.autograd.backward(heads, grads, inputs=pi_inputs)
             if self._dist is not None:
                 self._dist.all_reduce_grads(self._params.grad, *self._params.span('policy'))
             self.optimizer_policy.step()
@@ -2843,13 +2883,15 @@ class SAC_Base(AuxHeadsMixin):
         update, which is what a log line sees); `log_c_alpha` = the value the policy step itself used."""
         if self._pi_stats_src is None:
             return
-        logp, scale = self._pi_stats_src
+        logp, scale, *off = self._pi_stats_src
         E, Es = self.ensemble_q_num, self.ensemble_q_sample
         native.policy_loss_fwd_bwd(logp, self._pi_q.view(E, -1), self._subsets['pi_c'] if Es != E else None, Es,
                                    self.log_c_alpha if log_c_alpha is None else log_c_alpha, scale,
                                    self._stats['loss_policy'],
                                    torch.empty_like(self._grad_logp), torch.empty_like(self._grad_q),
                                    self._stats['c_entropy'])
+        if off:     # the offline loss' term of the step: (loc | scale) rows, noise, stored actions
+            native.policy_offline_term(off[0], off[1], off[2], self._stats['loss_policy'])
 
     def _write_train_summaries(self, step: int) -> None:
         self.summary_available = True

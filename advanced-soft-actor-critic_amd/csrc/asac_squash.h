@@ -28,6 +28,11 @@ __device__ __forceinline__ float squash_jac(float x) {
     return fmaxf(1.f - t * t, kSquashFloor);
 }
 
+// The offline loss (reference sac_base.py:1899-1900) adds mean_b sum_d (u - a)^2 to the policy objective, u = loc + eps * scale
+// the pre-tanh sample and a the stored action: its gradient at u.  The one expression of the policy-step kernels (mlp.hip)
+// and of asac_policy_offline_term (returns.hip): one evaluation order, the same bits everywhere.
+__device__ __forceinline__ float offline_grad_u(float u, float av, float inv_n) { return (2.f * (u - av)) * inv_n; }
+
 // ------------------------------------------------------------------------------------------------
 // rsample + tanh + squash-corrected log-prob, optionally fused with the probability of the STORED
 // actions under the same Gaussian.  One lane per row (A is small: 1..64).  loc / scale rows are

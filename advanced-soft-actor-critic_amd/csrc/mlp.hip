@@ -386,6 +386,9 @@ struct MlpArgs : MlpFwdArgs {
     const float* grad_a;       // [grad_a_members][N][A]  d objective / d tanh-action, summed over members
     int32_t grad_a_members;
     const float* log_alpha;    // dL/dlogp = exp(*log_alpha) / N
+    // ... with the offline loss (reference sac_base.py:1899-1900): + mean_b sum_d (u - stored action)^2 on the pre-tanh sample u
+    const float* off_action;   // stored action of (row, d) at off_action[row * off_row_stride + d], or NULL (no term)
+    int64_t off_row_stride;
 };
 
 // a TM x 64 input tile, 4 slots per thread: global -> registers (fetch) and registers -> LDS (put), so a tile
@@ -1172,13 +1175,15 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
             if (row < a.N) {
                 const float loc = head_value(a.d, d, raw_l), sc = head_value(a.d, A + d, raw_s);
                 const float ev = a.eps[row * A + d];
-                const float t = tanhf(loc + ev * sc);
+                const float u = loc + ev * sc;
+                const float t = tanhf(u);
                 const float one_m = 1.f - t * t;
                 float ga = 0.f;
                 for (int m = 0; m < a.grad_a_members; ++m) ga += a.grad_a[((int64_t)m * a.N + row) * A + d];
                 const float gl = expf(*a.log_alpha) * (1.f / (float)a.N);
                 float gx = ga * one_m;
                 if (one_m > 1e-2f) gx += gl * ((float)A * 2.f * t);     // squash-correction floor, operators.py:12-14
+                if (a.off_action) gx += offline_grad_u(u, a.off_action[row * a.off_row_stride + d], 1.f / (float)a.N);
                 g_loc = gx * head_deriv(a.d, d, raw_l);
                 g_scale = (gx * ev - gl / sc) * head_deriv(a.d, A + d, raw_s);
             }
@@ -1420,6 +1425,8 @@ __device__ __forceinline__ void ps_put_tile(const float (&v)[kPsSlots], float* x
     }
 }
 
+// OFFLINE: the offline term rides in the sampling backward (pi.off_action); the plain instantiation has none of it
+template <bool OFFLINE>
 __global__ __launch_bounds__(kPsThreads) void k_policy_step(const PolicyStepArgs a_by_value) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const ASAC_KARG PolicyStepArgs& a = *static_cast<const ASAC_KARG PolicyStepArgs*>(kernarg_base());   // (asac_common.h)
@@ -1452,6 +1459,11 @@ __global__ __launch_bounds__(kPsThreads) void k_policy_step(const PolicyStepArgs
         const int lrow = threadIdx.x / (A > 0 ? A : 1), d = threadIdx.x - lrow * A;
         if ((int)threadIdx.x < kPsRows * A && row0 + lrow < N) ev = a.pi.eps[(row0 + lrow) * A + d];
         gl = expf(*a.pi.log_alpha) * (1.f / (float)N);
+    }
+    [[maybe_unused]] float av = 0.f;       // the stored action of the lane's (row, action dim): requested here, used in the head phase
+    if constexpr (OFFLINE) {
+        const int lrow = threadIdx.x / (A > 0 ? A : 1), d = threadIdx.x - lrow * A;
+        if ((int)threadIdx.x < kPsRows * A && row0 + lrow < N) av = a.pi.off_action[(row0 + lrow) * a.pi.off_row_stride + d];
     }
     if (sample_here) {
         // ---- the policy on the tile, once, for the action: weights -> LDS (they return from the registers later) ------
@@ -1655,13 +1667,15 @@ __global__ __launch_bounds__(kPsThreads) void k_policy_step(const PolicyStepArgs
         const float raw_l = P.delta[lrow * kP + d], raw_s = P.delta[lrow * kP + A + d];
         if (row < N) {
             const float loc = head_value(a.pi.d, d, raw_l), sc = head_value(a.pi.d, A + d, raw_s);
-            const float t = tanhf(loc + ev * sc);
+            const float u = loc + ev * sc;
+            const float t = tanhf(u);
             const float one_m = 1.f - t * t;
             float ga = 0.f;
             ga += L.ga[0][lrow * kHeadPad + d];
             ga += L.ga[1][lrow * kHeadPad + d];
             float gx = ga * one_m;
             if (one_m > 1e-2f) gx += gl * ((float)A * 2.f * t);
+            if constexpr (OFFLINE) gx += offline_grad_u(u, av, 1.f / (float)N);
             g_loc = gx * head_deriv(a.pi.d, d, raw_l);
             g_scale = (gx * ev - gl / sc) * head_deriv(a.pi.d, A + d, raw_s);
         }
@@ -2779,21 +2793,40 @@ int asac_mlp_backward_policy_q(const asac_mlp_job_t* job, const float* q_table, 
                                as_stream(stream));
 }
 
-int asac_mlp_backward_policy_sample(const asac_mlp_job_t* job, const float* eps, const float* grad_a, int grad_a_members,
-                                    const float* log_alpha, float* grad_params, float* workspace, int reduce_mode,
-                                    void* stream) {
+// both policy-sample entry points; off_action == NULL: no offline term
+static int backward_policy_sample(const char* where, const asac_mlp_job_t* job, const float* eps, const float* grad_a,
+                                  int grad_a_members, const float* log_alpha, const float* off_action,
+                                  int64_t off_row_stride, float* grad_params, float* workspace, int reduce_mode,
+                                  void* stream) {
     if (!bwd_job_ok(job) || job->E != 1 || job->x1 || job->desc->in1 != 0 || !eps || !grad_a || grad_a_members < 1 ||
         !log_alpha || !grad_params || !workspace)
-        return bad_arg("asac_mlp_backward_policy_sample");
-    if (!gauss_head(*job->desc) || job->desc->head_cols[0] > 16)
-        return bad_arg("asac_mlp_backward_policy_sample: not a Gaussian-head policy");
+        return bad_arg(where);
+    if (!gauss_head(*job->desc) || job->desc->head_cols[0] > 16) return bad_arg(where);
     MlpArgs a = make_args(*job);
     a.eps = eps;
     a.grad_a = grad_a;
     a.grad_a_members = grad_a_members;
     a.log_alpha = log_alpha;
-    return mlp_backward_common("asac_mlp_backward_policy_sample", *job, a, grad_params, workspace, reduce_mode, nullptr,
-                               as_stream(stream));
+    a.off_action = off_action;             // (the kernel indexes the stored actions with 64 bits)
+    a.off_row_stride = off_row_stride;
+    return mlp_backward_common(where, *job, a, grad_params, workspace, reduce_mode, nullptr, as_stream(stream));
+}
+
+int asac_mlp_backward_policy_sample(const asac_mlp_job_t* job, const float* eps, const float* grad_a, int grad_a_members,
+                                    const float* log_alpha, float* grad_params, float* workspace, int reduce_mode,
+                                    void* stream) {
+    return backward_policy_sample("asac_mlp_backward_policy_sample", job, eps, grad_a, grad_a_members, log_alpha, nullptr, 0,
+                                  grad_params, workspace, reduce_mode, stream);
+}
+
+int asac_mlp_backward_policy_sample_offline(const asac_mlp_job_t* job, const float* eps, const float* grad_a,
+                                            int grad_a_members, const float* log_alpha, const float* off_action,
+                                            int64_t off_row_stride, float* grad_params, float* workspace, int reduce_mode,
+                                            void* stream) {
+    if (!off_action || !job || !job->desc || off_row_stride < job->desc->head_cols[0])
+        return bad_arg("asac_mlp_backward_policy_sample_offline: stored actions");
+    return backward_policy_sample("asac_mlp_backward_policy_sample_offline", job, eps, grad_a, grad_a_members, log_alpha,
+                                  off_action, off_row_stride, grad_params, workspace, reduce_mode, stream);
 }
 
 int asac_policy_step_fused_ok(const asac_mlp_desc_t* q_desc, const float* q_params, int64_t q_member_stride,
@@ -2805,15 +2838,16 @@ int asac_policy_step_fused_ok(const asac_mlp_desc_t* q_desc, const float* q_para
     return mlp_tile_rows(N, 1) == kPsRows ? 1 : 0;        // the partials' tile count is asac_mlp_backward_tiles(N, 1)
 }
 
-int asac_policy_step_fused(const asac_mlp_desc_t* q_desc, const float* q_params, int64_t q_member_stride,
-                           const asac_mlp_desc_t* pi_desc, const float* pi_params, int64_t pi_member_stride,
-                           const float* x, int64_t x_row_stride, int64_t N, const float* action, const float* eps,
-                           const float* log_alpha, const int32_t* subset, float* q_out, float* a_tanh_out,
-                           float* logp_out, float* ls_out, float* pi_grad_params, float* workspace, int reduce_mode,
-                           void* stream) {
+// both one-launch entry points; off_action == NULL: the plain instantiation, no offline term
+static int policy_step_fused(const char* where, const asac_mlp_desc_t* q_desc, const float* q_params, int64_t q_member_stride,
+                             const asac_mlp_desc_t* pi_desc, const float* pi_params, int64_t pi_member_stride,
+                             const float* x, int64_t x_row_stride, int64_t N, const float* action, const float* eps,
+                             const float* log_alpha, const int32_t* subset, const float* off_action, int64_t off_row_stride,
+                             float* q_out, float* a_tanh_out, float* logp_out, float* ls_out, float* pi_grad_params,
+                             float* workspace, int reduce_mode, void* stream) {
     if (!asac_policy_step_fused_ok(q_desc, q_params, q_member_stride, pi_desc, pi_params, pi_member_stride, N) ||
         !x || !eps || !log_alpha || !pi_grad_params || !workspace || (!action && (!a_tanh_out || !logp_out)))
-        return bad_arg("asac_policy_step_fused");
+        return bad_arg(where);
     PolicyStepArgs a{};
     asac_mlp_job_t pi{}, q{};           // both networks on the rows of x; the critics' second input: the [N][A] actions
     pi.desc = pi_desc, pi.params = pi_params, pi.member_stride = pi_member_stride;
@@ -2822,7 +2856,7 @@ int asac_policy_step_fused(const asac_mlp_desc_t* q_desc, const float* q_params,
     q.x1 = action, q.x1_row_stride = pi_desc->head_cols[0];
     a.q = make_args(q);
     a.pi = make_args(pi);
-    if (!offsets32(a.q) || !offsets32(a.pi)) return bad_arg("asac_policy_step_fused: offsets");
+    if (!offsets32(a.q) || !offsets32(a.pi)) return bad_arg(where);
     a.q.subset = subset;
     a.a_out = a_tanh_out;
     a.logp_out = logp_out;
@@ -2830,17 +2864,46 @@ int asac_policy_step_fused(const asac_mlp_desc_t* q_desc, const float* q_params,
     a.pi.eps = eps;
     a.pi.log_alpha = log_alpha;
     a.pi.partial = workspace;
+    a.pi.off_action = off_action;          // (the kernel indexes the stored actions with 64 bits)
+    a.pi.off_row_stride = off_row_stride;
     a.q_out = q_out;
-    static bool attr_done = false;
-    if (int rc = set_lds_limit(reinterpret_cast<const void*>(k_policy_step), sizeof(PsLds), attr_done,
-                               "asac_policy_step_fused: hipFuncSetAttribute"))
+    static bool attr_done = false, attr_done_offline = false;
+    if (int rc = off_action ? set_lds_limit(reinterpret_cast<const void*>(k_policy_step<true>), sizeof(PsLds),
+                                            attr_done_offline, where)
+                            : set_lds_limit(reinterpret_cast<const void*>(k_policy_step<false>), sizeof(PsLds), attr_done, where))
         return rc;
     const int tiles = (int)((N + kPsRows - 1) / kPsRows);
     hipStream_t s = as_stream(stream);
-    ASAC_LAUNCH(k_policy_step, dim3((unsigned)tiles), dim3(kPsThreads), sizeof(PsLds), s, a);
+    if (off_action) ASAC_LAUNCH(k_policy_step<true>, dim3((unsigned)tiles), dim3(kPsThreads), sizeof(PsLds), s, a);
+    else ASAC_LAUNCH(k_policy_step<false>, dim3((unsigned)tiles), dim3(kPsThreads), sizeof(PsLds), s, a);
     if (reduce_mode != ASAC_MLP_REDUCE_DEFER)
         reduce_partials(pi_desc, workspace, tiles, 1, pi_member_stride, pi_grad_params, reduce_mode, nullptr, nullptr, 0.f, s);
-    return finish_launch("asac_policy_step_fused");
+    return finish_launch(where);
+}
+
+int asac_policy_step_fused(const asac_mlp_desc_t* q_desc, const float* q_params, int64_t q_member_stride,
+                           const asac_mlp_desc_t* pi_desc, const float* pi_params, int64_t pi_member_stride,
+                           const float* x, int64_t x_row_stride, int64_t N, const float* action, const float* eps,
+                           const float* log_alpha, const int32_t* subset, float* q_out, float* a_tanh_out,
+                           float* logp_out, float* ls_out, float* pi_grad_params, float* workspace, int reduce_mode,
+                           void* stream) {
+    return policy_step_fused("asac_policy_step_fused", q_desc, q_params, q_member_stride, pi_desc, pi_params,
+                             pi_member_stride, x, x_row_stride, N, action, eps, log_alpha, subset, nullptr, 0, q_out,
+                             a_tanh_out, logp_out, ls_out, pi_grad_params, workspace, reduce_mode, stream);
+}
+
+int asac_policy_step_fused_offline(const asac_mlp_desc_t* q_desc, const float* q_params, int64_t q_member_stride,
+                                   const asac_mlp_desc_t* pi_desc, const float* pi_params, int64_t pi_member_stride,
+                                   const float* x, int64_t x_row_stride, int64_t N, const float* action, const float* eps,
+                                   const float* log_alpha, const int32_t* subset, const float* off_action,
+                                   int64_t off_row_stride, float* q_out, float* a_tanh_out, float* logp_out, float* ls_out,
+                                   float* pi_grad_params, float* workspace, int reduce_mode, void* stream) {
+    if (!off_action || !pi_desc || off_row_stride < pi_desc->head_cols[0])
+        return bad_arg("asac_policy_step_fused_offline: stored actions");
+    return policy_step_fused("asac_policy_step_fused_offline", q_desc, q_params, q_member_stride, pi_desc, pi_params,
+                             pi_member_stride, x, x_row_stride, N, action, eps, log_alpha, subset, off_action,
+                             off_row_stride, q_out, a_tanh_out, logp_out, ls_out, pi_grad_params, workspace, reduce_mode,
+                             stream);
 }
 
 static bool fits32(int64_t v) { return v >= 0 && v < 0x1fffffffLL; }

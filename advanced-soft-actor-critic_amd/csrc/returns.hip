@@ -481,6 +481,36 @@ __global__ __launch_bounds__(256) void k_policy_loss(const float* __restrict__ l
     }
 }
 
+// The offline term of the policy objective (reference sac_base.py:1899-1900): *loss_inout += mean_b sum_d (u - a)^2 with
+// u = loc + eps * scale (the pre-tanh sample) and a the stored action; optionally its gradient at u.  One workgroup, each
+// thread its rows in order, a fixed tree over the threads.  For the logged objective and the autograd path: the fused
+// policy step forms the gradient inside its own launch.
+__global__ __launch_bounds__(256) void k_policy_offline_term(const float* __restrict__ loc, const float* __restrict__ scale,
+                                                             int64_t ls_rs, const float* __restrict__ eps,
+                                                             const float* __restrict__ off_action, int64_t off_rs, int N,
+                                                             int A, float* __restrict__ loss_inout,
+                                                             float* __restrict__ grad_u_out) {
+    const float inv_n = 1.f / (float)N;
+    float part = 0.f;
+    for (int b = threadIdx.x; b < N; b += blockDim.x) {
+        for (int d = 0; d < A; ++d) {
+            const float u = loc[(int64_t)b * ls_rs + d] + eps[(int64_t)b * A + d] * scale[(int64_t)b * ls_rs + d];
+            const float av = off_action[(int64_t)b * off_rs + d];
+            const float diff = u - av;
+            part += diff * diff;
+            if (grad_u_out) grad_u_out[(int64_t)b * A + d] = offline_grad_u(u, av, inv_n);
+        }
+    }
+    __shared__ float red[256];
+    red[threadIdx.x] = part;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *loss_inout += red[0] * inv_n;
+}
+
 // Temperature objective, continuous head (reference sac_base.py:1931-1944):
 //   L = mean_b( log_alpha * (-logp_b - target) ),  dL/dlog_alpha = mean_b(-logp_b) - target
 // written straight into the flat gradient slot of log_c_alpha.
@@ -745,6 +775,17 @@ int asac_policy_loss_fwd_bwd(const float* logp, const float* q, const int32_t* s
     ASAC_LAUNCH(k_policy_loss, dim3(1), dim3(256), 0, as_stream(stream), logp, q, subset, E, E_sample, B,
                 log_alpha, scale, scale_row_stride, A, loss_out, grad_logp, grad_q, entropy_out);
     return finish_launch("asac_policy_loss_fwd_bwd");
+}
+
+int asac_policy_offline_term(const float* loc, const float* scale, int64_t ls_row_stride, const float* eps,
+                             const float* off_action, int64_t off_row_stride, int N, int A, float* loss_inout,
+                             float* grad_u_out, void* stream) {
+    if (!loc || !scale || !eps || !off_action || !loss_inout || N <= 0 || A <= 0 || ls_row_stride < A || off_row_stride < A)
+        return bad_arg("asac_policy_offline_term");
+    // (launched once, not under the repeat knob: it accumulates into *loss_inout)
+    hipLaunchKernelGGL(k_policy_offline_term, dim3(1), dim3(256), 0, as_stream(stream), loc, scale, ls_row_stride, eps,
+                       off_action, off_row_stride, N, A, loss_inout, grad_u_out);
+    return finish_launch("asac_policy_offline_term");
 }
 
 int asac_alpha_grad(const float* logp, int B, float target, float* grad_slot, void* stream) {

@@ -338,6 +338,9 @@ _SIGNATURES = {
     'asac_mlp_backward_policy_q': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     'asac_mlp_backward_policy_sample': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    'asac_mlp_backward_policy_sample_offline': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+                                                          C.c_void_p]),
     'asac_struct_size': (C.c_int64, [C.c_char_p]),
     'asac_policy_sample_q_forward_ok': (C.c_int, [C.POINTER(PiQJob)]),
     'asac_policy_sample_q_forward_jobs_ok': (C.c_int, [C.POINTER(PiQJob), C.POINTER(MlpJob), C.c_int]),
@@ -349,6 +352,12 @@ _SIGNATURES = {
                                          C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    'asac_policy_step_fused_offline': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.POINTER(MlpDesc), C.c_void_p,
+                                                 C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    'asac_policy_offline_term': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                           C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'asac_mlp_param_extent': (C.c_int64, [C.POINTER(MlpDesc)]),
     'asac_adam_step_partials': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
                                           C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
@@ -726,8 +735,8 @@ def set_profiler(p: 'LaunchProfiler | None') -> None:
     _profiler = p
 
 
-def _profiled(fn):
-    name = 'asac_' + fn.__name__
+def _profiled(fn, name=None):
+    name = name or 'asac_' + fn.__name__
 
     def wrapper(*a, **k):
         if _profiler is None:
@@ -1389,9 +1398,15 @@ def mlp_backward_policy_q(job: MlpJob, q_table, subset, E_sample, grad_x1):
            'asac_mlp_backward_policy_q')
 
 
-@_profiled
-def mlp_backward_policy_sample(job: MlpJob, eps, grad_a, log_alpha, grad_params, workspace, reduce_mode):
-    """Policy step: sampling backward + policy backward of the stock Gaussian-head policy (E = 1, no x1) in one launch."""
+def _offline_view(offline, N, A):
+    """pointer and row stride of the stored actions of the offline loss: an [N, A] view whose rows may be strided"""
+    assert offline.dtype == torch.float32 and tuple(offline.shape) == (N, A), 'offline: [N, A] float32 stored actions'
+    assert offline.stride(1) == 1, 'offline: the action dimension must be contiguous'
+    assert N == 1 or offline.stride(0) >= A, 'offline: overlapping rows'
+    return _p(offline), (offline.stride(0) if N > 1 else max(offline.stride(0), A))
+
+
+def _mlp_backward_policy_sample(job: MlpJob, eps, grad_a, log_alpha, grad_params, workspace, reduce_mode):
     global _last_work
     _last_work = _pass_flops(job, backward=True)
     N, A = job.N, job.desc.contents.head_cols[0]
@@ -1401,17 +1416,65 @@ def mlp_backward_policy_sample(job: MlpJob, eps, grad_a, log_alpha, grad_params,
                                                   _stream()), 'asac_mlp_backward_policy_sample')
 
 
+_mlp_backward_policy_sample = _profiled(_mlp_backward_policy_sample, 'asac_mlp_backward_policy_sample')
+
+
+@_profiled
+def mlp_backward_policy_sample_offline(job: MlpJob, eps, grad_a, log_alpha, offline, grad_params, workspace, reduce_mode):
+    """`mlp_backward_policy_sample` with the offline loss' term on the pre-tanh sample (stored actions `offline`)."""
+    global _last_work
+    _last_work = _pass_flops(job, backward=True)
+    N, A = job.N, job.desc.contents.head_cols[0]
+    assert eps.is_contiguous() and eps.numel() == N * A and grad_a.is_contiguous() and grad_a.numel() % (N * A) == 0
+    po, rso = _offline_view(offline, N, A)
+    _check(load().asac_mlp_backward_policy_sample_offline(C.byref(job), _p(eps), _p(grad_a), grad_a.numel() // (N * A),
+                                                          _p(log_alpha), po, rso, _p(grad_params), _p(workspace),
+                                                          int(reduce_mode), _stream()),
+           'asac_mlp_backward_policy_sample_offline')
+
+
+def mlp_backward_policy_sample(job: MlpJob, eps, grad_a, log_alpha, grad_params, workspace, reduce_mode, offline=None):
+    """Policy step: sampling backward + policy backward of the stock Gaussian-head policy (E = 1, no x1) in one launch.
+    `offline`: the stored actions ([N, A], rows may be strided) of the offline loss, or None."""
+    if offline is None:
+        return _mlp_backward_policy_sample(job, eps, grad_a, log_alpha, grad_params, workspace, reduce_mode)
+    return mlp_backward_policy_sample_offline(job, eps, grad_a, log_alpha, offline, grad_params, workspace, reduce_mode)
+
+
 def policy_step_fused_ok(q_desc, q_params, q_member_stride, pi_desc, pi_params, pi_member_stride, N) -> bool:
     return bool(load().asac_policy_step_fused_ok(C.byref(q_desc), _p(q_params), q_member_stride, C.byref(pi_desc),
                                                  _p(pi_params), pi_member_stride, N))
 
 
-@_profiled
 def policy_step_fused(q_desc, q_params, q_member_stride, pi_desc, pi_params, pi_member_stride, x, N, action, eps,
                       log_alpha, q_out, pi_grad_params, workspace, reduce_mode, subset=None, a_out=None, logp_out=None,
-                      ls_out=None):
+                      ls_out=None, offline=None):
     """The stock networks' whole policy step (two critics) in one launch: critics forward on (x, action), objective
-    gradient, critics backward to the action, sampling backward, policy backward (per-tile partials / reduced)."""
+    gradient, critics backward to the action, sampling backward, policy backward (per-tile partials / reduced).
+    `offline`: the stored actions ([N, A], rows may be strided) of the offline loss, or None."""
+    if offline is not None:
+        _offline_view(offline, N, pi_desc.head_cols[0])       # (refused here, before anything is launched)
+        return policy_step_fused_offline(q_desc, q_params, q_member_stride, pi_desc, pi_params, pi_member_stride, x, N,
+                                         action, eps, log_alpha, q_out, pi_grad_params, workspace, reduce_mode, subset,
+                                         a_out, logp_out, ls_out, offline)
+    return _policy_step_fused_plain(q_desc, q_params, q_member_stride, pi_desc, pi_params, pi_member_stride, x, N, action,
+                                    eps, log_alpha, q_out, pi_grad_params, workspace, reduce_mode, subset, a_out, logp_out,
+                                    ls_out)
+
+
+@_profiled
+def policy_step_fused_offline(q_desc, q_params, q_member_stride, pi_desc, pi_params, pi_member_stride, x, N, action, eps,
+                              log_alpha, q_out, pi_grad_params, workspace, reduce_mode, subset, a_out, logp_out, ls_out,
+                              offline):
+    """`policy_step_fused` with the offline loss' term on the pre-tanh sample (stored actions `offline`)."""
+    return _policy_step_fused(q_desc, q_params, q_member_stride, pi_desc, pi_params, pi_member_stride, x, N, action, eps,
+                              log_alpha, q_out, pi_grad_params, workspace, reduce_mode, subset, a_out, logp_out, ls_out,
+                              offline)
+
+
+def _policy_step_fused(q_desc, q_params, q_member_stride, pi_desc, pi_params, pi_member_stride, x, N, action, eps,
+                       log_alpha, q_out, pi_grad_params, workspace, reduce_mode, subset=None, a_out=None, logp_out=None,
+                       ls_out=None, offline=None):
     global _last_work
     _last_work = (mlp_flops(q_desc, 2, N, backward=True, param_grads=False)
                   + mlp_flops(pi_desc, 1, N, backward=True, param_grads=True))
@@ -1425,11 +1488,23 @@ def policy_step_fused(q_desc, q_params, q_member_stride, pi_desc, pi_params, pi_
         assert ls_out is None or (ls_out.is_contiguous() and ls_out.numel() == 2 * N * A)
     assert q_out is None or (q_out.is_contiguous() and q_out.numel() % N == 0 and q_out.numel() >= 2 * N)
     assert subset is None or (subset.dtype == torch.int32 and subset.numel() == 2)
+    if offline is not None:
+        po, rso = _offline_view(offline, N, A)
+        _check(load().asac_policy_step_fused_offline(C.byref(q_desc), _p(q_params), q_member_stride, C.byref(pi_desc),
+                                                     _p(pi_params), pi_member_stride, p0, rs0, N, _p(action), _p(eps),
+                                                     _p(log_alpha), _p(subset), po, rso, _p(q_out), _p(a_out),
+                                                     _p(logp_out), _p(ls_out), _p(pi_grad_params), _p(workspace),
+                                                     int(reduce_mode), _stream()),
+               'asac_policy_step_fused_offline')
+        return
     _check(load().asac_policy_step_fused(C.byref(q_desc), _p(q_params), q_member_stride, C.byref(pi_desc), _p(pi_params),
                                          pi_member_stride, p0, rs0, N, _p(action), _p(eps), _p(log_alpha), _p(subset),
                                          _p(q_out), _p(a_out), _p(logp_out), _p(ls_out), _p(pi_grad_params), _p(workspace),
                                          int(reduce_mode), _stream()),
            'asac_policy_step_fused')
+
+
+_policy_step_fused_plain = _profiled(_policy_step_fused, 'asac_policy_step_fused')
 
 
 @_profiled
@@ -2079,6 +2154,21 @@ def policy_loss_fwd_bwd(logp, q, subset, E_sample, log_alpha, scale, loss_out, g
     _check(load().asac_policy_loss_fwd_bwd(_p(logp), _p(q), _p(subset), E, E_sample, B, _p(log_alpha), _p(scale),
                                            rs, A, _p(loss_out), _p(grad_logp), _p(grad_q), _p(entropy_out), _stream()),
            'asac_policy_loss_fwd_bwd')
+
+
+@_profiled
+def policy_offline_term(ls, eps, offline, loss_inout, grad_u_out=None):
+    """The offline loss' term of the policy objective: `loss_inout += mean_b sum_d (u - a)^2`, u = loc + eps * scale from
+    the [N, 2A] rows `ls` = (loc | scale), a the stored actions `offline` ([N, A], rows may be strided); with
+    `grad_u_out` ([N, A]) also its gradient at u."""
+    N, A = eps.shape[0], eps.shape[-1]
+    assert ls.dtype == torch.float32 and tuple(ls.shape) == (N, 2 * A) and ls.stride(1) == 1
+    assert eps.is_contiguous() and eps.numel() == N * A
+    assert grad_u_out is None or (grad_u_out.is_contiguous() and grad_u_out.numel() == N * A)
+    po, rso = _offline_view(offline, N, A)
+    rs = ls.stride(0) if N > 1 else max(ls.stride(0), 2 * A)
+    _check(load().asac_policy_offline_term(_p(ls), C.c_void_p(ls.data_ptr() + 4 * A), rs, _p(eps), po, rso, N, A,
+                                           _p(loss_inout), _p(grad_u_out), _stream()), 'asac_policy_offline_term')
 
 
 @_profiled

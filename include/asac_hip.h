@@ -468,6 +468,15 @@ int asac_policy_loss_fwd_bwd(const float* logp, const float* q, const int32_t* s
                              int B, const float* log_alpha, const float* scale, int64_t scale_row_stride, int A,
                              float* loss_out, float* grad_logp, float* grad_q, float* entropy_out, void* stream);
 
+/* The offline loss' term of that objective (sac_base.py:1899-1900): *loss_inout += mean_b sum_d (u - a)^2 with
+ * u = loc + eps * scale the pre-tanh sample and a the stored action; grad_u_out [N][A] (may be NULL) = 2 (u - a) / N.
+ * One workgroup, fixed summation order.  loc, scale: rows ls_row_stride floats apart; eps [N][A]; off_action: rows
+ * off_row_stride floats apart.  For the logged objective and the autograd path; the fused policy step forms the
+ * gradient inside its own launch (the *_offline entry points below). */
+int asac_policy_offline_term(const float* loc, const float* scale, int64_t ls_row_stride, const float* eps,
+                             const float* off_action, int64_t off_row_stride, int N, int A, float* loss_inout,
+                             float* grad_u_out, void* stream);
+
 /* Temperature gradient of the continuous head (sac_base.py:1931-1944):
  * *grad_slot = mean_b(-logp_b) - target, where target = target_c_alpha * (-A).  grad_slot is the
  * flat-gradient element of log_c_alpha. */
@@ -694,6 +703,16 @@ int asac_policy_step_fused(const asac_mlp_desc_t* q_desc, const float* q_params,
                            const float* log_alpha, const int32_t* subset, float* q_out, float* a_tanh_out,
                            float* logp_out, float* ls_out, float* pi_grad_params, float* workspace, int reduce_mode,
                            void* stream);
+/* ... with the offline loss (sac_base.py:1899-1900): the objective gains mean_b sum_d (u - a)^2, u = loc + eps * scale the
+ * pre-tanh sample, a = off_action[row * off_row_stride + d] the stored action (non-NULL, off_row_stride >= A); its
+ * gradient 2 (u - a) / N joins the sampling backward inside the same launch.  Bit for bit the chain with
+ * asac_mlp_backward_policy_sample_offline.  asac_policy_step_fused is this entry point without the term. */
+int asac_policy_step_fused_offline(const asac_mlp_desc_t* q_desc, const float* q_params, int64_t q_member_stride,
+                                   const asac_mlp_desc_t* pi_desc, const float* pi_params, int64_t pi_member_stride,
+                                   const float* x, int64_t x_row_stride, int64_t N, const float* action, const float* eps,
+                                   const float* log_alpha, const int32_t* subset, const float* off_action,
+                                   int64_t off_row_stride, float* q_out, float* a_tanh_out, float* logp_out, float* ls_out,
+                                   float* pi_grad_params, float* workspace, int reduce_mode, void* stream);
 
 /* The policy step's policy backward (sac_base.py:1883-1906, stock Gaussian-head ModelPolicy): the
  * gradient of the objective w.r.t. (loc | scale) — asac_squash_sample_bwd's math with dL/dlogp =
@@ -703,6 +722,12 @@ int asac_policy_step_fused(const asac_mlp_desc_t* q_desc, const float* q_params,
 int asac_mlp_backward_policy_sample(const asac_mlp_job_t* job, const float* eps, const float* grad_a, int grad_a_members,
                                     const float* log_alpha, float* grad_params, float* workspace, int reduce_mode,
                                     void* stream);
+/* ... with the offline loss' term 2 (u - a) / N added to the gradient at the pre-tanh sample u, a =
+ * off_action[row * off_row_stride + d] (non-NULL, off_row_stride >= A). */
+int asac_mlp_backward_policy_sample_offline(const asac_mlp_job_t* job, const float* eps, const float* grad_a,
+                                            int grad_a_members, const float* log_alpha, const float* off_action,
+                                            int64_t off_row_stride, float* grad_params, float* workspace, int reduce_mode,
+                                            void* stream);
 
 /* floats of one member's parameter block that the network actually uses (<= member_stride) */
 int64_t asac_mlp_param_extent(const asac_mlp_desc_t* desc_host);

@@ -79,6 +79,16 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// "Every global load of this wave has landed", said to the compiler: a real `s_waitcnt vmcnt(0)`, which its wait-counter
+// pass reads.  A register a load fills and only SOME waves consume (a bias or head-bias slot written to LDS under
+// `threadIdx.x < 64`, the noise of the lanes that have a (row, action dim)) stays "in flight" in that pass's books on every
+// wave that branches round the consumer, and the next reuse of the register gets a full `vmcnt(0)` — wherever that is.  In
+// the backward kernels it fell behind the parameter-gradient stores: the chain waves waited for the acknowledgement of
+// their own bias-gradient / head-tile stores at the top of every reverse layer's dX product.  Placed where the loads have
+// to be in anyway (the staging barrier; the policy's weights leaving the registers), it costs nothing there and the
+// phases behind it carry no vmcnt wait at all.
+__device__ __forceinline__ void loads_landed() { __builtin_amdgcn_s_waitcnt(0x0F70); }   // vmcnt(0), expcnt / lgkmcnt open
+
 __device__ __forceinline__ int round4(int v) { return (v + 3) & ~3; }
 
 // stage a row-major [rows][cols] global matrix into LDS [64][kP], zero padded to 64 x 64
@@ -1007,6 +1017,18 @@ struct RetIn<true> {
 // dX chains have four column tiles, i.e. work for four waves — the others share the staging (its loads, LDS writes and
 // address arithmetic are dealt over all 512 / 1024 threads) and the weight-gradient tiles (ps_grad_weight: two / one
 // 16 x 16 tiles per wave and layer instead of four; the same MFMA chain per tile: the same partial sums).
+// Barriers and waits (all of this for W8 != 0 alone; the generic instantiations compile to the text they had):
+//   * `__syncthreads()` here IS an LDS-only barrier already — `s_waitcnt lgkmcnt(0)` + `s_barrier` in this kernel's ISA,
+//     no vmcnt drain (workgroup-scope release needs none on gfx950) — and `lds_barrier()` gives instruction for
+//     instruction the same code.  What held the chain waves up behind a store was the compiler's own `s_waitcnt
+//     vmcnt(0)` in the middle of a reverse layer's dX operand reads (see `loads_landed`, called at the staging barrier).
+//     Invariant it rests on: no thread reads global memory another thread of the launch has written (the slabs,
+//     grad_bias, loss_partial, y_out and the input gradients are the NEXT launch's), and every LDS word a phase reads was
+//     written in front of a barrier.
+//   * the Q-loss mode's per-row operands are requested in the staging, not one round trip per row in the loss phase
+//   * reverse layers alternate between two delta tiles: one barrier per layer; the second tile lies in dynamic LDS behind
+//     the tile struct (behind RET's arrays), and `MlpBwdLds` and every other instantiation's LDS stay as they were
+//   * layer 0's dX product is formed only when an input gradient is asked for
 template <int TM, bool WIDE, int NB, bool RET = false, int W8 = 0>      // W8: 0, or the number of waves (8 / 16)
 __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArgs a, const RetIn<RET> rv) {
     static_assert(W8 == 0 || ((W8 == 8 || W8 == 16) && TM == 16 && NB == 3 && !WIDE), "8 / 16 waves: 16-row tiles of the stock networks");
@@ -1029,6 +1051,7 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
     const int col = ct * 16 + (lane & 15);
 
     MLP_STAMP(0);
+    [[maybe_unused]] float ql_tq[4] = {0.f, 0.f, 0.f, 0.f}, ql_w[4] = {1.f, 1.f, 1.f, 1.f}, ql_y[4] = {0.f, 0.f, 0.f, 0.f};
     // ---- staging: input tile, every weight, the incoming gradient tile (padded to 16 columns) -------
     // (a first layer wider than 64 inputs: second halves in the spare tiles x[kMaxB] / w[nb], desc_ok keeps nb < kMaxB)
     constexpr bool wide = WIDE;              // K0 > 64
@@ -1048,6 +1071,21 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
         }
         StagedNet<THREADS> regs;
         net_fetch_fixed<THREADS, NB>(q, regs);
+        if constexpr (W8 != 0) {
+            // Q-loss mode: the loss phase's per-row operands (target-network value, IS weight, y) of the head wave's four
+            // rows per lane, requested with the weights — read where they are used, each row's pair sits under its own
+            // `row < N` and costs the phase a memory round trip of its own, four in a row
+            if (!a.gout && !a.eps && !a.q_table && wave < RT) {       // (the mode: uniform)
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) {
+                    const int64_t lr_row = row0 + wave * 16 + 4 * (lane >> 4) + rr;
+                    const int64_t rc = lr_row < a.N ? lr_row : a.N - 1;
+                    ql_tq[rr] = a.tq[(int64_t)e * a.N + rc];
+                    if (a.w) ql_w[rr] = a.w[rc];          // (a.w: uniform)
+                    if constexpr (!RET) ql_y[rr] = a.y[rc];
+                }
+            }
+        }
         if constexpr (RET) {
             const asac_vtrace_args_t& v = rv.v;
             const int n = v.n, pitch = (n + 1) | 1;
@@ -1094,6 +1132,7 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
         net_put<THREADS>(a.d, P, K0, wide, regs, L);
         L.delta[r * kP + c] = gin;
     }
+    if constexpr (W8 != 0) loads_landed();
     __syncthreads();
     MLP_STAMP(1);
     if constexpr (RET) {     // one lane per row of the tile: y = V(s_0) + scan; first read in the loss phase (barriers between)
@@ -1233,11 +1272,16 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
                         if constexpr (RET) {
                             const int pitch = (rv.v.n + 1) | 1;
                             y_row = reinterpret_cast<const float*>(smem_raw + sizeof(MlpBwdLds<TM>))[(2 * pitch + 1) * TM + lrow];
+                        } else if constexpr (W8 != 0) {
+                            y_row = ql_y[r];
                         } else {
                             y_row = a.y[row];
                         }
-                        part += clipped_q_loss_row(raw[r] + L.head_bias[0], a.tq[(int64_t)e * a.N + row], y_row,
-                                                   a.w ? a.w[row] : 1.f, a.clip_eps, &g);
+                        if constexpr (W8 != 0)          // (the staging's prefetch: the same words)
+                            part += clipped_q_loss_row(raw[r] + L.head_bias[0], ql_tq[r], y_row, ql_w[r], a.clip_eps, &g);
+                        else
+                            part += clipped_q_loss_row(raw[r] + L.head_bias[0], a.tq[(int64_t)e * a.N + row], y_row,
+                                                       a.w ? a.w[row] : 1.f, a.clip_eps, &g);
                     }
                     L.delta[lrow * kP] = inv_n * g;
                 }
@@ -1286,39 +1330,50 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
 
     // ---- blocks in reverse ---------------------------------------------------------------------------------
     f32x4 g_hi = {0.f, 0.f, 0.f, 0.f};       // input gradient of columns 64.. (wide first layer)
+    // W8: a SECOND delta tile behind the tile struct (behind RET's arrays) — a layer's delta goes to the tile the previous
+    // layer did not use, whose last readers (two layers up) are a barrier behind already: one barrier per layer, not two
+    float* dtile = L.delta;
+    [[maybe_unused]] float* spare = nullptr;
+    if constexpr (W8 != 0) {
+        spare = reinterpret_cast<float*>(smem_raw + sizeof(MlpBwdLds<TM>));
+        if constexpr (RET) spare += (2 * ((rv.v.n + 1) | 1) + 2) * TM;
+    }
 #pragma unroll
     for (int l = kMaxB - 1; l >= 0; --l) {
         if (l < nb) {
             const int W = fixed ? kMaxW : a.d.width[l];
             const int Kin = (l == 0) ? K0 : (fixed ? kMaxW : a.d.width[l - 1]);
-            __syncthreads();   // readers of the previous delta tile are done
+            if constexpr (W8 != 0) dtile = dtile == spare ? L.delta : spare;
+            else __syncthreads();   // readers of the previous delta tile are done
             if (comp) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = rt * 16 + 4 * (lane >> 4) + r;
-                    L.delta[row * kP + col] = col < W ? g[r] * z[l][r] : 0.f;     // z holds gelu'(pre-activation)
+                    dtile[row * kP + col] = col < W ? g[r] * z[l][r] : 0.f;     // z holds gelu'(pre-activation)
                 }
             }
             __syncthreads();
             if (l == 2) MLP_STAMP(16);
             if (part) {
                 if (l == 0 && wide) {
-                    grad_weight<TM>(L.delta, 0, L.x[0], W, kMaxW, part + a.d.w_off[0], K0);
-                    grad_weight<TM>(L.delta, 0, x_hi, W, K0 - kMaxW, part + a.d.w_off[0] + kMaxW, K0);
+                    grad_weight<TM>(dtile, 0, L.x[0], W, kMaxW, part + a.d.w_off[0], K0);
+                    grad_weight<TM>(dtile, 0, x_hi, W, K0 - kMaxW, part + a.d.w_off[0] + kMaxW, K0);
                 } else if constexpr (W8 != 0) {
                     // (the waves without a column tile take the weight-gradient tiles; waves 0..3 go straight on to the
                     // bias gradients and the dX chain: the two run side by side)
-                    grad_weight_tiles(L.delta, 0, L.x[l], W, Kin, part + a.d.w_off[l], wave - 4, W8 - 4);
+                    grad_weight_tiles(dtile, 0, L.x[l], W, Kin, part + a.d.w_off[l], wave - 4, W8 - 4);
                 } else {
-                    grad_weight<TM>(L.delta, 0, L.x[l], W, Kin, part + a.d.w_off[l]);
+                    grad_weight<TM>(dtile, 0, L.x[l], W, Kin, part + a.d.w_off[l]);
                 }
                 if (l == 2) MLP_STAMP(17);
-                grad_bias<TM>(L.delta, 0, W, part + a.d.b_off[l]);
+                grad_bias<TM>(dtile, 0, W, part + a.d.b_off[l]);
                 if (l == 2) MLP_STAMP(18);
             }
-            if (l == 0 && wide && (a.gx0 || a.gx1)) g_hi = gemm_tile_nt(L.delta, w_hi, round4(W), rt, ct);
-            if (comp) {
-                f32x4 gin = gemm_tile_nt(L.delta, L.w[l], fixed ? kMaxW : round4(W), rt, ct);   // d x_{l-1}[row][k]
+            if (l == 0 && wide && (a.gx0 || a.gx1)) g_hi = gemm_tile_nt(dtile, w_hi, round4(W), rt, ct);
+            // (W8: nobody asked for the input gradient — the headline's states have no parameters behind them — so the first
+            // layer's dX product, the kernel's tail, is not formed)
+            if (comp && (W8 == 0 || l > 0 || a.gx0 || a.gx1)) {
+                f32x4 gin = gemm_tile_nt(dtile, L.w[l], fixed ? kMaxW : round4(W), rt, ct);   // d x_{l-1}[row][k]
                 if (a.d.residual[l]) gin += g;
                 g = gin;
             }
@@ -1360,6 +1415,13 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
 // weights travel in registers meanwhile and take over the critics' LDS once they are done with it; in the policy
 // phase the 16 (heads: 8) independent weight-gradient tiles of a layer are dealt over all 8 waves.  Every MFMA
 // chain has the operand order of the three separate kernels: results are bit-identical to theirs.
+// Barriers and waits: as in k_mlp_bwd's 16-wave form — every `__syncthreads()` of this kernel compiles to `s_waitcnt
+// lgkmcnt(0)` + `s_barrier` (no vmcnt drain: the policy's weights cross eleven of them in flight, under counted waits);
+// no thread reads global memory another thread of the launch wrote (q_out, a_out, logp_out, ls_out and the partial slabs
+// belong to later launches); `loads_landed()` where the policy's weights leave the registers keeps the compiler from
+// putting a full `vmcnt(0)` behind the head's weight-gradient stores (it did: the noise / temperature registers were
+// still "in flight" on the waves that never consume them).  Both reverse chains alternate between two delta tiles (one
+// barrier per layer); the critics' layer-0 dX product is formed by the column tile(s) that hold action columns alone.
 constexpr int kPsWaves = ASAC_PS_WAVES;
 constexpr int kPsThreads = 64 * kPsWaves;
 constexpr int kPsSlots = 1024 / kPsThreads;         // of the 16 x 64 input tile per thread
@@ -1372,13 +1434,14 @@ struct PsQLds {       // one critic: weights, scalar head, bias, two activation 
     float head_bias[kHeadPad];
     float xs[2][kPsRows * kP];
 };
-struct PsPiLds {      // the policy's backward: weights, heads, block inputs x_0..x_3, one delta tile
+struct PsPiLds {      // the policy's backward: weights, heads, block inputs x_0..x_3, two delta tiles
     float w[3][kMaxW * kP];
     float head[kHeadPad * kP];
     float bias[3][kMaxW];
     float head_bias[kHeadPad];
     float x[4][kPsRows * kP];
     float delta[kPsRows * kP];
+    float delta2[kPsRows * kP];            // the reverse layers alternate between the two: one barrier per layer
 };
 struct PsLds {
     PsQLds q[2];                           // the policy phase's PsPiLds overlays this
@@ -1598,15 +1661,18 @@ __global__ __launch_bounds__(kPsThreads) void k_policy_step(const PolicyStepArgs
     // ---- critics backward to the action ---------------------------------------------------------------------------
     f32x4 g = {0.f, 0.f, 0.f, 0.f};
     if (qwave) g = gemm_tile_nt(qdelta, Q.head, kHeadPad, 0, ct);
+    // a layer's delta goes to the activation tile the previous layer's did NOT use (x_3's first: the head has read it, and
+    // the critics get no parameter gradients, so nobody wants it again); that tile's last readers, two layers up, are a
+    // barrier behind already: one barrier per layer.  Layer 0's dX is wanted for the action columns alone.
 #pragma unroll
     for (int l = 2; l >= 0; --l) {
-        __syncthreads();
+        qdelta = Q.xs[cur ^ (l & 1)];
         if (qwave) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) qdelta[(4 * (lane >> 4) + r) * kP + col] = g[r] * z[l][r];
         }
         __syncthreads();
-        if (qwave) {
+        if (qwave && (l > 0 || (ct * 16 < K0q && ct * 16 + 16 > S))) {
             f32x4 gin = gemm_tile_nt(qdelta, Q.w[l], kMaxW, 0, ct);
             if (a.q.d.residual[l]) gin += g;
             g = gin;
@@ -1623,6 +1689,7 @@ __global__ __launch_bounds__(kPsThreads) void k_policy_step(const PolicyStepArgs
     net_put_fixed<kPsThreads, 3>(rp, P);
     ps_put_tile(in_pi, P.x[0]);
     if (threadIdx.x < kPsRows * kHeadPad) P.delta[(threadIdx.x >> 4) * kP + (threadIdx.x & 15)] = 0.f;
+    loads_landed();         // (the policy's weights have just left the registers; the noise and the temperature came before them)
     __syncthreads();
     MLP_STAMP(6);
     f32x4 zp[3];
@@ -1706,17 +1773,18 @@ __global__ __launch_bounds__(kPsThreads) void k_policy_step(const PolicyStepArgs
 #pragma unroll
     for (int l = 2; l >= 0; --l) {
         const int Kin = l == 0 ? K0p : kMaxW;
-        __syncthreads();
+        // (layers 2 and 0 in the second tile, layer 1 in the head's: as in the critics' backward, one barrier per layer)
+        float* pdelta = (l & 1) ? P.delta : P.delta2;
         if (wave < 4) {
             const int pc = wave * 16 + (lane & 15);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) P.delta[(4 * (lane >> 4) + r) * kP + pc] = gp[r] * zp[l][r];
+            for (int r = 0; r < 4; ++r) pdelta[(4 * (lane >> 4) + r) * kP + pc] = gp[r] * zp[l][r];
         }
         __syncthreads();
-        ps_grad_weight(P.delta, 0, P.x[l], kMaxW, Kin, part + a.pi.d.w_off[l]);
-        grad_bias<kPsRows>(P.delta, 0, kMaxW, part + a.pi.d.b_off[l]);
+        ps_grad_weight(pdelta, 0, P.x[l], kMaxW, Kin, part + a.pi.d.w_off[l]);
+        grad_bias<kPsRows>(pdelta, 0, kMaxW, part + a.pi.d.b_off[l]);
         if (l > 0 && wave < 4) {
-            f32x4 gin = gemm_tile_nt(P.delta, P.w[l], kMaxW, 0, wave);
+            f32x4 gin = gemm_tile_nt(pdelta, P.w[l], kMaxW, 0, wave);
             if (a.pi.d.residual[l]) gin += gp;
             gp = gin;
         }
@@ -2574,14 +2642,15 @@ static int launch_backward(const char* where, const asac_mlp_desc_t* desc, MlpAr
         return 0;
     };
     const size_t lds = sizeof(MlpBwdLds<TM>);
+    constexpr size_t spare = w8 ? (size_t)TM * kP * sizeof(float) : 0;      // the 8- / 16-wave kernels' second delta tile
     if (ret) {             // (asac_mlp_backward_qloss_return_ok has said yes: stock network, the tile's steps fit)
-        const size_t lds_ret = lds + (size_t)(2 * ((ret->v.n + 1) | 1) + 2) * TM * sizeof(float);
+        const size_t lds_ret = lds + (size_t)(2 * ((ret->v.n + 1) | 1) + 2) * TM * sizeof(float) + spare;
         // one thread per (row, step) of the tile: the launch's own thread count bounds n (16 waves: n <= 64)
         if (!stock || TM * ret->v.n > stock_threads || lds_ret > 128 * 1024) return bad_arg(where);
         return launch(k_mlp_bwd<TM, false, 3, true, w8>, attr_ret, 128 * 1024, stock_threads, lds_ret, *ret);
     }
     if (wide) return launch(k_mlp_bwd<TM, true, 0>, attr_wide, lds, threads_of<TM>(), lds, RetIn<false>{});
-    if (stock) return launch(k_mlp_bwd<TM, false, 3, false, w8>, attr_stock, lds, stock_threads, lds, RetIn<false>{});
+    if (stock) return launch(k_mlp_bwd<TM, false, 3, false, w8>, attr_stock, lds + spare, stock_threads, lds + spare, RetIn<false>{});
     return launch(k_mlp_bwd<TM, false, 0>, attr_done, lds, threads_of<TM>(), lds, RetIn<false>{});
 }
 
@@ -3107,7 +3176,8 @@ int asac_mlp_backward_qloss_return_ok(const asac_mlp_job_t* job, const asac_vtra
     if (wide_input(*job->desc) || !stock3(*job->desc, job->params, job->member_stride)) return 0;
     const int tm = mlp_tile_rows(job->N, job->E);
     const size_t lds = (tm == 16 ? sizeof(MlpBwdLds<16>) : sizeof(MlpBwdLds<32>)) +
-                       (size_t)(2 * ((ret->n + 1) | 1) + 2) * tm * sizeof(float);
+                       (size_t)(2 * ((ret->n + 1) | 1) + 2) * tm * sizeof(float) +
+                       (tm == 16 && ASAC_BWD_WAVES ? 16 * kP * sizeof(float) : 0);      // (the second delta tile)
     // one thread per (row, step) of a tile: 16-row tiles run ASAC_BWD_WAVES waves (n <= 64 with 16), 32-row tiles 512 threads
     const int threads = tm == 16 ? 64 * ASAC_BWD_WAVES : 32 * 16;
     return tm * ret->n <= threads && lds <= 128 * 1024;

@@ -152,10 +152,13 @@ class ModelPolicy(ModelBasePolicy):
         if self.c_action_size:
             z = self.c_dense(h)
             mean, logstd = self.mean_dense(z), self.logstd_dense(z)
-            c_policy = torch.distributions.Normal(torch.tanh(mean / 5.) * 5.,
-                                                  torch.exp(torch.clamp(logstd, -20, 0.5)),
-                                                  validate_args=False)
+            c_policy = torch.distributions.Normal(*self.c_bounded(mean, logstd), validate_args=False)
         return d_policy, c_policy
+
+    @staticmethod
+    def c_bounded(mean, logstd):
+        """`c_head_raw` / `heads_raw` -> (loc, scale) of the continuous head's Normal"""
+        return torch.tanh(mean / 5.) * 5., torch.exp(torch.clamp(logstd, -20, 0.5))
 
 
 class ModelTermination(nn.Module):

@@ -103,6 +103,21 @@ def fused_discrete_applies(*, enabled, plain_learner, d_action_sizes, c_action_s
                 and native.discrete_sizes_ok(d_action_sizes, ensemble_q_num, n_step, batch_size))
 
 
+def fused_hybrid_applies(*, enabled, plain_learner, d_action_sizes, c_action_size, discrete_dqn_like, offline_loss, siamese,
+                         use_prediction, data_parallel, float32_on_device, clip_epsilon, plain_gaussian, ensemble_q_num,
+                         n_step, batch_size) -> bool:
+    """Does a step of this configuration run the policy-based learner's arithmetic of a HYBRID action space on the
+    `asac_hybrid_*` launches (`hip_config['fused_hybrid']`, default off)?  Only a plain `SAC_Base` step (`plain_learner`:
+    not an `OptionBase`) with discrete branches and continuous actions and a policy (no DQN-like target), without an offline
+    loss, a siamese or a prediction head or a data-parallel context, on float32 device tensors, with the clipped Q loss
+    (`clip_epsilon > 0`: the reference's doubling at 0 stays eager) and a continuous head that (loc, scale) fully describe
+    (`plain_gaussian`), within the entry points' size limits.  Everything else runs the eager code."""
+    return bool(enabled and plain_learner and len(d_action_sizes) > 0 and c_action_size > 0 and not discrete_dqn_like
+                and not offline_loss and not siamese and not use_prediction and not data_parallel and float32_on_device
+                and clip_epsilon > 0 and plain_gaussian
+                and native.hybrid_sizes_ok(d_action_sizes, c_action_size, ensemble_q_num, n_step, batch_size))
+
+
 def fused_dqn_applies(*, enabled, plain_learner, d_action_sizes, c_action_size, discrete_dqn_like, offline_loss, siamese,
                       use_prediction, curiosity, data_parallel, float32_on_device, ensemble_q_num, n_step, batch_size) -> bool:
     """Does a step of this configuration run the pure-discrete, DQN-like learner's arithmetic on the `asac_dqn_*`
@@ -369,6 +384,10 @@ class SAC_Base(AuxHeadsMixin):
         self._fused_act = bool(hip_config.get('fused_act', True))               # asac_act_policy (policy-based acting)
         # asac_siamese_* (ATC / BYOL loss and gradients as one launch an encoder); off by default: NOTES.md, "siamese losses"
         self._fused_siamese = bool(hip_config.get('fused_siamese', False))
+        # asac_hybrid_* (hybrid action spaces).  Off by default: the default learner's hybrid step is held to the
+        # `step/hybrid/*` entries of tests/parity_tolerances.json, 4x the errors observed on the eager composition, and
+        # another summation order cannot promise to stay inside them
+        self._fused_hybrid = bool(hip_config.get('fused_hybrid', False))
         self._siamese_ws = {}            # (N, E) / ('byol', encoder index) -> the launch's zeroed exchange words
         self._fused_rpm_loss = bool(hip_config.get('fused_rpm_loss', True))
         # one backward walk per prediction model (gates and model gradients from it): sac_aux._train_rpm
@@ -629,6 +648,9 @@ class SAC_Base(AuxHeadsMixin):
         # pure-discrete learner (`_discrete_fused`): the branch table and d loss / d (head outputs) of its two loss launches
         self._branches = native.branches(self.d_action_sizes) if self.d_action_sizes else None
         self._discrete_grads = {}       # batch rows -> (d loss_q / d q [E, B, D], d loss_policy / d logits [B, D])
+        # hybrid learner (`_hybrid_fused`): batch rows -> the discrete returns' targets (the continuous ones go to `_y_buf` /
+        # `_y_td_buf`) and the gradients its two loss launches write
+        self._hybrid_bufs = {}
         # the one hand-over between steps that goes through `self`, from the Q step's return target to the policy step
         # (`_train_policy` has the reference's signature: no room for either): `_ls_y` = the policy's output over the
         # return's window, read by `_step_policy`; `_pi_sampled` = the return's sampling launch also drew the policy
@@ -1254,6 +1276,19 @@ class SAC_Base(AuxHeadsMixin):
             float32_on_device=self._params.flat.dtype == torch.float32 and self._params.flat.is_cuda,
             ensemble_q_num=self.ensemble_q_num, n_step=self.n_step, batch_size=B)
 
+    def _hybrid_fused(self, B: int) -> bool:
+        """the step's arithmetic on a hybrid action space runs on the `asac_hybrid_*` launches (`fused_hybrid_applies`), B
+        rows a batch.  `plain_gaussian`: known without a forward pass for the stock policy's `forward` only (a `Normal`
+        on `ModelPolicy.c_bounded`); a policy with its own `forward` keeps the eager code"""
+        return fused_hybrid_applies(
+            enabled=self._fused_hybrid, plain_learner=type(self)._plain_learner, d_action_sizes=self.d_action_sizes,
+            c_action_size=self.c_action_size, discrete_dqn_like=self.discrete_dqn_like,
+            offline_loss=self.offline_enabled and self.offline_loss, siamese=self.siamese is not None,
+            use_prediction=self.use_prediction, data_parallel=self._dist is not None,
+            float32_on_device=self._params.flat.dtype == torch.float32 and self._params.flat.is_cuda,
+            clip_epsilon=self.clip_epsilon, plain_gaussian=type(self.model_policy).forward is ModelPolicy.forward,
+            ensemble_q_num=self.ensemble_q_num, n_step=self.n_step, batch_size=B)
+
     def _dqn_fused(self, B: int, acting: bool = False) -> bool:
         """the step's DQN-like arithmetic runs on the `asac_dqn_*` launches (`fused_dqn_applies`), B rows a batch; `acting`:
         the acting launch, where neither the batch nor the window plays a part"""
@@ -1365,6 +1400,22 @@ class SAC_Base(AuxHeadsMixin):
                                        torch.zeros(B, self.d_action_summed_size, **f32))
         return self._discrete_grads[B]
 
+    def _hybrid_heads(self, state, obs_list):
+        """hybrid learner on the `asac_hybrid_*` launches -> (logits [.., D], loc [.., A], scale [.., A]) with the stock
+        policy's trunk evaluated once: the discrete branches' raw head outputs (the launches normalise them per branch
+        themselves) and the parameters of the continuous head's Normal; no distribution objects"""
+        logits, mean, logstd = self.model_policy.heads_raw(state)
+        return (logits, *self.model_policy.c_bounded(mean, logstd))
+
+    def _hybrid_buffers(self, B: int):
+        if B not in self._hybrid_bufs:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            E, D = self.ensemble_q_num, self.d_action_summed_size
+            self._hybrid_bufs[B] = dict(
+                d_y=torch.zeros(B, **f32), d_y_td=torch.zeros(B, **f32), grad_qd=torch.zeros(E, B, D, **f32),
+                grad_cq=torch.zeros(E, B, **f32), grad_logits=torch.zeros(B, D, **f32), grad_logp=torch.zeros(B, **f32))
+        return self._hybrid_bufs[B]
+
     def _stored_action_ratios(self, d_policy, n_mu_probs, nx_actions):
         """discrete branches -> (pi, mu) [B, n]: the stored actions' probability under the policy and under the behaviour
         policy, as products over the branches"""
@@ -1429,10 +1480,12 @@ class SAC_Base(AuxHeadsMixin):
         instead, 1329: the extra row's probability is discarded either way).  With `q_online`
         ([E, B], continuous-only action spaces) the TD error mean_e|q_e - y| is produced by the
         same launch into `td_out`; with `d_q_online` (the online critics' discrete head outputs [B, D] each, pure-discrete
-        learner on the `asac_discrete_*` launches) likewise.
+        learner on the `asac_discrete_*` launches) likewise; a hybrid learner on the `asac_hybrid_*` launches hands over
+        both and gets the summed TD error from its one launch.
         """
         n_actions = nx_actions[:, :-1]
         fused_d = self._discrete_fused(n_rewards.shape[0])
+        fused_h = ls is None and sample is None and self._hybrid_fused(n_rewards.shape[0])
         d_logits = None
         if ls is None and sample is None and self._fpi is not None and self.c_action_size and nx_states.dim() == 3:
             # the stock policy over the window and the window's sample as ONE launch (`_return_sample_epilogue`)
@@ -1447,6 +1500,9 @@ class SAC_Base(AuxHeadsMixin):
         elif fused_d:   # the return's launch forms the branch probabilities from the logits: no distribution objects
             d_policy = c_policy = loc = scale = None
             plain, d_logits = False, self._discrete_logits(nx_states, nx_obses_list)
+        elif fused_h:   # ... and the window's sample comes from (loc, scale)
+            d_policy = c_policy = None
+            (d_logits, loc, scale), plain = self._hybrid_heads(nx_states, nx_obses_list), True
         else:
             d_policy, c_policy, loc, scale, plain = self._policy(nx_states, nx_obses_list)
             ls = self._ls
@@ -1493,6 +1549,31 @@ class SAC_Base(AuxHeadsMixin):
             self.noise.subset_(sub_eval, E)
             d_y = self.get_dqn_like_d_y(n_last_masks, n_padding_masks, n_rewards, n_dones,
                                         eval_next.index_select(0, sub_eval.long()), target_next)
+        elif fused_h:   # 1383-1464 on a hybrid space: both heads' V, ratios and scans in ONE launch
+            assert launch and q_table is None
+            B = n_rewards.shape[0]
+            sub_dnext, sub_dn = self._subsets[subset_prefix + '_dnext'], self._subsets[subset_prefix + '_dn']
+            self.noise.subset_(sub_dnext, E)
+            self.noise.subset_(sub_dn, E)
+            sub_cn, sub_cnext = self._subsets[subset_prefix + '_cn'], self._subsets[subset_prefix + '_cnext']
+            self.noise.subset_(sub_cn, E)
+            self.noise.subset_(sub_cnext, E)
+            d_out = self._hybrid_buffers(B)['d_y_td' if subset_prefix == 'td' else 'd_y']
+            d_args = self._vtrace_args(n_rewards, n_dones, n_last_masks, n_padding_masks, d_out)
+            d_args.subset_n, d_args.subset_next, d_args.E_sample = sub_dn.data_ptr(), sub_dnext.data_ptr(), self.ensemble_q_sample
+            d_args.log_alpha = self.log_d_alpha.data_ptr()
+            if self.use_n_step_is:
+                d_args.mu_prob, d_args.mu_stride_b, d_args.mu_stride_t = \
+                    n_mu_probs.data_ptr(), n_mu_probs.stride(0), n_mu_probs.stride(1)
+            q_tab = torch.stack([q[1] for q in nx_qs]).squeeze(-1)            # [E, B, n+1]
+            ret = self._c_return(q_tab, logp, c_pi, n_mu_probs, sub_cn, sub_cnext, n_rewards, n_dones, n_last_masks,
+                                 n_padding_masks, y_out)
+            ret.args.A = self.c_action_size
+            with_td = d_q_online is not None    # mean_e (|(1/K) sum_j a_j q_e - d_y| + |c_q_e - c_y|) from the same launch
+            native.hybrid_return(d_args, ret.args, self._branches, [q[0] for q in nx_qs], d_logits, action=nx_actions,
+                                 q_online=d_q_online, c_q_online=q_online if with_td else None,
+                                 td_out=td_out if with_td else None)
+            return d_out.unsqueeze(-1), y_out.unsqueeze(-1)
         elif fused_d:   # 1383-1421, policy-based branch: subset means, branch softmax, V, ratios and the scan in ONE launch
             sub_next, sub_n = self._subsets[subset_prefix + '_dnext'], self._subsets[subset_prefix + '_dn']
             self.noise.subset_(sub_next, E)
@@ -1759,6 +1840,19 @@ class SAC_Base(AuxHeadsMixin):
             with learner_backward():
                 torch.autograd.backward(heads, list(grad_q.unbind(0)))
             return self._finish_rep_q(None, None)
+        if self.d_action_sizes and aux is None and self._hybrid_fused(state.shape[0]):
+            # hybrid: both heads' loss terms and d(sum_e l_e) / d(discrete head outputs, continuous values) from one launch;
+            # back-propagation starts at the heads and the stacked continuous values
+            heads = [q[0] for q in q_list]
+            with torch.no_grad():
+                t_q = self._c_q_values(True, state.detach(), c_action, obs_list)
+            buf = self._hybrid_buffers(state.shape[0])
+            native.hybrid_q_loss_grad(self._branches, [h.detach() for h in heads], d_action, c_q.detach().contiguous(),
+                                      t_q.contiguous(), d_y, c_y, priority_is, self.clip_epsilon, self._loss_q_e,
+                                      buf['grad_qd'], buf['grad_cq'])
+            with learner_backward():
+                torch.autograd.backward(heads + [c_q], list(buf['grad_qd'].unbind(0)) + [buf['grad_cq']])
+            return self._finish_rep_q(None, None)
         if self.d_action_sizes:
             qs = torch.stack([torch.sum(d_action * q[0], dim=-1, keepdim=True) / self.d_action_branch_size
                               for q in q_list])                                   # [E, B, 1]
@@ -1958,6 +2052,33 @@ class SAC_Base(AuxHeadsMixin):
                 torch.autograd.backward([logits], [grad_logits], inputs=pi_inputs)
             self.optimizer_policy.step()
             return
+        if self._hybrid_fused(state.shape[0]):
+            # hybrid: the critics only supply values (the discrete ones at the stored continuous action, the continuous ones
+            # at the sample); objective, both entropy statistics and d loss / d (logits, logp, continuous values) from one
+            # launch; back-propagation starts there, restricted to the policy.  Draws in the eager order: pi_d, noise, pi_c
+            logits, loc, scale = self._hybrid_heads(state, obs_list)
+            with torch.no_grad():
+                d_qs = [q(state, action[..., dsum:], obs_list)[0] for q in self.model_q_list]
+            sub_d = self._subsets['pi_d']
+            self.noise.subset_(sub_d, E)
+            self.noise.normal_(self._eps_pi)
+            a_tanh, logp = squash_sample(loc, scale, self._eps_pi)
+            c_qs = torch.stack([q(state, a_tanh, obs_list)[1] for q in self.model_q_list]).squeeze(-1)   # [E, B]
+            sub_c = self._subsets['pi_c']
+            self.noise.subset_(sub_c, E)
+            buf = self._hybrid_buffers(state.shape[0])
+            native.hybrid_policy_loss_grad(
+                self._branches, logits.detach(), d_qs, sub_d, mu_d_policy_probs, self.log_d_alpha,
+                self.d_policy_entropy_penalty, logp.detach(), c_qs.detach().contiguous(),
+                sub_c if self.ensemble_q_sample != E else None, self.ensemble_q_sample, self.log_c_alpha, scale.detach(),
+                self._stats['loss_policy'], buf['grad_logits'], buf['grad_logp'], buf['grad_cq'], self._stats['d_entropy'],
+                self._stats['c_entropy'])
+            pi_inputs = list(self.model_policy.parameters())
+            with direct_param_grads(only=pi_inputs):
+                torch.autograd.backward([logits, logp, c_qs], [buf['grad_logits'], buf['grad_logp'], buf['grad_cq']],
+                                        inputs=pi_inputs)
+            self.optimizer_policy.step()
+            return
         d_policy, c_policy, loc, scale, plain = self._policy(state, obs_list)
         loss_d = loss_c = None
         with torch.no_grad():
@@ -2064,6 +2185,22 @@ class SAC_Base(AuxHeadsMixin):
                 seg0 = self._params.segments['alpha'][0]
                 native.discrete_alpha_grad(self._branches, self._discrete_logits(state, obs_list), self.target_d_alpha,
                                            self._params.grad[seg0:seg0 + 1])
+            self.optimizer_alpha.step()
+            return
+        if ls is None and logp is None and self._hybrid_fused(state.shape[0]):
+            # hybrid: both temperature gradients straight into their slots [log_d_alpha, log_c_alpha] from one launch, the
+            # continuous one on log pi of a fresh sample
+            with torch.no_grad():
+                logits, loc, scale = self._hybrid_heads(state, obs_list)
+                self.noise.normal_(self._eps_alpha)
+                loc, scale = loc.contiguous(), scale.contiguous()
+                scratch = torch.empty_like(loc)
+                logp = torch.empty(loc.shape[:-1], dtype=torch.float32, device=self.device)
+                native.squash_sample_fwd(loc, scale, self._eps_alpha, scratch, logp)
+                seg0 = self._params.segments['alpha'][0]
+                native.hybrid_alpha_grad(self._branches, logits, self.target_d_alpha, logp,
+                                         self.target_c_alpha * -float(self.c_action_size),
+                                         self._params.grad[seg0:seg0 + 2])
             self.optimizer_alpha.step()
             return
         with torch.no_grad():
@@ -2182,6 +2319,15 @@ class SAC_Base(AuxHeadsMixin):
             self._get_y(n_last_masks, n_padding_masks, nx_obses_list, nx_target_states, nx_actions, n_rewards, n_dones,
                         n_mu_probs, eps_buf=self._eps_td, subset_prefix='td', y_out=self._y_td_buf, td_out=self._td_error,
                         d_q_online=heads)
+            return self._td_error, False
+        if c_q is None and ls is None and sample is None and self._hybrid_fused(state.shape[0]):
+            # hybrid: the return's launch writes mean_e (|(1/K) sum_j a_j q_e - d_y| + |c_q_e - c_y|) itself
+            assert not sidecars and pending_alpha is None and td_update is None
+            q_list = [q(state, c_action, obs_list) for q in self.model_q_list]
+            c_q = torch.stack([q[1] for q in q_list]).squeeze(-1).contiguous()
+            self._get_y(n_last_masks, n_padding_masks, nx_obses_list, nx_target_states, nx_actions, n_rewards, n_dones,
+                        n_mu_probs, eps_buf=self._eps_td, subset_prefix='td', y_out=self._y_td_buf, td_out=self._td_error,
+                        q_online=c_q, d_q_online=[q[0] for q in q_list])
             return self._td_error, False
         if c_q is None and self._dqn_fused(state.shape[0]):
             # DQN-like: the return's launch writes mean_e |(1/K) sum_j a_j q_e - y| itself

@@ -593,6 +593,18 @@ _SIGNATURES = {
                                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'asac_discrete_alpha_grad': (C.c_int, [C.POINTER(Branches), C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_hybrid_return': (C.c_int, [C.POINTER(VtraceArgs), C.POINTER(VtraceArgs), C.POINTER(DiscreteReturn), C.c_void_p,
+                                     C.c_void_p]),
+    'asac_hybrid_q_loss_grad': (C.c_int, [C.POINTER(Branches), C.POINTER(Members), C.c_void_p, C.c_int64, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                          C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_hybrid_policy_loss_grad': (C.c_int, [C.POINTER(Branches), C.c_void_p, C.c_int64, C.POINTER(Members), C.c_void_p,
+                                               C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                               C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
+    'asac_hybrid_alpha_grad': (C.c_int, [C.POINTER(Branches), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float,
+                                         C.c_int, C.c_void_p, C.c_void_p]),
     'asac_dqn_return': (C.c_int, [C.POINTER(VtraceArgs), C.POINTER(DqnJob), C.c_void_p]),
     'asac_dqn_q_loss_grad': (C.c_int, [C.POINTER(VtraceArgs), C.POINTER(DqnJob), C.c_void_p, C.c_int64, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
@@ -3092,6 +3104,93 @@ def discrete_alpha_grad(br: Branches, logits, target, grad_slot, probs_out=None,
     _check(load().asac_discrete_alpha_grad(C.byref(br), _p(logits), _discrete_rows(logits, D, 'logits'), _p(target), B,
                                            _p(grad_slot), _p(probs_out), _p(row_entropy_out), _stream()),
            'asac_discrete_alpha_grad')
+
+
+# ------------------------------------------------------------------------------------------------
+# hybrid action spaces, policy-based SAC (csrc/hybrid.hip)
+# ------------------------------------------------------------------------------------------------
+MAX_ACTION = 64         # ASAC_MAX_ACTION
+
+
+def hybrid_sizes_ok(d_action_sizes, c_action_size: int, E: int, n: int, B: int) -> bool:
+    """the limits of the `hybrid_*` entry points: those of the `discrete_*` ones and 1 <= A <= ASAC_MAX_ACTION"""
+    return discrete_sizes_ok(d_action_sizes, E, n, B) and 0 < c_action_size <= MAX_ACTION
+
+
+def _ensemble_rows(t, E, B, name):
+    assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == E * B and t.shape[0] == E, name
+
+
+@_profiled
+def hybrid_return(d_args: VtraceArgs, c_args: VtraceArgs, br: Branches, q_target, logits, action=None, q_online=None,
+                  c_q_online=None, td_out=None):
+    """Both returns of a hybrid space in one launch.  `d_args`: what `discrete_return` takes; `c_args`: what
+    `vtrace_return_min` takes (`A` set with and without importance sampling); they share reward, masks and ratios and
+    write different `y_out`.  q_target / logits / action / q_online: the discrete side's, as for `discrete_return`.  With
+    `td_out` [B] (then `q_online` [B, D] each and `c_q_online` [E, B] contiguous) the launch also writes
+    mean_e (|(1/K) sum_j a_j q_e - d_y| + |c_q_e - c_y|)."""
+    job = _discrete_return_job(d_args, br, q_target, logits, action, q_online)
+    if td_out is not None:
+        E = len(q_online)
+        _ensemble_rows(c_q_online, E, d_args.B, 'c_q_online')
+        assert td_out.dtype == torch.float32 and td_out.is_contiguous() and td_out.numel() == d_args.B
+        c_args.q_online, c_args.E_online = c_q_online.data_ptr(), E
+    _check(load().asac_hybrid_return(C.byref(d_args), C.byref(c_args), C.byref(job), _p(td_out), _stream()),
+           'asac_hybrid_return')
+
+
+@_profiled
+def hybrid_q_loss_grad(br: Branches, q_d, action, c_q, t_q, d_y, c_y, w, clip_eps, loss_out, grad_qd, grad_cq):
+    """q_d: the online members' discrete head outputs [B, D]; action [B, >= D]; c_q, t_q [E, B] contiguous; d_y, c_y, w
+    (optional): B float32 elements each ([B] or [B, 1]); -> loss_out [E], grad_qd [E, B, D] and grad_cq [E, B] contiguous
+    <- d (sum_e loss_e) / d (head outputs, continuous values)"""
+    B, D, E = action.shape[0], br.D, len(q_d)
+
+    def col(t, name):
+        assert t.is_cuda and t.dtype == torch.float32 and t.numel() == B and t.shape[0] == B, name
+        return t.stride(0) if B > 1 else 1
+    _ensemble_rows(c_q, E, B, 'c_q'), _ensemble_rows(t_q, E, B, 't_q'), _ensemble_rows(grad_cq, E, B, 'grad_cq')
+    assert loss_out.dtype == torch.float32 and loss_out.numel() >= E and loss_out.is_contiguous()
+    assert grad_qd.dtype == torch.float32 and grad_qd.shape == (E, B, D) and grad_qd.is_contiguous()
+    _check(load().asac_hybrid_q_loss_grad(
+        C.byref(br), C.byref(members(list(q_d), D)), _p(action), _discrete_rows(action, D, 'action'), _p(c_q), _p(t_q),
+        _p(d_y), col(d_y, 'd_y'), _p(c_y), col(c_y, 'c_y'), _p(w), col(w, 'w') if w is not None else 0, B, float(clip_eps),
+        _p(loss_out), _p(grad_qd), _p(grad_cq), _stream()), 'asac_hybrid_q_loss_grad')
+
+
+@_profiled
+def hybrid_policy_loss_grad(br: Branches, logits, q_d, subset_d, mu, log_d_alpha, entropy_penalty, logp, c_q, subset_c,
+                            E_sample, log_c_alpha, scale, loss_out, grad_logits, grad_logp, grad_cq, d_entropy_out,
+                            c_entropy_out):
+    """logits [B, D]; q_d: the online members' discrete head outputs [B, D]; mu [B, >= D]; logp [B] and c_q [E, B]
+    contiguous; scale [B, A]; subset_d / subset_c: int32 [E_sample] device tensors or None (members 0..E_sample-1); ->
+    loss_out [1], grad_logits [B, D], grad_logp [B], grad_cq [E, B], d_entropy_out [1], c_entropy_out [1]"""
+    B, D, E = logits.shape[0], br.D, len(q_d)
+    _ensemble_rows(c_q, E, B, 'c_q'), _ensemble_rows(grad_cq, E, B, 'grad_cq')
+    for t in (logp, grad_logp):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B
+    assert scale.is_cuda and scale.dtype == torch.float32 and scale.dim() == 2 and scale.shape[0] == B
+    A = scale.shape[1]
+    assert scale.stride(1) == 1 or A == 1
+    _check(load().asac_hybrid_policy_loss_grad(
+        C.byref(br), _p(logits), _discrete_rows(logits, D, 'logits'), C.byref(members(list(q_d), D)), _p(subset_d), _p(mu),
+        _discrete_rows(mu, D, 'mu'), _p(log_d_alpha), float(entropy_penalty), _p(logp), _p(c_q), _p(subset_c),
+        int(E_sample), _p(log_c_alpha), _p(scale), max(scale.stride(0), A), A, B, _p(loss_out), _p(grad_logits),
+        _discrete_rows(grad_logits, D, 'grad_logits'), _p(grad_logp), _p(grad_cq), _p(d_entropy_out), _p(c_entropy_out),
+        _stream()), 'asac_hybrid_policy_loss_grad')
+
+
+@_profiled
+def hybrid_alpha_grad(br: Branches, logits, target_d, logp, target_c, grad_slots):
+    """grad_slots [2] <- (mean_b (1/K) sum_j p_j (-cl(p_j) - target_d_j), mean_b(-logp_b) - target_c): the flat-gradient
+    elements of [log_d_alpha, log_c_alpha]; logits [B, D], target_d [D] (device), logp [B] contiguous"""
+    B, D = logits.shape[0], br.D
+    assert target_d.is_cuda and target_d.dtype == torch.float32 and target_d.numel() == D and target_d.is_contiguous()
+    assert logp.is_cuda and logp.dtype == torch.float32 and logp.is_contiguous() and logp.numel() == B
+    assert grad_slots.dtype == torch.float32 and grad_slots.is_contiguous() and grad_slots.numel() == 2
+    _check(load().asac_hybrid_alpha_grad(C.byref(br), _p(logits), _discrete_rows(logits, D, 'logits'), _p(target_d),
+                                         _p(logp), float(target_c), B, _p(grad_slots), _stream()),
+           'asac_hybrid_alpha_grad')
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1705,6 +1705,66 @@ int asac_discrete_alpha_grad(const asac_branches_t* branches, const float* logit
                              void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Hybrid action spaces, policy-based SAC (d_action_sizes set AND c_action_size > 0, discrete_dqn_like False): the
+ * learner's row-wise arithmetic around the networks as one launch per item (csrc/hybrid.hip).  The reference's hybrid Q
+ * loss, TD error, policy objective and temperature loss each add a discrete and a continuous term per row; each launch
+ * forms both.  Notation and tables as above; the continuous head's tensors as for the continuous entry points
+ * (asac_vtrace_return_min, asac_q_loss_fwd_bwd, asac_policy_loss_fwd_bwd, asac_alpha_grad).  Batch means: lane partials
+ * in a fixed tree, one division by B, no float atomics: equal inputs give equal bits.  Nothing allocates or synchronises.
+ * Limits: D <= 64, K <= 8, E <= 8, n <= ASAC_DISCRETE_MAX_STEPS, 1 <= A <= ASAC_MAX_ACTION; the return takes any B, the
+ * three single-workgroup reductions B <= ASAC_DISCRETE_MAX_ROWS.  Bad arguments return hipErrorInvalidValue without a
+ * launch; B == 0 launches nothing.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Both returns of SAC_Base._get_y on a hybrid space (sac_base.py:1383-1464 + _v_trace 1244-1295) in ONE launch.
+ *   d_args, job  exactly what asac_discrete_return reads (subset MEANS, branch softmax, log_alpha = log_d_alpha, the
+ *                discrete pi / mu under use_n_step_is)
+ *   c_args       exactly what asac_vtrace_return_min reads (q [E, B, n+1], subset MINIMUM, logp, log_alpha = log_c_alpha,
+ *                pi_prob / mu_prob with mu_offset = D and A; A is checked with and without importance sampling)
+ * The two blocks must name the same B, n, reward, masks (pointers and strides), gamma_ratio / lambda_ratio, gamma, v_rho,
+ * v_c and use_n_step_is, and different y_out: a step's reward and masks are loaded once for both scans.  Writes
+ * d_args->y_out (the bits of asac_discrete_return) and c_args->y_out (the bits of asac_vtrace_return_min).
+ * td_error_out (optional) f32[B]: needs job->q_online, job->action, c_args->q_online [E, B] and c_args->E_online == E;
+ *   td[b] = (1/E) sum_e (|(1/K) sum_j a_j q_e[b, j] - d_y_b| + |c_q_e[b] - c_y_b|)      (sac_base.py:2233-2244)
+ * per member the discrete addend first, members in ascending order.  td_error_out INSIDE either block must be NULL. */
+int asac_hybrid_return(const asac_vtrace_args_t* d_args, const asac_vtrace_args_t* c_args,
+                       const asac_discrete_return_t* job, float* td_error_out, void* stream);
+
+/* Q loss of a hybrid space and its gradients (sac_base.py:1533-1568), one workgroup per member:
+ *   qs[e][b] = (1/K) sum_j a[b][j] q_e[b][j]
+ *   loss_out[e] = mean_b w_b [ (qs - d_y_b)^2 + max((tq + clamp(cq - tq, +-eps) - c_y_b)^2, (cq - c_y_b)^2) ]
+ *   grad_qd [E, B, D] = d (sum_e l_e) / d (discrete head outputs)   (asac_discrete_q_loss_grad's term)
+ *   grad_cq [E, B]    = d (sum_e l_e) / d cq                         (the bits of asac_q_loss_fwd_bwd: same side on ties)
+ * q_d: the members' discrete head outputs [B, D]; cq, tq [E, B] contiguous; d_y, c_y, w (may be NULL): element b at
+ * b * stride.  clip_eps <= 0 is refused (the reference's doubling quirk there stays with the caller). */
+int asac_hybrid_q_loss_grad(const asac_branches_t* branches, const asac_members_t* q_d, const float* action,
+                            int64_t action_stride, const float* cq, const float* tq, const float* d_y, int64_t d_y_stride,
+                            const float* c_y, int64_t c_y_stride, const float* w, int64_t w_stride, int B, float clip_eps,
+                            float* loss_out, float* grad_qd, float* grad_cq, void* stream);
+
+/* Policy objective of a hybrid space, value + gradients (sac_base.py:1858-1903, 1910-1911), one workgroup:
+ *   L = mean_b [ ld_b + lc_b ];  ld_b = asac_discrete_policy_loss_grad's row term (entropy penalty included, means over
+ *   subset_d of q_d);  lc_b = alpha_c logp_b - min_{e in subset_c} cq[e][b]
+ * loss_out f32[1]; grad_logits [B, D] rows grad_stride apart; grad_logp [B] = alpha_c / B and grad_cq [E, B] = -1/B at
+ * the first arg-min member of subset_c, 0 elsewhere (the bits of asac_policy_loss_fwd_bwd); d_entropy_out = mean_b H_pi;
+ * c_entropy_out = mean_b sum_d (log scale + 1/2 + 1/2 log 2 pi), scale [B, A] rows scale_stride apart.  E = q_d->E
+ * members in cq [E, B]; subset_d / subset_c: DEVICE i32[E_sample] or NULL (members 0..E_sample-1). */
+int asac_hybrid_policy_loss_grad(const asac_branches_t* branches, const float* logits, int64_t logits_stride,
+                                 const asac_members_t* q_d, const int32_t* subset_d, const float* mu, int64_t mu_stride,
+                                 const float* log_d_alpha, float entropy_penalty, const float* logp, const float* cq,
+                                 const int32_t* subset_c, int E_sample, const float* log_c_alpha, const float* scale,
+                                 int64_t scale_stride, int A, int B, float* loss_out, float* grad_logits,
+                                 int64_t grad_stride, float* grad_logp, float* grad_cq, float* d_entropy_out,
+                                 float* c_entropy_out, void* stream);
+
+/* Both temperature gradients (sac_base.py:1924-1944), one workgroup: grad_slots f32[2] = the flat-gradient elements of
+ * [log_d_alpha, log_c_alpha];  slot 0 as asac_discrete_alpha_grad (target_d: DEVICE f32[D]), slot 1 =
+ * mean_b(-logp_b) - target_c as asac_alpha_grad (logp [B] contiguous).  Each slot has the bits of that launch. */
+int asac_hybrid_alpha_grad(const asac_branches_t* branches, const float* logits, int64_t logits_stride,
+                           const float* target_d, const float* logp, float target_c, int B, float* grad_slots,
+                           void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Pure-discrete, DQN-like learner (d_action_sizes set, c_action_size == 0, discrete_dqn_like True: critics only): the
  * arithmetic around the critics as three launches (csrc/dqn.hip; the per-row target is csrc/asac_dqn.h's, one
  * implementation for both launches that form it).  Branch table, member tables and limits as above.

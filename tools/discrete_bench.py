@@ -7,11 +7,14 @@
           profiler.  With the flag off the step runs exactly the code of the commit before the discrete kernels, so this is
           the A/B against it without a second checkout; bench.py has no discrete configuration.
 
-    python tools/discrete_bench.py [--steps 600] [--fill 16384] [--dqn-like]
+    python tools/discrete_bench.py [--steps 600] [--fill 16384] [--dqn-like | --hybrid]
 
 `--dqn-like`: the same A/B with `discrete_dqn_like=True` (critics only, double-DQN target; csrc/dqn.hip,
 `hip_config['fused_dqn']`), and — acting is not part of the step's figure — the device kernels of ONE `choose_action` call in
 train mode with the flag off and on, from torch's profiler.
+
+`--hybrid`: the same A/B on a hybrid action space, `d_action_sizes=[3, 2]` and `c_action_size=2` (csrc/hybrid.hip,
+`hip_config['fused_hybrid']`, default off: the `eager` column is what a default learner runs).
 
 The two ways alternate (off, on, off, on, ...: a drift of the box's clocks hits both) and every timed window ends in a device
 synchronise; the median of the rounds is reported, all rounds are listed.  BOTH captured learners stay alive while the tool
@@ -41,7 +44,10 @@ def count_kernels(fn):
     return sum(e.count for e in prof.key_averages() if e.device_type == torch.autograd.DeviceType.CUDA)
 
 
-def step_row(steps, fill, dqn_like=False):
+C_ACTION_SIZE_HYBRID = 2
+
+
+def step_row(steps, fill, dqn_like=False, hybrid=False):
     import bench
     from asac_amd import native
     from algorithm.sac_base import SAC_Base
@@ -49,14 +55,17 @@ def step_row(steps, fill, dqn_like=False):
     cfg = bench.CONFIGS['cfg2']
     plugin = pu.plugin(cfg['plugin'])
     rng = np.random.default_rng(1)
-    episodes = [pu.synthetic_episode(rng, cfg['obs_shapes'], D_ACTION_SIZES, 0, cfg['hidden'], cfg['episode_len'])
+    c_size = C_ACTION_SIZE_HYBRID if hybrid else 0
+    episodes = [pu.synthetic_episode(rng, cfg['obs_shapes'], D_ACTION_SIZES, c_size, cfg['hidden'], cfg['episode_len'])
                 for _ in range(max(4, fill // cfg['episode_len']))]
 
     flag, prefix = ('fused_dqn', 'asac_dqn_') if dqn_like else ('fused_discrete', 'asac_discrete_')
+    if hybrid:
+        flag, prefix = 'fused_hybrid', 'asac_hybrid_'
 
     def learner(fused, use_graph):
         torch.manual_seed(0)
-        agent = SAC_Base(cfg['obs_names'], cfg['obs_shapes'], D_ACTION_SIZES, 0, None, plugin, device='cuda:0',
+        agent = SAC_Base(cfg['obs_names'], cfg['obs_shapes'], D_ACTION_SIZES, c_size, None, plugin, device='cuda:0',
                          n_step=cfg['n_step'], burn_in_step=cfg['burn_in_step'], batch_size=cfg['batch_size'],
                          ensemble_q_num=cfg['ensemble_q_num'], ensemble_q_sample=cfg['ensemble_q_sample'],
                          replay_config={'capacity': cfg['capacity']}, discrete_dqn_like=dqn_like,
@@ -66,7 +75,8 @@ def step_row(steps, fill, dqn_like=False):
         return agent
 
     agents = {}
-    row = {'mode': 'step', 'dqn_like': dqn_like, 'd_action_sizes': D_ACTION_SIZES, 'batch': cfg['batch_size'],
+    row = {'mode': 'step', 'dqn_like': dqn_like, 'd_action_sizes': D_ACTION_SIZES, 'c_action_size': c_size,
+           'batch': cfg['batch_size'],
            'n_step': cfg['n_step'], 'steps': steps, 'rounds': ROUNDS}
     for fused in (False, True):
         tag = 'fused' if fused else 'eager'
@@ -77,11 +87,12 @@ def step_row(steps, fill, dqn_like=False):
         seen = prof.summary()
         row['native_launches_' + tag] = sum(v['calls'] for v in seen.values())
         row['discrete_launches_' + tag] = {k: v['calls'] for k, v in seen.items()
-                                           if k.startswith(prefix) or k == 'asac_vtrace_return_direct'}
+                                           if k.startswith(prefix) or k in ('asac_vtrace_return_direct',
+                                                                            'asac_vtrace_return_min')}
         row['device_kernels_' + tag] = count_kernels(agent.train)
         if dqn_like:                 # one `choose_action` call in train mode, 8 agents
             obs = [torch.randn(8, *shape, device='cuda') for shape in cfg['obs_shapes']]
-            act_args = (obs, torch.zeros(8, sum(D_ACTION_SIZES), device='cuda'),
+            act_args = (obs, torch.zeros(8, sum(D_ACTION_SIZES) + c_size, device='cuda'),
                         torch.zeros(8, *agent.seq_hidden_state_shape, device='cuda'))
             agent.choose_action_device(*act_args)
             row['acting_device_kernels_' + tag] = count_kernels(lambda: agent.choose_action_device(*act_args))
@@ -115,10 +126,12 @@ def main():
     ap.add_argument('--steps', type=int, default=600)
     ap.add_argument('--fill', type=int, default=16384, help='rows put into the replay before the first step')
     ap.add_argument('--dqn-like', action='store_true', help='discrete_dqn_like=True: the A/B of hip_config[\'fused_dqn\']')
+    ap.add_argument('--hybrid', action='store_true', help='c_action_size=2 beside the branches: the A/B of hip_config[\'fused_hybrid\']')
     args = ap.parse_args()
+    assert not (args.dqn_like and args.hybrid), 'one A/B at a time'
     assert torch.cuda.is_available(), 'needs the GPU: nothing is measured without one'
     import asac_amd  # noqa: F401
-    print(json.dumps(step_row(args.steps, args.fill, args.dqn_like)), flush=True)
+    print(json.dumps(step_row(args.steps, args.fill, args.dqn_like, args.hybrid)), flush=True)
 
 
 if __name__ == '__main__':

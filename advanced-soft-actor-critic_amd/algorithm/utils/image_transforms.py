@@ -11,13 +11,18 @@ what runs for anything the kernel does not take (other dtypes, inputs that requi
 
 ONE LAUNCH (`asac_image_augment`, csrc/image.hip): float32 CUDA tensors.  The draws are made on the device from a counter in
 device memory the instance owns, so a step captured into a graph (`CapturedStep`) draws afresh on every replay; `drawn()`
-reports what the last call drew.
+reports what the last call drew.  `RandomResizedCrop` and `ElasticTransform` with NEAREST interpolation, and a `RandomChoice`
+among them, are one launch of a second entry point (`asac_image_warp`) with the same draw protocol and its own `drawn()`
+record (counter, choice, top, left, height, width); BILINEAR, a field whose blur has over 63 taps or reaches past the plane,
+and a choice that mixes them with the ops above stay module code.
 
-WARNING, captured steps: a module-code draw (`RandomChoice`'s pick, `RandomCrop`'s offsets, a sigma or brightness range) is
-a host value.  Captured into a graph it is FROZEN: every replay applies the same member with the same parameters, and
-nothing reports it.  Inside a captured step keep to what `_native_ops` reduces to a launch."""
+WARNING, captured steps: a module-code draw (`RandomChoice`'s pick, `RandomCrop`'s offsets, a sigma or brightness range, a
+resized crop's window, an elastic displacement field) is a host value.  Captured into a graph it is FROZEN: every replay
+applies the same member with the same parameters, and nothing reports it.  Inside a captured step keep to what `_native_ops`
+reduces to a launch."""
 import enum
 import itertools
+import math
 from collections.abc import Sequence
 
 import torch
@@ -26,8 +31,9 @@ from torch.nn import functional as F
 
 from . import transform as _noise
 
-__all__ = ['GaussianBlur', 'ColorJitter', 'RandomCrop', 'Resize', 'RandomChoice', 'Compose', 'InterpolationMode',
-           'gaussian_kernel1d', 'gaussian_blur', 'adjust_brightness', 'crop', 'resize']
+__all__ = ['GaussianBlur', 'ColorJitter', 'RandomCrop', 'Resize', 'RandomResizedCrop', 'ElasticTransform', 'RandomChoice',
+           'Compose', 'InterpolationMode', 'gaussian_kernel1d', 'gaussian_blur', 'adjust_brightness', 'crop', 'resize',
+           'resized_crop', 'get_resized_crop_params', 'elastic_displacement', 'elastic']
 
 
 class InterpolationMode(enum.Enum):
@@ -67,12 +73,14 @@ def gaussian_kernel1d(k: int, sigma: float, dtype=torch.float32, device=None):
     return w / w.sum()
 
 
-def gaussian_blur(x, kernel_size, sigma: float):
-    """reflect padding k // 2, then the depthwise product with the outer product of the two 1-D kernels"""
+def gaussian_blur(x, kernel_size, sigma):
+    """reflect padding k // 2, then the depthwise product with the outer product of the two 1-D kernels; `sigma`: a float,
+    or the pair (along x, along y)"""
     kx, ky = kernel_size
+    sx, sy = _pair(sigma, 'sigma')
     lead, f = _frames(x)
     dtype = f.dtype if f.is_floating_point() else torch.float32
-    w2 = torch.outer(gaussian_kernel1d(ky, sigma, dtype, f.device), gaussian_kernel1d(kx, sigma, dtype, f.device))
+    w2 = torch.outer(gaussian_kernel1d(ky, sy, dtype, f.device), gaussian_kernel1d(kx, sx, dtype, f.device))
     C = f.shape[1]
     padded = F.pad(f.to(dtype), [kx // 2, kx // 2, ky // 2, ky // 2], mode='reflect')
     out = F.conv2d(padded, w2.expand(C, 1, ky, kx), groups=C)
@@ -104,6 +112,89 @@ def resize(x, size):
     if out_hw == tuple(f.shape[-2:]):
         return x
     out = F.interpolate(f, size=out_hw, mode='bilinear', align_corners=False, antialias=True)
+    return out.reshape(*lead, *out.shape[1:])
+
+
+def _interpolation(value, who):
+    """-> 'nearest' | 'bilinear' (the two the warps take)"""
+    if value in (InterpolationMode.NEAREST, 'nearest', 0):
+        return 'nearest'
+    if value in (InterpolationMode.BILINEAR, 'bilinear', 2):
+        return 'bilinear'
+    raise NotImplementedError(f'{who}: interpolation {value!r} is not supported')
+
+
+def resized_crop(x, top: int, left: int, height: int, width: int, size, interpolation=InterpolationMode.BILINEAR):
+    """the window, resampled to `size` (h, w).  NEAREST: torch's legacy rule src = min(floor(dst * in / out), in - 1), no
+    antialiasing; BILINEAR: as `resize`"""
+    mode = _interpolation(interpolation, 'resized_crop')
+    lead, f = _frames(crop(x, top, left, height, width))
+    size = tuple(int(s) for s in _pair(size, 'size'))
+    if mode == 'nearest':
+        dtype = f.dtype
+        out = F.interpolate(f if f.is_floating_point() else f.to(torch.float32), size=size, mode='nearest').to(dtype)
+    else:
+        out = F.interpolate(f, size=size, mode='bilinear', align_corners=False, antialias=True)
+    return out.reshape(*lead, *out.shape[1:])
+
+
+def get_resized_crop_params(H: int, W: int, scale, ratio):
+    """torchvision's RandomResizedCrop.get_params, host draws -> (top, left, height, width)"""
+    log_lo, log_hi = math.log(ratio[0]), math.log(ratio[1])
+    area = H * W
+    for _ in range(10):
+        target_area = area * torch.empty(1).uniform_(scale[0], scale[1]).item()
+        aspect = math.exp(torch.empty(1).uniform_(log_lo, log_hi).item())
+        w = int(round(math.sqrt(target_area * aspect)))
+        h = int(round(math.sqrt(target_area / aspect)))
+        if 0 < w <= W and 0 < h <= H:
+            top = int(torch.randint(0, H - h + 1, size=()))
+            left = int(torch.randint(0, W - w + 1, size=()))
+            return top, left, h, w
+    in_ratio = W / H
+    if in_ratio < min(ratio):
+        w = W
+        h = int(round(w / min(ratio)))
+    elif in_ratio > max(ratio):
+        h = H
+        w = int(round(h * max(ratio)))
+    else:
+        w, h = W, H
+    return (H - h) // 2, (W - w) // 2, h, w
+
+
+def elastic_displacement(noise, alpha, sigma):
+    """noise [2, H, W] in [-1, 1) -> the displacement [H, W, 2] in grid units (torchvision's ElasticTransform._get_params):
+    field 0 moves along x, field 1 along y; each is blurred with k = int(8 * its sigma + 1) taps (made odd) on BOTH axes and
+    the sigma PAIR, then scaled by alpha[0] / H resp. alpha[1] / W — torchvision divides x by the height, y by the width"""
+    alpha, sigma = _pair(alpha, 'alpha'), _pair(sigma, 'sigma')
+    H, W = noise.shape[-2:]
+    fields = []
+    for i, n in enumerate((H, W)):
+        d = noise[i][None, None]
+        if sigma[i] > 0.:
+            k = _elastic_taps(sigma)[i]
+            d = gaussian_blur(d, [k, k], sigma)
+        fields.append(d[0, 0] * alpha[i] / n)
+    return torch.stack(fields, dim=-1)
+
+
+def elastic(x, displacement, interpolation=InterpolationMode.BILINEAR):
+    """`grid_sample` at the identity grid plus `displacement` [H, W, 2] (zeros outside, align_corners=False): ONE field for
+    every frame and channel of the call"""
+    mode = _interpolation(interpolation, 'elastic')
+    lead, f = _frames(x)
+    H, W = f.shape[-2:]
+    dtype = f.dtype
+    if not f.is_floating_point():
+        f = f.to(torch.float32)
+    gx = torch.linspace((-W + 1) / W, (W - 1) / W, W, dtype=f.dtype, device=f.device)
+    gy = torch.linspace((-H + 1) / H, (H - 1) / H, H, dtype=f.dtype, device=f.device)
+    identity = torch.stack([gx[None, :].expand(H, W), gy[:, None].expand(H, W)], dim=-1)
+    grid = (identity + displacement.to(f)).expand(f.shape[0], H, W, 2)
+    out = F.grid_sample(f, grid, mode=mode, padding_mode='zeros', align_corners=False)
+    if out.dtype != dtype:
+        out = out.round().to(dtype)
     return out.reshape(*lead, *out.shape[1:])
 
 
@@ -164,6 +255,44 @@ def _resolve(op, H, W):
     raise AssertionError(k)
 
 
+_WARP_KINDS = ('RESIZED_CROP', 'ELASTIC')
+
+
+def _is_warp_table(ops) -> bool:
+    """a table for `asac_image_warp`: every member a warp or a copy, at least one a warp"""
+    return any(op.kind in _WARP_KINDS for op in ops) and all(op.kind in _WARP_KINDS or op.kind == 'COPY' for op in ops)
+
+
+def _elastic_taps(sigma):
+    """torchvision's kernel sizes of the two fields: int(8 sigma + 1), made odd"""
+    taps = []
+    for s in sigma:
+        k = int(8 * s + 1)
+        taps.append(k + 1 - k % 2)
+    return taps
+
+
+def _resolve_warp(op, H, W):
+    """-> (fields of native.ImageWarpOp, (Ho, Wo)) for an [H, W] frame, or None where the kernel does not take it"""
+    from asac_amd import native
+    k, p = op.kind, op.p
+    if k == 'RESIZED_CROP':
+        (s0, s1), (r0, r1) = p['scale'], p['ratio']
+        return dict(kind=native.IMAGE_WARP_RESIZED_CROP, scale_lo=s0, scale_hi=s1, ratio_lo=r0, ratio_hi=r1), tuple(p['size'])
+    if k == 'ELASTIC':
+        sigma = p['sigma']
+        if min(sigma) <= 0.:                                # (a field without a blur: module code)
+            return None
+        k0, k1 = _elastic_taps(sigma)
+        if max(k0, k1) > native.IMAGE_WARP_MAX_KERNEL or max(k0, k1) // 2 >= min(H, W):
+            return None
+        return dict(kind=native.IMAGE_WARP_ELASTIC, k0=k0, k1=k1, alpha0=p['alpha'][0], alpha1=p['alpha'][1], sigma0=sigma[0],
+                    sigma1=sigma[1]), (H, W)
+    if k == 'COPY':
+        return dict(kind=native.IMAGE_WARP_COPY), (H, W)
+    raise AssertionError(k)
+
+
 _instance_ids = itertools.count(1)
 
 
@@ -179,6 +308,10 @@ class _Launcher(nn.Module):
         self._device_state = {}            # device -> (state int64 [2], drawn float64 [6])
         self._tables = {}                  # (H, W) -> (ctypes table, (Ho, Wo), whether it draws) | None
         self._last_device = None
+        self._last_warp = False            # whether the last launch was `asac_image_warp` (its own `drawn` record)
+        # (noise, displacement): two float32 [2, H, W] tensors on the device that an elastic call's field is copied to, for
+        # tests and inspection; None, None: not kept
+        self._field_out = (None, None)
         self._counter0 = 0
 
     def reseed(self, seed: int, counter: int = 0, instance_id: int | None = None):
@@ -206,11 +339,14 @@ class _Launcher(nn.Module):
         return got
 
     def drawn(self) -> dict:
-        """what the last launch drew: counter, choice, top, left (-1: none), sigma, factor (NaN: none).  Synchronises."""
+        """what the last launch drew: counter, choice, top, left (-1: none), sigma, factor (NaN: none); after a warp launch
+        counter, choice, top, left, height, width (-1: none).  Synchronises."""
         from asac_amd import native
         if self._last_device is None:
             raise RuntimeError('no launch yet')
         rec = self._device_state[self._last_device][1].tolist()
+        if self._last_warp:                # a warp table's record: counter, choice, top, left, height, width (-1: none)
+            return {k: int(v) for k, v in zip(native.IMAGE_WARP_DRAWN, rec)}
         out = dict(zip(native.IMAGE_DRAWN, rec))
         for k in ('counter', 'choice', 'top', 'left'):
             out[k] = int(out[k])
@@ -231,10 +367,13 @@ class _Launcher(nn.Module):
         H, W = x.shape[-2:]
         if H * W > native.IMAGE_MAX_PLANE or x.numel() == 0 or len(ops) > native.IMAGE_MAX_OPS:
             return None
+        warp = _is_warp_table(ops)
         if (H, W) not in self._tables:
-            resolved = [_resolve(op, H, W) for op in ops]
+            resolved = [(_resolve_warp if warp else _resolve)(op, H, W) for op in ops]
             if any(r is None for r in resolved) or len({r[1] for r in resolved}) != 1:
                 self._tables[(H, W)] = None        # a member outside the kernel's limits, or members of different sizes
+            elif warp:                             # (every warp table draws)
+                self._tables[(H, W)] = (native.warp_image_ops([r[0] for r in resolved]), resolved[0][1], True)
             else:
                 # (a table that draws nothing launches without the counter: no workgroup arrives anywhere)
                 draws = len(resolved) > 1 or any(_draws(r[0], H, W) for r in resolved)
@@ -248,8 +387,11 @@ class _Launcher(nn.Module):
         if self.seed is None:
             self.seed = torch.initial_seed()
         y = torch.empty(*f.shape[:2], Ho, Wo, dtype=torch.float32, device=x.device)
-        native.image_augment(f, y, table, self.seed, self.instance_id, state if draws else None, drawn)
-        self._last_device = x.device
+        if warp:
+            native.warp_image(f, y, table, self.seed, self.instance_id, state, drawn, *self._field_out)
+        else:
+            native.image_augment(f, y, table, self.seed, self.instance_id, state if draws else None, drawn)
+        self._last_device, self._last_warp = x.device, warp
         return y.reshape(*lead, *y.shape[1:])
 
 
@@ -267,6 +409,14 @@ def _native_ops(transform):
         return [_Op('CROP_RESIZE', crop=transform.size, size=None)]
     if isinstance(transform, Resize):
         return [_Op('CROP_RESIZE', crop=None, size=transform.size)]
+    if isinstance(transform, RandomResizedCrop):
+        if transform.interpolation != 'nearest':            # (the antialiased bilinear resize: module code)
+            return None
+        return [_Op('RESIZED_CROP', size=transform.size, scale=transform.scale, ratio=transform.ratio)]
+    if isinstance(transform, ElasticTransform):
+        if transform.interpolation != 'nearest':
+            return None
+        return [_Op('ELASTIC', alpha=transform.alpha, sigma=transform.sigma)]
     if type(transform) is _noise.SaltAndPepperNoise:
         return [_Op('SALT_PEPPER', snr=float(transform.snr), p=float(transform.p))]
     if type(transform) is _noise.GaussianNoise:
@@ -289,6 +439,9 @@ def _native_ops(transform):
             if ops is None or len(ops) != 1:
                 return None
             table.append(ops[0])
+        # the warps are another entry point: a choice between them and the ops of `asac_image_augment` is no one launch
+        if any(op.kind in _WARP_KINDS for op in table) and not _is_warp_table(table):
+            return None
         return table if table else None
     return None
 
@@ -411,6 +564,66 @@ class Resize(_Launcher):
 
     def extra_repr(self):
         return f'size={self.size}'
+
+
+class RandomResizedCrop(_Launcher):
+    """A window of a random share `scale` of the frame's area and a random aspect `ratio` (log-uniform), one per call
+    (`get_resized_crop_params`), resampled to `size`.  NEAREST is one launch with the window drawn on the device; BILINEAR
+    (antialiased) is module code, whose host draws are FROZEN inside a captured step (see the module)."""
+
+    def __init__(self, size, scale=(0.08, 1.0), ratio=(3. / 4., 4. / 3.), interpolation=InterpolationMode.BILINEAR, antialias=True):
+        super().__init__()
+        self.size = tuple(int(s) for s in _pair(size, 'size'))
+        if min(self.size) < 1:
+            raise ValueError(f'size should be positive, got {self.size}')
+        if not (isinstance(scale, Sequence) and isinstance(ratio, Sequence)):
+            raise TypeError('Scale and ratio should be sequences')
+        self.scale = tuple(float(s) for s in _pair(scale, 'scale'))
+        self.ratio = tuple(float(r) for r in _pair(ratio, 'ratio'))
+        if not (0. < self.scale[0] <= self.scale[1] and 0. < self.ratio[0] <= self.ratio[1]):
+            raise ValueError('scale and ratio should be positive and of the form (min, max)')
+        self.interpolation = _interpolation(interpolation, 'RandomResizedCrop')
+        if antialias is not True and self.interpolation == 'bilinear':
+            raise NotImplementedError('RandomResizedCrop: antialias=False is not supported')
+
+    def forward(self, x):
+        y = self._launch(_native_ops(self), x)
+        if y is not None:
+            return y
+        top, left, h, w = get_resized_crop_params(x.shape[-2], x.shape[-1], self.scale, self.ratio)
+        return resized_crop(x, top, left, h, w, self.size, self.interpolation)
+
+    def extra_repr(self):
+        return f'size={self.size}, scale={self.scale}, ratio={self.ratio}, interpolation={self.interpolation}'
+
+
+class ElasticTransform(_Launcher):
+    """Moves every pixel by one smooth random displacement field per call (`elastic_displacement` of uniform noise, strength
+    `alpha`, smoothness `sigma`: floats or (x, y) pairs), shared by all frames and channels of the call, zeros outside.
+    NEAREST is one launch with the field drawn on the device; BILINEAR is module code, whose host-drawn field is FROZEN inside
+    a captured step (see the module)."""
+
+    def __init__(self, alpha=50.0, sigma=5.0, interpolation=InterpolationMode.BILINEAR, fill=0):
+        super().__init__()
+        if fill not in (0, 0., None):
+            raise NotImplementedError('ElasticTransform: fill is not supported')
+        for name, value in (('alpha', alpha), ('sigma', sigma)):
+            if isinstance(value, bool) or not isinstance(value, (int, float, Sequence)) or isinstance(value, str):
+                raise TypeError(f'{name} should be a number or a sequence of numbers')
+        self.alpha = tuple(float(a) for a in _pair(alpha, 'alpha'))
+        self.sigma = tuple(float(s) for s in _pair(sigma, 'sigma'))
+        self.interpolation = _interpolation(interpolation, 'ElasticTransform')
+
+    def forward(self, x):
+        y = self._launch(_native_ops(self), x)
+        if y is not None:
+            return y
+        H, W = x.shape[-2:]
+        noise = (torch.rand(2, H, W) * 2 - 1).to(x.device)
+        return elastic(x, elastic_displacement(noise, self.alpha, self.sigma), self.interpolation)
+
+    def extra_repr(self):
+        return f'alpha={self.alpha}, sigma={self.sigma}, interpolation={self.interpolation}'
 
 
 class Compose(_Launcher):

@@ -252,6 +252,13 @@ class ImageOp(C.Structure):
                 ('b', C.c_float), ('c', C.c_float)]
 
 
+class ImageWarpOp(C.Structure):
+    """asac_image_warp_op_t: one member of a `warp_image` table"""
+    _fields_ = [('kind', C.c_int32), ('k0', C.c_int32), ('k1', C.c_int32), ('scale_lo', C.c_float), ('scale_hi', C.c_float),
+                ('ratio_lo', C.c_float), ('ratio_hi', C.c_float), ('alpha0', C.c_float), ('alpha1', C.c_float),
+                ('sigma0', C.c_float), ('sigma1', C.c_float)]
+
+
 _SIGNATURES = {
     'asac_version': (C.c_int, []),
     'asac_last_error': (C.c_char_p, []),
@@ -640,6 +647,9 @@ _SIGNATURES = {
                                               C.c_void_p, C.c_void_p]),
     'asac_image_augment': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.POINTER(ImageOp), C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_image_warp': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  C.POINTER(ImageWarpOp), C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -3604,3 +3614,41 @@ def image_augment(x, y, ops, seed=0, instance=0, state=None, drawn=None):
     _check(load().asac_image_augment(_p(x), _p(y), N * Cc, Cc, H, W, y.shape[2], y.shape[3], ops, len(ops),
                                      C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint32(int(instance) & 0x0FFFFFFF), _p(state),
                                      _p(drawn), _stream()), 'asac_image_augment')
+
+
+# ------------------------------------------------------------------------------------------------
+# image warps (csrc/image.hip): RandomResizedCrop / ElasticTransform with nearest sampling
+# ------------------------------------------------------------------------------------------------
+IMAGE_WARP_MAX_KERNEL = 63
+IMAGE_WARP_COPY, IMAGE_WARP_RESIZED_CROP, IMAGE_WARP_ELASTIC = range(3)
+IMAGE_WARP_DRAWN = ('counter', 'choice', 'top', 'left', 'height', 'width')     # the f64 record of a call's draws
+
+
+def warp_image_ops(ops):
+    """a host table (ctypes array of `ImageWarpOp`) from dicts of its fields; kept by the caller for as long as it launches"""
+    assert 1 <= len(ops) <= IMAGE_MAX_OPS
+    arr = (ImageWarpOp * len(ops))()
+    for slot, fields in zip(arr, ops):
+        for k, v in fields.items():
+            setattr(slot, k, v)
+    return arr
+
+
+def warp_image(x, y, ops, seed=0, instance=0, state=None, drawn=None, noise_out=None, disp_out=None):
+    """x [N, C, H, W] -> y [N, C, Ho, Wo] (float32, contiguous) through the op of the table `ops` (`warp_image_ops`), or
+    through one member per call picked on the device where it has several: one launch.  state: as for `image_augment`, None
+    only for a table that is one COPY; drawn: float64 [6] | None, see `IMAGE_WARP_DRAWN`; noise_out / disp_out: None, or
+    float32 [2, H, W] that receive an ELASTIC call's field noise and its displacement (x, y) in grid units"""
+    N, Cc, H, W = x.shape
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+    assert y.is_cuda and y.dtype == torch.float32 and y.is_contiguous() and y.dim() == 4 and y.shape[:2] == x.shape[:2]
+    assert state is None or (state.is_cuda and state.dtype == torch.int64 and state.numel() == IMAGE_STATE_WORDS)
+    assert drawn is None or (drawn.is_cuda and drawn.dtype == torch.float64 and drawn.numel() == len(IMAGE_WARP_DRAWN))
+    for t in (noise_out, disp_out):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (2, H, W))
+    _check(load().asac_image_warp(_p(x), _p(y), N * Cc, Cc, H, W, y.shape[2], y.shape[3], ops, len(ops),
+                                  C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint32(int(instance) & 0x0FFFFFFF), _p(state),
+                                  _p(drawn), _p(noise_out), _p(disp_out), _stream()), 'asac_image_warp')
+
+
+warp_image = _profiled(warp_image, 'asac_image_warp')

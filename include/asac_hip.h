@@ -2083,6 +2083,51 @@ typedef struct {
 int asac_image_augment(const float* x, float* y, int64_t planes, int C, int H, int W, int Ho, int Wo, const asac_image_op_t* ops,
                        int n_ops, uint64_t seed, uint32_t instance, int64_t* state, double* drawn, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Image warps (csrc/image.hip; `RandomResizedCrop` and `ElasticTransform` of algorithm/utils/image_transforms.py with
+ * NEAREST interpolation), ONE launch per call.  x [planes][H][W] -> y [planes][Ho][Wo], float32, contiguous;
+ * H * W <= ASAC_IMAGE_MAX_PLANE.  Every output pixel is a copy of an input pixel's bits (or zero): the planes are gathered
+ * straight from global memory, a workgroup of the capped grid takes several planes in turn.
+ *
+ * `ops`: a HOST table of 1 .. ASAC_IMAGE_MAX_OPS descriptors, copied into the launch; several: one is picked per call,
+ * uniformly, on the device.  Every op but RESIZED_CROP needs Ho == H and Wo == W.
+ *   COPY          y = x
+ *   RESIZED_CROP  torchvision's window rule: up to 10 tries of area = H W U(scale), aspect = exp(U(log ratio)),
+ *                 w = rint(sqrt(area aspect)), h = rint(sqrt(area / aspect)), the first with 0 < w <= W and 0 < h <= H wins
+ *                 and its offsets are drawn uniformly; after 10 rejections the central window of the nearest allowed aspect.
+ *                 The window is resampled to Ho x Wo by torch's legacy nearest rule,
+ *                 src = min(floor(dst * (float)in / out), in - 1): shrinking and enlarging alike.
+ *   ELASTIC       one displacement field per call, shared by all planes: 2 H W uniforms in [-1, 1), field f (0: x, 1: y)
+ *                 blurred separably with k_f taps on both axes (odd, <= ASAC_IMAGE_WARP_MAX_KERNEL, k / 2 < min(H, W);
+ *                 the taps along x from sigma0, along y from sigma1, both > 0; reflect indexing) and scaled by alpha0 / H
+ *                 (x) or alpha1 / W (y).  Pixel (i, j) reads the input at the rounded (half to even) unnormalised
+ *                 coordinate ((g + 1) * n - 1) / 2 of g = linspace((1 - n) / n, (n - 1) / n, n)[.] + field, zero outside.
+ *                 Every workgroup builds the field in LDS (3 H W floats) from the call's Philox stream.
+ *
+ * Draws: `state`, seed, instance and the last-arriver finish exactly as for asac_image_augment; `state` may be NULL only
+ * for a table that is one COPY.  `drawn` (NULL or 6 doubles) receives counter, choice, top, left, height, width of this call
+ * (-1 where the chosen op has no window).  `noise_out` / `disp_out`: NULL, or [2][H][W] floats that receive the field's raw
+ * noise and the final displacement (x, then y, in grid units) when the chosen op is ELASTIC.
+ * Anything outside the limits returns hipErrorInvalidValue without a launch.
+ * ------------------------------------------------------------------------------------------- */
+#define ASAC_IMAGE_WARP_MAX_KERNEL 63
+#define ASAC_IMAGE_WARP_COPY 0
+#define ASAC_IMAGE_WARP_RESIZED_CROP 1
+#define ASAC_IMAGE_WARP_ELASTIC 2
+
+typedef struct {
+    int32_t kind;
+    int32_t k0, k1;                 /* ELASTIC: taps of the x field, of the y field */
+    float scale_lo, scale_hi;       /* RESIZED_CROP: the window's share of the frame's area */
+    float ratio_lo, ratio_hi;       /* RESIZED_CROP: its aspect w / h */
+    float alpha0, alpha1;           /* ELASTIC */
+    float sigma0, sigma1;           /* ELASTIC */
+} asac_image_warp_op_t;
+
+int asac_image_warp(const float* x, float* y, int64_t planes, int C, int H, int W, int Ho, int Wo,
+                    const asac_image_warp_op_t* ops, int n_ops, uint64_t seed, uint32_t instance, int64_t* state, double* drawn,
+                    float* noise_out, float* disp_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

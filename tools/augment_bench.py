@@ -7,7 +7,12 @@ Frames: 768 (usv_search's batch 256 x n-step 3) of 84 x 84 x 3 and of 30 x 30 x 
 device synchronise) and `captured` (the call inside a `CapturedStep`, microseconds a replay).  The two ways alternate
 (module, launch, module, launch, ...); the median of the rounds is reported, all rounds are listed.  One JSON line per row.
 
-    python tools/augment_bench.py [--calls 200] [--frames 768]"""
+`--warp`: the rows of `asac_image_warp` instead — `RandomResizedCrop` and `ElasticTransform(100, 5)` with NEAREST and the
+two-member `RandomChoice` of ugv_parking, plus the elastic transform on ONE plane: what building the field costs a call (every
+workgroup builds it, so the rest of the full row is the planes).  The module code of the elastic transform copies its host
+noise to the device, which no capture takes: in `captured` mode its side of these rows stays eager (`module_mode`).
+
+    python tools/augment_bench.py [--warp] [--calls 200] [--frames 768]"""
 import argparse
 import json
 import sys
@@ -44,6 +49,25 @@ def transforms(size):
     }
 
 
+def warp_transforms(size):
+    import algorithm.nn_models as m
+    from algorithm.utils import image_transforms as T
+    nearest = T.InterpolationMode.NEAREST
+
+    def rrc():
+        return T.RandomResizedCrop(size=(size, size), scale=(0.8, 0.9), interpolation=nearest)
+
+    def elastic():
+        return T.ElasticTransform(alpha=100, sigma=5, interpolation=nearest)
+
+    return {
+        'resized_crop_nearest': rrc,
+        'elastic_100_5': elastic,
+        'elastic_100_5_one_plane': elastic,
+        'choice_of_two': lambda: T.RandomChoice([m.Transform(rrc()), m.Transform(elastic())]),
+    }
+
+
 def module_code(module):
     """the same transform with every launch switched off"""
     from algorithm.utils.image_transforms import _Launcher
@@ -66,7 +90,7 @@ def timed(fn, calls):
     return (time.perf_counter() - t0) / calls * 1e6
 
 
-def row(name, build, x, calls, mode):
+def row(name, build, x, calls, mode, capture_module=True):
     from algorithm.captured_step import CapturedStep
     from asac_amd import native
     ways = {'module': module_code(build()), 'launch': build()}
@@ -78,7 +102,7 @@ def row(name, build, x, calls, mode):
         with native.LaunchProfiler(repeat=1) as prof:
             mod(x)
         out['image_launches_' + tag] = sum(v['calls'] for k, v in prof.summary().items() if k.startswith('asac_image_'))
-        if mode == 'captured':
+        if mode == 'captured' and (tag == 'launch' or capture_module):
             step = CapturedStep.capture(lambda mod=mod: mod(x), x.device)
             step.replay()
             fns[tag] = step.replay
@@ -91,6 +115,8 @@ def row(name, build, x, calls, mode):
     for tag in ways:
         out['us_' + tag] = median(runs[tag])
         out['us_' + tag + '_rounds'] = runs[tag]
+    if mode == 'captured' and not capture_module:
+        out['module_mode'] = 'eager'
     out['ratio'] = round(out['us_module'] / out['us_launch'], 2)
     # what one read and one write of the frames would take at 1 TB/s, for scale
     out['bytes_moved'] = 2 * x.numel() * 4
@@ -102,17 +128,21 @@ def main():
     ap.add_argument('--calls', type=int, default=200)
     ap.add_argument('--frames', type=int, default=768)
     ap.add_argument('--only', default=None, help='one op name')
+    ap.add_argument('--warp', action='store_true', help='the rows of asac_image_warp')
     args = ap.parse_args()
     import asac_amd  # noqa: F401
     assert torch.cuda.is_available(), 'needs cuda:0'
     gen = torch.Generator().manual_seed(0)
     for size in (84, 30):
         x = torch.rand(args.frames, 3, size, size, generator=gen).cuda()
-        for name, build in transforms(size).items():
+        for name, build in (warp_transforms if args.warp else transforms)(size).items():
             if args.only and name != args.only:
                 continue
+            frames = x[:1, :1] if name.endswith('_one_plane') else x
             for mode in ('eager', 'captured'):
-                print(json.dumps(row(name, build, x, args.calls, mode)), flush=True)
+                # (the elastic module code's host noise cannot be captured)
+                print(json.dumps(row(name, build, frames, args.calls, mode, capture_module=not args.warp or 'resized' in name)),
+                      flush=True)
 
 
 if __name__ == '__main__':

@@ -1,6 +1,7 @@
 // Per-row pieces of the branched categorical policy (reference nn_models/policy.py: one OneHotCategorical per discrete
-// action branch, concatenated), shared by the four kernels of discrete.hip.  ONE implementation: a value two kernels both
-// form (p at the step's state in the policy step and in the temperature step) has the same bits in both.
+// action branch, concatenated), under every kernel over a categorical head: the rows of asac_discrete_rows.h (discrete.hip,
+// hybrid.hip, dqn.hip), asac_dqn.h, act.hip, drnd.hip.  ONE implementation: a value two kernels both form (p at the step's
+// state in the policy step and in the temperature step) has the same bits in both.
 //   p  = softmax(z)           = exp(z - max) / sum_j exp(z_j - max)        (torch softmax)
 //   lp = z - logsumexp(z)     = z - (log(sum_j exp(z_j - max)) + max)      (torch logsumexp)
 //   cl(p) = log(max(p, 1e-8))                                              (sac_base.py: torch.log(probs.clamp(min=1e-8)))

@@ -120,6 +120,26 @@ __device__ __forceinline__ float clipped_q_loss_row(float qv, float tv, float yv
     return fmaxf(la, lb) * wv;
 }
 
+// Policy objective of the continuous head, row b (reference sac_base.py:1882-1903): the (first) arg-min member of the
+// subset of q [E, B] (NULL: members 0..Es-1), the row's column of grad_q (-inv_b there, else 0), grad_logp[b] =
+// alpha * inv_b; returns the row's value alpha * logp_b - min
+__device__ __forceinline__ float policy_loss_row(const float* logp, const float* q, const int32_t* subset, int E, int Es,
+                                                 int B, int b, float alpha, float inv_b, float* grad_logp, float* grad_q) {
+    int best = subset ? subset[0] : 0;
+    float m = q[(int64_t)best * B + b];
+    for (int k = 1; k < Es; ++k) {
+        const int e = subset ? subset[k] : k;
+        const float v = q[(int64_t)e * B + b];
+        if (v < m) {
+            m = v;
+            best = e;
+        }
+    }
+    for (int e = 0; e < E; ++e) grad_q[(int64_t)e * B + b] = (e == best) ? -inv_b : 0.f;
+    grad_logp[b] = alpha * inv_b;
+    return alpha * logp[b] - m;
+}
+
 __device__ __forceinline__ float wave_min(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));

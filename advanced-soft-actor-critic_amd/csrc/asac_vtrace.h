@@ -140,8 +140,9 @@ __device__ __forceinline__ float vtrace_step_finish_v(const Args& a, const Vtrac
     return v_t;
 }
 
-__device__ __forceinline__ float vtrace_step_finish(const asac_vtrace_args_t& a, const VtraceStepRaw& r, float alpha,
-                                                    float* d, float* c) {
+template <typename Args>
+__device__ __forceinline__ float vtrace_step_finish(const Args& a, const VtraceStepRaw& r, float alpha, float* d,
+                                                    float* c) {
     const float v_t = r.m0 - alpha * r.lp0, v_next = r.m1 - alpha * r.lp1;
     return vtrace_step_finish_v(a, r, v_t, v_next, d, c);
 }

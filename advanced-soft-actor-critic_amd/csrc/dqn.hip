@@ -1,6 +1,7 @@
 // Pure-discrete, DQN-like learner (d_action_sizes set, c_action_size == 0, discrete_dqn_like): the arithmetic around the
 // critics, three launches (reference sac_base.py: get_dqn_like_d_y 1194-1242 + _get_y 1363-1382, _train_rep_q 1533-1538 /
-// 1563-1568, _get_td_error 2219-2244, _choose_action 904-930 without RND).  The per-row target is asac_dqn.h's.
+// 1563-1568, _get_td_error 2219-2244, _choose_action 904-930 without RND).  The per-row target is asac_dqn.h's, the loss
+// launch's gradient row asac_discrete_rows.h's (the one asac_discrete_q_loss_grad writes).
 //
 //   asac_dqn_return       one lane per row, workgroups of 64 rows, no exchange between them: y (and the TD error)
 //   asac_dqn_q_loss_grad  one workgroup per online member: each forms its rows' y itself (row-local, kept in registers),
@@ -9,7 +10,7 @@
 //   asac_dqn_act          one lane per row: greedy one-hot per branch from the first critic's heads, epsilon-random rows
 //                         from uniforms drawn by the caller
 // No float atomics: equal inputs give equal bits.  The argument blocks are read in place from the kernel-argument segment.
-#include "asac_common.h"
+#include "asac_discrete_rows.h"
 #include "asac_dqn.h"
 
 namespace asac {
@@ -51,10 +52,7 @@ __global__ __launch_bounds__(kDiscThreads) void k_dqn_q_loss(const DqnLossDev by
         const float wv = v.w ? v.w[(int64_t)b * v.w_stride] : 1.f;
         const float diff = dqn_stored_q(x, e, b) - y;
         part += diff * diff * wv;
-        const float gq = 2.f * diff * wv / (float)B / (float)K;
-        const float* act = x.action + (int64_t)b * x.action_stride;
-        float* g = v.grad + ((int64_t)e * B + b) * D;
-        for (int j = 0; j < D; ++j) g[j] = gq * act[j];
+        disc_q_grad_row(diff, wv, x.action + (int64_t)b * x.action_stride, v.grad + ((int64_t)e * B + b) * D, B, D, K);
     }
     const float total = disc_tree_sum(red, part);
     if (threadIdx.x == 0) v.loss[e] = total / (float)B;

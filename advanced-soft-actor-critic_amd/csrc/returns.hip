@@ -448,19 +448,7 @@ __global__ __launch_bounds__(256) void k_policy_loss(const float* __restrict__ l
     const float inv_b = 1.f / (float)B;
     float part = 0.f, ent = 0.f;
     for (int b = threadIdx.x; b < B; b += blockDim.x) {
-        int best = subset ? subset[0] : 0;
-        float m = q[(int64_t)best * B + b];
-        for (int k = 1; k < Es; ++k) {
-            const int e = subset ? subset[k] : k;
-            const float v = q[(int64_t)e * B + b];
-            if (v < m) {
-                m = v;
-                best = e;
-            }
-        }
-        for (int e = 0; e < E; ++e) grad_q[(int64_t)e * B + b] = (e == best) ? -inv_b : 0.f;
-        grad_logp[b] = alpha * inv_b;
-        part += alpha * logp[b] - m;
+        part += policy_loss_row(logp, q, subset, E, Es, B, b, alpha, inv_b, grad_logp, grad_q);
         if (scale)
             for (int d = 0; d < A; ++d) ent += logf(scale[(int64_t)b * scale_rs + d]) + 1.4189385332046727f;
     }

@@ -168,6 +168,21 @@ def test_the_loss_launch_stores_the_bits_of_the_return_launch(B, n, sizes, E, Es
     assert torch.isfinite(out['y']).all() and torch.equal(out['y'], out['y_loss'])
 
 
+def test_the_loss_launch_shares_the_discrete_q_loss_launchs_bits():
+    """one implementation of the Q step's row (`disc_dot`, csrc/asac_discrete_rows.h `disc_q_grad_row`): on the smallest
+    case with two branches, `asac_discrete_q_loss_grad` given the y `asac_dqn_q_loss_grad` stored and the same weights
+    returns its loss and its gradient, `torch.equal`"""
+    import asac_amd  # noqa: F401
+    from asac_amd import native
+    c = qr.to(qr.make_case(5, 3, (3, 2), 3, 2, True, seed=5), torch.float32, 'cuda', strided=True)
+    out = _kernels(c)
+    assert c['w'] is not None and torch.isfinite(out['y_loss']).all()
+    loss, grad = torch.full_like(out['loss_q'], float('nan')), torch.full_like(out['grad_q'], float('nan'))
+    native.discrete_q_loss_grad(native.branches(c['sizes']), c['q_online'], c['action'], out['y_loss'], c['w'], loss, grad)
+    assert torch.isfinite(loss).all() and torch.equal(out['loss_q'], loss)
+    assert torch.isfinite(grad).all() and torch.equal(out['grad_q'], grad)
+
+
 # ------------------------------------------------------------------------------------------------
 # acting
 # ------------------------------------------------------------------------------------------------

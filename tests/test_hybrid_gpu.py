@@ -173,7 +173,8 @@ def test_the_planted_rows_are_what_they_claim():
 def test_the_launches_share_the_single_head_launches_bits(B, n, sizes, A, E, Es, use_is):
     """on the same inputs: d_y is `asac_discrete_return`'s, c_y `asac_vtrace_return_min`'s, the two temperature slots
     `asac_discrete_alpha_grad`'s and `asac_alpha_grad`'s, the policy launch's grad_cq / grad_logp
-    `asac_policy_loss_fwd_bwd`'s and the Q launch's grad_cq `asac_q_loss_fwd_bwd`'s — bit for bit"""
+    `asac_policy_loss_fwd_bwd`'s, the Q launch's grad_cq `asac_q_loss_fwd_bwd`'s, the policy launch's grad_logits /
+    d_entropy `asac_discrete_policy_loss_grad`'s and the Q launch's grad_qd `asac_discrete_q_loss_grad`'s — bit for bit"""
     import asac_amd  # noqa: F401
     from asac_amd import native
     c = _device_case(hr.make_case(B, n, sizes, A, E, Es, use_is, True, seed=B + n))
@@ -196,6 +197,17 @@ def test_the_launches_share_the_single_head_launches_bits(B, n, sizes, A, E, Es,
     native.q_loss_fwd_bwd(c['c_q_online'], c['c_t_q'], c['c_y'].reshape(-1).contiguous(), c['w'].reshape(-1).contiguous(),
                           c['clip_eps'], nan(E), grad_q)
     assert torch.isfinite(grad_q).all() and torch.equal(got['grad_cq'], grad_q)
+    # the discrete rows (csrc/asac_discrete_rows.h): the policy launch's grad_logits and d_entropy against
+    # `asac_discrete_policy_loss_grad`, the Q launch's grad_qd against `asac_discrete_q_loss_grad`.  (c_entropy is not
+    # `asac_policy_loss_fwd_bwd`'s: one divides by B, the other multiplies by 1 / B.)
+    grad_logits, d_entropy = nan(B, c['D']), nan(1)
+    native.discrete_policy_loss_grad(br, c['logits0'], c['q_online'], c['sub_pi'], Es, c['mu0'], c['log_alpha'],
+                                     c['penalty'], nan(1), grad_logits, d_entropy)
+    assert torch.isfinite(grad_logits).all() and torch.equal(got['grad_logits'], grad_logits)
+    assert torch.isfinite(d_entropy).all() and torch.equal(got['d_entropy'].reshape(1), d_entropy)
+    grad_qd = nan(E, B, c['D'])
+    native.discrete_q_loss_grad(br, c['q_online'], c['action_full'][:, 0], c['y'], c['w'], nan(E), grad_qd)
+    assert torch.isfinite(grad_qd).all() and torch.equal(got['grad_qd'], grad_qd)
 
 
 # ------------------------------------------------------------------------------------------------

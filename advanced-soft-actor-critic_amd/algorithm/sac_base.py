@@ -42,6 +42,7 @@ from .fused_mlp import StockMLP, describe_policy, describe_q
 from .nn_models import *  # noqa: F401,F403
 from .nn_models.layers.seq_layers import step_mask_cache
 from .nn_models.representation import ModelSimpleRep
+from .normalizer import Normalizer, fused_normalizer_applies
 from .param_grads import direct_param_grads, learner_backward
 from .batch_buffer import BatchBuffer
 from .captured_step import CapturedStep
@@ -388,6 +389,12 @@ class SAC_Base(AuxHeadsMixin):
         # `step/hybrid/*` entries of tests/parity_tolerances.json, 4x the errors observed on the eager composition, and
         # another summation order cannot promise to stay inside them
         self._fused_hybrid = bool(hip_config.get('fused_hybrid', False))
+        # asac_obs_whiten / asac_normalizer_update (`use_normalization`: the learner whitens once a step in front of the
+        # plugin's own representation class, algorithm/normalizer.py).  Off by default: the default learner's normalized step
+        # is held to the recorded tolerances of the `aux_norm` golden case, and another summation order in the statistics
+        # cannot promise to stay inside them
+        self._fused_normalizer = bool(hip_config.get('fused_normalizer', False))
+        self.normalizer = None
         self._siamese_ws = {}            # (N, E) / ('byol', encoder index) -> the launch's zeroed exchange words
         self._fused_rpm_loss = bool(hip_config.get('fused_rpm_loss', True))
         # one backward walk per prediction model (gates and model gradients from it): sac_aux._train_rpm
@@ -500,7 +507,17 @@ class SAC_Base(AuxHeadsMixin):
 
         # -- representation ----------------------------------------------------------------------
         rep_args = (self.obs_names, self.obs_shapes, self.d_action_sizes, self.c_action_size)
-        ModelRep = self._wrap_normalized_rep(nn.ModelRep) if self.use_normalization else nn.ModelRep
+        if fused_normalizer_applies(enabled=self._fused_normalizer, use_normalization=self.use_normalization,
+                                    plain_learner=type(self)._plain_learner, data_parallel=self._dist is not None,
+                                    float32_on_device=dev.type == 'cuda' and torch.get_default_dtype() == torch.float32):
+            # the plugin's own class: every `type(...) is ModelSimpleRep` test sees what it sees without normalization; the
+            # learner whitens in front of it (`_l_states_whitened` takes whitened observations, `get_l_states` raw ones)
+            ModelRep = nn.ModelRep
+            self.normalizer = Normalizer(self.obs_shapes, dev)
+            self.normalizer_step = self.normalizer.normalizer_step
+            self.running_means, self.running_variances = self.normalizer.running_means, self.normalizer.running_variances
+        else:
+            ModelRep = self._wrap_normalized_rep(nn.ModelRep) if self.use_normalization else nn.ModelRep
         self.model_rep = ModelRep(*rep_args, False, self.model_abs_dir, **rep_kw).to(dev)
         self.model_target_rep = ModelRep(*rep_args, True, self.model_abs_dir, **rep_kw).to(dev)
         if self._fuse_linear_tanh:     # the plugins' Linear + Tanh state heads: one launch per pass
@@ -508,12 +525,13 @@ class SAC_Base(AuxHeadsMixin):
             fuse_linear_tanh_heads(self.model_rep), fuse_linear_tanh_heads(self.model_target_rep)
         test_obs = [torch.rand(B, 1, *s, device=dev) for s in self.obs_shapes]
         test_pre_action = torch.rand(B, 1, A_all, device=dev)
+        test_rep_obs = test_obs if self.normalizer is None else self.normalizer.whiten(test_obs)
         with torch.no_grad():
             if self.seq_encoder == SEQ_ENCODER.ATTN:
                 test_index = torch.zeros((B, 1), dtype=torch.int32, device=dev)
-                st, hs, _ = self.model_rep(1, test_index, test_obs, test_pre_action, None)
+                st, hs, _ = self.model_rep(1, test_index, test_rep_obs, test_pre_action, None)
             else:
-                st, hs = self.model_rep(test_obs, test_pre_action, None)
+                st, hs = self.model_rep(test_rep_obs, test_pre_action, None)
         self.state_size, self.seq_hidden_state_shape = st.shape[-1], hs.shape[2:]
         for p in self.model_target_rep.parameters():
             p.requires_grad = False
@@ -1059,7 +1077,8 @@ class SAC_Base(AuxHeadsMixin):
         algorithm/agent.py): same computation, no host round trip; returns device tensors."""
         obs_list = list(obs_list)
         self._process_torch_obs_list(obs_list)
-        state, next_hidden = self.model_rep([o.unsqueeze(1) for o in obs_list], pre_action.unsqueeze(1),
+        rep_obs = obs_list if self.normalizer is None else self.normalizer.whiten(obs_list)
+        state, next_hidden = self.model_rep([o.unsqueeze(1) for o in rep_obs], pre_action.unsqueeze(1),
                                             pre_seq_hidden_state.unsqueeze(1))
         action, prob = self._choose_action(obs_list, state.squeeze(1), offline_action, disable_sample,
                                            force_rnd_if_available)
@@ -1084,7 +1103,8 @@ class SAC_Base(AuxHeadsMixin):
         cut = lambda x: x[:, -w:]  # noqa: E731
         obs = [cut(o) for o in ep_obses_list]
         self._process_torch_obs_list(obs)
-        state, attn_state, _ = self.model_rep(1, cut(ep_indexes), obs, cut(ep_pre_actions),
+        rep_obs = obs if self.normalizer is None else self.normalizer.whiten(obs)
+        state, attn_state, _ = self.model_rep(1, cut(ep_indexes), rep_obs, cut(ep_pre_actions),
                                               pre_seq_hidden_state=cut(ep_pre_attn_states),
                                               is_prev_hidden_state=False, padding_mask=cut(ep_padding_masks))
         action, prob = self._choose_action([o[:, -1] for o in obs], state.squeeze(1), offline_action,
@@ -1123,8 +1143,24 @@ class SAC_Base(AuxHeadsMixin):
         bnx_padding_masks = torch.concat([bn_padding_masks, bn_padding_masks[:, -1:]], dim=1)
         return bnx_indexes, bnx_padding_masks, gen_n_pre_actions(bn_actions, keep_last_action=True)
 
+    def whiten_obs(self, obs_list):
+        """`obs_list` as `model_rep.forward` expects it: whitened by the running statistics under
+        `hip_config['fused_normalizer']` (for callers that use `model_rep` directly), else unchanged — a `NormalizedRep`
+        whitens inside its forward"""
+        return list(obs_list) if self.normalizer is None else self.normalizer.whiten(obs_list)
+
     def get_l_states(self, l_indexes, l_padding_masks, l_obses_list, l_pre_actions, l_pre_seq_hidden_states,
                      is_target=False):
+        """The reference's contract: RAW observations in, whatever normalizes them."""
+        if self.normalizer is not None:
+            l_obses_list = self.normalizer.whiten(l_obses_list)
+        return self._l_states_whitened(l_indexes, l_padding_masks, l_obses_list, l_pre_actions, l_pre_seq_hidden_states,
+                                       is_target=is_target)
+
+    def _l_states_whitened(self, l_indexes, l_padding_masks, l_obses_list, l_pre_actions, l_pre_seq_hidden_states,
+                           is_target=False):
+        """`get_l_states` on observations the representation takes as they are: the step's own passes over `w.rep_in`,
+        whitened once a step by `_window_views`"""
         rep = self.model_target_rep if is_target else self.model_rep
         if self.seq_encoder == SEQ_ENCODER.ATTN:
             st, attn, _ = rep(l_indexes.shape[1], l_indexes, l_obses_list, l_pre_actions,
@@ -2398,8 +2434,11 @@ class SAC_Base(AuxHeadsMixin):
                 'action': ep_actions[0], 'reward': ep_rewards[0], 'done': ep_dones[0],
                 'mu_prob': ep_probs[0], 'pre_seq_hidden_state': ep_pre_seq_hidden_states[0]}
         if self.use_normalization:
-            self._update_normalizer(obs_dev if obs_dev is not None
-                                    else [torch.from_numpy(o[0]).to(self.device) for o in ep_obses_list])
+            ep_obs = obs_dev if obs_dev is not None else [torch.from_numpy(o[0]).to(self.device) for o in ep_obses_list]
+            if self.normalizer is not None:
+                self.normalizer.update(ep_obs)       # one launch for all observations
+            else:
+                self._update_normalizer(ep_obs)
         self.replay_buffer.add(rows, ignore_size=1)
 
     # ==========================================================================================
@@ -2465,8 +2504,10 @@ class SAC_Base(AuxHeadsMixin):
         # (no burn-in: the window views are then the whole buffers, nothing copies them in front of the launch; a batch of
         # more than 256 rows with deferred weights keeps `window_gather_pad_w`)
         weights = self._defer_is_weights
+        # (a normalized learner: the first network launch would read RAW rows from the ring — the gather runs on its own,
+        # the whiten launch follows and the stock chain reads the whitened buffer)
         if (self._head_gather_sidecar and self._lookahead == 0 and self.burn_in_step == 0 and self._dist is None
-                and self._stock_c_only()
+                and self.normalizer is None and self._stock_c_only()
                 and type(self.model_rep) is ModelSimpleRep and self.optimizer_rep is None
                 and self.clip_epsilon > 0 and self.siamese is None and not self.use_prediction
                 and not self._wide_critics and len(self.obs_names) == 1 and not (weights and rb.batch_size > 256)):
@@ -2559,9 +2600,15 @@ class SAC_Base(AuxHeadsMixin):
         w.stock = self._stock_c_only()
         w.rep_trainable = self.optimizer_rep is not None
         self.noise.prefill(self._eps_all)          # (torch fallback: one launch for all Gaussian draws)
+        rep_obs = w.bnx_obses_list
+        if self.normalizer is not None:
+            # the step's ONE whitening, behind the batch's gather and with the statistics of train time: all window
+            # observations -> static buffers of their shapes.  Every representation pass of the step reads these
+            # (`_l_states_whitened`); whatever else reads observations (`w.nx_obs`, `w.obs_b`) keeps the raw buffers
+            rep_obs = self.normalizer.whiten(w.bnx_obses_list, static=True)
         if type(self.model_rep) is ModelSimpleRep:
             # the stock concatenation rep ignores index / mask / previous actions: do not build them
-            w.rep_in = (None, None, w.bnx_obses_list, None, w.bnx_hidden)
+            w.rep_in = (None, None, rep_obs, None, w.bnx_hidden)
         else:
             if derived is not None:
                 # (the gather delivered them as derived keys of its launch: no `asac_window_aux`)
@@ -2570,7 +2617,7 @@ class SAC_Base(AuxHeadsMixin):
             else:
                 bnx_indexes, bnx_padding_masks, bnx_pre_actions = self.get_bnx_data(
                     w.bn_indexes, w.bn_pad, w.bn_actions, pre_action_out=joint_pre_action)
-            w.rep_in = (bnx_indexes, bnx_padding_masks, w.bnx_obses_list, bnx_pre_actions, w.bnx_hidden)
+            w.rep_in = (bnx_indexes, bnx_padding_masks, rep_obs, bnx_pre_actions, w.bnx_hidden)
         return w
 
     def _step_rep_and_q(self, w) -> None:
@@ -2595,23 +2642,24 @@ class SAC_Base(AuxHeadsMixin):
         from_b = (self._rep_from_burn_in and self.seq_encoder is None and b > 0 and w.rep_trainable
                   and type(self.model_rep) is not ModelSimpleRep)     # (a fixed representation's one pass serves the whole step)
         rep_in, pb = w.rep_in, b
+        # (a normalized learner's window is whitened already: its passes go around `get_l_states`' whitening)
+        l_states = self.get_l_states if self.normalizer is None else self._l_states_whitened
         if from_b:
             tail = lambda x: None if x is None else x[:, b:]  # noqa: E731
             idx, pad, obs, pre, hidden = w.rep_in
             rep_in, pb = (tail(idx), tail(pad), [o[:, b:] for o in obs], tail(pre), tail(hidden)), 0
         with (self._rep_twin if self._rep_twin else contextlib.nullcontext()), cat_mode():
             with torch.no_grad() if one_position else contextlib.nullcontext():
-                bnx_states, next_hidden = self.get_l_states(*rep_in, is_target=False)
+                bnx_states, next_hidden = l_states(*rep_in, is_target=False)
             with torch.no_grad():
-                w.bnx_target_states, _ = self.get_l_states(*rep_in, is_target=True)
+                w.bnx_target_states, _ = l_states(*rep_in, is_target=True)
         w.nx_target_states = w.bnx_target_states[:, pb:]
         state_base = (bnx_states, pb)
         if one_position:
             at = lambda x: None if x is None else x[:, b:b + 1]  # noqa: E731
             idx, pad, obs, pre, hidden = w.rep_in
             with cat_mode():
-                state_b, _ = self.get_l_states(at(idx), at(pad), [o[:, b:b + 1] for o in obs], at(pre), at(hidden),
-                                               is_target=False)
+                state_b, _ = l_states(at(idx), at(pad), [o[:, b:b + 1] for o in obs], at(pre), at(hidden), is_target=False)
             state_base = (state_b, 0)
         aux = None
         if with_aux:
@@ -2624,7 +2672,7 @@ class SAC_Base(AuxHeadsMixin):
                           state_base=state_base)
         if w.rep_trainable:   # states under the updated representation (reference 2097-2103)
             with torch.no_grad(), cat_mode():
-                w.bnx_states, w.next_hidden = self.get_l_states(*w.rep_in, is_target=False)
+                w.bnx_states, w.next_hidden = l_states(*w.rep_in, is_target=False)
         else:
             w.bnx_states, w.next_hidden = bnx_states.detach(), next_hidden.detach()
 

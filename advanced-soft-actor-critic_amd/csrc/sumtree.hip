@@ -611,6 +611,8 @@ int64_t asac_struct_size(const char* name) {
     ASAC_SZ(asac_branches_t);
     ASAC_SZ(asac_members_t);
     ASAC_SZ(asac_discrete_return_t);
+    ASAC_SZ(asac_whiten_job_t);
+    ASAC_SZ(asac_normalizer_job_t);
 #undef ASAC_SZ
     return -1;
 }

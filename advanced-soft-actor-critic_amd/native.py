@@ -259,6 +259,18 @@ class ImageWarpOp(C.Structure):
                 ('sigma0', C.c_float), ('sigma1', C.c_float)]
 
 
+class WhitenJob(C.Structure):
+    """asac_whiten_job_t: one observation of an `obs_whiten` launch (pitches in elements, 0: dense)"""
+    _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('mean', C.c_void_p), ('variance', C.c_void_p), ('D', C.c_int64),
+                ('rows', C.c_int64), ('src_row_pitch', C.c_int64), ('dst_row_pitch', C.c_int64)]
+
+
+class NormalizerJob(C.Structure):
+    """asac_normalizer_job_t: one observation of a `normalizer_update` launch"""
+    _fields_ = [('x', C.c_void_p), ('mean', C.c_void_p), ('variance', C.c_void_p), ('D', C.c_int64),
+                ('x_row_pitch', C.c_int64), ('dtype', C.c_int32), ('reserved_', C.c_int32)]
+
+
 _SIGNATURES = {
     'asac_version': (C.c_int, []),
     'asac_last_error': (C.c_char_p, []),
@@ -650,6 +662,9 @@ _SIGNATURES = {
     'asac_image_warp': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.POINTER(ImageWarpOp), C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
+    'asac_normalizer_row_lanes': (C.c_int, []),
+    'asac_obs_whiten': (C.c_int, [C.POINTER(WhitenJob), C.c_int, C.c_void_p, C.c_void_p]),
+    'asac_normalizer_update': (C.c_int, [C.POINTER(NormalizerJob), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -3652,3 +3667,75 @@ def warp_image(x, y, ops, seed=0, instance=0, state=None, drawn=None, noise_out=
 
 
 warp_image = _profiled(warp_image, 'asac_image_warp')
+
+
+# ------------------------------------------------------------------------------------------------
+# observation normalization (csrc/normalize.hip): one-launch whitening, one-launch statistics update
+# ------------------------------------------------------------------------------------------------
+NORM_MAX_OBS = 8
+NORM_ROW_LANES = 64        # logical row lanes of the update's sums (ASAC_NORM_ROW_LANES): the tests' bound derives from it
+NORM_F32, NORM_U8 = 0, 1
+
+
+def whiten_jobs(specs):
+    """a host table (ctypes array of `WhitenJob`) from (src, dst, mean, variance) tensors: src / dst float32 with unit
+    innermost stride whose trailing `mean.dim()` dimensions are dense and whose leading ones fold into rows of one pitch;
+    kept by the caller (with the tensors) for as long as it launches.  -> None where a tensor does not have that form"""
+    if not 1 <= len(specs) <= NORM_MAX_OBS:
+        return None
+    arr = (WhitenJob * len(specs))()
+    for slot, (src, dst, mean, variance) in zip(arr, specs):
+        D = mean.numel()
+        ps, pd = _row_pitch(src, mean.dim(), D), _row_pitch(dst, mean.dim(), D)
+        if (ps is None or pd is None or src.shape != dst.shape or src.dtype != torch.float32 or dst.dtype != torch.float32
+                or mean.dtype != torch.float32 or variance.dtype != torch.float32 or not mean.is_contiguous()
+                or not variance.is_contiguous() or variance.numel() != D or not (src.is_cuda and dst.is_cuda and mean.is_cuda)):
+            return None
+        slot.src, slot.dst, slot.mean, slot.variance = src.data_ptr(), dst.data_ptr(), mean.data_ptr(), variance.data_ptr()
+        slot.D, slot.rows, slot.src_row_pitch, slot.dst_row_pitch = D, src.numel() // D, ps, pd
+    return arr
+
+
+def _row_pitch(t, inner_dims, D):
+    """elements between consecutive rows of `t` seen as [rows, D] (D = the product of its last `inner_dims` dimensions,
+    dense), or None where the leading dimensions do not fold into one pitch"""
+    lead = t.dim() - inner_dims
+    if lead < 0 or D == 0 or t.numel() == 0:
+        return None
+    expect = 1
+    for size, stride in zip(reversed(t.shape[lead:]), reversed(t.stride()[lead:])):
+        if size != 1 and stride != expect:
+            return None
+        expect *= size
+    if expect != D:
+        return None
+    pitch = None
+    for size, stride in zip(reversed(t.shape[:lead]), reversed(t.stride()[:lead])):
+        if size == 1:
+            continue
+        if pitch is None:
+            pitch, span = stride, stride * size
+        elif stride == span:
+            span = stride * size
+        else:
+            return None
+    if pitch is None:
+        return D
+    return pitch if pitch >= D else None
+
+
+@_profiled
+def obs_whiten(jobs, step):
+    """dst = clamp((src - mean) / sqrt(variance / (step + 1)), -5, 5) for every job of the table (`whiten_jobs`): one
+    launch; `step` int32 on the device, read when the launch runs"""
+    assert step.is_cuda and step.dtype == torch.int32
+    _check(load().asac_obs_whiten(jobs, len(jobs), _p(step), _stream()), 'asac_obs_whiten')
+
+
+@_profiled
+def normalizer_update(jobs, T, step, counter):
+    """the running statistics of every job of the table (ctypes array of `NormalizerJob`) over an episode of T rows, and
+    step += T: one launch; `counter`: one zeroed int32 word owned by the caller, left zero"""
+    assert step.is_cuda and step.dtype == torch.int32 and counter.is_cuda and counter.dtype == torch.int32
+    _check(load().asac_normalizer_update(jobs, len(jobs), int(T), _p(step), _p(counter), _stream()),
+           'asac_normalizer_update')

@@ -2128,6 +2128,62 @@ int asac_image_warp(const float* x, float* y, int64_t planes, int C, int H, int 
                     const asac_image_warp_op_t* ops, int n_ops, uint64_t seed, uint32_t instance, int64_t* state, double* drawn,
                     float* noise_out, float* disp_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Observation normalization (csrc/normalize.hip; `use_normalization` of the reference, sac_base.py:302-336 and 766-781).
+ * Both entry points take a HOST table of 1 .. ASAC_NORM_MAX_OBS jobs, one per observation, copied into the launch.
+ *
+ * asac_obs_whiten: ONE launch for all observations of a call.  Per element, with j the index inside the row,
+ *     dst = clamp((src - mean[j]) / sqrt(variance[j] / (float)(*step + 1)), -5, 5)
+ * — the module expression's operations in its order: IEEE divide and square root, the int32 `step + 1` rounded to float
+ * as torch's promotion does, NaN kept as torch.clamp keeps it.  `step`, `mean` and `variance` are read from device memory
+ * when the launch RUNS: a captured launch replayed after a later update whitens with the newer statistics.
+ *   src / dst   float32, `rows` rows of D elements, consecutive rows `*_row_pitch` elements apart (0: D, dense).
+ *               dst == src with equal pitches (in place) is allowed; any other overlap is refused.
+ *   16-byte units where D, both pitches and all four pointers allow it, else 4-byte units.
+ *
+ * asac_normalizer_update: ONE launch per episode of T rows for all observations.  Per column j of a job
+ *     step' = step + T;  d_t = x_t - mean;  mean' = mean + sum_t (d_t / (float)step');
+ *     variance' = variance + sum_t (x_t - mean') * d_t
+ *   x       [T][D] rows `x_row_pitch` elements apart (0: D), ASAC_NORM_F32, or ASAC_NORM_U8 taken as its integer value
+ *   order   row t belongs to lane t mod ASAC_NORM_ROW_LANES, every lane adds its rows in ascending t, the lane partials
+ *           are combined by the binary tree p[l] += p[l + off], off = LANES / 2 .. 1.  No float atomics: equal inputs
+ *           give equal bits.  A workgroup owns 64 columns and all their rows; no float crosses a workgroup.
+ *   step    int32 on the device; every workgroup reads it, the LAST to arrive at `counter` writes step + T.
+ *   counter one zeroed 32-bit word (asac_ordered_finish.h); every launch leaves it zero.
+ * Under the measurement repeat knob only the first repetition writes.
+ * Anything outside the limits returns hipErrorInvalidValue without a launch.
+ * ------------------------------------------------------------------------------------------- */
+#define ASAC_NORM_MAX_OBS 8
+#define ASAC_NORM_ROW_LANES 64
+#define ASAC_NORM_F32 0
+#define ASAC_NORM_U8 1
+
+typedef struct {
+    const float* src;
+    float* dst;
+    const float* mean;             /* [D] */
+    const float* variance;         /* [D] */
+    int64_t D;
+    int64_t rows;
+    int64_t src_row_pitch;         /* elements; 0: D */
+    int64_t dst_row_pitch;
+} asac_whiten_job_t;
+
+typedef struct {
+    const void* x;
+    float* mean;                   /* [D], updated in place */
+    float* variance;
+    int64_t D;
+    int64_t x_row_pitch;           /* elements; 0: D */
+    int32_t dtype;                 /* ASAC_NORM_F32 | ASAC_NORM_U8 */
+    int32_t reserved_;
+} asac_normalizer_job_t;
+
+int asac_normalizer_row_lanes(void);
+int asac_obs_whiten(const asac_whiten_job_t* jobs_host, int n_jobs, const int32_t* step, void* stream);
+int asac_normalizer_update(const asac_normalizer_job_t* jobs_host, int n_jobs, int T, int32_t* step,
+                           unsigned int* counter, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

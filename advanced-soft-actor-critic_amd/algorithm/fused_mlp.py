@@ -368,6 +368,7 @@ class StockMLP:
         self._anchor = torch.zeros(1, device=device, requires_grad=True)   # keeps the node in the graph
         self.accumulate = True     # False: parameter gradients overwrite the flat gradient buffer
         self._workspace = None
+        self._forward_saves = {}    # (forward_save_buffer)
         self._start, self._deferred_rows = start, None
         self.device = device
 
@@ -431,6 +432,30 @@ class StockMLP:
         self._deferred_rows = N if defer else None
         return g0
 
+    def forward_save_buffer(self, N: int):
+        """the buffer a policy-forward rider saves N rows' forward in (`backward_qloss_return_rider` of the critics):
+        allocated once per N and kept, so the addresses a captured step holds stay valid"""
+        buf = self._forward_saves.get(N)
+        if buf is None:
+            buf = self._forward_saves[N] = torch.zeros(native.policy_forward_save_floats(N), dtype=torch.float32, device=self.device)
+        return buf
+
+    def backward_qloss_return_rider_ok(self, N: int, ret, policy: 'StockMLP', x_pi, save) -> bool:
+        return (policy.E == 1 and x_pi.dim() == 2 and
+                native.mlp_backward_qloss_return_rider_ok(self._pass(None, None, N=N), ret, policy._pass(x_pi, None), save))
+
+    def backward_qloss_return_rider(self, x0, x1, target_q, ret, weights, clip_eps, loss_out, policy: 'StockMLP', x_pi, save,
+                                    defer=False, state_grads=False):
+        """`backward_qloss_return` whose launch also runs `policy`'s forward on the rows `x_pi` [N, in0] on further
+        workgroups and saves it in `save` (`policy.forward_save_buffer`) for `policy.policy_step_fused_loaded`."""
+        N = x0.shape[-2]
+        g0 = torch.empty((self.E, N, self.in0), dtype=torch.float32, device=self.device) if state_grads else None
+        native.mlp_backward_qloss_return_rider(self._pass(x0, x1), target_q, ret, weights, clip_eps, loss_out,
+                                               self.grad_params, self._workspace_for(N), self._reduce_mode(defer),
+                                               policy._pass(x_pi, None), save, grad_x0=g0)
+        self._deferred_rows = N if defer else None
+        return g0
+
     def backward_policy_q(self, x0, x1, q_table, subset, E_sample):
         """-> [E, N, in1] action gradients of mean_b(-min_{e in subset} q_e) (`q_table` [E, N] from the
         forward on the same inputs)."""
@@ -468,6 +493,17 @@ class StockMLP:
                                  self.member_stride, x0, N, action, eps, log_alpha, q_out, self.grad_params,
                                  self._workspace_for(N), self._reduce_mode(defer), subset=subset, a_out=a_out,
                                  logp_out=logp_out, ls_out=ls_out, offline=offline)
+        self._deferred_rows = N if defer else None
+
+    def policy_step_fused_loaded(self, critics: 'StockMLP', x0, action, eps, log_alpha, saved, q_out=None, defer=False,
+                                 subset=None, offline=None):
+        """`policy_step_fused` with the action given, the policy's forward on the rows of `x0` LOADED from `saved` (what
+        the critics' `backward_qloss_return_rider` wrote for these parameters and rows): same results, bit for bit."""
+        N = x0.shape[-2]
+        assert subset is not None or critics.E == 2
+        native.policy_step_fused_loaded(critics.desc, critics.params, critics.member_stride, self.desc, self.params,
+                                        self.member_stride, x0, N, action, eps, log_alpha, saved, q_out, self.grad_params,
+                                        self._workspace_for(N), self._reduce_mode(defer), subset=subset, offline=offline)
         self._deferred_rows = N if defer else None
 
     def adam_partials(self, opt, loss_out=None):

@@ -364,6 +364,8 @@ class SAC_Base(AuxHeadsMixin):
         self._fused_td_chain = bool(hip_config.get('fused_td_chain', True))
         self._fused_td_update = bool(hip_config.get('fused_td_update', True))
         self._fused_q_return = bool(hip_config.get('fused_q_return', True))
+        # the policy step LOADS the policy's forward a rider of the Q-loss backward launch saved (`_stock_q_backward`)
+        self._policy_forward_rider = bool(hip_config.get('policy_forward_rider', True))
         self._fused_q_state_grads = bool(hip_config.get('fused_q_state_grads', True))
         self._gru_backward_at = bool(hip_config.get('gru_backward_at', True))
         self._adjacent_cat = bool(hip_config.get('adjacent_cat', True))
@@ -672,8 +674,13 @@ class SAC_Base(AuxHeadsMixin):
         # the one hand-over between steps that goes through `self`, from the Q step's return target to the policy step
         # (`_train_policy` has the reference's signature: no room for either): `_ls_y` = the policy's output over the
         # return's window, read by `_step_policy`; `_pi_sampled` = the return's sampling launch also drew the policy
-        # step's action at t = 0 into `_pi_a` / `_pi_logp`, taken and cleared by `_train_policy_stock`
+        # step's action at t = 0 into `_pi_a` / `_pi_logp`, taken and cleared by `_train_policy_stock`; `_pi_saved` = the
+        # Q-loss backward launch also ran the policy's forward on the policy step's rows as a rider: (save buffer, data
+        # pointer, row stride, N of those rows), set or cleared by every `_stock_q_backward`, taken and cleared by
+        # `_train_policy_stock`, which loads the forward only for exactly those rows and the action `_pi_sampled` hands it
         self._ls_y = None
+        self._pi_saved = None
+        self._rider_plan_cache = None   # (rows and return it was decided for, the save buffer or None): `_rider_plan`
         self._cq_buf, self._tq_buf, self._cq_td_buf = (torch.zeros(E, B, 1, **f32) for _ in range(3))
         self._pi_q, self._pi_stats_src = torch.zeros(E, B, 1, **f32), None
         self._pi_a, self._pi_logp, self._pi_sampled = torch.zeros(B, A1, **f32), torch.zeros(B, **f32), False
@@ -1680,16 +1687,43 @@ class SAC_Base(AuxHeadsMixin):
                                   launch=False)
         return c_y, ret
 
-    def _stock_q_backward(self, x0, a0, ret, c_y, priority_is, fold, fused_return, state_grads=False):
+    def _rider_plan(self, x_pi, ret):
+        """the save buffer when the Q-loss backward launch may carry the policy's forward on the rows `x_pi` and the policy
+        step will be the one-launch form that loads it, else None; decided once per (rows, return shape), not per call"""
+        key = (x_pi.data_ptr(), x_pi.stride(0), x_pi.shape[0], ret.args.n)
+        cached = self._rider_plan_cache
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        B, fq, fpi = x_pi.shape[0], self._fq, self._fpi
+        save = None
+        if self._fused_policy_step and self.ensemble_q_sample == 2 and fpi.policy_step_fused_ok(fq, B):
+            save = fpi.forward_save_buffer(B)
+            if not (fq.backward_qloss_return_rider_ok(B, ret.args, fpi, x_pi, save) and
+                    native.policy_step_fused_loaded_ok(fq.desc, fq.params, fq.member_stride, fpi.desc, fpi.params,
+                                                       fpi.member_stride, B, save)):
+                save = None
+        self._rider_plan_cache = (key, save)
+        return save
+
+    def _stock_q_backward(self, x0, a0, ret, c_y, priority_is, fold, fused_return, state_grads=False, rider_rows=None):
         """[online critics forward, clipped double-Q loss, backward] in one launch (the backward recomputes the forward
         on chip anyway).  With `fused_return` its own workgroups form the return target `ret` where that form applies
         (short windows); otherwise the return's launch goes first.  `fold`: the tile reduction of the parameter
-        gradients is folded into the Adam launch, issued here.  -> d loss / d x0 [E, B, S] with `state_grads`."""
+        gradients is folded into the Adam launch, issued here.  -> d loss / d x0 [E, B, S] with `state_grads`.
+        `rider_rows`: the policy step's state rows [B, S] when its action is already drawn — the launch then runs the
+        policy's forward on them on further workgroups (`_rider_plan`) and `_pi_saved` hands it to the policy step."""
         w = priority_is.reshape(-1).contiguous() if priority_is is not None else None
         t_q = self._tq_buf.view(self.ensemble_q_num, -1)
+        self._pi_saved = None
         if fused_return and self._fq.backward_qloss_return_ok(x0.shape[-2], ret.args):
-            g0 = self._fq.backward_qloss_return(x0, a0, t_q, ret.args, w, self.clip_epsilon, self._loss_q_e,
-                                                defer=fold, state_grads=state_grads)
+            save = self._rider_plan(rider_rows, ret) if rider_rows is not None else None
+            if save is not None:
+                g0 = self._fq.backward_qloss_return_rider(x0, a0, t_q, ret.args, w, self.clip_epsilon, self._loss_q_e,
+                                                          self._fpi, rider_rows, save, defer=fold, state_grads=state_grads)
+                self._pi_saved = (save, rider_rows.data_ptr(), rider_rows.stride(0), rider_rows.shape[0])
+            else:
+                g0 = self._fq.backward_qloss_return(x0, a0, t_q, ret.args, w, self.clip_epsilon, self._loss_q_e,
+                                                    defer=fold, state_grads=state_grads)
         else:
             self._launch_return(ret)
             g0 = self._fq.backward_qloss(x0, a0, t_q, c_y.reshape(-1), w, self.clip_epsilon, self._loss_q_e,
@@ -1753,7 +1787,10 @@ class SAC_Base(AuxHeadsMixin):
         opt = self.optimizer_q_list[0]
         fold = self._dist is None and opt.start == self._fq._start and self._params.span('rep')[0] == self._params.span('rep')[1]
         # (behind the one-launch forward the backward may form the return itself; behind the chain form it never did)
-        self._stock_q_backward(x0, a0, ret, c_y, priority_is, fold, fused_return=fused is not None and self._fused_q_return)
+        # (... and, with the policy step's action drawn by that forward, carry the policy's forward for the policy step)
+        rider_rows = x0 if (self._policy_forward_rider and fused is not None and policy_sample and x0.dim() == 2) else None
+        self._stock_q_backward(x0, a0, ret, c_y, priority_is, fold, fused_return=fused is not None and self._fused_q_return,
+                               rider_rows=rider_rows)
         if not fold:
             self._finish_rep_q(None, None)
 
@@ -2020,6 +2057,7 @@ class SAC_Base(AuxHeadsMixin):
         B = x.shape[0]
         fusable = (self._fused_policy_step and self.ensemble_q_sample == 2 and self._fpi.policy_step_fused_ok(self._fq, B))
         sample_out = None
+        saved, self._pi_saved, given = self._pi_saved, None, False
         if ls is None and not self._pi_sampled and fusable:
             # nothing of the policy's forward is at hand (trainable representation: the state is new): the one-launch
             # policy step samples the action itself
@@ -2032,7 +2070,7 @@ class SAC_Base(AuxHeadsMixin):
                 ls = self._fpi._launch_forward(x, None)[0]
             loc, scale = ls[..., :A], ls[..., A:]
             if self._pi_sampled:        # drawn by the target computation's launch from the same `ls`
-                a_tanh, logp, self._pi_sampled = self._pi_a, self._pi_logp, False
+                a_tanh, logp, self._pi_sampled, given = self._pi_a, self._pi_logp, False, True
             else:
                 self.noise.normal_(self._eps_pi)
                 a_tanh = torch.empty((B, A), dtype=torch.float32, device=self.device)
@@ -2045,7 +2083,14 @@ class SAC_Base(AuxHeadsMixin):
             logp, scale, sample_out[2] if sample_out is not None else ls, self._eps_pi, offline)
         opt = self.optimizer_policy
         fold = self._dist is None and (opt.start, opt.stop) == (self._fpi._start, self._fpi._start + self._fpi.member_stride)
-        if fusable and a_tanh.is_contiguous():
+        if (fusable and given and saved is not None and a_tanh.is_contiguous()
+                and saved[1:] == (x.data_ptr(), x.stride(0), B)):
+            # ... with the policy's forward on exactly these rows saved by the Q-loss backward launch's rider: loaded, not
+            # run again (same launch count, bit-identical)
+            self._fpi.policy_step_fused_loaded(self._fq, x, a_tanh, self._eps_pi, self.log_c_alpha, saved[0],
+                                               q_out=self._pi_q, defer=fold, subset=sub if E != 2 else None,
+                                               offline=offline)
+        elif fusable and a_tanh.is_contiguous():
             # two critics sampled (of two or more): critics forward, objective gradient, critics backward to the action,
             # sampling backward and policy backward in ONE launch (bit-identical to the chain below)
             self._fpi.policy_step_fused(self._fq, x, None if sample_out is not None else a_tanh, self._eps_pi,

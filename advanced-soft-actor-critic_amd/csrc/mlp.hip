@@ -26,6 +26,8 @@
 #include "asac_vtrace.h"
 
 #include <cmath>
+#include <string>
+#include <type_traits>
 
 namespace asac {
 
@@ -1029,14 +1031,37 @@ struct RetIn<true> {
 //   * reverse layers alternate between two delta tiles: one barrier per layer; the second tile lies in dynamic LDS behind
 //     the tile struct (behind RET's arrays), and `MlpBwdLds` and every other instantiation's LDS stay as they were
 //   * layer 0's dX product is formed only when an input gradient is asked for
-template <int TM, bool WIDE, int NB, bool RET = false, int W8 = 0>      // W8: 0, or the number of waves (8 / 16)
-__global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArgs a, const RetIn<RET> rv) {
+// RIDER (the Q-loss backward forming its own return, 16 waves): the launch carries a second, unrelated role on further
+// workgroups (blockIdx.z == 1) — the POLICY's forward on the policy step's 16-row tiles, saved for the loaded form of
+// k_policy_step two launches on (policy_forward_rider below).  Its inputs (the policy's parameters, the state rows) are
+// untouched between here and there; its workgroups branch off at the kernel's top, so the Q job's workgroups run the
+// text they ran.  The third kernel argument exists in this instantiation alone and is read through the kernarg segment
+// by the rider's workgroups only.
+template <bool RIDER>
+struct RiderIn {};
+template <>
+struct RiderIn<true>;
+__device__ __forceinline__ void policy_forward_rider(const ASAC_KARG RiderIn<true>& rd, unsigned char* smem);
+template <bool RET>
+constexpr size_t rider_karg_offset();
+
+template <int TM, bool WIDE, int NB, bool RET = false, int W8 = 0, bool RIDER = false>      // W8: 0, or the number of waves (8 / 16)
+__global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArgs a, const RetIn<RET> rv, const RiderIn<RIDER> rider_by_value) {
     static_assert(W8 == 0 || ((W8 == 8 || W8 == 16) && TM == 16 && NB == 3 && !WIDE), "8 / 16 waves: 16-row tiles of the stock networks");
+    static_assert(!RIDER || (RET && W8 == 16), "the rider's workgroups are k_policy_step's: 16 waves on a 16-row tile");
     constexpr int THREADS = W8 ? 64 * W8 : threads_of<TM>();
     constexpr int RT = TM / 16;
     constexpr bool fixed = NB > 0;                            // NB blocks of 64 (see net_fetch_fixed)
     static_assert(!(fixed && WIDE), "the fixed-shape path has a first layer of <= 64 inputs");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    if constexpr (RIDER) {
+        if (blockIdx.z != 0) {
+            policy_forward_rider(*reinterpret_cast<const ASAC_KARG RiderIn<true>*>(
+                                     static_cast<const ASAC_KARG unsigned char*>(kernarg_base()) + rider_karg_offset<RET>()),
+                                 smem_raw);
+            return;
+        }
+    }
     MlpBwdLds<TM>& L = *reinterpret_cast<MlpBwdLds<TM>*>(smem_raw);
     const int e = blockIdx.y;
     const int64_t row0 = (int64_t)blockIdx.x * TM;
@@ -1452,6 +1477,28 @@ struct PsLds {
 };
 static_assert(sizeof(PsPiLds) <= 2 * sizeof(PsQLds), "the policy phase reuses the critics' LDS");
 
+// The policy's forward of a tile as the rider of the Q-loss backward launch saved it (policy_forward_rider below), all 16
+// rows of the tile, dead rows included: what the loaded form of k_policy_step reads instead of running the forward again
+struct SavedPolicyTile {
+    float x[3][kPsRows * kMaxW];             // x_1..x_3, dense rows
+    f32x4 zp[3][4 * 64];                     // gelu'(z_l): [layer][wave 0-3][lane], the MFMA C fragment of that lane
+    float head[kPsRows * kHeadPad];          // raw head values (bias added, transform not applied)
+};
+static_assert(sizeof(SavedPolicyTile) == 25600, "SavedPolicyTile");
+constexpr int kSavedTileFloats = sizeof(SavedPolicyTile) / sizeof(float);
+// ... parked in LDS BEHIND PsLds (outside the critics' overlay: it costs no registers across the critic phase)
+struct PsParked {
+    float x[3][kPsRows * kP];
+    f32x4 zp[3][4 * 64];
+    float head[kPsRows * kHeadPad];
+};
+struct PsLdsLoaded {
+    PsLds l;
+    PsParked k;
+};
+static_assert(sizeof(PsLds) % 16 == 0 && offsetof(PsParked, zp) % 16 == 0, "the parked fragments are read 16 bytes a lane");
+static_assert(sizeof(PsLdsLoaded) <= 160 * 1024, "one workgroup per CU: the whole LDS");
+
 struct PolicyStepArgs {
     MlpArgs q, pi;          // q: x0 = states, x1 = sampled actions, subset = the TWO members the objective samples (device
                             // indices, NULL = members 0 and 1); pi: x0 = states, eps, log_alpha, partial
@@ -1462,6 +1509,9 @@ struct PolicyStepArgs {
     float* a_out;           // [N][A]
     float* logp_out;        // [N]
     float* ls_out;          // [N][2A] (loc | scale) or NULL
+};
+struct PolicyStepArgsLoaded : PolicyStepArgs {
+    const float* saved;     // [tiles] SavedPolicyTile: the policy's forward on pi.x0's rows, from an earlier launch
 };
 
 // a 16-row input tile: kPsSlots of the 16 x 64 slots per thread
@@ -1489,12 +1539,22 @@ __device__ __forceinline__ void ps_put_tile(const float (&v)[kPsSlots], float* x
 }
 
 // OFFLINE: the offline term rides in the sampling backward (pi.off_action); the plain instantiation has none of it
-template <bool OFFLINE>
-__global__ __launch_bounds__(kPsThreads) void k_policy_step(const PolicyStepArgs a_by_value) {
+// LOADED (action given only): the policy's forward on the tile — x_1..x_3, gelu'(z_l), the raw head — is not run again
+// behind the critics but LOADED: an earlier launch saved it (a.saved: SavedPolicyTile, written by the rider of the Q-loss
+// backward launch from the same parameters and rows).  The tile is requested with the weights, parked in LDS behind
+// PsLds (PsParked: outside the critics' overlay, no registers across the critic phase) in front of the staging barrier,
+// and read from there by the sampling backward, the weight-gradient tiles and the reverse layers.  The invariants above
+// hold: the saved tile is another LAUNCH's output, every parked word is written in front of the first barrier, and
+// `loads_landed()` stays where the policy's weights leave the registers.
+template <bool OFFLINE, bool LOADED = false>
+__global__ __launch_bounds__(kPsThreads) void k_policy_step(
+    const std::conditional_t<LOADED, PolicyStepArgsLoaded, PolicyStepArgs> a_by_value) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const ASAC_KARG PolicyStepArgs& a = *static_cast<const ASAC_KARG PolicyStepArgs*>(kernarg_base());   // (asac_common.h)
+    using Args = std::conditional_t<LOADED, PolicyStepArgsLoaded, PolicyStepArgs>;
+    const ASAC_KARG Args& a = *static_cast<const ASAC_KARG Args*>(kernarg_base());   // (asac_common.h)
     PsLds& L = *reinterpret_cast<PsLds*>(smem_raw);
     PsPiLds& P = *reinterpret_cast<PsPiLds*>(smem_raw);
+    [[maybe_unused]] PsParked& K = reinterpret_cast<PsLdsLoaded*>(smem_raw)->k;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int m = wave >> 2, ct = wave & 3;           // critic phase: member, column tile
     const int col = ct * 16 + (lane & 15);
@@ -1509,13 +1569,26 @@ __global__ __launch_bounds__(kPsThreads) void k_policy_step(const PolicyStepArgs
     // mean_b -min_{e in subset} q_e, so they are not evaluated at all); the order of the subset breaks ties
     const int e0 = a.q.subset ? a.q.subset[0] : 0, e1 = a.q.subset ? a.q.subset[1] : 1;
     const StageScalars s0 = stage_scalars<3>(a.q, e0), s1 = stage_scalars<3>(a.q, e1), sp = stage_scalars<3>(a.pi, 0);
-    const bool sample_here = a.q.x1 == nullptr;
+    const bool sample_here = !LOADED && a.q.x1 == nullptr;
     float in_q[kPsSlots] = {}, in_pi[kPsSlots];
     if (!sample_here) ps_fetch_tile(s0, row0, in_q);
     ps_fetch_tile(sp, row0, in_pi);
     StagedNet<kPsThreads> r0, r1, rp;
     net_fetch_fixed<kPsThreads, 3>(s0, r0);
     net_fetch_fixed<kPsThreads, 3>(s1, r1);
+    // the saved forward of the tile: requested in front of the policy's weights, so that parking it (below, with the
+    // critics' weights) leaves those in flight.  Every thread loads and stores (threads beyond a part's size repeat one of
+    // its slots: the same value to the same word) — no register a load fills is consumed by some waves only
+    [[maybe_unused]] float sv_x[3], sv_h;
+    [[maybe_unused]] f32x4 sv_z;
+    if constexpr (LOADED) {
+        static_assert(kPsThreads == 1024, "the parked tile is dealt over sixteen waves");
+        const SavedPolicyTile& sv = *reinterpret_cast<const SavedPolicyTile*>(a.saved + (int64_t)blockIdx.x * kSavedTileFloats);
+#pragma unroll
+        for (int l = 0; l < 3; ++l) sv_x[l] = sv.x[l][threadIdx.x];
+        sv_z = (&sv.zp[0][0])[threadIdx.x < 768 ? threadIdx.x : 767];
+        sv_h = sv.head[threadIdx.x & 255];
+    }
     net_fetch_fixed<kPsThreads, 3>(sp, rp);
     float ev = 0.f, gl = 0.f;       // the sampling backward's per-(row, action dim) inputs
     {
@@ -1588,6 +1661,12 @@ __global__ __launch_bounds__(kPsThreads) void k_policy_step(const PolicyStepArgs
     }
     net_put_fixed<kPsThreads, 3>(r0, L.q[0]);
     net_put_fixed<kPsThreads, 3>(r1, L.q[1]);
+    if constexpr (LOADED) {
+#pragma unroll
+        for (int l = 0; l < 3; ++l) K.x[l][(threadIdx.x >> 6) * kP + (threadIdx.x & 63)] = sv_x[l];
+        (&K.zp[0][0])[threadIdx.x < 768 ? threadIdx.x : 767] = sv_z;
+        K.head[threadIdx.x & 255] = sv_h;
+    }
     __syncthreads();
     if (sample_here) {         // the sampled actions into the critics' input tiles
         if ((int)threadIdx.x < kPsRows * A) {
@@ -1688,11 +1767,21 @@ __global__ __launch_bounds__(kPsThreads) void k_policy_step(const PolicyStepArgs
     // ---- the policy takes over: parameters registers -> LDS, forward recompute ------------------------------------
     net_put_fixed<kPsThreads, 3>(rp, P);
     ps_put_tile(in_pi, P.x[0]);
-    if (threadIdx.x < kPsRows * kHeadPad) P.delta[(threadIdx.x >> 4) * kP + (threadIdx.x & 15)] = 0.f;
+    // (LOADED: the raw head tile comes from the parked copy, and no forward follows)
+    if (threadIdx.x < kPsRows * kHeadPad)
+        P.delta[(threadIdx.x >> 4) * kP + (threadIdx.x & 15)] = LOADED ? K.head[threadIdx.x] : 0.f;
     loads_landed();         // (the policy's weights have just left the registers; the noise and the temperature came before them)
     __syncthreads();
     MLP_STAMP(6);
+    // block inputs of the policy's backward: x_0 from the staging, x_1..x_3 recomputed below or parked
+    const float* const px[4] = {P.x[0], LOADED ? K.x[0] : P.x[1], LOADED ? K.x[1] : P.x[2], LOADED ? K.x[2] : P.x[3]};
     f32x4 zp[3];
+    if constexpr (LOADED) {
+        if (wave < 4) {
+#pragma unroll
+            for (int l = 0; l < 3; ++l) zp[l] = K.zp[l][threadIdx.x];
+        }
+    } else {
 #pragma unroll
     for (int l = 0; l < 3; ++l) {
         if (wave < 4) {
@@ -1726,6 +1815,7 @@ __global__ __launch_bounds__(kPsThreads) void k_policy_step(const PolicyStepArgs
         for (int r = 0; r < 4; ++r) P.delta[(4 * (lane >> 4) + r) * kP + hc] = raw[r] + P.head_bias[hc];
     }
     __syncthreads();
+    }
     MLP_STAMP(8);
     if ((int)threadIdx.x < kPsRows * A) {
         const int lrow = threadIdx.x / A, d = threadIdx.x - lrow * A;
@@ -1753,8 +1843,8 @@ __global__ __launch_bounds__(kPsThreads) void k_policy_step(const PolicyStepArgs
     MLP_STAMP(9);
     // ---- policy backward: parameter-gradient partials of this tile ------------------------------------------------
     float* part = a.pi.partial + (int64_t)blockIdx.x * a.pi.member_stride;
-    ps_grad_weight(P.delta, 0, P.x[3], A, kMaxW, part + a.pi.d.head_w_off[0]);
-    ps_grad_weight(P.delta, A, P.x[3], A, kMaxW, part + a.pi.d.head_w_off[1], 4);
+    ps_grad_weight(P.delta, 0, px[3], A, kMaxW, part + a.pi.d.head_w_off[0]);
+    ps_grad_weight(P.delta, A, px[3], A, kMaxW, part + a.pi.d.head_w_off[1], 4);
     if (wave == 7) {        // the two head biases: 16 columns x 16 rows
         const int c = lane & 15, rq = (lane >> 4) * 4;
         float sb = 0.f;
@@ -1781,7 +1871,7 @@ __global__ __launch_bounds__(kPsThreads) void k_policy_step(const PolicyStepArgs
             for (int r = 0; r < 4; ++r) pdelta[(4 * (lane >> 4) + r) * kP + pc] = gp[r] * zp[l][r];
         }
         __syncthreads();
-        ps_grad_weight(pdelta, 0, P.x[l], kMaxW, Kin, part + a.pi.d.w_off[l]);
+        ps_grad_weight(pdelta, 0, px[l], kMaxW, Kin, part + a.pi.d.w_off[l]);
         grad_bias<kPsRows>(pdelta, 0, kMaxW, part + a.pi.d.b_off[l]);
         if (l > 0 && wave < 4) {
             f32x4 gin = gemm_tile_nt(pdelta, P.w[l], kMaxW, 0, wave);
@@ -1919,6 +2009,76 @@ __device__ __forceinline__ StageScalars stage_scalars_stock_like(const ASAC_KARG
 #pragma unroll
     for (int l = 0; l < 3; ++l) { ASAC_PIN(q.w_off[l]); ASAC_PIN(q.b_off[l]); }
     return q;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The policy forward of a 16-row tile, SAVED: k_mlp_bwd<.., RIDER>'s second role.  One workgroup of kPsThreads stages the
+// policy as k_policy_step does (net_fetch_fixed / ps_fetch_tile, dead rows zero) and runs the statements of that kernel's
+// forward recompute — same gemm_tile K, bias, gelu_parts2 and residual add: the very values, bit for bit — then stores
+// what the policy's backward wants of them, all 16 rows of the tile: x_1..x_3, the GELU derivatives as the MFMA C
+// fragments waves 0-3 hold, and the raw head tile (SavedPolicyTile).  Nothing of the launch reads what it writes.
+template <>
+struct RiderIn<true> {
+    StockJobArg pi;          // the policy on its state rows (E = 1, no second input)
+    float* save;             // [tiles] SavedPolicyTile
+};
+template <bool RET>
+constexpr size_t rider_karg_offset() {        // of the third kernel argument: explicit arguments lie in order, each at its alignment
+    constexpr size_t a1 = alignof(RetIn<RET>), a2 = alignof(RiderIn<true>);
+    return ((((sizeof(MlpArgs) + a1 - 1) / a1 * a1) + sizeof(RetIn<RET>)) + a2 - 1) / a2 * a2;
+}
+__device__ __forceinline__ void policy_forward_rider(const ASAC_KARG RiderIn<true>& rd, unsigned char* smem) {
+    PsPiLds& P = *reinterpret_cast<PsPiLds*>(smem);         // (workgroups of kPsThreads: launch_backward checks)
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int tile = blockIdx.x + blockIdx.y * gridDim.x;
+    const StageScalars sp = stage_scalars_stock(rd.pi, 0);
+    const int64_t row0 = (int64_t)tile * kPsRows;
+    if (row0 >= sp.N) return;               // (uniform: the grid's second plane has the Q job's workgroup count)
+    SavedPolicyTile& out = *reinterpret_cast<SavedPolicyTile*>(rd.save + (int64_t)tile * kSavedTileFloats);
+    const int K0p = sp.in0;
+    const int residual_bits = rd.pi.residual_bits;
+    float in_pi[kPsSlots];
+    ps_fetch_tile(sp, row0, in_pi);
+    StagedNet<kPsThreads> rp;
+    net_fetch_fixed<kPsThreads, 3>(sp, rp);
+    net_put_fixed<kPsThreads, 3>(rp, P);
+    ps_put_tile(in_pi, P.x[0]);
+    __syncthreads();
+#pragma unroll
+    for (int l = 0; l < 3; ++l) {
+        if (wave < 4) {
+            const float* xin = P.x[l];
+            float* xout = P.x[l + 1];
+            const f32x4 acc = l > 0 ? gemm_tile(xin, P.w[l], kMaxW, 0, wave) : gemm_tile(xin, P.w[l], round4(K0p), 0, wave);
+            const int pc = wave * 16 + (lane & 15);
+            const float bias = P.bias[l][pc];
+            const bool res = ((residual_bits >> l) & 1) != 0;
+            f32x2_g ya, yb, da, db;
+            gelu_parts2((f32x2_g){acc[0] + bias, acc[1] + bias}, ya, da);
+            gelu_parts2((f32x2_g){acc[2] + bias, acc[3] + bias}, yb, db);
+            const float yv[4] = {ya.x, ya.y, yb.x, yb.y};
+            out.zp[l][threadIdx.x] = f32x4{da.x, da.y, db.x, db.y};
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 4 * (lane >> 4) + r;
+                float y = yv[r];
+                if (res) y += xin[row * kP + pc];
+                xout[row * kP + pc] = y;
+            }
+        }
+        __syncthreads();
+    }
+    if (wave == 0) {
+        const f32x4 raw = gemm_tile(P.x[3], P.head, kMaxW, 0, 0);
+        const int hc = lane & 15;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) out.head[(4 * (lane >> 4) + r) * kHeadPad + hc] = raw[r] + P.head_bias[hc];
+    }
+#pragma unroll
+    for (int l = 0; l < 3; ++l) {           // x_1..x_3: one float per thread and layer, rows dense
+        const int r = threadIdx.x >> 6, c = threadIdx.x & 63;
+        out.x[l][r * kMaxW + c] = P.x[l + 1][r * kP + c];
+    }
 }
 
 // RING: the rows and the stored actions come from the replay ring (`ring`), not from a gathered batch
@@ -2629,8 +2789,8 @@ static int launch_forward_multi(const asac_mlp_job_t* jobs, int n_jobs, const Si
 #endif
 template <int TM>
 static int launch_backward(const char* where, const asac_mlp_desc_t* desc, MlpArgs& a, int E, int tiles, hipStream_t s,
-                           const RetIn<true>* ret = nullptr) {
-    static bool attr_done = false, attr_wide = false, attr_stock = false, attr_ret = false;
+                           const RetIn<true>* ret = nullptr, const RiderIn<true>* rider = nullptr) {
+    static bool attr_done = false, attr_wide = false, attr_stock = false, attr_ret = false, attr_rider = false;
     const bool wide = wide_input(*desc);
     const bool stock = !wide && stock3(*desc, a.params, a.member_stride) && offsets32(a);
     constexpr int w8 = TM == 16 ? ASAC_BWD_WAVES : 0;                // (16-row tiles of the stock networks: see k_mlp_bwd)
@@ -2638,7 +2798,7 @@ static int launch_backward(const char* where, const asac_mlp_desc_t* desc, MlpAr
     auto launch = [&](auto kernel, bool& attr, size_t lds_limit, int threads, size_t lds,
                       const auto& ret_in) -> int {
         if (int rc = set_lds_limit(reinterpret_cast<const void*>(kernel), lds_limit, attr, where)) return rc;
-        ASAC_LAUNCH(kernel, dim3(tiles, E), dim3(threads), lds, s, a, ret_in);
+        ASAC_LAUNCH(kernel, dim3(tiles, E), dim3(threads), lds, s, a, ret_in, RiderIn<false>{});
         return 0;
     };
     const size_t lds = sizeof(MlpBwdLds<TM>);
@@ -2647,6 +2807,17 @@ static int launch_backward(const char* where, const asac_mlp_desc_t* desc, MlpAr
         const size_t lds_ret = lds + (size_t)(2 * ((ret->v.n + 1) | 1) + 2) * TM * sizeof(float) + spare;
         // one thread per (row, step) of the tile: the launch's own thread count bounds n (16 waves: n <= 64)
         if (!stock || TM * ret->v.n > stock_threads || lds_ret > 128 * 1024) return bad_arg(where);
+        if (rider) {       // (asac_mlp_backward_qloss_return_rider_ok has said yes) a second plane of workgroups: the policy's tiles
+            if constexpr (w8 == 16 && kPsThreads == 64 * w8) {
+                auto kernel = k_mlp_bwd<TM, false, 3, true, w8, true>;
+                if (int rc = set_lds_limit(reinterpret_cast<const void*>(kernel), 128 * 1024, attr_rider, where)) return rc;
+                const size_t lds_both = lds_ret > sizeof(PsPiLds) ? lds_ret : sizeof(PsPiLds);
+                ASAC_LAUNCH(kernel, dim3(tiles, E, 2), dim3(stock_threads), lds_both, s, a, *ret, *rider);
+                return 0;
+            } else {
+                return bad_arg(where);
+            }
+        }
         return launch(k_mlp_bwd<TM, false, 3, true, w8>, attr_ret, 128 * 1024, stock_threads, lds_ret, *ret);
     }
     if (wide) return launch(k_mlp_bwd<TM, true, 0>, attr_wide, lds, threads_of<TM>(), lds, RetIn<false>{});
@@ -2671,16 +2842,32 @@ static void reduce_partials(const asac_mlp_desc_t* desc, const float* workspace,
 }
 
 static int mlp_backward_common(const char* where, const asac_mlp_job_t& j, MlpArgs& a, float* grad_params, float* workspace,
-                               int reduce_mode, float* loss_out, hipStream_t s, const RetIn<true>* ret = nullptr) {
+                               int reduce_mode, float* loss_out, hipStream_t s, const RetIn<true>* ret = nullptr,
+                               const RiderIn<true>* rider = nullptr) {
     const int tiles = (int)asac_mlp_backward_tiles(j.N, j.E);
     a.partial = grad_params ? workspace : nullptr;
     a.loss_partial = workspace ? workspace + (int64_t)tiles * j.E * j.member_stride : nullptr;
-    if (int rc = mlp_tile_rows(j.N, j.E) == 16 ? launch_backward<16>(where, j.desc, a, j.E, tiles, s, ret)
-                                               : launch_backward<32>(where, j.desc, a, j.E, tiles, s, ret))
+    if (int rc = mlp_tile_rows(j.N, j.E) == 16 ? launch_backward<16>(where, j.desc, a, j.E, tiles, s, ret, rider)
+                                               : launch_backward<32>(where, j.desc, a, j.E, tiles, s, ret, rider))
         return rc;
     if (grad_params && reduce_mode != ASAC_MLP_REDUCE_DEFER)
         reduce_partials(j.desc, workspace, tiles, j.E, j.member_stride, grad_params, reduce_mode,
                         loss_out ? a.loss_partial : nullptr, loss_out, 1.f / (float)j.N, s);
+    return finish_launch(where);
+}
+
+// the launch of k_policy_step<OFFLINE, LOADED> on `args` (PolicyStepArgs / PolicyStepArgsLoaded) and the tile reduction
+template <bool OFFLINE, bool LOADED, typename ARGS>
+static int launch_policy_step(const char* where, const ARGS& args, const asac_mlp_desc_t* pi_desc, int64_t pi_member_stride,
+                              int64_t N, float* pi_grad_params, float* workspace, int reduce_mode, hipStream_t s) {
+    static bool attr_done = false;
+    constexpr size_t lds = LOADED ? sizeof(PsLdsLoaded) : sizeof(PsLds);      // (loaded: the whole LDS of a CU)
+    auto kernel = k_policy_step<OFFLINE, LOADED>;
+    if (int rc = set_lds_limit(reinterpret_cast<const void*>(kernel), lds, attr_done, where)) return rc;
+    const int tiles = (int)((N + kPsRows - 1) / kPsRows);
+    ASAC_LAUNCH(kernel, dim3((unsigned)tiles), dim3(kPsThreads), lds, s, args);
+    if (reduce_mode != ASAC_MLP_REDUCE_DEFER)
+        reduce_partials(pi_desc, workspace, tiles, 1, pi_member_stride, pi_grad_params, reduce_mode, nullptr, nullptr, 0.f, s);
     return finish_launch(where);
 }
 
@@ -2907,17 +3094,18 @@ int asac_policy_step_fused_ok(const asac_mlp_desc_t* q_desc, const float* q_para
     return mlp_tile_rows(N, 1) == kPsRows ? 1 : 0;        // the partials' tile count is asac_mlp_backward_tiles(N, 1)
 }
 
-// both one-launch entry points; off_action == NULL: the plain instantiation, no offline term
+// the one-launch entry points; off_action == NULL: the plain instantiation, no offline term; saved != NULL: the loaded form
+// (its entry points have asked asac_policy_step_fused_loaded_ok)
 static int policy_step_fused(const char* where, const asac_mlp_desc_t* q_desc, const float* q_params, int64_t q_member_stride,
                              const asac_mlp_desc_t* pi_desc, const float* pi_params, int64_t pi_member_stride,
                              const float* x, int64_t x_row_stride, int64_t N, const float* action, const float* eps,
                              const float* log_alpha, const int32_t* subset, const float* off_action, int64_t off_row_stride,
                              float* q_out, float* a_tanh_out, float* logp_out, float* ls_out, float* pi_grad_params,
-                             float* workspace, int reduce_mode, void* stream) {
+                             float* workspace, int reduce_mode, void* stream, const float* saved = nullptr) {
     if (!asac_policy_step_fused_ok(q_desc, q_params, q_member_stride, pi_desc, pi_params, pi_member_stride, N) ||
-        !x || !eps || !log_alpha || !pi_grad_params || !workspace || (!action && (!a_tanh_out || !logp_out)))
+        !x || !eps || !log_alpha || !pi_grad_params || !workspace || (!action && (saved || !a_tanh_out || !logp_out)))
         return bad_arg(where);
-    PolicyStepArgs a{};
+    PolicyStepArgsLoaded a{};           // (the plain launches take its PolicyStepArgs part)
     asac_mlp_job_t pi{}, q{};           // both networks on the rows of x; the critics' second input: the [N][A] actions
     pi.desc = pi_desc, pi.params = pi_params, pi.member_stride = pi_member_stride;
     q.desc = q_desc, q.params = q_params, q.member_stride = q_member_stride;
@@ -2936,18 +3124,14 @@ static int policy_step_fused(const char* where, const asac_mlp_desc_t* q_desc, c
     a.pi.off_action = off_action;          // (the kernel indexes the stored actions with 64 bits)
     a.pi.off_row_stride = off_row_stride;
     a.q_out = q_out;
-    static bool attr_done = false, attr_done_offline = false;
-    if (int rc = off_action ? set_lds_limit(reinterpret_cast<const void*>(k_policy_step<true>), sizeof(PsLds),
-                                            attr_done_offline, where)
-                            : set_lds_limit(reinterpret_cast<const void*>(k_policy_step<false>), sizeof(PsLds), attr_done, where))
-        return rc;
-    const int tiles = (int)((N + kPsRows - 1) / kPsRows);
+    a.saved = saved;
+    const PolicyStepArgs& plain = a;
     hipStream_t s = as_stream(stream);
-    if (off_action) ASAC_LAUNCH(k_policy_step<true>, dim3((unsigned)tiles), dim3(kPsThreads), sizeof(PsLds), s, a);
-    else ASAC_LAUNCH(k_policy_step<false>, dim3((unsigned)tiles), dim3(kPsThreads), sizeof(PsLds), s, a);
-    if (reduce_mode != ASAC_MLP_REDUCE_DEFER)
-        reduce_partials(pi_desc, workspace, tiles, 1, pi_member_stride, pi_grad_params, reduce_mode, nullptr, nullptr, 0.f, s);
-    return finish_launch(where);
+    if (saved)
+        return off_action ? launch_policy_step<true, true>(where, a, pi_desc, pi_member_stride, N, pi_grad_params, workspace, reduce_mode, s)
+                          : launch_policy_step<false, true>(where, a, pi_desc, pi_member_stride, N, pi_grad_params, workspace, reduce_mode, s);
+    return off_action ? launch_policy_step<true, false>(where, plain, pi_desc, pi_member_stride, N, pi_grad_params, workspace, reduce_mode, s)
+                      : launch_policy_step<false, false>(where, plain, pi_desc, pi_member_stride, N, pi_grad_params, workspace, reduce_mode, s);
 }
 
 int asac_policy_step_fused(const asac_mlp_desc_t* q_desc, const float* q_params, int64_t q_member_stride,
@@ -2973,6 +3157,40 @@ int asac_policy_step_fused_offline(const asac_mlp_desc_t* q_desc, const float* q
                              pi_member_stride, x, x_row_stride, N, action, eps, log_alpha, subset, off_action,
                              off_row_stride, q_out, a_tanh_out, logp_out, ls_out, pi_grad_params, workspace, reduce_mode,
                              stream);
+}
+
+int asac_policy_step_fused_loaded_ok(const asac_mlp_desc_t* q_desc, const float* q_params, int64_t q_member_stride,
+                                     const asac_mlp_desc_t* pi_desc, const float* pi_params, int64_t pi_member_stride, int64_t N,
+                                     const float* saved) {
+    if (!saved || (reinterpret_cast<uintptr_t>(saved) & 15) || kPsThreads != 1024) return 0;
+    return asac_policy_step_fused_ok(q_desc, q_params, q_member_stride, pi_desc, pi_params, pi_member_stride, N);
+}
+
+int asac_policy_step_fused_loaded(const asac_mlp_desc_t* q_desc, const float* q_params, int64_t q_member_stride,
+                                  const asac_mlp_desc_t* pi_desc, const float* pi_params, int64_t pi_member_stride,
+                                  const float* x, int64_t x_row_stride, int64_t N, const float* action, const float* eps,
+                                  const float* log_alpha, const int32_t* subset, const float* saved, float* q_out,
+                                  float* pi_grad_params, float* workspace, int reduce_mode, void* stream) {
+    if (!action || !asac_policy_step_fused_loaded_ok(q_desc, q_params, q_member_stride, pi_desc, pi_params, pi_member_stride, N, saved))
+        return bad_arg("asac_policy_step_fused_loaded");
+    return policy_step_fused("asac_policy_step_fused_loaded", q_desc, q_params, q_member_stride, pi_desc, pi_params,
+                             pi_member_stride, x, x_row_stride, N, action, eps, log_alpha, subset, nullptr, 0, q_out, nullptr,
+                             nullptr, nullptr, pi_grad_params, workspace, reduce_mode, stream, saved);
+}
+
+int asac_policy_step_fused_loaded_offline(const asac_mlp_desc_t* q_desc, const float* q_params, int64_t q_member_stride,
+                                          const asac_mlp_desc_t* pi_desc, const float* pi_params, int64_t pi_member_stride,
+                                          const float* x, int64_t x_row_stride, int64_t N, const float* action,
+                                          const float* eps, const float* log_alpha, const int32_t* subset,
+                                          const float* off_action, int64_t off_row_stride, const float* saved, float* q_out,
+                                          float* pi_grad_params, float* workspace, int reduce_mode, void* stream) {
+    if (!off_action || !pi_desc || off_row_stride < pi_desc->head_cols[0])
+        return bad_arg("asac_policy_step_fused_loaded_offline: stored actions");
+    if (!action || !asac_policy_step_fused_loaded_ok(q_desc, q_params, q_member_stride, pi_desc, pi_params, pi_member_stride, N, saved))
+        return bad_arg("asac_policy_step_fused_loaded_offline");
+    return policy_step_fused("asac_policy_step_fused_loaded_offline", q_desc, q_params, q_member_stride, pi_desc, pi_params,
+                             pi_member_stride, x, x_row_stride, N, action, eps, log_alpha, subset, off_action, off_row_stride,
+                             q_out, nullptr, nullptr, nullptr, pi_grad_params, workspace, reduce_mode, stream, saved);
 }
 
 static bool fits32(int64_t v) { return v >= 0 && v < 0x1fffffffLL; }
@@ -3183,25 +3401,64 @@ int asac_mlp_backward_qloss_return_ok(const asac_mlp_job_t* job, const asac_vtra
     return tm * ret->n <= threads && lds <= 128 * 1024;
 }
 
-int asac_mlp_backward_qloss_return(const asac_mlp_job_t* job, const float* target_q, const asac_vtrace_args_t* ret,
-                                   const float* weights, float clip_eps, float* loss_out, float* grad_x0, float* grad_params,
-                                   float* workspace, int reduce_mode, void* stream) {
-    if (!bwd_job_ok(job) || !target_q || !ret || !grad_params || !workspace || clip_eps <= 0.f)
-        return bad_arg("asac_mlp_backward_qloss_return");
-    if (!scalar_head(*job->desc)) return bad_arg("asac_mlp_backward_qloss_return: not a scalar-head network");
-    if (reduce_mode != ASAC_MLP_REDUCE_DEFER && !loss_out) return bad_arg("asac_mlp_backward_qloss_return: loss_out");
+int64_t asac_policy_forward_save_floats(int64_t N) { return N > 0 ? (N + kPsRows - 1) / kPsRows * kSavedTileFloats : 0; }
+
+int asac_mlp_backward_qloss_return_rider_ok(const asac_mlp_job_t* job, const asac_vtrace_args_t* ret,
+                                            const asac_mlp_job_t* pi_job, const float* save) {
+    if (!pi_job || !save || !asac_mlp_backward_qloss_return_ok(job, ret)) return 0;
+    // the hosting launch runs k_policy_step's workgroup shape: sixteen waves on 16-row tiles
+    if (mlp_tile_rows(job->N, job->E) != kPsRows || 64 * ASAC_BWD_WAVES != kPsThreads) return 0;
+    const asac_mlp_job_t& p = *pi_job;
+    if (!p.desc || !desc_ok(*p.desc) || p.N <= 0 || p.E != 1 || !p.x0 || p.x0_window_T != 0) return 0;
+    if (!stock3(*p.desc, p.params, p.member_stride) || !gauss_head(*p.desc) || p.desc->in1 != 0 ||
+        2 * p.desc->head_cols[0] > kHeadPad)
+        return 0;
+    if (!job_fits32(p) || !fits32(p.member_stride) || (reinterpret_cast<uintptr_t>(save) & 15)) return 0;
+    // one workgroup per policy tile in the grid's second plane, which has the Q job's workgroup count
+    return (p.N + kPsRows - 1) / kPsRows <= asac_mlp_backward_tiles(job->N, job->E) * job->E ? 1 : 0;
+}
+
+// both entry points of the Q-loss backward that forms its own return; pi_job != NULL: with the policy-forward rider
+static int backward_qloss_return(const char* where, const asac_mlp_job_t* job, const float* target_q,
+                                 const asac_vtrace_args_t* ret, const float* weights, float clip_eps, float* loss_out,
+                                 float* grad_x0, float* grad_params, float* workspace, int reduce_mode,
+                                 const asac_mlp_job_t* pi_job, float* save, void* stream) {
+    auto refuse = [&](const char* why) { return bad_arg((std::string(where) + why).c_str()); };
+    if (!bwd_job_ok(job) || !target_q || !ret || !grad_params || !workspace || clip_eps <= 0.f) return refuse("");
+    if (!scalar_head(*job->desc)) return refuse(": not a scalar-head network");
+    if (reduce_mode != ASAC_MLP_REDUCE_DEFER && !loss_out) return refuse(": loss_out");
     if (!asac_mlp_backward_qloss_return_ok(job, ret) || (ret->use_n_step_is && (!ret->mu_prob || !ret->pi_prob || ret->A <= 0)))
-        return bad_arg("asac_mlp_backward_qloss_return: return arguments");
+        return refuse(": return arguments");
     MlpArgs a = make_args(*job);
-    if (!offsets32(a)) return bad_arg("asac_mlp_backward_qloss_return: offsets");
+    if (!offsets32(a)) return refuse(": offsets");
     a.tq = target_q;
     a.y = ret->y_out;
     a.w = weights;
     a.clip_eps = clip_eps;
     a.gx0 = grad_x0;
     RetIn<true> rv{*ret, vtrace_scan_lanes(ret->B, ret->n)};
-    return mlp_backward_common("asac_mlp_backward_qloss_return", *job, a, grad_params, workspace, reduce_mode, loss_out,
-                               as_stream(stream), &rv);
+    if (pi_job) {
+        RiderIn<true> rd{stock_job_arg(pi_rows(*pi_job)), save};
+        return mlp_backward_common(where, *job, a, grad_params, workspace, reduce_mode, loss_out, as_stream(stream), &rv, &rd);
+    }
+    return mlp_backward_common(where, *job, a, grad_params, workspace, reduce_mode, loss_out, as_stream(stream), &rv);
+}
+
+int asac_mlp_backward_qloss_return(const asac_mlp_job_t* job, const float* target_q, const asac_vtrace_args_t* ret,
+                                   const float* weights, float clip_eps, float* loss_out, float* grad_x0, float* grad_params,
+                                   float* workspace, int reduce_mode, void* stream) {
+    return backward_qloss_return("asac_mlp_backward_qloss_return", job, target_q, ret, weights, clip_eps, loss_out, grad_x0,
+                                 grad_params, workspace, reduce_mode, nullptr, nullptr, stream);
+}
+
+int asac_mlp_backward_qloss_return_rider(const asac_mlp_job_t* job, const float* target_q, const asac_vtrace_args_t* ret,
+                                         const float* weights, float clip_eps, float* loss_out, float* grad_x0,
+                                         float* grad_params, float* workspace, int reduce_mode, const asac_mlp_job_t* pi_job,
+                                         float* save, void* stream) {
+    if (!asac_mlp_backward_qloss_return_rider_ok(job, ret, pi_job, save))
+        return bad_arg("asac_mlp_backward_qloss_return_rider: the policy job");
+    return backward_qloss_return("asac_mlp_backward_qloss_return_rider", job, target_q, ret, weights, clip_eps, loss_out,
+                                 grad_x0, grad_params, workspace, reduce_mode, pi_job, save, stream);
 }
 
 int asac_mlp_backward_qloss(const asac_mlp_job_t* job, const float* target_q, const float* y, const float* weights,

@@ -354,6 +354,23 @@ _SIGNATURES = {
     'asac_mlp_backward_qloss_return_ok': (C.c_int, [C.POINTER(MlpJob), C.POINTER(VtraceArgs)]),
     'asac_mlp_backward_qloss_return': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.POINTER(VtraceArgs), C.c_void_p, C.c_float,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    'asac_policy_forward_save_floats': (C.c_int64, [C.c_int64]),
+    'asac_mlp_backward_qloss_return_rider_ok': (C.c_int, [C.POINTER(MlpJob), C.POINTER(VtraceArgs), C.POINTER(MlpJob),
+                                                          C.c_void_p]),
+    'asac_mlp_backward_qloss_return_rider': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.POINTER(VtraceArgs), C.c_void_p,
+                                                       C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                       C.POINTER(MlpJob), C.c_void_p, C.c_void_p]),
+    'asac_policy_step_fused_loaded_ok': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.POINTER(MlpDesc), C.c_void_p,
+                                                   C.c_int64, C.c_int64, C.c_void_p]),
+    'asac_policy_step_fused_loaded': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.POINTER(MlpDesc), C.c_void_p,
+                                                C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_int, C.c_void_p]),
+    'asac_policy_step_fused_loaded_offline': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.POINTER(MlpDesc),
+                                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                        C.c_void_p]),
     'asac_mlp_backward_policy_q': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     'asac_mlp_backward_policy_sample': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -1425,6 +1442,38 @@ def mlp_backward_qloss_return(job: MlpJob, target_q, ret: VtraceArgs, weights, c
                                                  _stream()), 'asac_mlp_backward_qloss_return')
 
 
+def policy_forward_save_floats(N: int) -> int:
+    """floats of the buffer the policy-forward rider saves N rows' forward in (`mlp_backward_qloss_return_rider`)"""
+    return int(load().asac_policy_forward_save_floats(int(N)))
+
+
+def mlp_backward_qloss_return_rider_ok(job: MlpJob, ret: VtraceArgs, pi_job, save) -> bool:
+    """may the Q-loss backward launch carry the policy's forward on `pi_job`'s rows (saved in `save`) as a rider?"""
+    return bool(load().asac_mlp_backward_qloss_return_rider_ok(C.byref(job), C.byref(ret),
+                                                               C.byref(pi_job) if pi_job is not None else None, _p(save)))
+
+
+def _mlp_backward_qloss_return_rider(job: MlpJob, target_q, ret: VtraceArgs, weights, clip_eps, loss_out, grad_params,
+                                     workspace, reduce_mode, pi_job: MlpJob, save, grad_x0=None):
+    """`mlp_backward_qloss_return` with the policy's forward on `pi_job`'s rows riding on further workgroups of the launch:
+    `save` (float32, `policy_forward_save_floats(pi_job.N)`) receives what `policy_step_fused_loaded` reads.  The Q job's
+    outputs are `mlp_backward_qloss_return`'s, bit for bit."""
+    global _last_work
+    _last_work = _pass_flops(job, backward=True) + _pass_flops(pi_job)
+    E, N = job.E, job.N
+    assert target_q.is_contiguous() and target_q.numel() == E * N
+    assert grad_x0 is None or (grad_x0.is_contiguous() and grad_x0.numel() == E * N * job.desc.contents.in0)
+    assert save.dtype == torch.float32 and save.is_contiguous() and save.numel() >= policy_forward_save_floats(pi_job.N)
+    _check(load().asac_mlp_backward_qloss_return_rider(C.byref(job), _p(target_q), C.byref(ret), _p(weights),
+                                                       float(clip_eps), _p(loss_out), _p(grad_x0), _p(grad_params),
+                                                       _p(workspace), int(reduce_mode), C.byref(pi_job), _p(save),
+                                                       _stream()), 'asac_mlp_backward_qloss_return_rider')
+
+
+# (one launch of the step under the name it has without the rider: the kernel tables key on it)
+mlp_backward_qloss_return_rider = _profiled(_mlp_backward_qloss_return_rider, 'asac_mlp_backward_qloss_return')
+
+
 @_profiled
 def mlp_backward_policy_q(job: MlpJob, q_table, subset, E_sample, grad_x1):
     """Policy step: action gradients of mean_b(-min_{e in subset} q_e) through the stock Q ensemble."""
@@ -1542,6 +1591,54 @@ def _policy_step_fused(q_desc, q_params, q_member_stride, pi_desc, pi_params, pi
 
 
 _policy_step_fused_plain = _profiled(_policy_step_fused, 'asac_policy_step_fused')
+
+
+def policy_step_fused_loaded_ok(q_desc, q_params, q_member_stride, pi_desc, pi_params, pi_member_stride, N, saved) -> bool:
+    return bool(load().asac_policy_step_fused_loaded_ok(C.byref(q_desc), _p(q_params), q_member_stride, C.byref(pi_desc),
+                                                        _p(pi_params), pi_member_stride, N, _p(saved)))
+
+
+def _policy_step_fused_loaded(q_desc, q_params, q_member_stride, pi_desc, pi_params, pi_member_stride, x, N, action, eps,
+                              log_alpha, saved, q_out, pi_grad_params, workspace, reduce_mode, subset=None, offline=None):
+    global _last_work
+    _last_work = (mlp_flops(q_desc, 2, N, backward=True, param_grads=False)
+                  + mlp_flops(pi_desc, 1, N, backward=True, param_grads=True))
+    p0, rs0, _ = _rows_view(x)
+    A = pi_desc.head_cols[0]
+    assert eps.is_contiguous() and eps.numel() == N * A
+    assert action is not None and action.is_contiguous() and action.numel() == N * A
+    assert saved.dtype == torch.float32 and saved.is_contiguous() and saved.numel() >= policy_forward_save_floats(N)
+    assert q_out is None or (q_out.is_contiguous() and q_out.numel() % N == 0 and q_out.numel() >= 2 * N)
+    assert subset is None or (subset.dtype == torch.int32 and subset.numel() == 2)
+    if offline is not None:
+        po, rso = _offline_view(offline, N, A)
+        _check(load().asac_policy_step_fused_loaded_offline(C.byref(q_desc), _p(q_params), q_member_stride,
+                                                            C.byref(pi_desc), _p(pi_params), pi_member_stride, p0, rs0, N,
+                                                            _p(action), _p(eps), _p(log_alpha), _p(subset), po, rso,
+                                                            _p(saved), _p(q_out), _p(pi_grad_params), _p(workspace),
+                                                            int(reduce_mode), _stream()),
+               'asac_policy_step_fused_loaded_offline')
+        return
+    _check(load().asac_policy_step_fused_loaded(C.byref(q_desc), _p(q_params), q_member_stride, C.byref(pi_desc),
+                                                _p(pi_params), pi_member_stride, p0, rs0, N, _p(action), _p(eps),
+                                                _p(log_alpha), _p(subset), _p(saved), _p(q_out), _p(pi_grad_params),
+                                                _p(workspace), int(reduce_mode), _stream()),
+           'asac_policy_step_fused_loaded')
+
+
+# (recorded under the names of the launches they stand in for)
+_policy_step_fused_loaded_plain = _profiled(_policy_step_fused_loaded, 'asac_policy_step_fused')
+_policy_step_fused_loaded_offline = _profiled(_policy_step_fused_loaded, 'asac_policy_step_fused_offline')
+
+
+def policy_step_fused_loaded(q_desc, q_params, q_member_stride, pi_desc, pi_params, pi_member_stride, x, N, action, eps,
+                             log_alpha, saved, q_out, pi_grad_params, workspace, reduce_mode, subset=None, offline=None):
+    """`policy_step_fused` with the action given, loading the policy's forward on the rows of `x` from `saved` (what
+    `mlp_backward_qloss_return_rider` wrote for the same parameters and rows) instead of recomputing it: same results,
+    bit for bit."""
+    fn = _policy_step_fused_loaded_plain if offline is None else _policy_step_fused_loaded_offline
+    return fn(q_desc, q_params, q_member_stride, pi_desc, pi_params, pi_member_stride, x, N, action, eps, log_alpha, saved,
+              q_out, pi_grad_params, workspace, reduce_mode, subset, offline)
 
 
 @_profiled

@@ -671,6 +671,24 @@ int asac_mlp_backward_qloss_return(const asac_mlp_job_t* job, const float* targe
                                    const float* weights, float clip_eps, float* loss_out, float* grad_x0, float* grad_params,
                                    float* workspace, int reduce_mode, void* stream);
 
+/* asac_mlp_backward_qloss_return carrying a RIDER: further workgroups of the same launch (a second plane of its grid)
+ * run the POLICY's forward on the 16-row tiles of `pi_job` (E = 1, stock three-block Gaussian-head policy on its state
+ * rows x0; x1, out and the window fields unused) and save, per tile and for all 16 rows (rows >= N are evaluated on zeros),
+ * what the policy's backward needs of it — the values the forward recompute inside asac_policy_step_fused produces, bit
+ * for bit:   save [tiles][6400] floats = x_1..x_3 [3][16][64] | gelu'(z_l) [3][4 waves][64 lanes][4] (the MFMA C fragment
+ * each lane holds) | raw head values [16][16];  tiles = ceil(pi_job->N / 16), asac_policy_forward_save_floats(N) floats,
+ * 16-byte aligned.  asac_policy_step_fused_loaded reads it.  The Q job's own outputs are those of
+ * asac_mlp_backward_qloss_return, bit for bit; the rider reads nothing this launch writes.
+ * `_ok`: asac_mlp_backward_qloss_return_ok, the Q job on 16-row tiles, a qualifying policy job, a save buffer, and no more
+ * policy tiles than the Q job has workgroups (NULL job, N <= 0, a non-stock policy or a NULL buffer: 0). */
+int64_t asac_policy_forward_save_floats(int64_t N);
+int asac_mlp_backward_qloss_return_rider_ok(const asac_mlp_job_t* job, const asac_vtrace_args_t* ret,
+                                            const asac_mlp_job_t* pi_job, const float* save);
+int asac_mlp_backward_qloss_return_rider(const asac_mlp_job_t* job, const float* target_q, const asac_vtrace_args_t* ret,
+                                         const float* weights, float clip_eps, float* loss_out, float* grad_x0,
+                                         float* grad_params, float* workspace, int reduce_mode, const asac_mlp_job_t* pi_job,
+                                         float* save, void* stream);
+
 /* The policy step's Q backward (sac_base.py:1896-1903): the gradient of mean_b(-min_{e in subset} q_e)
  * w.r.t. the ensemble outputs is formed on chip from the value table q_table [E][N] the preceding
  * asac_mlp_forward produced (-1/N at the first arg-min member of the subset, else 0) and pushed back to
@@ -713,6 +731,26 @@ int asac_policy_step_fused_offline(const asac_mlp_desc_t* q_desc, const float* q
                                    const float* log_alpha, const int32_t* subset, const float* off_action,
                                    int64_t off_row_stride, float* q_out, float* a_tanh_out, float* logp_out, float* ls_out,
                                    float* pi_grad_params, float* workspace, int reduce_mode, void* stream);
+
+/* asac_policy_step_fused (action given) LOADING the policy's forward instead of running it again behind the critics:
+ * `saved` is what the rider of asac_mlp_backward_qloss_return_rider wrote for the SAME policy parameters and the same N
+ * rows x (the caller's responsibility: neither may have changed in between).  The tile's saved values are requested with
+ * the weights and parked in LDS beside the critics; the launch then computes what asac_policy_step_fused computes, bit for
+ * bit.  action must not be NULL.  `_ok`: asac_policy_step_fused_ok and a 16-byte aligned `saved`. */
+int asac_policy_step_fused_loaded_ok(const asac_mlp_desc_t* q_desc, const float* q_params, int64_t q_member_stride,
+                                     const asac_mlp_desc_t* pi_desc, const float* pi_params, int64_t pi_member_stride, int64_t N,
+                                     const float* saved);
+int asac_policy_step_fused_loaded(const asac_mlp_desc_t* q_desc, const float* q_params, int64_t q_member_stride,
+                                  const asac_mlp_desc_t* pi_desc, const float* pi_params, int64_t pi_member_stride,
+                                  const float* x, int64_t x_row_stride, int64_t N, const float* action, const float* eps,
+                                  const float* log_alpha, const int32_t* subset, const float* saved, float* q_out,
+                                  float* pi_grad_params, float* workspace, int reduce_mode, void* stream);
+int asac_policy_step_fused_loaded_offline(const asac_mlp_desc_t* q_desc, const float* q_params, int64_t q_member_stride,
+                                          const asac_mlp_desc_t* pi_desc, const float* pi_params, int64_t pi_member_stride,
+                                          const float* x, int64_t x_row_stride, int64_t N, const float* action,
+                                          const float* eps, const float* log_alpha, const int32_t* subset,
+                                          const float* off_action, int64_t off_row_stride, const float* saved, float* q_out,
+                                          float* pi_grad_params, float* workspace, int reduce_mode, void* stream);
 
 /* The policy step's policy backward (sac_base.py:1883-1906, stock Gaussian-head ModelPolicy): the
  * gradient of the objective w.r.t. (loc | scale) — asac_squash_sample_bwd's math with dL/dlogp =

@@ -3,7 +3,8 @@
 // the stock policy) and prints the time between stamps, averaged over launches.  The policy -> sample -> critics forward
 // runs at the step's N = 1 280 rows, E = 2, A = 2, S = 6 with all three side jobs on, on plain rows and on ring-addressed
 // rows; its side waves (threads 256, 320, 384) stamp the end of their two steps.  The one-launch policy step is stamped
-// twice: with the action given, and with the action sampled inside the launch (the headline step's form).
+// three times: with the action given, with the action sampled inside the launch, and with the action given and the
+// policy's forward loaded from a saved tile (the headline step's form; the saved values are zeros here: timing only).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Iinclude -Iadvanced-soft-actor-critic_amd/csrc \
 //         tools/mlp_phases.hip -o tools/mlp_phases
 #define ASAC_MLP_STAMPS 1
@@ -96,23 +97,38 @@ int main() {
         const int reps = 200;
         // (form 1: the action sampled inside the launch, as the headline step issues it — the policy's first run on the tile
         // and the sampling lie between stamps 0 and 1, with the staging)
-        for (int form = 0; form < 2; ++form) {
+        // (form 2: the action given and the policy's forward LOADED from the tile an earlier launch saved — no stamp 7: the
+        // forward and the head product are not in that instantiation; the row between stamps 6 and 8 is the fragments' LDS reads)
+        float* saved = nullptr;
+        if (hipMalloc(&saved, asac_policy_forward_save_floats(N) * 4) != hipSuccess) { printf("hipMalloc failed\n"); return 1; }
+        hipMemset(saved, 0, asac_policy_forward_save_floats(N) * 4);
+        for (int form = 0; form < 3; ++form) {
         double acc[16] = {0};
         for (int r = 0; r < reps; ++r) {
+            if (form == 2)
+                asac_policy_step_fused_loaded(&dq, params, stride, &dp, params, stride, x0, S, N, act, eps, la, nullptr, saved, qout,
+                                              grad, ws, ASAC_MLP_REDUCE_DEFER, nullptr);
+            else
             asac_policy_step_fused(&dq, params, stride, &dp, params, stride, x0, S, N, form ? nullptr : act, eps, la, nullptr, qout,
                                    form ? a2 : nullptr, form ? lp2 : nullptr, form ? lsout : nullptr, grad, ws, ASAC_MLP_REDUCE_DEFER, nullptr);
             hipDeviceSynchronize();
             unsigned long long st[32];
             hipMemcpyFromSymbol(st, HIP_SYMBOL(asac::g_mlp_stamps), sizeof st);
+            if (form == 2) st[7] = st[6];
             for (int i = 1; i <= 13; ++i) acc[i] += (double)(st[i] - st[i - 1]) / 100.0;
             acc[0] += (double)(st[13] - st[0]) / 100.0;
         }
         static const char* names[] = {"", "staging", "critics forward", "critic heads", "dq", "critics backward", "policy -> LDS",
                                       "policy forward", "policy head", "sampling backward", "head grads + g", "reverse L3",
                                       "reverse L2", "reverse L1"};
-        printf("policy_step_fused%s: workgroup 0 total %.2f us\n", form ? " (action sampled inside)" : "", acc[0] / reps);
-        for (int i = 1; i <= 13; ++i) printf("   %-18s %6.2f us\n", i == 1 && form ? "staging + sampling" : names[i], acc[i] / reps);
+        printf("policy_step_fused%s: workgroup 0 total %.2f us\n",
+               form == 2 ? " (policy forward loaded)" : form ? " (action sampled inside)" : "", acc[0] / reps);
+        for (int i = 1; i <= 13; ++i) {
+            if (form == 2 && i == 7) continue;       // (no forward in the loaded form)
+            printf("   %-18s %6.2f us\n", i == 1 && form == 1 ? "staging + sampling" : form == 2 && i == 8 ? "fragment reads" : names[i], acc[i] / reps);
         }
+        }
+        hipFree(saved);
         asac_pi_q_job_t job{};
         job.pi.desc = &dp; job.pi.params = params; job.pi.member_stride = stride; job.pi.x0 = x5; job.pi.x0_row_stride = S;
         job.pi.N = N5; job.pi.out = lsout; job.pi.E = 1;

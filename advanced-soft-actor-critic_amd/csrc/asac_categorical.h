@@ -6,7 +6,8 @@
 //   lp = z - logsumexp(z)     = z - (log(sum_j exp(z_j - max)) + max)      (torch logsumexp)
 //   cl(p) = log(max(p, 1e-8))                                              (sac_base.py: torch.log(probs.clamp(min=1e-8)))
 //   H  = -sum_j p_j lp_j                                                   (torch Categorical.entropy)
-// Sums run over the branch's entries in index order by one lane.  Accurate expf / logf, -ffp-contract=off.
+// Sums run over the branch's entries in index order by one lane (those of CatSum's comment compensated).
+// Accurate expf / logf, -ffp-contract=off.
 #pragma once
 #include "asac_common.h"
 #include "asac_vtrace.h"
@@ -55,10 +56,24 @@ __device__ __forceinline__ float cat_cl(float p) { return logf(fmaxf(p, kCatProb
 // d cl(p) / d p * p: 1 where the clamp passes the gradient (torch: p >= min), else 0
 __device__ __forceinline__ float cat_cl_open(float p) { return p >= kCatProbFloor ? 1.f : 0.f; }
 
+// a running float32 sum that carries its rounding error along (Kahan; nothing here is compiled with fast-math, so the
+// compensation survives).  For the sums over up to 64 entries, 64 steps or 8 members whose plain running error shows at
+// the limits: the branch sums the policy step's gradient cancels against a term of their own size afterwards (lp_i + H_k,
+// g_i - S_k), V over a row's entries, the rows' loss terms, the members' mean, the DQN-like target's reward sum
+struct CatSum {
+    float s = 0.f, c = 0.f;
+    __device__ __forceinline__ void add(float t) {
+        const float y = t - c;
+        const float u = s + y;
+        c = (u - s) - y;
+        s = u;
+    }
+};
+
 __device__ __forceinline__ float cat_entropy(const float* z, int s, const CatStats& st) {
-    float h = 0.f;
-    for (int j = 0; j < s; ++j) h += cat_prob(z[j], st) * cat_logp(z[j], st);
-    return -h;
+    CatSum h;
+    for (int j = 0; j < s; ++j) h.add(cat_prob(z[j], st) * cat_logp(z[j], st));
+    return -h.s;
 }
 
 // index drawn from a branch of s entries with probabilities p[0..s) by the inverse CDF on one uniform u in [0, 1):
@@ -75,18 +90,18 @@ __device__ __forceinline__ int inverse_cdf(const float* p, int s, float u) {
 
 // mean over the members of a device-resident subset of element `off` of each member's tensor (the members are separate
 // tensors of one shape: a pointer table instead of a stack).  Every member's load is requested before the first add
-// (members beyond the real ones re-read the last real one: a valid address, the value is not added); sum in subset order,
-// one division (torch mean).  `tab`: the table read in place from the kernel-argument segment.
+// (members beyond the real ones re-read the last real one: a valid address, the value is not added); sum in subset order
+// (compensated: CatSum), one division (torch mean).  `tab`: the table read in place from the kernel-argument segment.
 __device__ __forceinline__ float cat_member_mean(const ASAC_KARG asac_members_t& tab, const int32_t* subset, int Es,
                                                  int64_t off) {
     float v[ASAC_DISCRETE_MAX_MEMBERS];
 #pragma unroll
     for (int e = 0; e < ASAC_DISCRETE_MAX_MEMBERS; ++e) v[e] = tab.base[member(subset, min(e, Es - 1))][off];
-    float s = 0.f;
+    CatSum s;
 #pragma unroll
     for (int e = 0; e < ASAC_DISCRETE_MAX_MEMBERS; ++e)
-        if (e < Es) s += v[e];
-    return s / (float)Es;
+        if (e < Es) s.add(v[e]);
+    return s.s / (float)Es;
 }
 
 // ... the minimum over the subset instead (the option's target, option_base.py:337-338): the same loads, fminf in subset

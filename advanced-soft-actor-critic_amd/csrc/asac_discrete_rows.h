@@ -23,7 +23,7 @@ struct DiscReturnGeom {
 struct DiscReturnLds {
     float *z, *qn, *qx;              // [P][Dp] logits; the statistic over subset_n / subset_next of the target members' values
     float *a, *mu;                   // [P][Dp] stored action, mu * stored action      (importance sampling only)
-    float *vn, *vx, *lpa, *mup;      // [P] V with subset_n / subset_next, log pi(stored action), prod_j (mu_j a_j, zeros -> 1)
+    float *vn, *vx, *lpa, *mup;      // [P] V with subset_n / subset_next, pi(stored action), prod_j (mu_j a_j, zeros -> 1)
     float* rest;                     // the kernel's own arrays
 };
 // LDS floats of the carve (every part a multiple of four floats) ...
@@ -74,7 +74,7 @@ __device__ __forceinline__ void disc_return_stage(const ASAC_KARG asac_vtrace_ar
     }
 }
 
-// phase 1, one lane per window position: branch softmax, V with subset_n and with subset_next, log pi(stored action),
+// phase 1, one lane per window position: branch softmax, V with subset_n and with subset_next, pi(stored action),
 // prod mu.  kOption: per entry of the next position the termination mix (1 - beta) (Qx_j - c_j) + beta vbar
 // (option_base.py:349-351), beta / vbar the [P] arrays of the step INTO the position
 template <bool kOption>
@@ -89,7 +89,9 @@ __device__ __forceinline__ void disc_return_values(const ASAC_KARG asac_vtrace_a
     const float alpha = expf(*a.log_alpha);
     if (tid >= P || row0 + tid / T >= a.B) return;
     const int pos = tid;
-    float vn = 0.f, vx = 0.f, lpa = 0.f, mu = 1.f;
+    CatSum vn, vx;
+    double lpa = 0.;                 // sum_k log pi_k(stored action), see below
+    float mu = 1.f;
     const float beta = kOption ? s_beta[pos] : 0.f, vbar = kOption ? s_vbar[pos] : 0.f;
     int j0 = 0;
     for (int k = 0; k < K; ++k) {
@@ -101,11 +103,11 @@ __device__ __forceinline__ void disc_return_values(const ASAC_KARG asac_vtrace_a
         for (int j = 0; j < sz; ++j) {
             const float p = cat_prob(s.z[o0 + j], cs);
             const float c = alpha * cat_cl(p);
-            vn += p * (s.qn[o0 + j] - c);
+            vn.add(p * (s.qn[o0 + j] - c));
             if (kOption)
-                vx += p * ((1.f - beta) * (s.qx[o0 + j] - c) + beta * vbar);
+                vx.add(p * ((1.f - beta) * (s.qx[o0 + j] - c) + beta * vbar));
             else
-                vx += p * (s.qx[o0 + j] - c);
+                vx.add(p * (s.qx[o0 + j] - c));
             if (is) {
                 const float av = s.a[o0 + j];
                 if (av > amax) amax = av, arg = j;             // the first maximum (torch max(-1)[1])
@@ -113,11 +115,14 @@ __device__ __forceinline__ void disc_return_values(const ASAC_KARG asac_vtrace_a
                 mu *= (m == 0.f) ? 1.f : m;
             }
         }
-        if (is) lpa += cat_logp(s.z[o0 + arg], cs);
+        if (is) lpa += ((double)s.z[o0 + arg] - (double)cs.m) - log((double)cs.sum);
         j0 += sz;
     }
-    s.vn[pos] = vn / (float)K, s.vx[pos] = vx / (float)K;
-    s.lpa[pos] = lpa, s.mup[pos] = mu;
+    s.vn[pos] = vn.s / (float)K, s.vx[pos] = vx.s / (float)K;
+    // pi(stored action) = exp(sum_k lp_k).  Over eight branches the sum reaches -13 and below, where float32 steps are
+    // 1e-6, and exp turns the sum's rounding into that RELATIVE error of an unclamped ratio: the K terms (one per
+    // position, from the branch's float32 max and sum) are formed and added in double, and pi is rounded once
+    s.lpa[pos] = (float)exp(lpa), s.mup[pos] = mu;
 }
 
 // (1/K) sum_j a_j q_e[b, j] of the Eon online members at the step's state (TD error variant) -> s_qs [R][8]
@@ -221,30 +226,31 @@ __device__ __forceinline__ DiscRowTerm disc_policy_row(const ASAC_KARG DiscPolic
     const float* z = x.logits + (int64_t)b * x.logits_stride;
     const float* mu = x.mu + (int64_t)b * x.mu_stride;
     const int64_t qrow = (int64_t)b * x.q.stride_b;
-    float main = 0.f, h_mu = 0.f, h_pi = 0.f;
+    CatSum main_sum, h_mu_sum;
+    float h_pi = 0.f;
     int j0 = 0;
     for (int k = 0; k < K; ++k) {
         const int s = x.br.size[k];
         const CatStats cs = cat_stats(z + j0, s);
-        float S = 0.f;
+        CatSum Sk;
         for (int j = 0; j < s; ++j) {
             const float p = cat_prob(z[j0 + j], cs);
             const float c = alpha * cat_cl(p);
             const float qbar = cat_member_mean(x.q, x.subset, Es, qrow + j0 + j);
             const float g = (c - qbar + alpha * cat_cl_open(p)) / (float)K;
-            main += p * (c - qbar);
-            S += p * g;
+            main_sum.add(p * (c - qbar));
+            Sk.add(p * g);
             const float m = mu[j0 + j];
-            h_mu += m * cat_cl(m);
+            h_mu_sum.add(m * cat_cl(m));
         }
-        const float H = cat_entropy(z + j0, s, cs);
+        const float H = cat_entropy(z + j0, s, cs), S = Sk.s;
         h_pi += H;
         keep.m[k * kDiscThreads + tid] = cs.m, keep.sum[k * kDiscThreads + tid] = cs.sum;
         keep.S[k * kDiscThreads + tid] = S, keep.H[k * kDiscThreads + tid] = H;
         j0 += s;
     }
-    main = main / (float)K;
-    h_mu = -h_mu / (float)K;
+    const float main = main_sum.s / (float)K;
+    const float h_mu = -h_mu_sum.s / (float)K;
     h_pi = h_pi / (float)K;
     const float dh = h_mu - h_pi;
     const DiscRowTerm out = {main + x.penalty * (dh * dh / 2.f), h_pi};
@@ -276,20 +282,21 @@ __device__ __forceinline__ DiscRowTerm disc_alpha_row(const ASAC_KARG asac_branc
                                                       const float* target, float* probs, bool want_h) {
     const ASAC_KARG asac_branches_t& br = *brp;
     const int K = br.K;
-    float row = 0.f, h = 0.f;
+    CatSum row;
+    float h = 0.f;
     int j0 = 0;
     for (int k = 0; k < K; ++k) {
         const int s = br.size[k];
         const CatStats cs = cat_stats(z + j0, s);
         for (int j = 0; j < s; ++j) {
             const float p = cat_prob(z[j0 + j], cs);
-            row += p * (-cat_cl(p) - target[j0 + j]);
+            row.add(p * (-cat_cl(p) - target[j0 + j]));
             if (probs) probs[j0 + j] = p;
         }
         if (want_h) h += cat_entropy(z + j0, s, cs);
         j0 += s;
     }
-    return {row / (float)K, h / (float)K};
+    return {row.s / (float)K, h / (float)K};
 }
 
 }  // namespace asac

@@ -24,17 +24,17 @@ template <int M>
 __device__ __forceinline__ float dqn_row_target(const ASAC_KARG asac_vtrace_args_t& a, const ASAC_KARG asac_dqn_job_t& x,
                                                 int b) {
     const int n = a.n, K = x.branches.K, Es = a.E_sample;
-    // the row's steps: L, done at L, gamma^(L+1), the discounted reward sum in index order
+    // the row's steps: L, done at L, gamma^(L+1), the discounted reward sum in index order (compensated)
     int L = -1;
     bool done_at = false, done_t = false;
-    float g = 0.f;
+    CatSum g;
     double gp = 1., gp_at = 1.;        // gamma^(t+1), exact to float after the rounding below
     const int64_t m0 = (int64_t)b * a.mask_stride;
     const float* rw = a.reward + (int64_t)b * a.reward_stride;
     for (int t = 0; t < n; ++t) {
         const bool gone = a.last_mask[m0 + t] | a.padding_mask[m0 + t];
         done_t = a.done[m0 + t];
-        g += a.gamma_ratio[t] * rw[t];
+        g.add(a.gamma_ratio[t] * rw[t]);
         gp *= (double)a.gamma;
         if (!gone) L = t, done_at = done_t, gp_at = gp;
     }
@@ -83,7 +83,7 @@ __device__ __forceinline__ float dqn_row_target(const ASAC_KARG asac_vtrace_args
 #pragma unroll
     for (int i = 1; i < M; ++i)
         if (i < Es) v = fminf(v, acc[i] / (float)K);
-    return g + (float)gp_at * v * (done_at ? 0.f : 1.f);
+    return g.s + (float)gp_at * v * (done_at ? 0.f : 1.f);
 }
 
 // (1/K) sum_j a[b, j] q_e[b, j] of online member e at the step's state

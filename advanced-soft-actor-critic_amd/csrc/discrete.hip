@@ -101,7 +101,7 @@ __global__ __launch_bounds__(kDiscThreads) void k_discrete_return(const DiscRetu
     // phase 2
     if (have_step) {
         const int pos = sr * T + st;
-        if (is) raw.ratio = expf(s.lpa[pos]) / fmaxf(s.mup[pos], 1e-8f);
+        if (is) raw.ratio = s.lpa[pos] / fmaxf(s.mup[pos], 1e-8f);
         float d, c;
         vtrace_step_finish_v(a, raw, s.vn[pos], s.vx[pos + 1], &d, &c);
         s_d[sr * pitch + st] = d;

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(kDiscThreads) void k_hybrid_return(const HybridRetu
     if (have_step) {
         const int pos = sr * T + st;
         VtraceStepRaw draw = craw;           // reward, g, keep and the two ratios of the step; its own pi / mu ratio
-        draw.ratio = is ? expf(s.lpa[pos]) / fmaxf(s.mup[pos], 1e-8f) : 1.f;
+        draw.ratio = is ? s.lpa[pos] / fmaxf(s.mup[pos], 1e-8f) : 1.f;
         float d, c;
         vtrace_step_finish_v(a, draw, s.vn[pos], s.vx[pos + 1], &d, &c);
         s_d[sr * pitch + st] = d;

@@ -206,3 +206,57 @@ def clamp_sides(c64):
 
 def as_numpy(d):
     return {k: np.asarray(v.detach().cpu().double().numpy()) for k, v in d.items()}
+
+
+ULP = 2.0 ** -23
+
+
+def over_the_bound(tag, want, kernel, eager):
+    """The rule the kernels over a categorical head are held to (tests/test_discrete_gpu.py, test_hybrid_gpu.py,
+    test_dqn_gpu.py, test_categorical_limits_gpu.py), on {name: float64 array} of the float64 restatement, the kernel and
+    the float32 eager composition: every element of the kernel's tensors is finite (written) and of the restatement's
+    shape; per tensor the kernel's largest absolute error may be at most twice the eager composition's, floor 4 units in
+    the last place at the tensor's largest magnitude -> ([(tensor, kernel error, eager error, floor)] of the tensors over
+    the bound, the largest share of the bound); prints every figure"""
+    assert set(kernel) == set(eager) == set(want)
+    bad, share = [], 0.
+    for name, ref in want.items():
+        assert np.isfinite(kernel[name]).all(), f'{name}: an element was not written'
+        assert kernel[name].shape == ref.shape, name
+        e_k, e_m = float(np.abs(kernel[name] - ref).max()), float(np.abs(eager[name] - ref).max())
+        floor = 4 * ULP * float(np.abs(ref).max())
+        bound = max(2 * e_m, floor)
+        share = max(share, e_k / bound if bound > 0 else 0.)
+        print(f'{tag} {name}: kernel {e_k:.3e}  eager {e_m:.3e}  floor {floor:.3e}  share {e_k / bound if bound else 0.:.2f}')
+        if e_k > bound:
+            bad.append((name, e_k, e_m, floor))
+    return bad, share
+
+
+GUARD = 64                      # floats in front of and behind every guarded output
+SENTINEL = -1.2345679e30        # finite, and no result of these kernels
+
+
+class Guarded:
+    """An allocator of the kernels' output tensors (the `alloc` of the test modules' `_kernels`): each one a NaN-filled,
+    contiguous view inside a larger buffer with GUARD floats of SENTINEL in front of it and behind it; `check()` after the
+    launches: every sentinel still has its bits"""
+
+    def __init__(self):
+        self.buffers = []
+
+    def __call__(self, *shape):
+        numel = int(np.prod(shape, dtype=np.int64))
+        buf = torch.full((GUARD + numel + GUARD,), SENTINEL, device='cuda')
+        view = buf[GUARD:GUARD + numel].view(shape)
+        view.fill_(float('nan'))
+        self.buffers.append((buf, numel))
+        return view
+
+    def check(self):
+        assert self.buffers
+        bits = torch.tensor(SENTINEL).view(torch.int32).item()
+        for i, (buf, numel) in enumerate(self.buffers):
+            words = buf.view(torch.int32)
+            assert bool((words[:GUARD] == bits).all()), f'output {i} ({numel} floats): written in front of the tensor'
+            assert bool((words[GUARD + numel:] == bits).all()), f'output {i} ({numel} floats): written behind the tensor'

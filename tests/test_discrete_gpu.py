@@ -42,11 +42,12 @@ def _vtrace_args(c, y_out, td_out=None):
     return a
 
 
-def _kernels(c):
-    """the four launches on the case's (strided, device) tensors, outputs pre-filled with NaN -> {name: tensor}"""
+def _kernels(c, alloc=None):
+    """the four launches on the case's (strided, device) tensors, outputs pre-filled with NaN (`alloc`: another allocator
+    of NaN-filled outputs, `discrete_ref.Guarded`) -> {name: tensor}"""
     from asac_amd import native
     B, D, E = c['B'], c['D'], c['E']
-    nan = lambda *shape: torch.full(shape, float('nan'), device='cuda')      # noqa: E731
+    nan = alloc or (lambda *shape: torch.full(shape, float('nan'), device='cuda'))
     br = native.branches(c['sizes'])
     out = {'y': nan(B), 'td': nan(B), 'loss_q': nan(E), 'grad_q': nan(E, B, D), 'loss_policy': nan(), 'grad_logits': nan(B, D),
            'd_entropy': nan(), 'p': nan(B, D), 'h_pi': nan(B), 'grad_alpha': nan(1)}
@@ -75,25 +76,15 @@ def _eager(c):
     return out
 
 
-def _compare(tag, c):
+def _compare(tag, c, alloc=None):
     """kernel and eager float32 against float64 -> [(tensor, kernel error, eager error, floor)] of the tensors over the
-    bound; prints every figure"""
+    bound (`discrete_ref.over_the_bound`); prints every figure"""
     want = dr.as_numpy(dr.all_formulas(dr.to(c, torch.float64, 'cpu')))
     dev = dr.to(c, torch.float32, 'cuda', strided=True)
     assert dev['logits'].stride(1) == c['D'] + 5 and dev['q_target'][0].stride(1) == c['D'] + 5      # strided views
     assert dev['done'].stride(0) == c['n'] + 2 and dev['reward'].stride(0) == c['n'] + 5
-    kernel, eager = dr.as_numpy(_kernels(dev)), dr.as_numpy(_eager(dev))
-    assert set(kernel) == set(eager) == set(want)
-    bad = []
-    for name, ref in want.items():
-        assert np.isfinite(kernel[name]).all(), f'{name}: an element was not written'
-        assert kernel[name].shape == ref.shape, name
-        e_k, e_m = float(np.abs(kernel[name] - ref).max()), float(np.abs(eager[name] - ref).max())
-        floor = 4 * ULP * float(np.abs(ref).max())
-        print(f'{tag} {name}: kernel {e_k:.3e}  eager {e_m:.3e}  floor {floor:.3e}')
-        if e_k > max(2 * e_m, floor):
-            bad.append((name, e_k, e_m, floor))
-    return bad
+    kernel, eager = dr.as_numpy(_kernels(dev, alloc)), dr.as_numpy(_eager(dev))
+    return dr.over_the_bound(tag, want, kernel, eager)[0]
 
 
 @pytest.mark.parametrize('use_is', [False, True], ids=['plain', 'is'])
@@ -181,6 +172,10 @@ OBSERVABLES = {'loss_q': dict(rtol=2e-4, atol=0.), 'loss_policy': dict(rtol=2e-4
                'tree': dict(rtol=2e-4, atol=1e-6), 'log_d_alpha': dict(rtol=2e-4, atol=2e-5)}
 
 
+ONE_STEP = {'asac_discrete_return': 2, 'asac_discrete_q_loss_grad': 1, 'asac_discrete_policy_loss_grad': 1,
+            'asac_discrete_alpha_grad': 1}
+
+
 def _run_fixture(case, golden_dir, fused):
     """the fixture's steps through the learner -> ({observable: |error| array of step 0}, [failures])"""
     from algorithm.fused import RecordedNoise
@@ -265,8 +260,7 @@ def test_one_step_issues_one_launch_per_item(golden_dir):
         agent.train()
     seen = prof.summary()
     agent.close()
-    assert _discrete_calls(seen) == {'asac_discrete_return': 2, 'asac_discrete_q_loss_grad': 1,
-                                     'asac_discrete_policy_loss_grad': 1, 'asac_discrete_alpha_grad': 1}
+    assert _discrete_calls(seen) == ONE_STEP
     assert 'asac_vtrace_return_direct' not in seen
 
 

@@ -12,6 +12,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from tests import dqn_ref as qr  # noqa: E402
+from tests.discrete_ref import over_the_bound  # noqa: E402
 from tests import parity_utils as pu  # noqa: E402
 from tests.golden.make_dqn_golden import CASES, SMALL  # noqa: E402
 
@@ -45,11 +46,12 @@ def _job(c, online=True):
                           q_online=c['q_online'] if online else None)
 
 
-def _kernels(c):
-    """the two launches on the case's (strided, device) tensors, outputs pre-filled with NaN -> {name: tensor}"""
+def _kernels(c, alloc=None):
+    """the two launches on the case's (strided, device) tensors, outputs pre-filled with NaN (`alloc`: another allocator
+    of NaN-filled outputs, `discrete_ref.Guarded`) -> {name: tensor}"""
     from asac_amd import native
     B, D, E = c['B'], c['D'], c['E']
-    nan = lambda *shape: torch.full(shape, float('nan'), device='cuda')      # noqa: E731
+    nan = alloc or (lambda *shape: torch.full(shape, float('nan'), device='cuda'))
     out = {'y': nan(B), 'td': nan(B), 'loss_q': nan(E), 'grad_q': nan(E, B, D), 'y_loss': nan(B)}
     native.dqn_return(_vtrace_args(c, out['y'], out['td']), _job(c))
     native.dqn_q_loss_grad(_vtrace_args(c, out['y_loss']), _job(c), c['w'], out['loss_q'], out['grad_q'])
@@ -63,28 +65,16 @@ def _eager(c):
     return qr.eager(c, lambda *a: SAC_Base.get_dqn_like_d_y(stub, *a))
 
 
-def _compare(tag, c):
+def _compare(tag, c, alloc=None):
     """kernel and eager float32 against float64 -> ([(tensor, kernel error, eager error, floor)] of the tensors over the
-    bound, the largest share of the bound); prints every figure"""
+    bound, the largest share of the bound) (`discrete_ref.over_the_bound`); prints every figure"""
     want = qr.all_formulas(qr.to(c, torch.float64, 'cpu'))
     dev = qr.to(c, torch.float32, 'cuda', strided=True)
     assert dev['q_eval'][0].stride(1) == c['D'] + 5 and dev['q_target'][0].stride(1) == c['D'] + 5      # strided views
     assert dev['done'].stride(0) == c['n'] + 2 and dev['reward'].stride(0) == c['n'] + 5
-    kernel, eager = qr.as_numpy(_kernels(dev)), qr.as_numpy(_eager(dev))
+    kernel, eager = qr.as_numpy(_kernels(dev, alloc)), qr.as_numpy(_eager(dev))
     assert np.array_equal(kernel.pop('y_loss'), kernel['y']), 'the loss launch stores the return launch\'s y'
-    assert set(kernel) == set(eager) == set(want)
-    bad, share = [], 0.
-    for name, ref in want.items():
-        assert np.isfinite(kernel[name]).all(), f'{name}: an element was not written'
-        assert kernel[name].shape == ref.shape, name
-        e_k, e_m = float(np.abs(kernel[name] - ref).max()), float(np.abs(eager[name] - ref).max())
-        floor = 4 * ULP * float(np.abs(ref).max())
-        bound = max(2 * e_m, floor)
-        share = max(share, e_k / bound if bound > 0 else 0.)
-        print(f'{tag} {name}: kernel {e_k:.3e}  eager {e_m:.3e}  floor {floor:.3e}  share {e_k / bound if bound else 0.:.2f}')
-        if e_k > bound:
-            bad.append((name, e_k, e_m, floor))
-    return bad, share
+    return over_the_bound(tag, want, kernel, eager)
 
 
 @pytest.mark.parametrize('E,Es', ENSEMBLES)
@@ -308,6 +298,9 @@ def _calls(summary, prefix='asac_dqn_'):
 OBSERVABLES = {'loss_q': dict(rtol=2e-4, atol=0.), 'td_error': dict(rtol=2e-4, atol=2e-5), 'tree': dict(rtol=2e-4, atol=1e-6)}
 
 
+ONE_STEP = {'asac_dqn_q_loss_grad': 1, 'asac_dqn_return': 1}
+
+
 def _run_fixture(case, golden_dir, fused):
     """the fixture's steps through the learner -> ({observable: (|error|, scale) of step 0}, [failures])"""
     from algorithm.fused import RecordedNoise
@@ -390,7 +383,7 @@ def test_one_step_issues_one_launch_per_item(golden_dir):
         agent.train()
     seen = prof.summary()
     agent.close()
-    assert _calls(seen) == {'asac_dqn_q_loss_grad': 1, 'asac_dqn_return': 1}
+    assert _calls(seen) == ONE_STEP
     assert not _calls(seen, 'asac_discrete_')
 
 

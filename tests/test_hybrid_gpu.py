@@ -77,18 +77,19 @@ def _device_case(c):
     return d
 
 
-def _outputs(c):
+def _outputs(c, alloc=None):
     B, D, E = c['B'], c['D'], c['E']
-    nan = lambda *shape: torch.full(shape, float('nan'), device='cuda')      # noqa: E731
+    nan = alloc or (lambda *shape: torch.full(shape, float('nan'), device='cuda'))
     return {'d_y': nan(B), 'c_y': nan(B), 'td': nan(B), 'loss_q': nan(E), 'grad_qd': nan(E, B, D), 'grad_cq': nan(E, B),
             'loss_policy': nan(), 'grad_logits': nan(B, D), 'grad_logp': nan(B), 'grad_cq_pi': nan(E, B), 'd_entropy': nan(),
             'c_entropy': nan(), 'grad_alpha': nan(2)}
 
 
-def _kernels(c):
-    """the four launches on the case's (strided, device) tensors, outputs pre-filled with NaN -> {name: tensor}"""
+def _kernels(c, alloc=None):
+    """the four launches on the case's (strided, device) tensors, outputs pre-filled with NaN (`alloc`: another allocator
+    of NaN-filled outputs, `discrete_ref.Guarded`) -> {name: tensor}"""
     from asac_amd import native
-    br, out = native.branches(c['sizes']), _outputs(c)
+    br, out = native.branches(c['sizes']), _outputs(c, alloc)
     native.hybrid_return(_d_args(c, out['d_y']), _c_args(c, out['c_y']), br, c['q_target'], c['logits'],
                          action=c['action_full'], q_online=c['q_online'], c_q_online=c['c_q_online'], td_out=out['td'])
     native.hybrid_q_loss_grad(br, c['q_online'], c['action_full'][:, 0], c['c_q_online'], c['c_t_q'], c['y'], c['c_y'],
@@ -116,23 +117,13 @@ def _eager(c):
     return out
 
 
-def _compare(tag, c):
+def _compare(tag, c, alloc=None):
     """kernel and eager float32 against float64 -> [(tensor, kernel error, eager error, floor)] of the tensors over the
-    bound; prints every figure"""
+    bound (`discrete_ref.over_the_bound`); prints every figure"""
     want = dr.as_numpy(hr.all_formulas(hr.to(c, torch.float64, 'cpu')))
     dev = _device_case(c)
-    kernel, eager = dr.as_numpy(_kernels(dev)), dr.as_numpy(_eager(dev))
-    assert set(kernel) == set(eager) == set(want)
-    bad = []
-    for name, ref in want.items():
-        assert np.isfinite(kernel[name]).all(), f'{name}: an element was not written'
-        assert kernel[name].shape == ref.shape, name
-        e_k, e_m = float(np.abs(kernel[name] - ref).max()), float(np.abs(eager[name] - ref).max())
-        floor = 4 * ULP * float(np.abs(ref).max())
-        print(f'{tag} {name}: kernel {e_k:.3e}  eager {e_m:.3e}  floor {floor:.3e}')
-        if e_k > max(2 * e_m, floor):
-            bad.append((name, e_k, e_m, floor))
-    return bad
+    kernel, eager = dr.as_numpy(_kernels(dev, alloc)), dr.as_numpy(_eager(dev))
+    return dr.over_the_bound(tag, want, kernel, eager)[0]
 
 
 @pytest.mark.parametrize('use_is', [False, True], ids=['plain', 'is'])

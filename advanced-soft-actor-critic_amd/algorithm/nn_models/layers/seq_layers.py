@@ -198,6 +198,10 @@ FUSED_GATE = True
 # launch per pass behind other projections (csrc/rope.hip)   (False: `self.rope(...)` as module code behind library GEMMs —
 # tests and tools/rope_bench.py)
 FUSED_ROPE = True
+# dropout of the attention weights (training mode, 0 < dropout < 1) inside the multi-head core's launches: the mask is drawn on
+# the device from a counter the module instance owns and regenerated by the backward (csrc/asac_dropout.h)   (False: the
+# baddbmm / softmax / F.dropout / bmm chain of the module code — tests and tools/attn_dropout_bench.py)
+FUSED_ATTN_DROPOUT = True
 
 
 class _AttnCoreFn(torch.autograd.Function):
@@ -272,6 +276,48 @@ class _AttnMhFn(torch.autograd.Function):
         native.attention_mh_backward(q, k, v, rest[0] if ctx.has_mask else None, ctx.heads, p_heads, g_out.contiguous(),
                                      None if g_w is None else g_w.contiguous(), g_q, g_k, g_v)
         return g_q, g_k, g_v, None, None, None
+
+
+class _AttnMhDropFn(torch.autograd.Function):
+    """`_AttnMhFn` with dropout of the softmax weights inside both launches (`asac_attention_mh_dropout_forward/backward`):
+    the weights returned are the DROPPED ones' head mean, as the reference returns them.  `draws` = (p, seed, instance id,
+    state, used): the module instance's stream of draws, its device state and this call's `used` record — the backward
+    launch reads the counter from it on the device, so a captured pair stays in step on every replay."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, heads, row_zero, draws):
+        from asac_amd import native
+        p, seed, instance, state, used = draws
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        B, Lq, E = q.shape
+        Lk = k.shape[1]
+        out = torch.empty(B, Lq, E, dtype=q.dtype, device=q.device)
+        weights = torch.empty(B, Lq, Lk, dtype=q.dtype, device=q.device)
+        keep = torch.empty(B, Lq, dtype=q.dtype, device=q.device)
+        keep_rows = torch.empty(B, Lq, dtype=q.dtype, device=q.device) if row_zero is not None else keep
+        p_heads = torch.empty(B, heads, Lq, Lk, dtype=q.dtype, device=q.device) if any(ctx.needs_input_grad[:3]) else None
+        native.attention_mh_dropout_forward(q, k, v, mask, heads, out, weights, keep, p_heads,
+                                            None if row_zero is None else row_zero.contiguous(),
+                                            keep_rows if row_zero is not None else None, p, seed, instance, state, used)
+        if p_heads is not None:
+            ctx.save_for_backward(q, k, v, p_heads, used, *([mask] if mask is not None else []))
+        ctx.heads, ctx.has_mask, ctx.draws = heads, mask is not None, (p, seed, instance)
+        ctx.mark_non_differentiable(keep, keep_rows)
+        ctx.set_materialize_grads(False)
+        return out, weights, keep, keep_rows
+
+    @staticmethod
+    def backward(ctx, g_out, g_w, _g_keep, _g_keep_rows=None):
+        from asac_amd import native
+        q, k, v, p_heads, used, *rest = ctx.saved_tensors
+        if g_out is None and g_w is None:
+            return None, None, None, None, None, None, None
+        if g_out is None:
+            g_out = torch.zeros(q.shape, dtype=q.dtype, device=q.device)
+        g_q, g_k, g_v = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        native.attention_mh_dropout_backward(q, k, v, rest[0] if ctx.has_mask else None, ctx.heads, p_heads, g_out.contiguous(),
+                                             None if g_w is None else g_w.contiguous(), g_q, g_k, g_v, *ctx.draws, used)
+        return g_q, g_k, g_v, None, None, None, None
 
 
 class _AttnProjFn(torch.autograd.Function):
@@ -874,6 +920,60 @@ class MultiheadAttention(nn.Module):
         self.q_proj, self.k_proj, self.v_proj = proj(), proj(), proj()
         self.out_proj = LinearLayers(embed_dim, dense_n=embed_dim, dense_depth=out_dense_depth,
                                      output_size=out_size, dropout=dropout)
+        # the attention-weight dropout's stream of draws (csrc/asac_dropout.h): plain attributes, no buffers — the state_dict
+        # keeps the reference's keys.  Instance id, seed and the per-device state are taken at the first dropout launch.
+        self._drop_instance = None         # from the one counter of algorithm/utils/image_transforms.py
+        self._drop_seed = None             # None: torch.initial_seed() at the first launch
+        self._drop_counter0 = 0            # where a device first launched on later starts counting
+        self._drop_states = {}             # device -> int64 [544]: the call counter and the arrival words
+        self._drop_used = None             # int64 [1]: the counter the last dropout launch drew with
+
+    def reseed(self, seed: int, counter: int = 0, instance_id: int | None = None):
+        """the attention-weight dropout's draws are a function of (seed, instance id, call counter): re-seat all three"""
+        self._drop_seed = int(seed)
+        if instance_id is not None:
+            self._drop_instance = int(instance_id)
+        for state in self._drop_states.values():
+            state.copy_(torch.tensor([int(counter)] + [0] * (state.numel() - 1), dtype=torch.int64))
+        self._drop_counter0 = int(counter)
+        return self
+
+    def dropout_drawn(self) -> int:
+        """the call counter the last dropout launch drew with.  Synchronises."""
+        if self._drop_used is None:
+            raise RuntimeError('no dropout launch yet')
+        return int(self._drop_used.item())
+
+    def dropout_state(self, device=None):
+        """(call counter, how many arrival words are not zero) of the dropout state on `device` (default: the only one), or
+        None where there is none yet.  Synchronises."""
+        if not self._drop_states:
+            return None
+        state = self._drop_states[device] if device is not None else next(iter(self._drop_states.values()))
+        return int(state[0].item()), int(torch.count_nonzero(state[1:]).item())
+
+    def _dropout_draws(self, device, bsz):
+        """(p, seed, instance id, state, used) of one dropout launch on `device`, or None where the module code has to run:
+        the state does not exist yet and the stream is capturing (allocating and seeding are not part of a capture), or
+        the batch is beyond the draw layout.  `used` is this CALL's record: a module applied twice before its backwards
+        (observations and next observations) keeps both counters apart."""
+        from asac_amd import native
+        if bsz * self.num_heads > native.ATTN_DROPOUT_MAX_BATCH_HEADS:
+            return None
+        state = self._drop_states.get(device)
+        if state is None:
+            if torch.cuda.is_current_stream_capturing():
+                return None
+            if self._drop_instance is None:
+                from algorithm.utils.image_transforms import _instance_ids
+                self._drop_instance = next(_instance_ids)
+            if self._drop_seed is None:
+                self._drop_seed = torch.initial_seed()
+            state = torch.tensor([self._drop_counter0] + [0] * (native.ATTN_DROPOUT_STATE_WORDS - 1), dtype=torch.int64,
+                                 device=device)
+            self._drop_states[device] = state
+        self._drop_used = torch.empty(1, dtype=torch.int64, device=device)
+        return self.dropout, self._drop_seed, self._drop_instance, state, self._drop_used
 
     def _split_heads(self, x):
         """[bsz, len, embed] -> [bsz * heads, len, head_dim], head-major like chunk+cat on dim 0"""
@@ -970,10 +1070,17 @@ class MultiheadAttention(nn.Module):
             q, k = _RopeFn.apply(q, k, query_index, key_index, self.pe.value, rope_tables)      # one launch per pass (csrc/rope.hip)
         elif rotary:
             q, k = self.rope(query_index, key_index, q, k)
+        drop_active = self.training and self.dropout > 0.
         if (FUSED_MULTIHEAD and (self.num_heads > 1 or self.head_dim > 16) and q.is_cuda and q.dtype == torch.float32
-                and not (self.training and self.dropout > 0.)):
+                and (not drop_active or (FUSED_ATTN_DROPOUT and self.dropout < 1.))):
             from asac_amd import native
-            if native.attention_mh_supported(q_len, k_len, self.num_heads, self.head_dim):
+            draws = None
+            supported = native.attention_mh_supported(q_len, k_len, self.num_heads, self.head_dim)
+            if supported and drop_active:
+                # the weights' dropout inside the core's launches; None: this call runs the module code below
+                draws = self._dropout_draws(q.device, bsz)
+                supported = draws is not None
+            if supported:
                 # several heads (or one wide head): scores, mask, softmax, weighted sum and the head average as one MFMA launch (csrc/attn_mh.hip)
                 m = attn_mask
                 if key_padding_mask is not None:
@@ -1001,6 +1108,8 @@ class MultiheadAttention(nn.Module):
                                                                                (lo.weight, lo.bias))
                 elif fused_qkv is not None:
                     out, weights, keep, keep_rows = _QkvAttnMhFn.apply(key, q_len, *fused_qkv, m, self.num_heads, rz)
+                elif draws is not None:
+                    out, weights, keep, keep_rows = _AttnMhDropFn.apply(q, k, v, m, self.num_heads, rz, draws)
                 else:
                     out, weights, keep, keep_rows = _AttnMhFn.apply(q, k, v, m, self.num_heads, rz)
                 scale = keep_rows if rz is not None else (keep if m is not None else None)

@@ -46,6 +46,27 @@ __device__ __forceinline__ bool finish_arrive(unsigned int* counter, unsigned in
 }
 __device__ __forceinline__ bool finish_arrive(unsigned int* counter) { return finish_arrive(counter, gridDim.x); }
 
+// two-level arrival, for launches of many short workgroups that publish NOTHING and only need to know who is last (the draw
+// counter of asac_dropout.h: a workgroup's part is a LOAD it has already waited for).  Arrivals at one word are served one
+// after the other by the memory side (about 30 ns each, csrc/image.hip) — and so are arrivals at different words of one
+// 128-byte line — so workgroup g arrives at leaf word g % n_leaves (n_leaves a power of two; the words `leaf_stride` uint32
+// apart: 32 or more puts each in a line of its own); the last one at a leaf resets it and arrives at the root; the last one
+// there resets the root.
+// Called by ONE lane of the workgroup, behind its own wait; true in the launch's last arriver.  Both levels end a launch
+// zero, as above, and nothing waits for another workgroup.
+__device__ __forceinline__ bool finish_arrive_two_level(unsigned int* leaves, unsigned int n_leaves, unsigned int leaf_stride,
+                                                        unsigned int* root) {
+    const unsigned int nb = gridDim.x, leaf = blockIdx.x & (n_leaves - 1);
+    const unsigned int at_leaf = nb / n_leaves + (leaf < (nb & (n_leaves - 1)) ? 1u : 0u);      // workgroups g < nb with g % n_leaves == leaf
+    unsigned int* const mine = leaves + leaf * leaf_stride;
+    if (__hip_atomic_fetch_add(mine, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != at_leaf - 1) return false;
+    finish_reset(mine);
+    const unsigned int used_leaves = nb < n_leaves ? nb : n_leaves;
+    if (__hip_atomic_fetch_add(root, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != used_leaves - 1) return false;
+    finish_reset(root);
+    return true;
+}
+
 // collect: base[0] + base[stride] + .. + base[(count - 1) * stride], added in that order by the calling lane; sixteen loads
 // requested at a time (one by one, each add waits for its own trip to memory; indices beyond `count` re-read the last slot: a
 // valid address, the value is not added)

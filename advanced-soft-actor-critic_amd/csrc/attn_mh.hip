@@ -13,7 +13,21 @@
 // Backward: dP = V dO^T (same shape as S), dS = P (dP - sum_keys P dP), dQ = K^T dS, and the two products over the QUERIES
 // (dV = P dO, dK = dS Q) with P / dS turned through LDS.  "Dead" rows (every key blocked) attend unmasked and report
 // keep = 0, as csrc/attn.hip and the reference do.
+//
+// Dropout of the attention weights (template parameter DROP, plain core only: `asac_attention_mh_dropout_forward / _backward`).
+// Those plugins build their blocks with dropout 0.005 / 0.01 and the reference never leaves training mode, so
+// `F.dropout(weights, p)` between the softmax and the product with V (seq_layers.py:269-274) is live in every pass:
+//   Pd = P (.) M s,  O = V^T Pd,  returned weights = mean_h(Pd) keep;   s = float32(1 / (1 - p))
+//   backward: dPd = V dO^T + (keep / H) g_w,  dP = dPd (.) M s,  dS = P (dP - sum_keys P dP) with the UNDROPPED P that p_heads
+//   saves,  dV = Pd dO  —  so the two turned tiles hold different things: the dV tile Pd, the dK tile dS.
+// M is never stored: entry (b, h, i, j) is a function of (seed, instance id, call counter, b, h, i, j) alone (asac_dropout.h;
+// one Philox block = the four keys a lane holds in one f32x4), not of the grid, of which wave walks the head or of NT.  The call
+// counter is device state of the module instance: every workgroup reads it once, workgroup 0 records it in `used`, the last
+// arriver of a two-level arrival (asac_ordered_finish.h; nothing polls) advances it — a captured launch draws afresh on every
+// replay — and the backward reads `used` through the pointer.  The DROP = false instantiations keep their code (same
+// registers, LDS and occupancy as before the parameter existed: NOTES.md, "Attention dropout").
 #include "asac_common.h"
+#include "asac_dropout.h"
 #include "asac_gelu.h"
 
 #include <cmath>
@@ -76,6 +90,10 @@ struct Args {
     const float* gy; const float* scale_in;   // gradient of y [B][Lq][E] (strides gy_sb, gy_st); the forward's keep_rows [B][Lq] or NULL
     int64_t gy_sb, gy_st;
     float* gpre; float* gx;                   // gradient of `pre` [B][Lq][E] and of the block's input [B][Lk][E]
+    // attention-weight dropout (DROP; the contract of asac_dropout.h)
+    uint64_t seed; uint32_t instance, thr; float drop_scale; int32_t advance;
+    int64_t* drop_state;                      // forward: the module instance's draw state (counter + arrival words)
+    int64_t* used;                            // forward: <- the call counter it drew with; backward: that record, read
 };
 
 // 16 bytes of channels [c0, c0 + 4) of a row, zero beyond d (and for rows beyond the window)
@@ -91,8 +109,13 @@ __device__ __forceinline__ f32x4 row4(const float* base, bool live, int c0, int 
 // PEC > 0 (forward, one tile a side, E = 16 PEC): the q / k / v projections of the block's input run in front of the scores — the
 // input tile is the B operand of 3 E / 16 weight tiles dealt over the waves (the arithmetic of csrc/rows_proj.hip), the results
 // go to LDS for this launch and to q / k / v for the backward: one launch less per block pass (10 of ~25 us).
-template <bool BWD, int NT, int PEC = 0>
+// DROP (plain core only): dropout of the softmax weights, Pd = P (.) M s.  The mask M is never stored: entry (b, h, i, j) is
+// word j & 3 of Philox block ((b H + h) 32 + i) 8 + (j >> 2) of the call — the four keys a lane holds in one f32x4 are one
+// block — so the backward regenerates it from the counter its forward left in `used`.  The forward's counter exchange is
+// done by lane 0 of the LAST wave (the one with the fewest heads), its trips beside the other waves' products.
+template <bool BWD, int NT, int PEC = 0, bool DROP = false>
 __global__ void __launch_bounds__(kThreads) k_attn_mh(const Args a) {
+    static_assert(!DROP || PEC == 0, "dropout: the plain core only");
     // per wave: P and dS tiles turned for the products over the queries; rows of 16 at a pitch of kTP = 20 floats: the four
     // lane quarters of a store then fall into four different 16-bank groups, rows stay 16-byte aligned for the b128 reads
     __shared__ float s_t[kWaves][2 * NT * NT][16 * kTP];
@@ -101,6 +124,19 @@ __global__ void __launch_bounds__(kThreads) k_attn_mh(const Args a) {
     const int Lq = a.Lq, Lk = a.Lk, H = a.H, d = a.d, E = H * d;
     const int QT = (Lq + 15) >> 4, KT = (Lk + 15) >> 4, CT = (d + 15) >> 4;
     const float scale = 1.f / sqrtf((float)d);
+    __shared__ uint32_t s_ctr[2];
+    DropDraw draw{};
+    if constexpr (DROP) {
+        draw.seed = a.seed, draw.instance = a.instance, draw.thr = a.thr, draw.scale = a.drop_scale;
+        if constexpr (BWD) draw.counter = (uint64_t)*a.used;
+        else if (threadIdx.x == kThreads - 64) draw.counter = (uint64_t)dropout_counter_load(a.drop_state);      // (in flight over the mask's loads)
+    }
+    // the factors (0 or s) of tile (km, qn) of head h as this lane holds it: keys 16 km + 4 qq + r of query 16 qn + x
+    auto drop4 = [&](int h, int km, int qn) {
+        float f[4];
+        dropout_factors4(draw, ((uint32_t)(b * H + h) * 32u + (uint32_t)(16 * qn + x)) * 8u + (uint32_t)(4 * km + qq), f);
+        return (f32x4){f[0], f[1], f[2], f[3]};
+    };
     constexpr int kPP = 16 * (PEC > 0 ? PEC : 1) + 4;      // LDS row pitch of the projected rows (conflict-free 16-byte reads)
     constexpr bool kF = PEC > 0 && !BWD, kB = PEC > 0 && BWD;
     __shared__ __attribute__((aligned(16))) float s_qkv[kF ? 3 : 1][kF ? 16 : 1][kF ? kPP : 4];
@@ -168,6 +204,14 @@ __global__ void __launch_bounds__(kThreads) k_attn_mh(const Args a) {
     for (int km = 0; km < NT; ++km)
 #pragma unroll
         for (int qn = 0; qn < NT; ++qn) wsum[km][qn] = zero4();
+    if constexpr (DROP && !BWD) {
+        if (threadIdx.x == kThreads - 64) s_ctr[0] = (uint32_t)draw.counter, s_ctr[1] = (uint32_t)(draw.counter >> 32);
+        __syncthreads();
+        draw.counter = ((uint64_t)s_ctr[1] << 32) | s_ctr[0];
+        // the arrival: its trips to memory run beside the other waves' products (this wave, which waits for the answers, is the
+        // one with the fewest heads)
+        if (threadIdx.x == kThreads - 64) dropout_counter_arrive(a.drop_state, a.used, (int64_t)draw.counter, a.advance != 0);
+    }
     float* tbuf = &s_t[wv][0][0];
     const float* gob = BWD ? a.g_out + (int64_t)b * Lq * E : nullptr;
     int GP = E;                                             // row pitch of the core's output gradient
@@ -258,7 +302,7 @@ __global__ void __launch_bounds__(kThreads) k_attn_mh(const Args a) {
 #pragma unroll
                 for (int km = 0; km < NT; ++km) {
                     P[km][qn] *= inv;
-                    wsum[km][qn] += P[km][qn];
+                    if constexpr (!DROP) wsum[km][qn] += P[km][qn];
                 }
                 if (a.p_heads) {
                     const int qi = 16 * qn + x;
@@ -269,6 +313,14 @@ __global__ void __launch_bounds__(kThreads) k_attn_mh(const Args a) {
                             const int kj = 16 * km + 4 * qq + r;
                             if (qi < Lq && kj < Lk) a.p_heads[(((int64_t)b * H + h) * Lq + qi) * Lk + kj] = P[km][qn][r];
                         }
+                }
+                if constexpr (DROP) {
+                    // the UNDROPPED softmax is what the backward reads; the product with V and the returned weights take Pd
+#pragma unroll
+                    for (int km = 0; km < NT; ++km) {
+                        if (km < KT && qn < QT) P[km][qn] *= drop4(h, km, qn);
+                        wsum[km][qn] += P[km][qn];
+                    }
                 }
             }
             // ---- weighted sum of the values: O[c][query] = sum_keys V[key][c] P[key][query] ----------------------------
@@ -337,19 +389,27 @@ __global__ void __launch_bounds__(kThreads) k_attn_mh(const Args a) {
                         if (km < KT && qn < QT) dP[km][qn] = mfma4(va[km], go[qn], dP[km][qn]);
             }
             f32x4 dS[NT][NT];
+            f32x4 Pd[DROP ? NT : 1][DROP ? NT : 1];                     // DROP: the dropped weights (the dV tile); dP above is dPd
 #pragma unroll
             for (int qn = 0; qn < NT; ++qn) {
                 const int qi = 16 * qn + x;
                 const float kp = dead[qn] ? 0.f : 1.f / (float)H;       // weights returned = mean_h(P) * keep
                 float dot = 0.f;
 #pragma unroll
-                for (int km = 0; km < NT; ++km)
+                for (int km = 0; km < NT; ++km) {
+                    f32x4 f = zero4();
+                    if constexpr (DROP) {
+                        if (km < KT && qn < QT) f = drop4(h, km, qn);
+                        Pd[km][qn] = P[km][qn] * f;
+                    }
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int kj = 16 * km + 4 * qq + r;
                         if (a.g_w && qi < Lq && kj < Lk) dP[km][qn][r] += kp * a.g_w[((int64_t)b * Lq + qi) * Lk + kj];
+                        if constexpr (DROP) dP[km][qn][r] *= f[r];      // dP = dPd (.) M s
                         dot += P[km][qn][r] * dP[km][qn][r];
                     }
+                }
                 dot = sum_over_q(dot);
 #pragma unroll
                 for (int km = 0; km < NT; ++km)
@@ -394,7 +454,9 @@ __global__ void __launch_bounds__(kThreads) k_attn_mh(const Args a) {
                 for (int qn = 0; qn < NT; ++qn)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        tbuf[((km * NT + qn) * 16 * kTP) + (4 * qq + r) * kTP + tpos(x)] = P[km][qn][r];
+                        // (the dV tile: the weights the forward multiplied V with)
+                        if constexpr (DROP) tbuf[((km * NT + qn) * 16 * kTP) + (4 * qq + r) * kTP + tpos(x)] = Pd[km][qn][r];
+                        else tbuf[((km * NT + qn) * 16 * kTP) + (4 * qq + r) * kTP + tpos(x)] = P[km][qn][r];
                         tbuf[((NT * NT + km * NT + qn) * 16 * kTP) + (4 * qq + r) * kTP + tpos(x)] = dS[km][qn][r];
                     }
             wave_sync();
@@ -642,6 +704,56 @@ int asac_attention_mh_backward(const float* q, const float* k, const float* v, c
     a.p_heads = const_cast<float*>(p_heads), a.g_out = grad_out, a.g_w = grad_weights, a.g_q = grad_q, a.g_k = grad_k, a.g_v = grad_v;
     launch<true>(a, as_stream(stream));
     return finish_launch("asac_attention_mh_backward");
+}
+
+// the draws' host checks: thr = floor(p 2^32) >= 1 and scale = float32(1 / (1 - p)) >= 1, finite, are what a p in (0, 1) gives;
+// the Philox block index of asac_dropout.h holds B * heads <= 2^24
+static bool drop_args_ok(int B, int heads, uint32_t thr, float scale) {
+    return thr >= 1u && scale >= 1.f && std::isfinite(scale) && (int64_t)B * heads <= ((int64_t)1 << 24);
+}
+
+int asac_attention_mh_dropout_forward(const float* q, const float* k, const float* v, const uint8_t* mask, int64_t mask_stride_b,
+                                      int64_t mask_stride_q, int64_t mask_stride_k, int B, int Lq, int Lk, int heads, int head_dim,
+                                      float* out, float* weights, float* keep, float* p_heads, const uint8_t* row_zero,
+                                      float* keep_rows, uint32_t thr, float scale, uint64_t seed, uint32_t instance,
+                                      int64_t* state, int64_t* used, void* stream) {
+    if (!q || !k || !v || !out || !weights || !keep || !state || !used || B <= 0 ||
+        !asac_attention_mh_supported(Lq, Lk, heads, head_dim) || !drop_args_ok(B, heads, thr, scale))
+        return bad_arg("asac_attention_mh_dropout_forward");
+    Args a{};
+    a.q = q, a.k = k, a.v = v, a.mask = mask, a.m_sb = mask_stride_b, a.m_si = mask_stride_q, a.m_sj = mask_stride_k;
+    a.B = B, a.Lq = Lq, a.Lk = Lk, a.H = heads, a.d = head_dim, a.out = out, a.w_avg = weights, a.keep = keep, a.p_heads = p_heads;
+    a.row_zero = row_zero, a.rz_sb = Lq, a.keep_rows = keep_rows;
+    a.seed = seed, a.instance = instance, a.thr = thr, a.drop_scale = scale, a.drop_state = state, a.used = used;
+    const dim3 grid((unsigned)B);
+    const bool one = Lq <= 16 && Lk <= 16;
+    // under the measurement repeat knob only the last repetition advances the counter: all of them draw alike
+    for (int rep = 0; rep < g_launch_repeat; ++rep) {
+        a.advance = rep == g_launch_repeat - 1;
+        if (one) hipLaunchKernelGGL((k_attn_mh<false, 1, 0, true>), grid, dim3(kThreads), 0, as_stream(stream), a);
+        else hipLaunchKernelGGL((k_attn_mh<false, 2, 0, true>), grid, dim3(kThreads), 0, as_stream(stream), a);
+    }
+    return finish_launch("asac_attention_mh_dropout_forward");
+}
+
+int asac_attention_mh_dropout_backward(const float* q, const float* k, const float* v, const uint8_t* mask, int64_t mask_stride_b,
+                                       int64_t mask_stride_q, int64_t mask_stride_k, int B, int Lq, int Lk, int heads, int head_dim,
+                                       const float* p_heads, const float* grad_out, const float* grad_weights, float* grad_q,
+                                       float* grad_k, float* grad_v, uint32_t thr, float scale, uint64_t seed, uint32_t instance,
+                                       const int64_t* used, void* stream) {
+    if (!q || !k || !v || !p_heads || !grad_out || !grad_q || !grad_k || !grad_v || !used || B <= 0 ||
+        !asac_attention_mh_supported(Lq, Lk, heads, head_dim) || !drop_args_ok(B, heads, thr, scale))
+        return bad_arg("asac_attention_mh_dropout_backward");
+    Args a{};
+    a.q = q, a.k = k, a.v = v, a.mask = mask, a.m_sb = mask_stride_b, a.m_si = mask_stride_q, a.m_sj = mask_stride_k;
+    a.B = B, a.Lq = Lq, a.Lk = Lk, a.H = heads, a.d = head_dim;
+    a.p_heads = const_cast<float*>(p_heads), a.g_out = grad_out, a.g_w = grad_weights, a.g_q = grad_q, a.g_k = grad_k, a.g_v = grad_v;
+    a.seed = seed, a.instance = instance, a.thr = thr, a.drop_scale = scale, a.used = const_cast<int64_t*>(used);
+    const dim3 grid((unsigned)B);
+    hipStream_t s = as_stream(stream);
+    if (Lq <= 16 && Lk <= 16) ASAC_LAUNCH((k_attn_mh<true, 1, 0, true>), grid, dim3(kThreads), 0, s, a);
+    else ASAC_LAUNCH((k_attn_mh<true, 2, 0, true>), grid, dim3(kThreads), 0, s, a);
+    return finish_launch("asac_attention_mh_dropout_backward");
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@ runtime bundled with PyTorch-ROCm), which is what lets these kernels run on torc
 torch-allocated HBM, and inside torch-captured hipGraphs.
 """
 import ctypes as C
+import math
 from pathlib import Path
 
 import torch  # noqa: F401  (must precede the dlopen below, see module docstring)
@@ -554,6 +555,14 @@ _SIGNATURES = {
     'asac_attention_mh_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_attention_mh_dropout_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint64,
+                                                    C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_attention_mh_dropout_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint64,
+                                                     C.c_uint32, C.c_void_p, C.c_void_p]),
     'asac_rows_proj_supported': (C.c_int, [C.c_int]),
     'asac_rows_proj_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -2668,6 +2677,65 @@ def attention_mh_backward(q, k, v, mask, heads, p_heads, grad_out, grad_weights,
     _check(load().asac_attention_mh_backward(_p(q), _p(k), _p(v), pm, sb, si, sj, B, Lq, Lk, heads, E // heads, _p(p_heads),
                                              _p(grad_out), _p(grad_weights), _p(grad_q), _p(grad_k), _p(grad_v), _stream()),
            'asac_attention_mh_backward')
+
+
+# attention-weight dropout inside those launches (csrc/asac_dropout.h)
+ATTN_DROPOUT_STATE_WORDS = 544      # int64: [0] the call counter, [16] the root arrival word, [32 + 16 g] leaf arrival word g < 32
+ATTN_DROPOUT_MAX_BATCH_HEADS = 1 << 24
+
+
+def dropout_threshold(p: float) -> int:
+    """floor(p * 2^32) in float64: an element is DROPPED iff its 32-bit Philox word is below it"""
+    return int(math.floor(float(p) * 4294967296.0))
+
+
+def dropout_scale(p: float) -> float:
+    """float32(1 / (1 - p)), the quotient formed in double precision (as ATen's dropout forms it)"""
+    return C.c_float(1.0 / (1.0 - float(p))).value
+
+
+def _drop_state_ok(state, used):
+    assert state.is_cuda and state.dtype == torch.int64 and state.is_contiguous() and state.numel() == ATTN_DROPOUT_STATE_WORDS
+    assert used.is_cuda and used.dtype == torch.int64 and used.numel() == 1 and used.device == state.device
+
+
+@_profiled
+def attention_mh_dropout_forward(q, k, v, mask, heads, out, weights, keep, p_heads, row_zero, keep_rows, p, seed, instance,
+                                 state, used):
+    """`attention_mh_forward` with dropout(p) of the softmax weights inside the launch; `state` int64 [544] (the instance's
+    call counter and arrival words), `used` int64 [1] <- the counter this call drew with"""
+    global _last_work
+    B, Lq, E = q.shape
+    Lk = k.shape[1]
+    _last_work = 4.0 * B * Lq * Lk * E
+    _dense_f32(q, k, v, out, weights, keep, p_heads)
+    _drop_state_ok(state, used)
+    pm, sb, si, sj = _mask3(mask, B)
+    if row_zero is not None:
+        assert row_zero.shape == (B, Lq) and row_zero.is_contiguous() and row_zero.element_size() == 1 and keep_rows is not None
+    _check(load().asac_attention_mh_dropout_forward(_p(q), _p(k), _p(v), pm, sb, si, sj, B, Lq, Lk, heads, E // heads, _p(out),
+                                                    _p(weights), _p(keep), _p(p_heads), _p(row_zero), _p(keep_rows),
+                                                    dropout_threshold(p), 1.0 / (1.0 - float(p)), int(seed) & (2 ** 64 - 1),
+                                                    int(instance) & 0xFFFFFFFF, _p(state), _p(used), _stream()),
+           'asac_attention_mh_dropout_forward')
+
+
+@_profiled
+def attention_mh_dropout_backward(q, k, v, mask, heads, p_heads, grad_out, grad_weights, grad_q, grad_k, grad_v, p, seed,
+                                  instance, used):
+    """the backward of `attention_mh_dropout_forward`: the mask is regenerated from the counter in `used` (read on the device)"""
+    global _last_work
+    B, Lq, E = q.shape
+    Lk = k.shape[1]
+    _last_work = 10.0 * B * Lq * Lk * E
+    _dense_f32(q, k, v, p_heads, grad_out, grad_weights, grad_q, grad_k, grad_v)
+    assert used.is_cuda and used.dtype == torch.int64 and used.numel() == 1
+    pm, sb, si, sj = _mask3(mask, B)
+    _check(load().asac_attention_mh_dropout_backward(_p(q), _p(k), _p(v), pm, sb, si, sj, B, Lq, Lk, heads, E // heads,
+                                                     _p(p_heads), _p(grad_out), _p(grad_weights), _p(grad_q), _p(grad_k),
+                                                     _p(grad_v), dropout_threshold(p), 1.0 / (1.0 - float(p)),
+                                                     int(seed) & (2 ** 64 - 1), int(instance) & 0xFFFFFFFF, _p(used), _stream()),
+           'asac_attention_mh_dropout_backward')
 
 
 # ------------------------------------------------------------------------------------------------

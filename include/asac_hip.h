@@ -1076,6 +1076,30 @@ int asac_attention_mh_backward(const float* q, const float* k, const float* v, c
                                const float* p_heads, const float* grad_out, const float* grad_weights, float* grad_q,
                                float* grad_k, float* grad_v, void* stream);
 
+/* The same core with DROPOUT of the softmax weights inside the launch (`nn.functional.dropout(weights, p)` between the softmax
+ * and the product with V, seq_layers.py:269-274, live whenever the module is in training mode):  Pd = P (.) M * scale,
+ * out = Pd V, weights = mean over the heads of Pd * keep;  backward dP = dPd (.) M * scale, dS from the UNDROPPED P (p_heads
+ * holds it, as above), grad_v from Pd.  The mask M is never stored.  Entry (b, h, i, j) is kept iff word j & 3 of
+ *   Philox4x32-10(counter = (((b * heads + h) * 32 + i) * 8 + (j >> 2), (5 << 28) | (instance & 0x0FFFFFFF), c lo, c hi), key = seed)
+ * is >= thr, c being the module instance's call counter (csrc/asac_dropout.h; tests/attn_dropout_ref.py restates it).
+ *   thr = floor(p * 2^32) >= 1 and scale = float32(1 / (1 - p)), both formed in float64 by the caller, p in (0, 1);
+ *   B * heads <= 2^24.
+ *   state: int64 [544] on the device, owned by the module instance, ZERO except [0] = the call counter before the first launch:
+ *   [16] and [32 + 16 g], g < 32, are arrival words (a 128-byte line each), which every launch leaves zero.  Every workgroup reads [0]; the last one to arrive
+ *   (csrc/asac_ordered_finish.h, two levels; nothing polls) stores [0] + 1, so a captured launch draws afresh on every
+ *   replay.  used: int64 [1] <- the counter this call drew with; the backward reads it THROUGH THE POINTER, so inside a
+ *   captured step it follows each replay's forward.  One state per concurrently running launch. */
+int asac_attention_mh_dropout_forward(const float* q, const float* k, const float* v, const uint8_t* mask, int64_t mask_stride_b,
+                                      int64_t mask_stride_q, int64_t mask_stride_k, int B, int Lq, int Lk, int heads, int head_dim,
+                                      float* out, float* weights, float* keep, float* p_heads, const uint8_t* row_zero,
+                                      float* keep_rows, uint32_t thr, float scale, uint64_t seed, uint32_t instance,
+                                      int64_t* state, int64_t* used, void* stream);
+int asac_attention_mh_dropout_backward(const float* q, const float* k, const float* v, const uint8_t* mask, int64_t mask_stride_b,
+                                       int64_t mask_stride_q, int64_t mask_stride_k, int B, int Lq, int Lk, int heads, int head_dim,
+                                       const float* p_heads, const float* grad_out, const float* grad_weights, float* grad_q,
+                                       float* grad_k, float* grad_v, uint32_t thr, float scale, uint64_t seed, uint32_t instance,
+                                       const int64_t* used, void* stream);
+
 /* asac_attention_mh_forward with the q / k / v projections of the block's input in front of the scores, in the same launch
  * (`self.q_proj(query), self.k_proj(key), self.v_proj(value)` with value = key and query = the last Lq positions of key,
  * seq_layers.py:239-333): x [B][Lk][E] with strides in floats (multiples of 4, 16-byte aligned), weights / biases = HOST arrays

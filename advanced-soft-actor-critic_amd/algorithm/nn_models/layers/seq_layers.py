@@ -202,6 +202,11 @@ FUSED_ROPE = True
 # the device from a counter the module instance owns and regenerated by the backward (csrc/asac_dropout.h)   (False: the
 # baddbmm / softmax / F.dropout / bmm chain of the module code — tests and tools/attn_dropout_bench.py)
 FUSED_ATTN_DROPOUT = True
+# the LIVE nn.Dropout modules inside the dense stacks around the core (`qkv_dense_depth=1`: ResBlock -> Dropout -> Linear three
+# times; `out_dense_depth=1`: ResBlock -> Dropout) inside one row launch per site and pass (csrc/rows_proj.hip), drawn like the
+# weights' dropout from a counter state the site owns   (False: the stacks module by module with ATen's dropout, which draws
+# from torch's generator — tests and tools/attn_dropout_bench.py --dense)
+FUSED_DENSE_DROPOUT = True
 
 
 class _AttnCoreFn(torch.autograd.Function):
@@ -488,6 +493,55 @@ class _QkvRopeRowsFn(torch.autograd.Function):
         return tuple(out)
 
 
+class _QkvDenseDropFn(torch.autograd.Function):
+    """`q_proj(x[:, -tail:]), k_proj(x), v_proj(x)` where each stack is ResBlock(E, E) -> LIVE nn.Dropout(p) -> nn.Linear(E, E),
+    as ONE MFMA launch per pass (`asac_rows_dense_proj_dropout_*`, csrc/rows_proj.hip).  `draws` = (p, seed, instance id, state,
+    used) of the module's 'qkv' site: the masks are drawn on the device and regenerated by the backward from the counter this
+    call's `used` holds.  `params`: (ResBlock weight, bias, Linear weight, bias) of q, k, v.  The twelve parameter gradients are
+    products over the rows (`asac_xty`): of the pre-activation gradients with x, of the output gradients with the dropped hidden
+    rows the forward wrote."""
+
+    @staticmethod
+    def forward(ctx, x, tail, draws, *params):
+        from asac_amd import native
+        p, seed, instance, state, used = draws
+        if x.stride(2) != 1 or (x.stride(0) | x.stride(1) | (x.data_ptr() >> 2)) & 3:
+            x = x.contiguous()
+        B, L, E = x.shape
+        tails = [tail, L, L]
+        new = lambda: [torch.empty(B, t, E, dtype=x.dtype, device=x.device) for t in tails]      # noqa: E731
+        outs, pres, hiddens = new(), new(), new()
+        pd = [t.detach() for t in params]
+        native.rows_dense_proj_dropout_forward(x, pd[0::4], pd[1::4], pd[2::4], pd[3::4], tails, outs, pres, hiddens, p, seed,
+                                               instance, state, used)
+        ctx.save_for_backward(x, used, *pres, *hiddens)
+        ctx.tail, ctx.params, ctx.draws = tail, params, (p, seed, instance)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, gq, gk, gv):
+        from asac_amd import native
+        x, used, *saved = ctx.saved_tensors
+        pres, hiddens = saved[:3], saved[3:]
+        B, L, E = x.shape
+        params, tails = ctx.params, [ctx.tail, L, L]
+        grads = [torch.zeros_like(pre) if g is None else g.contiguous() for g, pre in zip((gq, gk, gv), pres)]
+        gx = torch.empty(B, L, E, dtype=x.dtype, device=x.device)
+        gpres = [torch.empty_like(pre) for pre in pres]
+        native.rows_dense_proj_dropout_backward(grads, list(pres), tails, [t.detach() for t in params[0::4]],
+                                                [t.detach() for t in params[2::4]], gx, gpres, *ctx.draws, used)
+        x2 = x.reshape(-1, E)
+        xq2 = x2 if ctx.tail == L else x[:, -ctx.tail:].reshape(-1, E)
+        out, jobs = [gx if ctx.needs_input_grad[0] else None, None, None], []
+        for j, xin in enumerate((xq2, x2, x2)):
+            at = 3 + 4 * j
+            out.extend(_rows_param_grads(ctx.needs_input_grad[at:at + 2], params[4 * j:4 * j + 2], gpres[j].view(-1, E), xin, jobs))
+            out.extend(_rows_param_grads(ctx.needs_input_grad[at + 2:at + 4], params[4 * j + 2:4 * j + 4], grads[j].view(-1, E),
+                                         hiddens[j].view(-1, E), jobs))
+        _run_xty_jobs(jobs)
+        return tuple(out)
+
+
 class _RopeFn(torch.autograd.Function):
     """`self.rope(q_index, k_index, q, k)` as one launch per pass for both tensors (`asac_rope_*`, csrc/rope.hip)"""
 
@@ -708,6 +762,37 @@ class _OutResRowsFn(torch.autograd.Function):
         return gx.view(ctx.lead), gw, gb, None
 
 
+class _OutResDropRowsFn(torch.autograd.Function):
+    """`_OutResRowsFn` with the output stack's LIVE nn.Dropout(p) between the ResBlock and the row factor, inside both launches
+    (`asac_rows_resblock_dropout_*`): `dropout(x + gelu(linear(x))) * row_scale[..., None]`.  `draws`: the module's 'out' site,
+    as for `_QkvDenseDropFn`"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, row_scale, draws):
+        from asac_amd import native
+        p, seed, instance, state, used = draws
+        x2 = x.reshape(-1, x.shape[-1])
+        if x2.stride(1) != 1 or (x2.stride(0) | (x2.data_ptr() >> 2)) & 3:
+            x2 = x2.contiguous()
+        y, pre = torch.empty(x2.shape, dtype=x.dtype, device=x.device), torch.empty(x2.shape, dtype=x.dtype, device=x.device)
+        sc = None if row_scale is None else row_scale.reshape(-1).contiguous()
+        native.rows_resblock_dropout_forward(x2, weight.detach(), bias.detach(), sc, y, pre, p, seed, instance, state, used)
+        ctx.save_for_backward(x2, pre, used, *([sc] if sc is not None else []))
+        ctx.params, ctx.lead, ctx.draws = (weight, bias), x.shape, (p, seed, instance)
+        return y.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, gy):
+        from asac_amd import native
+        x2, pre, used, *rest = ctx.saved_tensors
+        weight, bias = ctx.params
+        gy2 = gy.reshape(x2.shape).contiguous()
+        gx, gpre = torch.empty_like(pre), torch.empty_like(pre)
+        native.rows_resblock_dropout_backward(gy2, pre, weight.detach(), rest[0] if rest else None, gx, gpre, *ctx.draws, used)
+        gw, gb = _rows_param_grads(ctx.needs_input_grad[1:3], ctx.params, gpre, x2)
+        return gx.view(ctx.lead), gw, gb, None, None
+
+
 class _OutResSavedFn(torch.autograd.Function):
     """`_OutResRowsFn` whose forward already ran (inside `asac_attention_mh_proj_forward`): y and pre are handed in, the
     backward is the same"""
@@ -859,16 +944,58 @@ def _is_tail_view(query, key):
 
 def _plain_resblock(ll, width):
     """the Linear of a `LinearLayers` stack that is exactly ONE residual GELU ResBlock width -> width, or None"""
-    from .linear_layers import ResBlock
     mods = [m for m in ll.dense if not (isinstance(m, nn.Dropout) and m.p == 0)]
-    if len(mods) != 1 or not isinstance(mods[0], ResBlock):
+    if len(mods) != 1 or not _fusable_resblock(mods[0], width):
         return None
-    rb = mods[0]
-    if not (rb.residual and type(rb.act) is nn.GELU and getattr(rb.act, 'approximate', 'none') == 'none'
-            and rb.linear.bias is not None and rb.linear.in_features == rb.linear.out_features == width
-            and _params_aligned16(rb.linear)):
+    return mods[0].linear
+
+
+def _live_dropout(mod) -> bool:
+    """an nn.Dropout that drops in this pass — the sub-module's OWN state, not the attention module's"""
+    return type(mod) is nn.Dropout and mod.training and 0. < mod.p < 1.
+
+
+def _fusable_resblock(rb, width) -> bool:
+    from .linear_layers import ResBlock
+    return (isinstance(rb, ResBlock) and rb.residual and type(rb.act) is nn.GELU
+            and getattr(rb.act, 'approximate', 'none') == 'none' and rb.linear.bias is not None
+            and rb.linear.in_features == rb.linear.out_features == width and _params_aligned16(rb.linear))
+
+
+def _dropout_resblock(ll, width):
+    """(the ResBlock's Linear, the nn.Dropout) of a `LinearLayers` stack that is exactly ONE residual exact-GELU ResBlock
+    width -> width and ONE LIVE nn.Dropout, or None"""
+    mods = list(ll.dense)
+    if len(mods) == 2 and _fusable_resblock(mods[0], width) and _live_dropout(mods[1]):
+        return mods[0].linear, mods[1]
+    return None
+
+
+def _dropout_dense_stack(ll, width):
+    """(the ResBlock's Linear, the nn.Dropout, the Linear) of a `LinearLayers` stack that is exactly ONE residual exact-GELU
+    ResBlock width -> width, ONE LIVE nn.Dropout and ONE nn.Linear width -> width with bias, or None"""
+    mods = list(ll.dense)
+    if (len(mods) == 3 and _fusable_resblock(mods[0], width) and _live_dropout(mods[1]) and type(mods[2]) is nn.Linear
+            and mods[2].bias is not None and mods[2].in_features == mods[2].out_features == width and _params_aligned16(mods[2])):
+        return mods[0].linear, mods[1], mods[2]
+    return None
+
+
+def _dense_qkv_ok(module, query, key):
+    """the three (ResBlock Linear, Dropout, Linear) of `module`'s q / k / v stacks for one `_QkvDenseDropFn` launch — the
+    envelope of `_rows_proj_ok` with `_dropout_dense_stack` in the place of `_plain_linear`, and one p — or None"""
+    if not (FUSED_DENSE_DROPOUT and FUSED_ROWS_PROJ and key.is_cuda):
         return None
-    return rb.linear
+    E = module.embed_dim
+    from asac_amd import native
+    if not native.rows_proj_supported(E):      # (first: the cheapest way out for the narrow toy plugins)
+        return None
+    if not (key.dtype == torch.float32 and key.dim() == 3 and key.stride(2) == 1 and (query is key or _is_tail_view(query, key))):
+        return None
+    stacks = [_dropout_dense_stack(ll, E) for ll in (module.q_proj, module.k_proj, module.v_proj)]
+    if any(s is None for s in stacks) or len({s[1].p for s in stacks}) != 1:
+        return None
+    return stacks
 
 
 def _params_aligned16(linear) -> bool:
@@ -927,16 +1054,60 @@ class MultiheadAttention(nn.Module):
         self._drop_counter0 = 0            # where a device first launched on later starts counting
         self._drop_states = {}             # device -> int64 [544]: the call counter and the arrival words
         self._drop_used = None             # int64 [1]: the counter the last dropout launch drew with
+        # the dense stacks' dropout launches ('qkv', 'out': seq_layers.FUSED_DENSE_DROPOUT) draw from the same (seed, instance
+        # id) under tags of their own, each site with a state and a `used` record of its own
+        self._dense_drop_states = {'qkv': {}, 'out': {}}
+        self._dense_drop_used = {'qkv': None, 'out': None}
 
     def reseed(self, seed: int, counter: int = 0, instance_id: int | None = None):
-        """the attention-weight dropout's draws are a function of (seed, instance id, call counter): re-seat all three"""
+        """the draws of the module's dropout launches (the attention weights', the dense stacks') are functions of (seed,
+        instance id, call counter): re-seat all three, in every state"""
         self._drop_seed = int(seed)
         if instance_id is not None:
             self._drop_instance = int(instance_id)
-        for state in self._drop_states.values():
-            state.copy_(torch.tensor([int(counter)] + [0] * (state.numel() - 1), dtype=torch.int64))
+        for states in (self._drop_states, *self._dense_drop_states.values()):
+            for state in states.values():
+                state.copy_(torch.tensor([int(counter)] + [0] * (state.numel() - 1), dtype=torch.int64))
         self._drop_counter0 = int(counter)
         return self
+
+    def dense_dropout_drawn(self, site: str) -> int:
+        """the call counter the last dense-stack dropout launch of `site` ('qkv' or 'out') drew with.  Synchronises."""
+        if self._dense_drop_used[site] is None:
+            raise RuntimeError(f'no {site} dropout launch yet')
+        return int(self._dense_drop_used[site].item())
+
+    def dense_dropout_state(self, site: str, device=None):
+        """`dropout_state` of the dense-stack dropout launch of `site` ('qkv' or 'out')"""
+        states = self._dense_drop_states[site]
+        if not states:
+            return None
+        state = states[device] if device is not None else next(iter(states.values()))
+        return int(state[0].item()), int(torch.count_nonzero(state[1:]).item())
+
+    def _new_drop_state(self, device):
+        """a draw state on `device` (the stream is not capturing); takes the instance id and the seed if nobody has yet"""
+        from asac_amd import native
+        if self._drop_instance is None:
+            from algorithm.utils.image_transforms import _instance_ids
+            self._drop_instance = next(_instance_ids)
+        if self._drop_seed is None:
+            self._drop_seed = torch.initial_seed()
+        return torch.tensor([self._drop_counter0] + [0] * (native.ATTN_DROPOUT_STATE_WORDS - 1), dtype=torch.int64, device=device)
+
+    def _dense_dropout_draws(self, site, device, rows, p):
+        """(p, seed, instance id, state, used) of one dense-stack dropout launch of `site` over `rows` rows on `device`, or None
+        where the module code has to run — the rules of `_dropout_draws`; `used` is this CALL's record"""
+        if rows * self.embed_dim >= 1 << 34:
+            return None
+        states = self._dense_drop_states[site]
+        state = states.get(device)
+        if state is None:
+            if torch.cuda.is_current_stream_capturing():
+                return None
+            state = states[device] = self._new_drop_state(device)
+        used = self._dense_drop_used[site] = torch.empty(1, dtype=torch.int64, device=device)
+        return p, self._drop_seed, self._drop_instance, state, used
 
     def dropout_drawn(self) -> int:
         """the call counter the last dropout launch drew with.  Synchronises."""
@@ -964,14 +1135,7 @@ class MultiheadAttention(nn.Module):
         if state is None:
             if torch.cuda.is_current_stream_capturing():
                 return None
-            if self._drop_instance is None:
-                from algorithm.utils.image_transforms import _instance_ids
-                self._drop_instance = next(_instance_ids)
-            if self._drop_seed is None:
-                self._drop_seed = torch.initial_seed()
-            state = torch.tensor([self._drop_counter0] + [0] * (native.ATTN_DROPOUT_STATE_WORDS - 1), dtype=torch.int64,
-                                 device=device)
-            self._drop_states[device] = state
+            state = self._drop_states[device] = self._new_drop_state(device)
         self._drop_used = torch.empty(1, dtype=torch.int64, device=device)
         return self.dropout, self._drop_seed, self._drop_instance, state, self._drop_used
 
@@ -1046,7 +1210,17 @@ class MultiheadAttention(nn.Module):
         fused_qkv = None
         rotary = self.pe in (POSITIONAL_ENCODING.ROPE, POSITIONAL_ENCODING.ROPE2)
         rope_tables = _fused_rope_tables(self, query, key, query_index, key_index) if rotary else None
-        if (self.pe is None or self.pe is False or rope_tables is not None) and same_kv and _rows_proj_ok(self, query, key):
+        plain_or_rotary = self.pe is None or self.pe is False or rope_tables is not None
+        dense, dense_draws = (_dense_qkv_ok(self, query, key) if plain_or_rotary and same_kv else None), None
+        if dense is not None:
+            # None: this call runs the module code below
+            dense_draws = self._dense_dropout_draws('qkv', key.device, bsz * k_len, dense[0][1].p)
+        if dense_draws is not None:
+            # dense q / k / v stacks with their live nn.Dropout: one launch per pass (csrc/rows_proj.hip); a rotary encoding
+            # follows as the `_RopeFn` launch
+            q, k, v = _QkvDenseDropFn.apply(key, q_len, dense_draws,
+                                            *(t for r, _, lin in dense for t in (r.weight, r.bias, lin.weight, lin.bias)))
+        elif plain_or_rotary and same_kv and _rows_proj_ok(self, query, key):
             qkv_params = [t for ll in (self.q_proj, self.k_proj, self.v_proj) for t in (_plain_linear(ll).weight, _plain_linear(ll).bias)]
             from asac_amd import native
             if rotary:
@@ -1096,6 +1270,12 @@ class MultiheadAttention(nn.Module):
                     rz = rz.reshape(-1, rz.shape[-1])
                     rz = rz if rz.dtype in (torch.bool, torch.uint8) else rz != 0
                 lo = _plain_resblock(self.out_proj, self.embed_dim) if FUSED_ROWS_PROJ else None
+                # an output stack with a LIVE nn.Dropout behind its ResBlock: the drop inside the ResBlock launch
+                lod = _dropout_resblock(self.out_proj, self.embed_dim) \
+                    if lo is None and FUSED_ROWS_PROJ and FUSED_DENSE_DROPOUT and native.rows_proj_supported(self.embed_dim) else None
+                out_draws = None
+                if lod is not None:
+                    out_draws = self._dense_dropout_draws('out', q.device, bsz * q_len, lod[1].p)
                 y_pre = None
                 block_done = False
                 if fused_qkv is not None and lo is not None and FUSED_BLOCK_BACKWARD:
@@ -1120,6 +1300,9 @@ class MultiheadAttention(nn.Module):
                 elif lo is not None and native.rows_proj_supported(self.embed_dim):
                     # the output ResBlock and the dead-row / padded-row factor: one launch
                     out = _OutResRowsFn.apply(out, lo.weight, lo.bias, scale)
+                elif out_draws is not None:
+                    # ... with the stack's live nn.Dropout between the ResBlock and the factor: still one launch
+                    out = _OutResDropRowsFn.apply(out, lod[0].weight, lod[0].bias, scale, out_draws)
                 else:
                     out = self.out_proj(out)
                     if scale is not None:

@@ -9,7 +9,12 @@
 //   element e      block index e >> 2, word e & 3;  KEPT iff word >= thr
 //   thr            floor(p * 2^32), formed in float64 on the host  (P(dropped) = thr / 2^32; p in (0, 1) -> thr < 2^32)
 //   kept elements are multiplied by s = float32(1 / (1 - p)), the quotient formed in double precision (ATen's `dropout`)
-// Tags 0..4 of the second word belong to csrc/image.hip; the instance ids come from the one counter of
+// Tags 0..4 of the second word belong to csrc/image.hip, 5 (kDropTag, dropout_factors4 below) to the attention weights of
+// csrc/attn_mh.hip, 6..9 to the dense stacks of csrc/rows_proj.hip (its row_factors4): there element (row r, feature f) of a
+// [rows][E] tensor uses block index r * (E / 4) + (f >> 2), word f & 3 — 6 / 7 / 8 the q / k / v stack with r = b * L + t, the
+// position in the FULL window (a draw does not depend on how many newest positions a job covers), 9 the output block with r
+// the flat row; rows * E < 2^34.  Every drawing launch SITE owns a state (one state per concurrently running launch).
+// tests/dense_dropout_ref.py restates that layout.  The instance ids come from the one counter of
 // algorithm/utils/image_transforms.py, so no two modules of a process share a stream.
 // tests/attn_dropout_ref.py restates this in NumPy.
 //

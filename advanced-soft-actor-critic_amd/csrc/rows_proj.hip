@@ -16,6 +16,7 @@
 // 16 bytes, backward four strided words of a weight column; the result tile holds four consecutive features of a row per
 // lane -> 16-byte stores.  Everything is L2-resident (weights 16 KB a matrix); the launches are latency, not bandwidth.
 #include "asac_common.h"
+#include "asac_dropout.h"
 #include "asac_gelu.h"
 #include "asac_rope.h"
 
@@ -53,6 +54,45 @@ struct ProjArgs {
     float* gu[2];                            // backward: the un-rotated gradients of jobs 0 and 1, dense like g
 };
 
+// The draws of the `nn.Dropout` modules inside the dense stacks (the contract of asac_dropout.h): element (row r, feature f)
+// is word f & 3 of Philox block r * (E / 4) + (f >> 2) — the four features a lane holds in one f32x4 are one block — under
+// a tag of its own in the second counter word: 6 / 7 / 8 the q / k / v stack (r = b * L + t, the position in the FULL window:
+// a draw does not depend on `tail`), 9 the output block (r the flat row).  Each launch owns a state (counter and arrival
+// words) of the layout of asac_dropout.h; the backward reads the counter its forward left in `used`.
+constexpr uint32_t kTagQkv = 6u, kTagOut = 9u;
+
+struct DrawArgs {
+    uint64_t seed; uint32_t instance, thr; float scale; int32_t advance;
+    int64_t* state;                          // forward: the launch site's draw state
+    int64_t* used;                           // forward: <- the counter drawn with; backward: read
+    __device__ __forceinline__ DropDraw draw() const { return DropDraw{seed, 0, instance, thr, scale}; }
+};
+
+__device__ __forceinline__ f32x4 row_factors4(const DropDraw& d, uint32_t tag, uint32_t block) {
+    const Philox p = philox4x32_10(block, (tag << 28) | (d.instance & 0x0FFFFFFFu), (uint32_t)d.counter,
+                                   (uint32_t)(d.counter >> 32), (uint32_t)d.seed, (uint32_t)(d.seed >> 32));
+    f32x4 f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) f[r] = p.c[r] >= d.thr ? d.scale : 0.f;
+    return f;
+}
+
+// the forward's counter exchange, by lane 0 of the LAST wave (the one with the fewest feature tiles): the load is issued first
+// thing, so that it is in flight over the work that stands between draw_begin and draw_share ...
+__device__ __forceinline__ DropDraw draw_begin(const DrawArgs& d) {
+    DropDraw draw = d.draw();
+    if (threadIdx.x == kThreads - 64) draw.counter = (uint64_t)dropout_counter_load(d.state);
+    return draw;
+}
+// ... the value reaches the other waves through LDS (a workgroup barrier), and the arrival's trips run beside their products
+__device__ __forceinline__ void draw_share(const DrawArgs& d, DropDraw& draw) {
+    __shared__ uint32_t s_ctr[2];
+    if (threadIdx.x == kThreads - 64) s_ctr[0] = (uint32_t)draw.counter, s_ctr[1] = (uint32_t)(draw.counter >> 32);
+    __syncthreads();
+    draw.counter = ((uint64_t)s_ctr[1] << 32) | s_ctr[0];
+    if (threadIdx.x == kThreads - 64) dropout_counter_arrive(d.state, d.used, (int64_t)draw.counter, d.advance != 0);
+}
+
 struct ResArgs {
     const float* x; int64_t xs;              // [rows][E], row stride xs
     const float* w; const float* b;
@@ -60,6 +100,21 @@ struct ResArgs {
     int64_t rows;
     float* y; float* pre;                    // [rows][E]
     const float* gy; float* gx; float* gpre;
+    DrawArgs d;                              // DROP
+};
+
+// the <= 3 dense stacks of one input: ResBlock(E, E) -> nn.Dropout(p) -> nn.Linear(E, E) each
+struct DenseArgs {
+    const float* x; int64_t xs_b, xs_t;      // input rows x[b][t][E] (feature stride 1)
+    int32_t B, L, J;
+    const float* w1[kMaxJobs]; const float* b1[kMaxJobs];      // the ResBlock's Linear
+    const float* w2[kMaxJobs]; const float* b2[kMaxJobs];      // the Linear behind the dropout
+    int32_t tail[kMaxJobs];                  // job j covers positions t >= L - tail[j]; its rows are dense [B][tail[j]][E]
+    float* y[kMaxJobs]; float* pre[kMaxJobs]; float* h[kMaxJobs];
+    const float* g[kMaxJobs];                // backward: gradients of y
+    float* gx;                               // [B][L][E] dense
+    float* gpre[kMaxJobs];
+    DrawArgs d;
 };
 
 // four strided words of a weight column block: W[n0 + s][k] for s < 4
@@ -195,10 +250,15 @@ __global__ void __launch_bounds__(kThreads) k_rows_proj_bwd(const ProjArgs a) {
     }
 }
 
-template <int EC>
+// DROP: dropout behind the ResBlock, y = (x + gelu(x W^T + b)) (.) M s * row_scale — the `nn.Dropout` of the output stack
+// (draws: row_factors4, tag kTagOut, r the flat row).  The counter exchange is done by lane 0 of the last wave, its load in
+// flight beside the rows' loads.  The DROP = false instantiations keep their code.
+template <int EC, bool DROP = false>
 __global__ void __launch_bounds__(kThreads) k_rows_res_fwd(const ResArgs a) {
     constexpr int E = 16 * EC;
     const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, q = l >> 4, x = l & 15;
+    DropDraw draw{};
+    if constexpr (DROP) draw = draw_begin(a.d);
     const int64_t row = (int64_t)blockIdx.x * 16 + x;
     const bool live = row < a.rows;
     const int64_t rc = live ? row : a.rows - 1;
@@ -207,6 +267,7 @@ __global__ void __launch_bounds__(kThreads) k_rows_res_fwd(const ResArgs a) {
 #pragma unroll
     for (int c = 0; c < EC; ++c) xv[c] = ld4(xp + 16 * c);
     const float s = a.scale ? a.scale[rc] : 1.f;
+    if constexpr (DROP) draw_share(a.d, draw);
     for (int nt = wv; nt < EC; nt += kWaves) {
         const float* wp = a.w + (16 * nt + x) * E + 4 * q;
         f32x4 wa[EC];
@@ -218,8 +279,14 @@ __global__ void __launch_bounds__(kThreads) k_rows_res_fwd(const ResArgs a) {
         for (int c = 0; c < EC; ++c) acc = mfma4(wa[c], xv[c], acc);
         acc += bias;
         f32x4 y;
+        if constexpr (DROP) {
+            const f32x4 f = row_factors4(draw, kTagOut, (uint32_t)rc * (uint32_t)(E / 4) + (uint32_t)(4 * nt + q));
 #pragma unroll
-        for (int r = 0; r < 4; ++r) y[r] = (gelu_f(acc[r]) + res[r]) * s;
+            for (int r = 0; r < 4; ++r) y[r] = (gelu_f(acc[r]) + res[r]) * f[r] * s;
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) y[r] = (gelu_f(acc[r]) + res[r]) * s;
+        }
         if (live) {
             st4(a.y + row * E + 16 * nt + 4 * q, y);
             st4(a.pre + row * E + 16 * nt + 4 * q, acc);
@@ -228,7 +295,8 @@ __global__ void __launch_bounds__(kThreads) k_rows_res_fwd(const ResArgs a) {
 }
 
 // g = gy * scale;  gpre = g * gelu'(pre);  gx = g + gpre W
-template <int EC>
+// (DROP: g = gy * scale (.) M s, the mask regenerated from the counter the forward left in `used`)
+template <int EC, bool DROP = false>
 __global__ void __launch_bounds__(kThreads) k_rows_res_bwd(const ResArgs a) {
     constexpr int E = 16 * EC;
     const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, q = l >> 4, x = l & 15;
@@ -238,10 +306,15 @@ __global__ void __launch_bounds__(kThreads) k_rows_res_bwd(const ResArgs a) {
     const float s = a.scale ? a.scale[rc] : 1.f;
     const float* gyp = a.gy + rc * E + 4 * q;
     const float* prp = a.pre + rc * E + 4 * q;
+    DropDraw draw{};
+    if constexpr (DROP) draw = a.d.draw(), draw.counter = (uint64_t)*a.d.used;
+    const uint32_t blk = (uint32_t)rc * (uint32_t)(E / 4) + (uint32_t)q;
     f32x4 gp[EC];
 #pragma unroll
     for (int c = 0; c < EC; ++c) {
-        const f32x4 g = ld4(gyp + 16 * c) * s, z = ld4(prp + 16 * c);
+        f32x4 g = ld4(gyp + 16 * c) * s;
+        const f32x4 z = ld4(prp + 16 * c);
+        if constexpr (DROP) g *= row_factors4(draw, kTagOut, blk + (uint32_t)(4 * c));
 #pragma unroll
         for (int r = 0; r < 4; ++r) gp[c][r] = live ? g[r] * gelu_grad(z[r]) : 0.f;
         if (live && (c & (kWaves - 1)) == wv) st4(a.gpre + row * E + 16 * c + 4 * q, gp[c]);
@@ -250,7 +323,170 @@ __global__ void __launch_bounds__(kThreads) k_rows_res_bwd(const ResArgs a) {
         f32x4 acc = zero4();
 #pragma unroll
         for (int c = 0; c < EC; ++c) acc = mfma4(wcol4<E>(a.w, 16 * c + 4 * q, 16 * kt + x), gp[c], acc);
-        if (live) st4(a.gx + row * E + 16 * kt + 4 * q, ld4(gyp + 16 * kt) * s + acc);
+        f32x4 g = ld4(gyp + 16 * kt) * s;
+        if constexpr (DROP) g *= row_factors4(draw, kTagOut, blk + (uint32_t)(4 * kt));
+        if (live) st4(a.gx + row * E + 16 * kt + 4 * q, g + acc);
+    }
+}
+
+// The dense q / k / v stacks of one input, dropout included, as one launch:
+//   pre_j = x W1_j^T + b1_j;  h_j = (x + gelu(pre_j)) (.) M_j s;  out_j = h_j W2_j^T + b2_j     over the rows t >= L - tail[j]
+// A workgroup owns 16 rows and walks the jobs; wave w owns the feature tiles w, w + 4, ... of BOTH layers.  The dropped hidden
+// rows change owner between the layers — every wave needs all features of the 16 rows as its B operand — through LDS behind
+// ONE workgroup barrier: the first layer's sums of all jobs stay in registers until the call counter has come back (its load
+// is issued first thing), then the epilogues of all jobs, the barrier, and the second layers.  A job none of whose rows lie in
+// the workgroup's tile (the cut query) is skipped by all four waves alike.
+template <int EC>
+__global__ void __launch_bounds__(kThreads) k_rows_dense_drop_fwd(const DenseArgs a) {
+    constexpr int E = 16 * EC, TPW = (EC + kWaves - 1) / kWaves, PP = E + 4;      // (pitch E + 4: conflict-free 16-byte reads)
+    __shared__ __attribute__((aligned(16))) float s_h[kMaxJobs][16][PP];
+    const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, q = l >> 4, x = l & 15;
+    DropDraw draw = draw_begin(a.d);
+    const int64_t rows = (int64_t)a.B * a.L, row = (int64_t)blockIdx.x * 16 + x;
+    const bool live = row < rows;
+    const int64_t rc = live ? row : rows - 1;
+    const int b = (int)(rc / a.L), t = (int)(rc - (int64_t)b * a.L);
+    const float* xp = a.x + b * a.xs_b + t * a.xs_t + 4 * q;
+    f32x4 xv[EC];
+#pragma unroll
+    for (int c = 0; c < EC; ++c) xv[c] = live ? ld4(xp + 16 * c) : zero4();
+    bool on[kMaxJobs], any_on[kMaxJobs];
+    int64_t at[kMaxJobs];
+    f32x4 pre[kMaxJobs][TPW];
+#pragma unroll
+    for (int j = 0; j < kMaxJobs; ++j) {
+        on[j] = any_on[j] = false, at[j] = 0;
+        if (j >= a.J) continue;
+        const int skip = a.L - a.tail[j];
+        on[j] = live && t >= skip;
+        any_on[j] = __any(on[j]) != 0;                      // (every wave holds the same 16 rows: alike in all four)
+        at[j] = ((int64_t)b * a.tail[j] + (on[j] ? t - skip : 0)) * E + 4 * q;
+        if (!any_on[j]) continue;
+#pragma unroll
+        for (int i = 0; i < TPW; ++i) {
+            const int nt = wv + i * kWaves;
+            if (nt >= EC) continue;
+            const float* wp = a.w1[j] + (16 * nt + x) * E + 4 * q;
+            f32x4 wa[EC];
+#pragma unroll
+            for (int c = 0; c < EC; ++c) wa[c] = ld4(wp + 16 * c);
+            const f32x4 bias = ld4(a.b1[j] + 16 * nt + 4 * q);
+            f32x4 acc = zero4();
+#pragma unroll
+            for (int c = 0; c < EC; ++c) acc = mfma4(wa[c], xv[c], acc);
+            pre[j][i] = acc + bias;
+            if (on[j]) st4(a.pre[j] + at[j] + 16 * nt, pre[j][i]);
+        }
+    }
+    draw_share(a.d, draw);
+    const uint32_t blk = (uint32_t)rc * (uint32_t)(E / 4) + (uint32_t)q;
+#pragma unroll
+    for (int j = 0; j < kMaxJobs; ++j) {
+        if (j >= a.J || !any_on[j]) continue;
+#pragma unroll
+        for (int i = 0; i < TPW; ++i) {
+            const int nt = wv + i * kWaves;
+            if (nt >= EC) continue;
+            const f32x4 f = row_factors4(draw, kTagQkv + (uint32_t)j, blk + (uint32_t)(4 * nt));
+            const f32x4 res = live ? ld4(xp + 16 * nt) : zero4();
+            f32x4 h;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) h[r] = (gelu_f(pre[j][i][r]) + res[r]) * f[r];
+            st4(&s_h[j][x][16 * nt + 4 * q], h);
+            if (on[j]) st4(a.h[j] + at[j] + 16 * nt, h);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kMaxJobs; ++j) {
+        if (j >= a.J || !any_on[j]) continue;
+        f32x4 hv[EC];
+#pragma unroll
+        for (int c = 0; c < EC; ++c) hv[c] = ld4(&s_h[j][x][16 * c + 4 * q]);
+#pragma unroll
+        for (int i = 0; i < TPW; ++i) {
+            const int nt = wv + i * kWaves;
+            if (nt >= EC) continue;
+            const float* wp = a.w2[j] + (16 * nt + x) * E + 4 * q;
+            f32x4 wa[EC];
+#pragma unroll
+            for (int c = 0; c < EC; ++c) wa[c] = ld4(wp + 16 * c);
+            const f32x4 bias = ld4(a.b2[j] + 16 * nt + 4 * q);
+            f32x4 acc = zero4();
+#pragma unroll
+            for (int c = 0; c < EC; ++c) acc = mfma4(wa[c], hv[c], acc);
+            if (on[j]) st4(a.y[j] + at[j] + 16 * nt, acc + bias);
+        }
+    }
+}
+
+//   g_h_j = (g_out_j W2_j) (.) M_j s;  g_pre_j = g_h_j gelu'(pre_j);  gx = sum_j (g_h_j + g_pre_j W1_j)
+// The tile of g_h a wave forms is the tile of gx it owns, so the residual term stays in its registers; the g_pre rows change
+// owner through LDS as the hidden rows do in the forward.  The mask is regenerated from the counter in `used`.
+template <int EC>
+__global__ void __launch_bounds__(kThreads) k_rows_dense_drop_bwd(const DenseArgs a) {
+    constexpr int E = 16 * EC, TPW = (EC + kWaves - 1) / kWaves, PP = E + 4;
+    __shared__ __attribute__((aligned(16))) float s_g[kMaxJobs][16][PP];
+    const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, q = l >> 4, x = l & 15;
+    DropDraw draw = a.d.draw();
+    draw.counter = (uint64_t)*a.d.used;
+    const int64_t rows = (int64_t)a.B * a.L, row = (int64_t)blockIdx.x * 16 + x;
+    const bool live = row < rows;
+    const int64_t rc = live ? row : rows - 1;
+    const int b = (int)(rc / a.L), t = (int)(rc - (int64_t)b * a.L);
+    const uint32_t blk = (uint32_t)rc * (uint32_t)(E / 4) + (uint32_t)q;
+    bool any_on[kMaxJobs];
+    f32x4 acc[TPW];
+#pragma unroll
+    for (int i = 0; i < TPW; ++i) acc[i] = zero4();
+#pragma unroll
+    for (int j = 0; j < kMaxJobs; ++j) {
+        any_on[j] = false;
+        if (j >= a.J) continue;
+        const int skip = a.L - a.tail[j];
+        const bool on = live && t >= skip;
+        any_on[j] = __any(on) != 0;
+        if (!any_on[j]) continue;
+        const int64_t at = ((int64_t)b * a.tail[j] + (on ? t - skip : 0)) * E + 4 * q;
+        f32x4 gv[EC];
+#pragma unroll
+        for (int c = 0; c < EC; ++c) gv[c] = on ? ld4(a.g[j] + at + 16 * c) : zero4();
+#pragma unroll
+        for (int i = 0; i < TPW; ++i) {
+            const int kt = wv + i * kWaves;
+            if (kt >= EC) continue;
+            const f32x4 z = ld4(a.pre[j] + at + 16 * kt);
+            f32x4 gh = zero4();
+#pragma unroll
+            for (int c = 0; c < EC; ++c) gh = mfma4(wcol4<E>(a.w2[j], 16 * c + 4 * q, 16 * kt + x), gv[c], gh);
+            gh *= row_factors4(draw, kTagQkv + (uint32_t)j, blk + (uint32_t)(4 * kt));
+            f32x4 gp;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) gp[r] = on ? gh[r] * gelu_grad(z[r]) : 0.f;
+            acc[i] += gh;
+            st4(&s_g[j][x][16 * kt + 4 * q], gp);
+            if (on) st4(a.gpre[j] + at + 16 * kt, gp);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kMaxJobs; ++j) {
+        if (j >= a.J || !any_on[j]) continue;
+        f32x4 gpv[EC];
+#pragma unroll
+        for (int c = 0; c < EC; ++c) gpv[c] = ld4(&s_g[j][x][16 * c + 4 * q]);
+#pragma unroll
+        for (int i = 0; i < TPW; ++i) {
+            const int kt = wv + i * kWaves;
+            if (kt >= EC) continue;
+#pragma unroll
+            for (int c = 0; c < EC; ++c) acc[i] = mfma4(wcol4<E>(a.w1[j], 16 * c + 4 * q, 16 * kt + x), gpv[c], acc[i]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < TPW; ++i) {
+        const int kt = wv + i * kWaves;
+        if (kt < EC && live) st4(a.gx + row * E + 16 * kt + 4 * q, acc[i]);
     }
 }
 
@@ -320,6 +556,11 @@ __global__ void __launch_bounds__(kThreads) k_rows_affine(const AffineArgs a) {
 
 inline bool width_ok(int E) { return E == 32 || E == 64 || E == 128; }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// the draws' host checks: thr = floor(p 2^32) >= 1 and scale = float32(1 / (1 - p)) >= 1, finite, are what a p in (0, 1) gives;
+// the Philox block index r (E / 4) + (f >> 2) is 32 bits wide: rows E < 2^34
+inline bool draw_args_ok(int64_t rows, int width, uint32_t thr, float scale) {
+    return thr >= 1u && scale >= 1.f && std::isfinite(scale) && rows < ((int64_t)1 << 34) / width;
+}
 
 }  // namespace rowsp
 }  // namespace asac
@@ -457,6 +698,96 @@ int asac_rows_resblock_backward(const float* grad_y, const float* pre, const flo
     const dim3 grid((unsigned)((rows + 15) / 16));
     RP_LAUNCH(k_rows_res_bwd, width, grid, as_stream(stream), a);
     return finish_launch("asac_rows_resblock_backward");
+}
+
+int asac_rows_resblock_dropout_forward(const float* x, int64_t x_row_stride, const float* weight, const float* bias,
+                                       const float* row_scale, int64_t rows, int width, float* y, float* pre, uint32_t thr,
+                                       float scale, uint64_t seed, uint32_t instance, int64_t* state, int64_t* used, void* stream) {
+    if (!x || !weight || !bias || !y || !pre || !state || !used || rows <= 0 || !width_ok(width) || x_row_stride < width ||
+        (x_row_stride & 3) || !aligned16(x) || !aligned16(weight) || !aligned16(bias) || !aligned16(y) || !aligned16(pre) ||
+        !draw_args_ok(rows, width, thr, scale))
+        return bad_arg("asac_rows_resblock_dropout_forward");
+    ResArgs a{};
+    a.x = x, a.xs = x_row_stride, a.w = weight, a.b = bias, a.scale = row_scale, a.rows = rows, a.y = y, a.pre = pre;
+    a.d = DrawArgs{seed, instance, thr, scale, 0, state, used};
+    const dim3 grid((unsigned)((rows + 15) / 16));
+    // under the measurement repeat knob only the last repetition advances the counter: all of them draw alike
+    for (int rep = 0; rep < g_launch_repeat; ++rep) {
+        a.d.advance = rep == g_launch_repeat - 1;
+        if (width == 32) hipLaunchKernelGGL((k_rows_res_fwd<2, true>), grid, dim3(kThreads), 0, as_stream(stream), a);
+        else if (width == 64) hipLaunchKernelGGL((k_rows_res_fwd<4, true>), grid, dim3(kThreads), 0, as_stream(stream), a);
+        else hipLaunchKernelGGL((k_rows_res_fwd<8, true>), grid, dim3(kThreads), 0, as_stream(stream), a);
+    }
+    return finish_launch("asac_rows_resblock_dropout_forward");
+}
+
+int asac_rows_resblock_dropout_backward(const float* grad_y, const float* pre, const float* weight, const float* row_scale,
+                                        int64_t rows, int width, float* grad_x, float* grad_pre, uint32_t thr, float scale,
+                                        uint64_t seed, uint32_t instance, const int64_t* used, void* stream) {
+    if (!grad_y || !pre || !weight || !grad_x || !grad_pre || !used || rows <= 0 || !width_ok(width) || !aligned16(grad_y) ||
+        !aligned16(pre) || !aligned16(grad_x) || !aligned16(grad_pre) || !draw_args_ok(rows, width, thr, scale))
+        return bad_arg("asac_rows_resblock_dropout_backward");
+    ResArgs a{};
+    a.gy = grad_y, a.pre = const_cast<float*>(pre), a.w = weight, a.scale = row_scale, a.rows = rows, a.gx = grad_x, a.gpre = grad_pre;
+    a.d = DrawArgs{seed, instance, thr, scale, 0, nullptr, const_cast<int64_t*>(used)};
+    const dim3 grid((unsigned)((rows + 15) / 16));
+    RP_LAUNCH_KIND(k_rows_res_bwd, true, width, grid, as_stream(stream), a);
+    return finish_launch("asac_rows_resblock_dropout_backward");
+}
+
+int asac_rows_dense_proj_dropout_forward(const float* x, int64_t x_stride_b, int64_t x_stride_t, int batch, int window, int width,
+                                         int n_jobs, const float* const* weights1, const float* const* biases1,
+                                         const float* const* weights2, const float* const* biases2, const int* tails,
+                                         float* const* outs, float* const* pres, float* const* hiddens, uint32_t thr, float scale,
+                                         uint64_t seed, uint32_t instance, int64_t* state, int64_t* used, void* stream) {
+    const char* what = "asac_rows_dense_proj_dropout_forward";
+    if (!x || !weights1 || !biases1 || !weights2 || !biases2 || !tails || !outs || !pres || !hiddens || !state || !used ||
+        batch <= 0 || window <= 0 || !width_ok(width) || n_jobs < 1 || n_jobs > kMaxJobs || !aligned16(x) || (x_stride_b & 3) ||
+        (x_stride_t & 3) || x_stride_t < width || !draw_args_ok((int64_t)batch * window, width, thr, scale))
+        return bad_arg(what);
+    DenseArgs a{};
+    a.x = x, a.xs_b = x_stride_b, a.xs_t = x_stride_t, a.B = batch, a.L = window, a.J = n_jobs;
+    for (int j = 0; j < n_jobs; ++j) {
+        if (tails[j] < 1 || tails[j] > window) return bad_arg(what);
+        for (const void* p : {(const void*)weights1[j], (const void*)biases1[j], (const void*)weights2[j], (const void*)biases2[j],
+                              (const void*)outs[j], (const void*)pres[j], (const void*)hiddens[j]})
+            if (!p || !aligned16(p)) return bad_arg(what);
+        a.w1[j] = weights1[j], a.b1[j] = biases1[j], a.w2[j] = weights2[j], a.b2[j] = biases2[j], a.tail[j] = tails[j];
+        a.y[j] = outs[j], a.pre[j] = pres[j], a.h[j] = hiddens[j];
+    }
+    a.d = DrawArgs{seed, instance, thr, scale, 0, state, used};
+    const dim3 grid((unsigned)(((int64_t)batch * window + 15) / 16));
+    for (int rep = 0; rep < g_launch_repeat; ++rep) {
+        a.d.advance = rep == g_launch_repeat - 1;
+        if (width == 32) hipLaunchKernelGGL(k_rows_dense_drop_fwd<2>, grid, dim3(kThreads), 0, as_stream(stream), a);
+        else if (width == 64) hipLaunchKernelGGL(k_rows_dense_drop_fwd<4>, grid, dim3(kThreads), 0, as_stream(stream), a);
+        else hipLaunchKernelGGL(k_rows_dense_drop_fwd<8>, grid, dim3(kThreads), 0, as_stream(stream), a);
+    }
+    return finish_launch(what);
+}
+
+int asac_rows_dense_proj_dropout_backward(const float* const* grads, const float* const* pres, const int* tails, int n_jobs,
+                                          const float* const* weights1, const float* const* weights2, int batch, int window,
+                                          int width, float* grad_x, float* const* grad_pres, uint32_t thr, float scale,
+                                          uint64_t seed, uint32_t instance, const int64_t* used, void* stream) {
+    const char* what = "asac_rows_dense_proj_dropout_backward";
+    if (!grads || !pres || !tails || !weights1 || !weights2 || !grad_x || !grad_pres || !used || batch <= 0 || window <= 0 ||
+        !width_ok(width) || n_jobs < 1 || n_jobs > kMaxJobs || !aligned16(grad_x) ||
+        !draw_args_ok((int64_t)batch * window, width, thr, scale))
+        return bad_arg(what);
+    DenseArgs a{};
+    a.B = batch, a.L = window, a.J = n_jobs, a.gx = grad_x;
+    for (int j = 0; j < n_jobs; ++j) {
+        if (tails[j] < 1 || tails[j] > window || !weights1[j] || !weights2[j]) return bad_arg(what);
+        for (const void* p : {(const void*)grads[j], (const void*)pres[j], (const void*)grad_pres[j]})
+            if (!p || !aligned16(p)) return bad_arg(what);
+        a.w1[j] = weights1[j], a.w2[j] = weights2[j], a.tail[j] = tails[j];
+        a.g[j] = grads[j], a.pre[j] = const_cast<float*>(pres[j]), a.gpre[j] = grad_pres[j];
+    }
+    a.d = DrawArgs{seed, instance, thr, scale, 0, nullptr, const_cast<int64_t*>(used)};
+    const dim3 grid((unsigned)(((int64_t)batch * window + 15) / 16));
+    RP_LAUNCH(k_rows_dense_drop_bwd, width, grid, as_stream(stream), a);
+    return finish_launch(what);
 }
 
 int asac_rows_affine_supported(int K, int N) { return K >= 1 && K <= 64 && N >= 16 && N <= 1024 && (N & 15) == 0; }

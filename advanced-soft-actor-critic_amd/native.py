@@ -572,6 +572,19 @@ _SIGNATURES = {
                                              C.c_void_p, C.c_void_p, C.c_void_p]),
     'asac_rows_resblock_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),
+    'asac_rows_dense_proj_dropout_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint64, C.c_uint32,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_rows_dense_proj_dropout_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                        C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float,
+                                                        C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    'asac_rows_resblock_dropout_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                                     C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint64, C.c_uint32,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_rows_resblock_dropout_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                                      C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint64, C.c_uint32,
+                                                      C.c_void_p, C.c_void_p]),
     'asac_rows_gate_supported': (C.c_int, [C.c_int, C.c_int]),
     'asac_rows_gate_forward': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                          C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -2828,6 +2841,81 @@ def rows_resblock_backward(grad_y, pre, weight, row_scale, grad_x, grad_pre):
     _last_work = 2.0 * rows * E * E
     _check(load().asac_rows_resblock_backward(_p(grad_y), _p(pre), _p(weight), _p(row_scale), rows, E, _p(grad_x), _p(grad_pre),
                                               _stream()), 'asac_rows_resblock_backward')
+
+
+# the nn.Dropout modules inside the dense stacks around the core, inside the row launches (csrc/rows_proj.hip; draws:
+# csrc/asac_dropout.h under tags 6 / 7 / 8 = q / k / v and 9 = the output block; state and `used` as for the core, one state per
+# launch site)
+ROWS_DROPOUT_TAG_QKV, ROWS_DROPOUT_TAG_OUT = 6, 9
+
+
+def _draw_args(p, seed, instance):
+    return dropout_threshold(p), 1.0 / (1.0 - float(p)), int(seed) & (2 ** 64 - 1), int(instance) & 0xFFFFFFFF
+
+
+@_profiled
+def rows_dense_proj_dropout_forward(x, weights1, biases1, weights2, biases2, tails, outs, pres, hiddens, p, seed, instance,
+                                    state, used):
+    """the <= 3 stacks ResBlock -> Dropout(p) -> Linear of one input, one launch: pres[j] = x W1^T + b1,
+    hiddens[j] = (x + gelu(pres[j])) * mask * s, outs[j] = hiddens[j] W2^T + b2 over x[:, L - tails[j]:]; x [B][L][E] with feature
+    stride 1; `used` int64 [1] <- the counter this call drew with"""
+    global _last_work
+    B, L, E = x.shape
+    n = len(outs)
+    assert x.stride(2) == 1 and n <= 3 and all(len(t) == n for t in (weights1, biases1, weights2, biases2, tails, pres, hiddens))
+    _dense_f32(*weights1, *biases1, *weights2, *biases2, *outs, *pres, *hiddens)
+    _drop_state_ok(state, used)
+    for o, pr, h, t in zip(outs, pres, hiddens, tails):
+        assert o.shape == pr.shape == h.shape == (B, t, E)
+    _last_work = 4.0 * B * sum(tails) * E * E
+    _check(load().asac_rows_dense_proj_dropout_forward(
+        _p(x), x.stride(0), x.stride(1), B, L, E, n, _ptr_array(weights1), _ptr_array(biases1), _ptr_array(weights2),
+        _ptr_array(biases2), (C.c_int * n)(*tails), _ptr_array(outs), _ptr_array(pres), _ptr_array(hiddens),
+        *_draw_args(p, seed, instance), _p(state), _p(used), _stream()), 'asac_rows_dense_proj_dropout_forward')
+
+
+@_profiled
+def rows_dense_proj_dropout_backward(grads, pres, tails, weights1, weights2, grad_x, grad_pres, p, seed, instance, used):
+    """the backward of `rows_dense_proj_dropout_forward`: grad_pres[j] and grad_x [B][L][E] = sum_j (g_h_j + grad_pres[j] W1_j);
+    the masks are regenerated from the counter in `used` (read on the device)"""
+    global _last_work
+    B, L, E = grad_x.shape
+    n = len(grads)
+    _dense_f32(*grads, *pres, *weights1, *weights2, grad_x, *grad_pres)
+    assert used.is_cuda and used.dtype == torch.int64 and used.numel() == 1
+    for g, pr, gp, t in zip(grads, pres, grad_pres, tails):
+        assert g.shape == pr.shape == gp.shape == (B, t, E)
+    _last_work = 4.0 * B * sum(tails) * E * E
+    _check(load().asac_rows_dense_proj_dropout_backward(
+        _ptr_array(grads), _ptr_array(pres), (C.c_int * n)(*tails), n, _ptr_array(weights1), _ptr_array(weights2), B, L, E,
+        _p(grad_x), _ptr_array(grad_pres), *_draw_args(p, seed, instance), _p(used), _stream()),
+        'asac_rows_dense_proj_dropout_backward')
+
+
+@_profiled
+def rows_resblock_dropout_forward(x, weight, bias, row_scale, y, pre, p, seed, instance, state, used):
+    """y = (x + gelu(x W^T + b)) * mask * s * row_scale[:, None], pre = x W^T + b; x [rows][E] with feature stride 1"""
+    global _last_work
+    rows, E = x.shape
+    assert x.stride(1) == 1
+    _dense_f32(weight, bias, y, pre, *([] if row_scale is None else [row_scale]))
+    _drop_state_ok(state, used)
+    _last_work = 2.0 * rows * E * E
+    _check(load().asac_rows_resblock_dropout_forward(_p(x), x.stride(0), _p(weight), _p(bias), _p(row_scale), rows, E, _p(y),
+                                                     _p(pre), *_draw_args(p, seed, instance), _p(state), _p(used), _stream()),
+           'asac_rows_resblock_dropout_forward')
+
+
+@_profiled
+def rows_resblock_dropout_backward(grad_y, pre, weight, row_scale, grad_x, grad_pre, p, seed, instance, used):
+    global _last_work
+    rows, E = grad_y.shape
+    _dense_f32(grad_y, pre, weight, grad_x, grad_pre, *([] if row_scale is None else [row_scale]))
+    assert used.is_cuda and used.dtype == torch.int64 and used.numel() == 1
+    _last_work = 2.0 * rows * E * E
+    _check(load().asac_rows_resblock_dropout_backward(_p(grad_y), _p(pre), _p(weight), _p(row_scale), rows, E, _p(grad_x),
+                                                      _p(grad_pre), *_draw_args(p, seed, instance), _p(used), _stream()),
+           'asac_rows_resblock_dropout_backward')
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1154,6 +1154,41 @@ int asac_rows_resblock_forward(const float* x, int64_t x_row_stride, const float
                                const float* row_scale, int64_t rows, int width, float* y, float* pre, void* stream);
 int asac_rows_resblock_backward(const float* grad_y, const float* pre, const float* weight, const float* row_scale,
                                 int64_t rows, int width, float* grad_x, float* grad_pre, void* stream);
+
+/* The `nn.Dropout` modules INSIDE the dense stacks around the core (`LinearLayers(E, E, dense_depth 1, dropout p)`:
+ * ResBlock -> nn.Dropout(p) [-> nn.Linear], linear_layers.py:24-119; live in every pass, the reference never leaves training
+ * mode), inside the row launches.  The draw contract is the core's (csrc/asac_dropout.h; thr, scale, seed, instance, state,
+ * used as for asac_attention_mh_dropout_forward; tests/dense_dropout_ref.py restates it): element (row r, feature f) is kept
+ * iff word f & 3 of
+ *   Philox4x32-10(counter = (r * (width / 4) + (f >> 2), (tag << 28) | (instance & 0x0FFFFFFF), c lo, c hi), key = seed)
+ * is >= thr; tag 6 / 7 / 8 = job 0 / 1 / 2 of the dense launch (q / k / v) with r = b * window + t, the position in the FULL
+ * window (a draw does not depend on tails[j]); tag 9 = the output block with r the flat row.  rows * width < 2^34.
+ * Each of the two launch sites owns a state int64 [544] of the core's layout — one state per concurrently running launch:
+ * never the core's.  The mask is never stored.
+ *
+ * asac_rows_dense_proj_dropout_forward: the <= 3 stacks of one input x (layout and tails as asac_rows_proj_forward), per job j
+ *   pres[j] = x W1_j^T + b1_j;  hiddens[j] = (x + gelu(pres[j])) (.) M_j * scale;  outs[j] = hiddens[j] W2_j^T + b2_j
+ * all three dense [batch][tails[j]][width] (hiddens: the operand of asac_xty for the gradients of W2_j / b2_j).
+ * asac_rows_dense_proj_dropout_backward: g_h_j = (grads[j] W2_j) (.) M_j * scale;  grad_pres[j] = g_h_j * gelu'(pres[j])
+ * (dense like grads[j]);  grad_x [batch][window][width] (dense, overwritten) = sum_j (g_h_j + grad_pres[j] W1_j), job j
+ * reaching the newest tails[j] positions only.
+ * asac_rows_resblock_dropout_forward / _backward: asac_rows_resblock_* with the drop in front of the row factor,
+ *   y = (x + gelu(x W^T + b)) (.) M * scale * row_scale;  g = grad_y * row_scale (.) M * scale, grad_pre and grad_x as there. */
+int asac_rows_dense_proj_dropout_forward(const float* x, int64_t x_stride_b, int64_t x_stride_t, int batch, int window, int width,
+                                         int n_jobs, const float* const* weights1, const float* const* biases1,
+                                         const float* const* weights2, const float* const* biases2, const int* tails,
+                                         float* const* outs, float* const* pres, float* const* hiddens, uint32_t thr, float scale,
+                                         uint64_t seed, uint32_t instance, int64_t* state, int64_t* used, void* stream);
+int asac_rows_dense_proj_dropout_backward(const float* const* grads, const float* const* pres, const int* tails, int n_jobs,
+                                          const float* const* weights1, const float* const* weights2, int batch, int window,
+                                          int width, float* grad_x, float* const* grad_pres, uint32_t thr, float scale,
+                                          uint64_t seed, uint32_t instance, const int64_t* used, void* stream);
+int asac_rows_resblock_dropout_forward(const float* x, int64_t x_row_stride, const float* weight, const float* bias,
+                                       const float* row_scale, int64_t rows, int width, float* y, float* pre, uint32_t thr,
+                                       float scale, uint64_t seed, uint32_t instance, int64_t* state, int64_t* used, void* stream);
+int asac_rows_resblock_dropout_backward(const float* grad_y, const float* pre, const float* weight, const float* row_scale,
+                                        int64_t rows, int width, float* grad_x, float* grad_pre, uint32_t thr, float scale,
+                                        uint64_t seed, uint32_t instance, const int64_t* used, void* stream);
 /* The gate an episode attention block puts behind its attention, with the padded-row factor, one launch per pass
  * (csrc/rows_gate.hip) — replaces, in `EpisodeMultiheadAttentionBlock.forward` (nn_models/layers/seq_layers.py:460-547),
  * `self.gatedlayer(residual_src, output)` (the gate layers of seq_layers.py:297-345) and the

@@ -10,7 +10,13 @@ csrc/asac_dropout.h, `seq_layers.FUSED_ATTN_DROPOUT`), in one process on one box
   step    train steps/s of `SAC_Base` at the sizes of bench.py's cfg_attn_h64 over tests/plugins/nn_attn_dropout.py
           (captured step) with the switch on and off
 
-    python tools/attn_dropout_bench.py [--p 0.005] [--reps 100] [--steps 400] [--modes core block step]
+    python tools/attn_dropout_bench.py [--p 0.005] [--reps 100] [--steps 400] [--modes core block step] [--dense]
+
+--dense measures the OTHER switch, `seq_layers.FUSED_DENSE_DROPOUT` (the live nn.Dropout modules of the dense q / k / v stacks
+and of the output block inside the row launches, csrc/rows_proj.hip), with the weights' switch left on: `block` builds the
+block with `qkv_dense_depth=1, out_dense_depth=1` (off: the stacks module by module with ATen's dropout — the path of the commit
+before those launches; at E = 12 the row kernels do not apply and both ways run the same code), `step` also records which
+replay path each learner took (`direct`: the captured step drew no torch random numbers and left torch's replay).
 
 The two ways alternate (off, on, off, on, ...: a drift of the box's clocks hits both); the median of the rounds is reported,
 all rounds are listed.  Launches per pass are taken with torch's profiler outside the timing.  One JSON line per shape and
@@ -101,12 +107,15 @@ def core_row(shape, p, repeat=100):
     return row
 
 
-def block_row(shape, p, reps):
+def block_row(shape, p, reps, dense=False):
     import algorithm.nn_models as m
     from algorithm.nn_models.layers import seq_layers
+    from asac_amd import native
     B, Lq, Lk, E, H = shape
+    switch = 'FUSED_DENSE_DROPOUT' if dense else 'FUSED_ATTN_DROPOUT'
     torch.manual_seed(0)
-    block = seq_layers.EpisodeMultiheadAttentionBlock(E, H, dropout=p, gate=m.GATE.RESIDUAL).cuda()
+    block = seq_layers.EpisodeMultiheadAttentionBlock(E, H, dropout=p, gate=m.GATE.RESIDUAL,
+                                                      **(dict(qkv_dense_depth=1, out_dense_depth=1) if dense else {})).cuda()
     assert block.training
     key = torch.randn(B, Lk, E, device='cuda')
     pad = torch.arange(Lk, device='cuda').unsqueeze(0) < torch.randint(0, 3, (B, 1), device='cuda')
@@ -118,23 +127,25 @@ def block_row(shape, p, reps):
         o, w = block(kk, seq_q_len=Lq, key_padding_mask=pad)
         (o.sum() + w.sum()).backward()
 
-    row = {'mode': 'block', 'shape': list(shape), 'p': p}
+    row = {'mode': 'block', 'switch': switch, 'shape': list(shape), 'p': p}
+    if dense:
+        row['same_path'] = not native.rows_proj_supported(E)
     runs = {False: [], True: []}
     for rnd in range(ROUNDS):
         for fused in (False, True):
-            seq_layers.FUSED_ATTN_DROPOUT = fused
+            setattr(seq_layers, switch, fused)
             runs[fused].append(round(events_ms(fn, reps), 4))
             if rnd == 0:
                 tag = 'fused' if fused else 'module'
                 launches, busy = count_launches(fn)
                 row['launches_' + tag], row['device_us_' + tag] = round(launches, 1), round(busy, 1)
-    seq_layers.FUSED_ATTN_DROPOUT = True
+    setattr(seq_layers, switch, True)
     row.update(ms_module=median(runs[False]), ms_fused=median(runs[True]), runs_module=runs[False], runs_fused=runs[True])
     row['fused_over_module'] = round(row['ms_fused'] / row['ms_module'], 4)
     return row
 
 
-def step_row(steps):
+def step_row(steps, dense=False):
     import bench
     from algorithm.nn_models.layers import seq_layers
     from algorithm.sac_base import SAC_Base
@@ -142,9 +153,10 @@ def step_row(steps):
     from tests import parity_utils as pu
     cfg = bench.CONFIGS['cfg_attn_h64']
     plugin = pu.plugin('nn_attn_dropout')
+    switch = 'FUSED_DENSE_DROPOUT' if dense else 'FUSED_ATTN_DROPOUT'
     agents = {}
     for fused in (False, True):      # (the switch is read at every forward: each learner captures its step under its own setting)
-        seq_layers.FUSED_ATTN_DROPOUT = fused
+        setattr(seq_layers, switch, fused)
         torch.manual_seed(0)
         agent = SAC_Base(cfg['obs_names'], cfg['obs_shapes'], [], cfg['c_action_size'], None, plugin, device='cuda:0',
                          seq_encoder=SEQ_ENCODER.ATTN, n_step=cfg['n_step'], burn_in_step=cfg['burn_in_step'],
@@ -158,7 +170,7 @@ def step_row(steps):
         torch.cuda.synchronize()
         assert agent._graph is not None
         agents[fused] = agent
-    seq_layers.FUSED_ATTN_DROPOUT = True
+    setattr(seq_layers, switch, True)
     runs = {False: [], True: []}
     for _ in range(3):
         for fused in (False, True):
@@ -169,9 +181,10 @@ def step_row(steps):
                 agent.train()
             torch.cuda.synchronize()
             runs[fused].append(round(steps / (time.perf_counter() - t0), 1))
+    replay = {fused: 'direct' if agents[fused]._graph.exec_handle is not None else 'torch' for fused in (False, True)}
     for agent in agents.values():
         agent.close()
-    row = {'mode': 'step', 'plugin': 'nn_attn_dropout', 'batch': cfg['batch_size'], 'steps': steps,
+    row = {'mode': 'step', 'switch': switch, 'replay_module': replay[False], 'replay_fused': replay[True], 'plugin': 'nn_attn_dropout', 'batch': cfg['batch_size'], 'steps': steps,
            'steps_per_s_module': median(runs[False]), 'steps_per_s_fused': median(runs[True]),
            'runs_module': runs[False], 'runs_fused': runs[True]}
     row['fused_over_module'] = round(row['steps_per_s_fused'] / row['steps_per_s_module'], 4)
@@ -184,15 +197,16 @@ def main():
     ap.add_argument('--reps', type=int, default=100)
     ap.add_argument('--steps', type=int, default=400)
     ap.add_argument('--modes', nargs='+', default=['core', 'block', 'step'])
+    ap.add_argument('--dense', action='store_true', help='measure FUSED_DENSE_DROPOUT (block, step) instead')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'needs the GPU: nothing is measured without one'
     import asac_amd  # noqa: F401
     for mode in args.modes:
         if mode == 'step':
-            print(json.dumps(step_row(args.steps)), flush=True)
+            print(json.dumps(step_row(args.steps, args.dense)), flush=True)
             continue
         for shape in SHAPES:
-            row = core_row(shape, args.p) if mode == 'core' else block_row(shape, args.p, args.reps)
+            row = core_row(shape, args.p) if mode == 'core' else block_row(shape, args.p, args.reps, args.dense)
             print(json.dumps(row), flush=True)
 
 

@@ -154,7 +154,7 @@ class _WideAffineGeluFn(torch.autograd.Function):
 def rows_resblock(block, x):
     """`ResBlock.forward` over >= MIN_ROWS rows on the device as one launch per pass, or None: without a residual path
     (widths differ) from a narrow input — `_AffineGeluFn`; with one at the widths of csrc/rows_proj.hip — the output-block
-    function of the attention layers (`seq_layers._OutResRowsFn`)"""
+    function of the attention layers (`fused_attention._OutResRowsFn`)"""
     from torch import nn
     lin = block.linear
     if not (ENABLED and x.is_cuda and x.dtype == torch.float32 and type(block.act) is nn.GELU
@@ -175,6 +175,6 @@ def rows_resblock(block, x):
             return _AffineGeluFn.apply(x, lin.weight, lin.bias)
         return None
     if native.rows_proj_supported(lin.in_features):
-        from algorithm.nn_models.layers.seq_layers import _OutResRowsFn
+        from .fused_attention import _OutResRowsFn
         return _OutResRowsFn.apply(x, lin.weight, lin.bias, None)
     return None

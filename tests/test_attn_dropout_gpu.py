@@ -294,6 +294,7 @@ def test_first_call_under_capture_runs_the_module_code():
 
 def test_paths_without_active_dropout_do_not_move(monkeypatch):
     from asac_amd import native
+    from algorithm import fused_attention
     from algorithm.nn_models.layers import seq_layers
     B, Lq, Lk, E, H = 4, 20, 27, 40, 8
     layer, c = _case(B, Lq, Lk, E, H, 'batch', 0.5)
@@ -320,7 +321,7 @@ def test_paths_without_active_dropout_do_not_move(monkeypatch):
         assert dev.dropout_state() is None and dev._drop_used is None, f'{name}: no state is created'
         qp, kp, vp = (proj(c[n].cuda()) for proj, n in zip((dev.q_proj, dev.k_proj, dev.v_proj), 'qkv'))
         mask3 = torch.logical_or(c['mask'].cuda(), c['kpm'].cuda().unsqueeze(1))
-        o_core, w_core, *_ = seq_layers._AttnMhFn.apply(qp.detach(), kp.detach(), vp.detach(), mask3, H, None)
+        o_core, w_core, *_ = fused_attention._AttnMhFn.apply(qp.detach(), kp.detach(), vp.detach(), mask3, H, None)
         assert torch.equal(got[1], w_core), f'{name}: the weights are the plain launch\'s, bit for bit'
     got_zero, got_eval = run(zero)[0], run(evald)[0]
     # (the output stack differs — a fused ResBlock launch without its nn.Dropout, module code with it — the core does not)

@@ -61,6 +61,7 @@ def test_a_residual_source_expanded_along_batch_or_positions_goes_through_the_ga
     """`_GateRowsFn` on x = one window for the whole batch / one position for the whole window (stride 0), RECURRENT: the values
     of the gate layer's module code on the same tensors"""
     import asac_amd  # noqa: F401
+    from algorithm.fused_attention import _GateRowsFn
     from algorithm.nn_models.layers import seq_layers as sl
     torch.manual_seed(0)
     B, L, E = 5, 7, 32
@@ -77,7 +78,7 @@ def test_a_residual_source_expanded_along_batch_or_positions_goes_through_the_ga
         x = src.expand(B, L, E)
         assert 0 in x.stride()
         if fused:
-            out = sl._GateRowsFn.apply(sl.GATE.RECURRENT.value, x, y, pad, *(ll.weight for ll in lins), layer.dense_x_z.bias)
+            out = _GateRowsFn.apply(sl.GATE.RECURRENT.value, x, y, pad, *(ll.weight for ll in lins), layer.dense_x_z.bias)
         else:
             out = layer(x, y) * (~pad).to(y.dtype).unsqueeze(-1)
         out.backward(g_out)

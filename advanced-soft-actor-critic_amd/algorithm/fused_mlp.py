@@ -423,9 +423,20 @@ class StockMLP:
     def backward_qloss_return_ok(self, N: int, ret) -> bool:
         return native.mlp_backward_qloss_return_ok(self._pass(None, None, N=N), ret)
 
-    def backward_qloss_return(self, x0, x1, target_q, ret, weights, clip_eps, loss_out, defer=False, state_grads=False):
-        """`backward_qloss` with the return target `ret` (native.VtraceArgs, its launch not issued) formed inside."""
+    def backward_qloss_return(self, x0, x1, target_q, ret, weights, clip_eps, loss_out, defer=False, state_grads=False,
+                              critic_saved=None):
+        """`backward_qloss` with the return target `ret` (native.VtraceArgs, its launch not issued) formed inside.
+        `critic_saved` (never with `state_grads`): the forward on (x0, x1) is LOADED from it — what the critic-forward rider
+        of the step's first network launch wrote for these parameters and rows (`critic_save_buffer`) — instead of
+        recomputed: same results, bit for bit."""
         N = x0.shape[-2]
+        if critic_saved is not None:
+            assert not state_grads
+            native.mlp_backward_qloss_return_loaded(self._pass(x0, x1), target_q, ret, weights, clip_eps, loss_out,
+                                                    self.grad_params, self._workspace_for(N), self._reduce_mode(defer),
+                                                    critic_saved)
+            self._deferred_rows = N if defer else None
+            return None
         g0 = torch.empty((self.E, N, self.in0), dtype=torch.float32, device=self.device) if state_grads else None
         native.mlp_backward_qloss_return(self._pass(x0, x1), target_q, ret, weights, clip_eps, loss_out, self.grad_params,
                                          self._workspace_for(N), self._reduce_mode(defer), grad_x0=g0)
@@ -445,16 +456,40 @@ class StockMLP:
                 native.mlp_backward_qloss_return_rider_ok(self._pass(None, None, N=N), ret, policy._pass(x_pi, None), save))
 
     def backward_qloss_return_rider(self, x0, x1, target_q, ret, weights, clip_eps, loss_out, policy: 'StockMLP', x_pi, save,
-                                    defer=False, state_grads=False):
+                                    defer=False, state_grads=False, critic_saved=None):
         """`backward_qloss_return` whose launch also runs `policy`'s forward on the rows `x_pi` [N, in0] on further
-        workgroups and saves it in `save` (`policy.forward_save_buffer`) for `policy.policy_step_fused_loaded`."""
+        workgroups and saves it in `save` (`policy.forward_save_buffer`) for `policy.policy_step_fused_loaded`.
+        `critic_saved`: as in `backward_qloss_return`."""
         N = x0.shape[-2]
+        if critic_saved is not None:
+            assert not state_grads
+            native.mlp_backward_qloss_return_loaded(self._pass(x0, x1), target_q, ret, weights, clip_eps, loss_out,
+                                                    self.grad_params, self._workspace_for(N), self._reduce_mode(defer),
+                                                    critic_saved, pi_job=policy._pass(x_pi, None), save=save)
+            self._deferred_rows = N if defer else None
+            return None
         g0 = torch.empty((self.E, N, self.in0), dtype=torch.float32, device=self.device) if state_grads else None
         native.mlp_backward_qloss_return_rider(self._pass(x0, x1), target_q, ret, weights, clip_eps, loss_out,
                                                self.grad_params, self._workspace_for(N), self._reduce_mode(defer),
                                                policy._pass(x_pi, None), save, grad_x0=g0)
         self._deferred_rows = N if defer else None
         return g0
+
+    def critic_save_buffer(self, N: int):
+        """the buffer a critic-forward rider saves this ensemble's forward on N rows in
+        (`native.policy_sample_q_forward_saving`): allocated once per N and kept, like `forward_save_buffer`"""
+        buf = self._forward_saves.get(('q', N))
+        if buf is None:
+            buf = self._forward_saves[('q', N)] = torch.zeros(native.critic_forward_save_floats(N, self.E),
+                                                              dtype=torch.float32, device=self.device)
+        return buf
+
+    def backward_qloss_return_loaded_ok(self, N: int, ret, saved, policy: 'StockMLP' = None, x_pi=None, save=None) -> bool:
+        if policy is None:
+            return native.mlp_backward_qloss_return_loaded_ok(self._pass(None, None, N=N), ret, saved)
+        return (policy.E == 1 and x_pi.dim() == 2 and
+                native.mlp_backward_qloss_return_loaded_ok(self._pass(None, None, N=N), ret, saved,
+                                                           policy._pass(x_pi, None), save))
 
     def backward_policy_q(self, x0, x1, q_table, subset, E_sample):
         """-> [E, N, in1] action gradients of mean_b(-min_{e in subset} q_e) (`q_table` [E, N] from the

@@ -366,6 +366,9 @@ class SAC_Base(AuxHeadsMixin):
         self._fused_q_return = bool(hip_config.get('fused_q_return', True))
         # the policy step LOADS the policy's forward a rider of the Q-loss backward launch saved (`_stock_q_backward`)
         self._policy_forward_rider = bool(hip_config.get('policy_forward_rider', True))
+        # the Q-loss backward LOADS the online critics' forward a rider of the step's first network launch saved
+        # (`_train_rep_q_stock`, `_critic_rider_plan`)
+        self._critic_forward_rider = bool(hip_config.get('critic_forward_rider', True))
         self._fused_q_state_grads = bool(hip_config.get('fused_q_state_grads', True))
         self._gru_backward_at = bool(hip_config.get('gru_backward_at', True))
         self._adjacent_cat = bool(hip_config.get('adjacent_cat', True))
@@ -681,6 +684,7 @@ class SAC_Base(AuxHeadsMixin):
         self._ls_y = None
         self._pi_saved = None
         self._rider_plan_cache = None   # (rows and return it was decided for, the save buffer or None): `_rider_plan`
+        self._critic_plan_cache = {}    # stored pair and window (a static set) -> the save buffer or None: `_critic_rider_plan`
         self._cq_buf, self._tq_buf, self._cq_td_buf = (torch.zeros(E, B, 1, **f32) for _ in range(3))
         self._pi_q, self._pi_stats_src = torch.zeros(E, B, 1, **f32), None
         self._pi_a, self._pi_logp, self._pi_sampled = torch.zeros(B, A1, **f32), torch.zeros(B, **f32), False
@@ -1705,25 +1709,53 @@ class SAC_Base(AuxHeadsMixin):
         self._rider_plan_cache = (key, save)
         return save
 
-    def _stock_q_backward(self, x0, a0, ret, c_y, priority_is, fold, fused_return, state_grads=False, rider_rows=None):
+    @staticmethod
+    def _critic_plan_key(x0, a0, T):
+        return (x0.data_ptr(), x0.stride(0), a0.data_ptr(), a0.stride(0), x0.shape[0], T)
+
+    def _critic_rider_plan(self, key, x0, ret):
+        """decides, once per static set (`key`: the stored pair's rows and the window), whether the step's first network
+        launch carries the online critics' forward for a Q-loss backward that loads it; allocates the save buffer — in the
+        eager warm-up: never while a capture is running.  The first step of a set therefore issues today's launches; the
+        forward launch still asks its own predicate each time (its grid depends on the sidecars it carries)."""
+        if key in self._critic_plan_cache or torch.cuda.is_current_stream_capturing():
+            return
+        B, fq = x0.shape[0], self._fq
+        save = None
+        if self._critic_forward_rider and self._fused_q_return and self._dist is None and x0.dim() == 2 \
+                and fq.backward_qloss_return_ok(B, ret.args):
+            save = fq.critic_save_buffer(B)
+            if not fq.backward_qloss_return_loaded_ok(B, ret.args, save):
+                save = None
+        self._critic_plan_cache[key] = save
+
+    def _stock_q_backward(self, x0, a0, ret, c_y, priority_is, fold, fused_return, state_grads=False, rider_rows=None,
+                          critic_saved=None):
         """[online critics forward, clipped double-Q loss, backward] in one launch (the backward recomputes the forward
         on chip anyway).  With `fused_return` its own workgroups form the return target `ret` where that form applies
         (short windows); otherwise the return's launch goes first.  `fold`: the tile reduction of the parameter
         gradients is folded into the Adam launch, issued here.  -> d loss / d x0 [E, B, S] with `state_grads`.
         `rider_rows`: the policy step's state rows [B, S] when its action is already drawn — the launch then runs the
-        policy's forward on them on further workgroups (`_rider_plan`) and `_pi_saved` hands it to the policy step."""
+        policy's forward on them on further workgroups (`_rider_plan`) and `_pi_saved` hands it to the policy step.
+        `critic_saved`: the online critics' forward on (x0, a0) as this step's first network launch saved it — loaded
+        instead of recomputed where the loaded form applies (no `state_grads`)."""
         w = priority_is.reshape(-1).contiguous() if priority_is is not None else None
         t_q = self._tq_buf.view(self.ensemble_q_num, -1)
         self._pi_saved = None
         if fused_return and self._fq.backward_qloss_return_ok(x0.shape[-2], ret.args):
             save = self._rider_plan(rider_rows, ret) if rider_rows is not None else None
+            # (the critics' forward is loaded where the first network launch saved it and the loaded form applies)
+            if critic_saved is not None and (state_grads or not self._fq.backward_qloss_return_loaded_ok(
+                    x0.shape[-2], ret.args, critic_saved, *((self._fpi, rider_rows, save) if save is not None else ()))):
+                critic_saved = None
             if save is not None:
                 g0 = self._fq.backward_qloss_return_rider(x0, a0, t_q, ret.args, w, self.clip_epsilon, self._loss_q_e,
-                                                          self._fpi, rider_rows, save, defer=fold, state_grads=state_grads)
+                                                          self._fpi, rider_rows, save, defer=fold, state_grads=state_grads,
+                                                          critic_saved=critic_saved)
                 self._pi_saved = (save, rider_rows.data_ptr(), rider_rows.stride(0), rider_rows.shape[0])
             else:
                 g0 = self._fq.backward_qloss_return(x0, a0, t_q, ret.args, w, self.clip_epsilon, self._loss_q_e,
-                                                    defer=fold, state_grads=state_grads)
+                                                    defer=fold, state_grads=state_grads, critic_saved=critic_saved)
         else:
             self._launch_return(ret)
             g0 = self._fq.backward_qloss(x0, a0, t_q, c_y.reshape(-1), w, self.clip_epsilon, self._loss_q_e,
@@ -1772,12 +1804,25 @@ class SAC_Base(AuxHeadsMixin):
                 fused, riders = ring, [self._head_gather['sidecar_w' if self._head_gather_w else 'sidecar']]
                 self._head_gather = None
         self._join_head_gather()
+        critic_saved, critic_key = None, None
         if fused is not None:
             self.noise.normal_(self._eps_y)
             if policy_sample:
                 self.noise.normal_(self._eps_pi)
                 self._pi_sampled = True
-            native.policy_sample_q_forward(fused, [job_tq], sidecars=riders if riders is not None else self._take_la_gather())
+            sidecars = riders if riders is not None else self._take_la_gather()
+            # the online critics' forward on the stored pair rides along where the plan of this static set says so and the
+            # launch has the CUs for it; the Q-loss backward below then loads it (same launches, bit-identical)
+            critic_key = self._critic_plan_key(x0, a0, T)
+            plan = self._critic_plan_cache.get(critic_key) if self._critic_forward_rider else None
+            if plan is not None:
+                job_online = self._fq._pass(x0, a0)
+                if native.policy_sample_q_forward_saving_ok(fused, [job_tq], sidecars, job_online, plan):
+                    critic_saved = plan
+            if critic_saved is not None:
+                native.policy_sample_q_forward_saving(fused, [job_tq], sidecars, job_online, critic_saved)
+            else:
+                native.policy_sample_q_forward(fused, [job_tq], sidecars=sidecars)
             _, c_y, ret = self._get_y(*window, eps_buf=self._eps_y, subset_prefix='y', y_out=self._y_buf,
                                       ls=ls[0].view(B, T, 2 * A), sample=(a_y, logp_y), stored_pi=c_pi,
                                       q_table=q_tab.view(E, B, T), launch=False)
@@ -1789,8 +1834,10 @@ class SAC_Base(AuxHeadsMixin):
         # (behind the one-launch forward the backward may form the return itself; behind the chain form it never did)
         # (... and, with the policy step's action drawn by that forward, carry the policy's forward for the policy step)
         rider_rows = x0 if (self._policy_forward_rider and fused is not None and policy_sample and x0.dim() == 2) else None
+        if critic_key is not None and self._critic_forward_rider:
+            self._critic_rider_plan(critic_key, x0, ret)
         self._stock_q_backward(x0, a0, ret, c_y, priority_is, fold, fused_return=fused is not None and self._fused_q_return,
-                               rider_rows=rider_rows)
+                               rider_rows=rider_rows, critic_saved=critic_saved)
         if not fold:
             self._finish_rep_q(None, None)
 

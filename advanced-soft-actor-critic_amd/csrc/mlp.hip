@@ -590,7 +590,9 @@ __device__ __forceinline__ void ring_tile_rows(const StageScalars& q, const Ring
     }
 }
 
-template <int THREADS, int NB>
+// FWD = false (a backward that loads its forward and forms no input gradient): nothing reads the first layer's weights or
+// the biases — they are not requested, and zeros take their places
+template <int THREADS, int NB, bool FWD = true>
 __device__ __forceinline__ void net_fetch_fixed(const StageScalars& q, StagedNet<THREADS>& r) {
     constexpr int U = 4096 / THREADS;
     const rsrc_t rp = make_rsrc(q.P);
@@ -599,7 +601,8 @@ __device__ __forceinline__ void net_fetch_fixed(const StageScalars& q, StagedNet
     for (int u = 0; u < U; ++u) {
         const int i = threadIdx.x + u * THREADS;
         const int rr = i >> 6, c = i & 63;
-        r.w[0][u] = __builtin_bit_cast(float, buf_ld(rp, c < K0 ? (unsigned)(q.w_off[0] + rr * K0 + c) * 4u : kOob));
+        if constexpr (FWD) r.w[0][u] = __builtin_bit_cast(float, buf_ld(rp, c < K0 ? (unsigned)(q.w_off[0] + rr * K0 + c) * 4u : kOob));
+        else r.w[0][u] = 0.f;
     }
 #pragma unroll
     for (int l = 1; l < NB; ++l) {
@@ -611,7 +614,10 @@ __device__ __forceinline__ void net_fetch_fixed(const StageScalars& q, StagedNet
         }
     }
 #pragma unroll
-    for (int l = 0; l < NB; ++l) r.bias[l] = __builtin_bit_cast(float, buf_ld(rp, (unsigned)(q.b_off[l] + (threadIdx.x & 63)) * 4u));
+    for (int l = 0; l < NB; ++l) {
+        if constexpr (FWD) r.bias[l] = __builtin_bit_cast(float, buf_ld(rp, (unsigned)(q.b_off[l] + (threadIdx.x & 63)) * 4u));
+        else r.bias[l] = 0.f;
+    }
     const int h0 = q.h0, h1 = q.h1;
 #pragma unroll
     for (int u = 0; u < 1024 / THREADS; ++u) {
@@ -1045,10 +1051,42 @@ __device__ __forceinline__ void policy_forward_rider(const ASAC_KARG RiderIn<tru
 template <bool RET>
 constexpr size_t rider_karg_offset();
 
-template <int TM, bool WIDE, int NB, bool RET = false, int W8 = 0, bool RIDER = false>      // W8: 0, or the number of waves (8 / 16)
-__global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArgs a, const RetIn<RET> rv, const RiderIn<RIDER> rider_by_value) {
+// LOADED (the Q-loss backward forming its own return, 16 waves, with or without the policy rider): the online critics'
+// forward on the tile — x_1..x_3, gelu'(z_l), the raw q — is not recomputed but LOADED: the step's first network launch
+// saved it on workgroups of its own (critic_forward_rider below: the recompute's statements on the same rows and
+// parameters, SavedCriticTile per (tile, member)).  The tile is requested with the weights: x_1..x_3 go straight into
+// L.x[1..3] and the raw q into the spare input tile L.x[kMaxB] (free: three blocks, no wide first layer) in front of the
+// staging barrier; the fragments are requested by waves 0..3 right behind that barrier, into z[l].  The three recompute
+// layers, their barriers and the head product are not in this instantiation; everything from clipped_q_loss_row on is
+// the text of the others.  Of the invariants above: the saved tile is another LAUNCH's output, and `loads_landed()` at
+// the staging barrier covers the loads issued in front of it.  ONE LDS hand-over has no workgroup barrier here: the
+// tile's y (RET) is written behind the staging barrier by threads 0..15 and read in the loss phase, which in the other
+// instantiations lies three recompute barriers on.  Writer and reader are both wave 0 (TM = 16: one row tile, the head
+// wave is wave 0), LDS serves a wave in order, and a wave-level fence stands between them (below).  The fourth kernel
+// argument exists in this form alone.  It forms no input gradient (its entry points take none), so the first layer's weights — read by that
+// dX alone — and the biases are not fetched (net_fetch_fixed<.., false>).
+struct SavedCriticTile {
+    float x[3][16 * kMaxW];                  // x_1..x_3, dense rows
+    f32x4 zp[3][4 * 64];                     // gelu'(z_l): [layer][wave 0-3][lane], the MFMA C fragment of that lane
+    float q[16];                             // raw q of the tile's rows (head bias added)
+};
+static_assert(sizeof(SavedCriticTile) == 24640, "SavedCriticTile");
+constexpr int kSavedCriticFloats = sizeof(SavedCriticTile) / sizeof(float);
+template <bool LOADED>
+struct LoadedIn {};
+template <>
+struct LoadedIn<true> {
+    const float* saved;      // [tiles][E] SavedCriticTile
+};
+
+template <int TM, bool WIDE, int NB, bool RET = false, int W8 = 0, bool RIDER = false, bool LOADED = false>      // W8: 0, or the number of waves (8 / 16)
+__global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArgs a, const RetIn<RET> rv, const RiderIn<RIDER> rider_by_value,
+                                                                    const LoadedIn<LOADED> ld) {
     static_assert(W8 == 0 || ((W8 == 8 || W8 == 16) && TM == 16 && NB == 3 && !WIDE), "8 / 16 waves: 16-row tiles of the stock networks");
     static_assert(!RIDER || (RET && W8 == 16), "the rider's workgroups are k_policy_step's: 16 waves on a 16-row tile");
+    static_assert(!LOADED || (RET && W8 == 16), "the saved tile is dealt over sixteen waves");
+    static_assert(!LOADED || (TM == 16 && NB == 3 && NB < kMaxB),
+                  "LOADED: y's writer and reader are wave 0 (one row tile); the raw q parks in the spare tile L.x[kMaxB]");
     constexpr int THREADS = W8 ? 64 * W8 : threads_of<TM>();
     constexpr int RT = TM / 16;
     constexpr bool fixed = NB > 0;                            // NB blocks of 64 (see net_fetch_fixed)
@@ -1077,6 +1115,7 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
 
     MLP_STAMP(0);
     [[maybe_unused]] float ql_tq[4] = {0.f, 0.f, 0.f, 0.f}, ql_w[4] = {1.f, 1.f, 1.f, 1.f}, ql_y[4] = {0.f, 0.f, 0.f, 0.f};
+    f32x4 z[kMaxB];          // gelu'(pre-activation) of this wave's fragment, per block (recomputed below, or LOADED)
     // ---- staging: input tile, every weight, the incoming gradient tile (padded to 16 columns) -------
     // (a first layer wider than 64 inputs: second halves in the spare tiles x[kMaxB] / w[nb], desc_ok keeps nb < kMaxB)
     constexpr bool wide = WIDE;              // K0 > 64
@@ -1095,7 +1134,7 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
             gin = (row < a.N && c < O) ? t : 0.f;
         }
         StagedNet<THREADS> regs;
-        net_fetch_fixed<THREADS, NB>(q, regs);
+        net_fetch_fixed<THREADS, NB, !LOADED>(q, regs);
         if constexpr (W8 != 0) {
             // Q-loss mode: the loss phase's per-row operands (target-network value, IS weight, y) of the head wave's four
             // rows per lane, requested with the weights — read where they are used, each row's pair sits under its own
@@ -1110,6 +1149,17 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
                     if constexpr (!RET) ql_y[rr] = a.y[rc];
                 }
             }
+        }
+        // LOADED: the saved forward of the tile, requested with the weights
+        [[maybe_unused]] float sv_x[3], sv_q;
+        if constexpr (LOADED) {
+            static_assert(!LOADED || THREADS == 16 * kMaxW, "one float of x_l per thread");
+            const SavedCriticTile& sv = *reinterpret_cast<const SavedCriticTile*>(
+                ld.saved + ((int64_t)blockIdx.x * gridDim.y + e) * kSavedCriticFloats);
+#pragma unroll
+            for (int l = 0; l < 3; ++l) sv_x[l] = sv.x[l][threadIdx.x];
+            sv_q = sv.q[threadIdx.x & 15];          // (every thread loads; the first sixteen park it: L.x[kMaxB], the wide
+                                                    // first layer's spare tile, is free on the fixed-shape path)
         }
         if constexpr (RET) {
             const asac_vtrace_args_t& v = rv.v;
@@ -1127,6 +1177,11 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
             }
             put_input_tile<THREADS, SLOTS>(in_lo, L.x[0]);
             net_put_fixed<THREADS, NB>(regs, L);
+            if constexpr (LOADED) {
+#pragma unroll
+                for (int l = 0; l < 3; ++l) L.x[l + 1][(threadIdx.x >> 6) * kP + (threadIdx.x & 63)] = sv_x[l];
+                if (threadIdx.x < 16) x_hi[threadIdx.x] = sv_q;
+            }
             if (have) {
                 float d, cc;
                 const float v_t = vtrace_step_finish(v, raw, expf(log_alpha), &d, &cc);
@@ -1160,7 +1215,8 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
     if constexpr (W8 != 0) loads_landed();
     __syncthreads();
     MLP_STAMP(1);
-    if constexpr (RET) {     // one lane per row of the tile: y = V(s_0) + scan; first read in the loss phase (barriers between)
+    if constexpr (RET) {     // one lane per row of the tile: y = V(s_0) + scan; first read in the loss phase (barriers between;
+                             // LOADED: no barrier — the same wave, and the fence behind this block)
         const asac_vtrace_args_t& v = rv.v;
         const int n = v.n, pitch = (n + 1) | 1;
         float* s_d = reinterpret_cast<float*>(smem_raw + sizeof(MlpBwdLds<TM>));
@@ -1173,11 +1229,27 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
             s_y[r] = y;
             if (e == 0) v.y_out[row0 + r] = y;
         }
+        if constexpr (LOADED) {      // wave 0 wrote s_y and wave 0 reads it in the loss phase, no workgroup barrier between
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
     }
 
     // ---- forward recompute ----------------------------------------------------------------------------
-    f32x4 z[kMaxB];          // gelu'(pre-activation) of this wave's fragment, per block
+    // (LOADED: x_1..x_3 arrived with the staging; the fragments are requested here, once the staged weights have left
+    // the registers — their first reader is the third layer's reverse step, the loss phase and the head gradients away;
+    // the last hidden layer is 64 wide)
     int K = K0;
+    if constexpr (LOADED) {
+        K = kMaxW;
+        if (comp) {
+            const SavedCriticTile& sv = *reinterpret_cast<const SavedCriticTile*>(
+                ld.saved + ((int64_t)blockIdx.x * gridDim.y + e) * kSavedCriticFloats);
+#pragma unroll
+            for (int l = 0; l < 3; ++l) z[l] = sv.zp[l][threadIdx.x];
+        }
+    } else {
 #pragma unroll
     for (int l = 0; l < kMaxB; ++l) {
         if (l < nb) {
@@ -1216,6 +1288,7 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
             if (l == 1) MLP_STAMP(24);
             K = W;
         }
+    }
     }
     const int H = K;   // width of the last hidden layer
     MLP_STAMP(2);
@@ -1283,7 +1356,9 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
     if (!a.gout && !a.eps && !a.q_table) {
         __shared__ float loss_red[4 * RT];
         if (wave < RT) {
-            const f32x4 raw = gemm_tile(L.x[nb], L.head, round4(H), wave, 0);
+            f32x4 raw;          // (LOADED: the saved raw q, bias added by the launch that saved it)
+            if constexpr (LOADED) raw = *reinterpret_cast<const f32x4*>(x_hi + 4 * (lane >> 4));
+            else raw = gemm_tile(L.x[nb], L.head, round4(H), wave, 0);
             float part = 0.f;
             if ((lane & 15) == 0) {
                 const float inv_n = 1.f / (float)a.N;
@@ -1302,7 +1377,9 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
                         } else {
                             y_row = a.y[row];
                         }
-                        if constexpr (W8 != 0)          // (the staging's prefetch: the same words)
+                        if constexpr (LOADED)
+                            part += clipped_q_loss_row(raw[r], ql_tq[r], y_row, ql_w[r], a.clip_eps, &g);
+                        else if constexpr (W8 != 0)          // (the staging's prefetch: the same words)
                             part += clipped_q_loss_row(raw[r] + L.head_bias[0], ql_tq[r], y_row, ql_w[r], a.clip_eps, &g);
                         else
                             part += clipped_q_loss_row(raw[r] + L.head_bias[0], a.tq[(int64_t)e * a.N + row], y_row,
@@ -1397,7 +1474,7 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
             if (l == 0 && wide && (a.gx0 || a.gx1)) g_hi = gemm_tile_nt(dtile, w_hi, round4(W), rt, ct);
             // (W8: nobody asked for the input gradient — the headline's states have no parameters behind them — so the first
             // layer's dX product, the kernel's tail, is not formed)
-            if (comp && (W8 == 0 || l > 0 || a.gx0 || a.gx1)) {
+            if (comp && (LOADED ? l > 0 : (W8 == 0 || l > 0 || a.gx0 || a.gx1))) {
                 f32x4 gin = gemm_tile_nt(dtile, L.w[l], fixed ? kMaxW : round4(W), rt, ct);   // d x_{l-1}[row][k]
                 if (a.d.residual[l]) gin += g;
                 g = gin;
@@ -1406,7 +1483,7 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
         }
     }
     // ---- input gradients --------------------------------------------------------------------------------------
-    if (comp && (a.gx0 || a.gx1)) {
+    if (!LOADED && comp && (a.gx0 || a.gx1)) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int64_t row = row0 + rt * 16 + 4 * (lane >> 4) + r;
@@ -2081,6 +2158,108 @@ __device__ __forceinline__ void policy_forward_rider(const ASAC_KARG RiderIn<tru
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The ONLINE critics' forward of a 16-row tile of the stored pair, SAVED: further workgroups of the step's first network
+// launch (k_pi_sample_q / k_pi_sample_q_ring<.., CRIDER>), one four-wave workgroup per (tile, member), behind the extra
+// jobs and in front of the sidecars.  It stages critic e and the tile (x0 | a0) as k_mlp_bwd's fixed-shape path does —
+// the plain host from the static batch, the ring host through the ring description extra job 0 reads (the gather's slot,
+// validity and padding: the tile holds what the gathered batch will) — and runs the statements of k_mlp_bwd's recompute
+// loop as waves 0..3 of the sixteen-wave form execute them (rt = 0, ct = wave), then the head product of its loss phase:
+// the very values, bit for bit.  Stored: SavedCriticTile at [tile][e].  Nothing of the launch reads what it writes; its
+// reader is the Q-loss backward, a launch behind.  The critics' parameters are the online ones, last written by the
+// previous step's Adam launch.
+template <bool CRIDER>
+struct CriticRiderIn {};
+template <>
+struct CriticRiderIn<true> {
+    StockJobArg q;           // the online critics on the stored pair: x0 = states, x1 = stored actions (ring host: unused)
+    float* save;             // [tiles][E] SavedCriticTile
+    int32_t blocks, E;       // tiles * E
+};
+struct CriticRiderLds {      // (the member names net_put_fixed expects)
+    float w[3][kMaxW * kP];
+    float head[kHeadPad * kP];
+    float x[4][16 * kP];
+    float bias[3][kMaxW];
+    float head_bias[kHeadPad];
+};
+static_assert(sizeof(CriticRiderLds) <= sizeof(PiQLds), "the rider lives in the hosting launch's dynamic LDS");
+// offset of the third kernel argument behind FIRST and SECOND: explicit arguments lie in order, each at its alignment
+template <typename FIRST, typename SECOND>
+constexpr size_t critic_rider_karg_offset() {
+    constexpr size_t a1 = alignof(SECOND), a2 = alignof(CriticRiderIn<true>);
+    return ((((sizeof(FIRST) + a1 - 1) / a1 * a1) + sizeof(SECOND)) + a2 - 1) / a2 * a2;
+}
+
+template <bool RING>
+__device__ __forceinline__ void critic_forward_rider(const ASAC_KARG CriticRiderIn<true>& rd, int local, unsigned char* smem,
+                                                     const ASAC_KARG RingArg* ring = nullptr) {
+    constexpr int THREADS = 256;             // (the hosting kernel has let waves 4.. of this workgroup go)
+    CriticRiderLds& L = *reinterpret_cast<CriticRiderLds*>(smem);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int E = rd.E;
+    const int e = local % E, tile = local / E;
+    const StageScalars sq = stage_scalars_stock(rd.q, e);
+    const int64_t row0 = (int64_t)tile * 16;
+    const int K0 = sq.in0 + sq.in1;
+    const int residual_bits = rd.q.residual_bits;
+    SavedCriticTile& out = *reinterpret_cast<SavedCriticTile*>(rd.save + ((int64_t)tile * E + e) * kSavedCriticFloats);
+    float in_lo[4];
+    [[maybe_unused]] int64_t id_lo[4];
+    [[maybe_unused]] RingStage R{};
+    if constexpr (RING) {
+        R = ring_stage<true>(*ring, ring->x_j0, 1, ring->x_a_off);
+        ring_tile_ids<THREADS, 4>(sq, R, row0, id_lo);
+    } else {
+        fetch_input_tile_fixed<THREADS, false>(sq, e, row0, in_lo);
+    }
+    StagedNet<THREADS> regs;
+    net_fetch_fixed<THREADS, 3>(sq, regs);
+    if constexpr (RING) ring_tile_rows<THREADS, 4, true>(sq, R, row0, id_lo, in_lo);
+    put_input_tile<THREADS>(in_lo, L.x[0]);
+    net_put_fixed<THREADS, 3>(regs, L);
+    __syncthreads();
+    const int rt = 0, ct = wave;
+    const int col = ct * 16 + (lane & 15);
+#pragma unroll
+    for (int l = 0; l < 3; ++l) {
+        const int W = kMaxW;
+        const float* xin = L.x[l];
+        float* xout = L.x[l + 1];
+        f32x4 acc = l > 0 ? gemm_tile(xin, L.w[l], kMaxW, rt, ct) : gemm_tile(xin, L.w[l], round4(K0), rt, ct);
+        const float bias = L.bias[l][col];
+        const bool res = ((residual_bits >> l) & 1) != 0;
+        f32x2_g ya, yb, da, db;
+        gelu_parts2((f32x2_g){acc[0] + bias, acc[1] + bias}, ya, da);
+        gelu_parts2((f32x2_g){acc[2] + bias, acc[3] + bias}, yb, db);
+        const float yv[4] = {ya.x, ya.y, yb.x, yb.y};
+        out.zp[l][threadIdx.x] = f32x4{da.x, da.y, db.x, db.y};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = rt * 16 + 4 * (lane >> 4) + r;
+            float y = yv[r];
+            if (res) y += xin[row * kP + col];
+            xout[row * kP + col] = col < W ? y : 0.f;
+        }
+        __syncthreads();
+    }
+    if (wave == 0) {
+        const f32x4 raw = gemm_tile(L.x[3], L.head, round4(kMaxW), wave, 0);
+        if ((lane & 15) == 0) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) out.q[4 * (lane >> 4) + r] = raw[r] + L.head_bias[0];
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < 3; ++l) {           // x_1..x_3: four floats per thread and layer, rows dense
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i = threadIdx.x + u * THREADS;
+            out.x[l][i] = L.x[l + 1][(i >> 6) * kP + (i & 63)];
+        }
+    }
+}
+
 // RING: the rows and the stored actions come from the replay ring (`ring`), not from a gathered batch
 // SINGLE: every workgroup of the launch has one tile (n_tiles <= tile_groups: the train step's launches).  The two paths
 // are two instantiations chosen by ONE branch in the kernel, not branches along the way: with the paths interleaved in
@@ -2489,8 +2668,13 @@ __device__ __forceinline__ void pi_q_tiles(const ASAC_KARG PiQLaunch& a, PiQLds&
 static_assert(sizeof(PiQLaunch) <= 672, "kernel arguments of k_pi_sample_q (was 1 240 bytes as four MlpFwdArgs)");
 static_assert(sizeof(PiQLaunch) + sizeof(SidecarsDev) <= 4096, "kernel arguments of k_pi_sample_q");
 
-template <int NSC>
-__global__ __launch_bounds__(kPiQThreads) void k_pi_sample_q(const PiQLaunch m_by_value, const SidecarsT<NSC> sc) {
+// CRIDER: the launch also carries the online critics' forward on the stored pair, saved for the loaded Q-loss backward
+// (critic_forward_rider above), in a block range of its own behind the extra jobs and in front of the sidecars.  A new
+// instantiation: the others are the text they were.  The third kernel argument exists in it alone and is read through
+// the kernarg segment by the rider's workgroups only.
+template <int NSC, bool CRIDER = false>
+__global__ __launch_bounds__(kPiQThreads) void k_pi_sample_q(const PiQLaunch m_by_value, const SidecarsT<NSC> sc,
+                                                             const CriticRiderIn<CRIDER> rider_by_value) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     // (`m_by_value` sits at offset 0 of the kernarg segment; it is read through `m`, field by field, where used)
     const ASAC_KARG PiQLaunch& m = *static_cast<const ASAC_KARG PiQLaunch*>(kernarg_base());
@@ -2511,7 +2695,19 @@ __global__ __launch_bounds__(kPiQThreads) void k_pi_sample_q(const PiQLaunch m_b
         }
         return;
     }
-    const int xb = blk - fused_blocks;
+    int xb = blk - fused_blocks;
+    if constexpr (CRIDER) {
+        const ASAC_KARG CriticRiderIn<true>& rd = *reinterpret_cast<const ASAC_KARG CriticRiderIn<true>*>(
+            static_cast<const ASAC_KARG unsigned char*>(kernarg_base()) + critic_rider_karg_offset<PiQLaunch, SidecarsT<NSC>>());
+        const int rb = xb - m.x_blocks;
+        if (rb >= 0) {
+            if (rb < rd.blocks) {
+                critic_forward_rider<false>(rd, rb, smem_raw);
+                return;
+            }
+            xb -= rd.blocks;
+        }
+    }
     if (xb >= m.x_blocks) {
         sidecar_run<NSC, true>(sc, xb - m.x_blocks, reinterpret_cast<float*>(smem_raw));
         return;
@@ -2538,8 +2734,16 @@ struct PiQLaunchRing {
 };
 static_assert(offsetof(PiQLaunchRing, m) == 0 && sizeof(PiQLaunchRing) <= 768, "kernel arguments of k_pi_sample_q_ring");
 
-template <int NSC>
-__global__ __launch_bounds__(kPiQThreads) void k_pi_sample_q_ring(const PiQLaunchRing m_by_value, const SidecarsT<NSC> sc) {
+// (the rider's argument offsets as the code object's metadata has them: .args of the four CRIDER kernels)
+static_assert(critic_rider_karg_offset<PiQLaunch, SidecarsT<1>>() == 904 &&
+                  critic_rider_karg_offset<PiQLaunch, SidecarsDev>() == 1600 &&
+                  critic_rider_karg_offset<PiQLaunchRing, SidecarsT<1>>() == 1000 &&
+                  critic_rider_karg_offset<PiQLaunchRing, SidecarsDev>() == 1696 && sizeof(CriticRiderIn<true>) == 144,
+              "kernel-argument offsets of the critic-forward rider");
+
+template <int NSC, bool CRIDER = false>
+__global__ __launch_bounds__(kPiQThreads) void k_pi_sample_q_ring(const PiQLaunchRing m_by_value, const SidecarsT<NSC> sc,
+                                                                  const CriticRiderIn<CRIDER> rider_by_value) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const ASAC_KARG PiQLaunchRing& mr = *static_cast<const ASAC_KARG PiQLaunchRing*>(kernarg_base());
     const ASAC_KARG PiQLaunch& m = mr.m;
@@ -2552,7 +2756,19 @@ __global__ __launch_bounds__(kPiQThreads) void k_pi_sample_q_ring(const PiQLaunc
         else pi_q_tiles<false, true>(m, L, &mr.ring);
         return;
     }
-    const int xb = blk - fused_blocks;
+    int xb = blk - fused_blocks;
+    if constexpr (CRIDER) {
+        const ASAC_KARG CriticRiderIn<true>& rd = *reinterpret_cast<const ASAC_KARG CriticRiderIn<true>*>(
+            static_cast<const ASAC_KARG unsigned char*>(kernarg_base()) + critic_rider_karg_offset<PiQLaunchRing, SidecarsT<NSC>>());
+        const int rb = xb - m.x_blocks;
+        if (rb >= 0) {
+            if (rb < rd.blocks) {
+                critic_forward_rider<true>(rd, rb, smem_raw, &mr.ring);
+                return;
+            }
+            xb -= rd.blocks;
+        }
+    }
     if (xb >= m.x_blocks) {
         sidecar_run<NSC, true, true>(sc, xb - m.x_blocks, reinterpret_cast<float*>(smem_raw));
         return;
@@ -2789,8 +3005,10 @@ static int launch_forward_multi(const asac_mlp_job_t* jobs, int n_jobs, const Si
 #endif
 template <int TM>
 static int launch_backward(const char* where, const asac_mlp_desc_t* desc, MlpArgs& a, int E, int tiles, hipStream_t s,
-                           const RetIn<true>* ret = nullptr, const RiderIn<true>* rider = nullptr) {
+                           const RetIn<true>* ret = nullptr, const RiderIn<true>* rider = nullptr,
+                           const LoadedIn<true>* loaded = nullptr) {
     static bool attr_done = false, attr_wide = false, attr_stock = false, attr_ret = false, attr_rider = false;
+    static bool attr_loaded = false, attr_rider_loaded = false;
     const bool wide = wide_input(*desc);
     const bool stock = !wide && stock3(*desc, a.params, a.member_stride) && offsets32(a);
     constexpr int w8 = TM == 16 ? ASAC_BWD_WAVES : 0;                // (16-row tiles of the stock networks: see k_mlp_bwd)
@@ -2798,7 +3016,7 @@ static int launch_backward(const char* where, const asac_mlp_desc_t* desc, MlpAr
     auto launch = [&](auto kernel, bool& attr, size_t lds_limit, int threads, size_t lds,
                       const auto& ret_in) -> int {
         if (int rc = set_lds_limit(reinterpret_cast<const void*>(kernel), lds_limit, attr, where)) return rc;
-        ASAC_LAUNCH(kernel, dim3(tiles, E), dim3(threads), lds, s, a, ret_in, RiderIn<false>{});
+        ASAC_LAUNCH(kernel, dim3(tiles, E), dim3(threads), lds, s, a, ret_in, RiderIn<false>{}, LoadedIn<false>{});
         return 0;
     };
     const size_t lds = sizeof(MlpBwdLds<TM>);
@@ -2809,10 +3027,26 @@ static int launch_backward(const char* where, const asac_mlp_desc_t* desc, MlpAr
         if (!stock || TM * ret->v.n > stock_threads || lds_ret > 128 * 1024) return bad_arg(where);
         if (rider) {       // (asac_mlp_backward_qloss_return_rider_ok has said yes) a second plane of workgroups: the policy's tiles
             if constexpr (w8 == 16 && kPsThreads == 64 * w8) {
+                const size_t lds_both = lds_ret > sizeof(PsPiLds) ? lds_ret : sizeof(PsPiLds);
+                if (loaded) {      // (... and the critics' own forward loaded: asac_mlp_backward_qloss_return_loaded_ok)
+                    auto kernel = k_mlp_bwd<TM, false, 3, true, w8, true, true>;
+                    if (int rc = set_lds_limit(reinterpret_cast<const void*>(kernel), 128 * 1024, attr_rider_loaded, where)) return rc;
+                    ASAC_LAUNCH(kernel, dim3(tiles, E, 2), dim3(stock_threads), lds_both, s, a, *ret, *rider, *loaded);
+                    return 0;
+                }
                 auto kernel = k_mlp_bwd<TM, false, 3, true, w8, true>;
                 if (int rc = set_lds_limit(reinterpret_cast<const void*>(kernel), 128 * 1024, attr_rider, where)) return rc;
-                const size_t lds_both = lds_ret > sizeof(PsPiLds) ? lds_ret : sizeof(PsPiLds);
-                ASAC_LAUNCH(kernel, dim3(tiles, E, 2), dim3(stock_threads), lds_both, s, a, *ret, *rider);
+                ASAC_LAUNCH(kernel, dim3(tiles, E, 2), dim3(stock_threads), lds_both, s, a, *ret, *rider, LoadedIn<false>{});
+                return 0;
+            } else {
+                return bad_arg(where);
+            }
+        }
+        if (loaded) {
+            if constexpr (w8 == 16) {
+                auto kernel = k_mlp_bwd<TM, false, 3, true, w8, false, true>;
+                if (int rc = set_lds_limit(reinterpret_cast<const void*>(kernel), 128 * 1024, attr_loaded, where)) return rc;
+                ASAC_LAUNCH(kernel, dim3(tiles, E), dim3(stock_threads), lds_ret, s, a, *ret, RiderIn<false>{}, *loaded);
                 return 0;
             } else {
                 return bad_arg(where);
@@ -2843,12 +3077,12 @@ static void reduce_partials(const asac_mlp_desc_t* desc, const float* workspace,
 
 static int mlp_backward_common(const char* where, const asac_mlp_job_t& j, MlpArgs& a, float* grad_params, float* workspace,
                                int reduce_mode, float* loss_out, hipStream_t s, const RetIn<true>* ret = nullptr,
-                               const RiderIn<true>* rider = nullptr) {
+                               const RiderIn<true>* rider = nullptr, const LoadedIn<true>* loaded = nullptr) {
     const int tiles = (int)asac_mlp_backward_tiles(j.N, j.E);
     a.partial = grad_params ? workspace : nullptr;
     a.loss_partial = workspace ? workspace + (int64_t)tiles * j.E * j.member_stride : nullptr;
-    if (int rc = mlp_tile_rows(j.N, j.E) == 16 ? launch_backward<16>(where, j.desc, a, j.E, tiles, s, ret, rider)
-                                               : launch_backward<32>(where, j.desc, a, j.E, tiles, s, ret, rider))
+    if (int rc = mlp_tile_rows(j.N, j.E) == 16 ? launch_backward<16>(where, j.desc, a, j.E, tiles, s, ret, rider, loaded)
+                                               : launch_backward<32>(where, j.desc, a, j.E, tiles, s, ret, rider, loaded))
         return rc;
     if (grad_params && reduce_mode != ASAC_MLP_REDUCE_DEFER)
         reduce_partials(j.desc, workspace, tiles, j.E, j.member_stride, grad_params, reduce_mode,
@@ -3292,13 +3526,41 @@ int asac_policy_sample_q_forward_jobs_ok(const asac_pi_q_job_t* job, const asac_
     return job && pi_q_job_ok(*job) && pi_q_extras_ok(*job, extra_jobs, n_extra) ? 1 : 0;
 }
 
-int asac_policy_sample_q_forward(const asac_pi_q_job_t* job, const asac_mlp_job_t* extra_jobs, int n_extra,
-                                 const asac_sidecar_t* sidecars_host, int n_sidecars, void* stream) {
-    if (!job || !pi_q_job_ok(*job)) return bad_arg("asac_policy_sample_q_forward");
-    if (!pi_q_extras_ok(*job, extra_jobs, n_extra)) return bad_arg("asac_policy_sample_q_forward: extra job");
+}  // extern "C"
+
+// workgroups of the launch in front of its sidecars' (and its critic-forward rider's): the fused job's and the extra jobs'
+static int pi_q_front_blocks(const asac_pi_q_job_t& job, const asac_mlp_job_t* extra_jobs, int n_extra) {
+    const int E = job.q.E;
+    const int tiles = (int)((job.pi.N + 15) / 16);
+    const int cap = 256 / E > 0 ? 256 / E : 1;
+    int blocks = (tiles <= cap ? tiles : cap) * E;
+    for (int k = 0; k < n_extra; ++k) blocks += mlp_tile_groups(extra_jobs[k].N, extra_jobs[k].E, 1, 16) * extra_jobs[k].E;
+    return blocks;
+}
+
+// the device's CU count, read once: the first network launch holds one workgroup per CU (its LDS), so a grid beyond it
+// runs a second round of workgroups
+static int device_cu_count() {
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+            return 0;
+        return n;
+    }();
+    return cus;
+}
+
+// asac_policy_sample_q_forward and its saving form (CR: with the critic-forward rider `rd`)
+template <bool CR>
+static int policy_sample_q_forward(const char* where, const asac_pi_q_job_t* job, const asac_mlp_job_t* extra_jobs, int n_extra,
+                                   const asac_sidecar_t* sidecars_host, int n_sidecars, void* stream,
+                                   const CriticRiderIn<CR>& rd, int rider_blocks) {
+    if (!job || !pi_q_job_ok(*job)) return bad_arg(where);
+    if (!pi_q_extras_ok(*job, extra_jobs, n_extra)) return bad_arg((std::string(where) + ": extra job").c_str());
     SidecarsDev sc{};
     if (sidecars_prepare(sidecars_host, n_sidecars, sc, job->ring.ids != nullptr))
-        return bad_arg("asac_policy_sample_q_forward: sidecar");
+        return bad_arg((std::string(where) + ": sidecar").c_str());
     PiQLaunch m{};
     const asac_mlp_job_t p = pi_rows(job->pi);
     asac_mlp_job_t q = pi_rows(job->q);         // (its rows are the policy's: pi_q_job_ok)
@@ -3346,45 +3608,92 @@ int asac_policy_sample_q_forward(const asac_pi_q_job_t* job, const asac_mlp_job_
                           RingKeyArg{static_cast<const uint8_t*>(ak.src), static_cast<const uint8_t*>(ak.pad_row), ak.row_bytes,
                                      ak.pad_word}};
         static bool ring_attr = false, ring_attr1 = false;
-        if (int rc = set_lds_limit(reinterpret_cast<const void*>(k_pi_sample_q_ring<ASAC_MAX_SIDECARS>), sizeof(PiQLds),
+        if (int rc = set_lds_limit(reinterpret_cast<const void*>(k_pi_sample_q_ring<ASAC_MAX_SIDECARS, CR>), sizeof(PiQLds),
                                    ring_attr, "asac_policy_sample_q_forward: hipFuncSetAttribute"))
             return rc;
-        if (int rc = set_lds_limit(reinterpret_cast<const void*>(k_pi_sample_q_ring<1>), sizeof(PiQLds), ring_attr1,
+        if (int rc = set_lds_limit(reinterpret_cast<const void*>(k_pi_sample_q_ring<1, CR>), sizeof(PiQLds), ring_attr1,
                                    "asac_policy_sample_q_forward: hipFuncSetAttribute"))
             return rc;
         const SidecarsDev no_sc{};
         for (int rep = 0; rep < g_launch_repeat; ++rep) {
             const bool last = rep == g_launch_repeat - 1;
-            const dim3 grid((unsigned)(m.blocks + blocks + (last ? sc.blocks : 0)));
+            const dim3 grid((unsigned)(m.blocks + blocks + rider_blocks + (last ? sc.blocks : 0)));
             if (sc.n <= 1)
-                hipLaunchKernelGGL(k_pi_sample_q_ring<1>, grid, dim3(kPiQThreads), sizeof(PiQLds), as_stream(stream), mr,
-                                   sidecars_first<1>(last ? sc : no_sc));
+                hipLaunchKernelGGL((k_pi_sample_q_ring<1, CR>), grid, dim3(kPiQThreads), sizeof(PiQLds), as_stream(stream), mr,
+                                   sidecars_first<1>(last ? sc : no_sc), rd);
             else
-                hipLaunchKernelGGL(k_pi_sample_q_ring<ASAC_MAX_SIDECARS>, grid, dim3(kPiQThreads), sizeof(PiQLds),
-                                   as_stream(stream), mr, last ? sc : no_sc);
+                hipLaunchKernelGGL((k_pi_sample_q_ring<ASAC_MAX_SIDECARS, CR>), grid, dim3(kPiQThreads), sizeof(PiQLds),
+                                   as_stream(stream), mr, last ? sc : no_sc, rd);
         }
-        return finish_launch("asac_policy_sample_q_forward");
+        return finish_launch(where);
     }
     static bool attr_done = false;
     static bool attr_done1 = false;
-    if (int rc = set_lds_limit(reinterpret_cast<const void*>(k_pi_sample_q<ASAC_MAX_SIDECARS>), sizeof(PiQLds), attr_done,
+    if (int rc = set_lds_limit(reinterpret_cast<const void*>(k_pi_sample_q<ASAC_MAX_SIDECARS, CR>), sizeof(PiQLds), attr_done,
                                "asac_policy_sample_q_forward: hipFuncSetAttribute"))
         return rc;
-    if (int rc = set_lds_limit(reinterpret_cast<const void*>(k_pi_sample_q<1>), sizeof(PiQLds), attr_done1,
+    if (int rc = set_lds_limit(reinterpret_cast<const void*>(k_pi_sample_q<1, CR>), sizeof(PiQLds), attr_done1,
                                "asac_policy_sample_q_forward: hipFuncSetAttribute"))
         return rc;
     const SidecarsDev none{};
     for (int rep = 0; rep < g_launch_repeat; ++rep) {      // (repeat knob: only the last repetition carries the sidecars)
         const bool last = rep == g_launch_repeat - 1;
-        const dim3 grid((unsigned)(m.blocks + blocks + (last ? sc.blocks : 0)));
+        const dim3 grid((unsigned)(m.blocks + blocks + rider_blocks + (last ? sc.blocks : 0)));
         if (sc.n <= 1)
-            hipLaunchKernelGGL(k_pi_sample_q<1>, grid, dim3(kPiQThreads), sizeof(PiQLds), as_stream(stream), m,
-                               sidecars_first<1>(last ? sc : none));
+            hipLaunchKernelGGL((k_pi_sample_q<1, CR>), grid, dim3(kPiQThreads), sizeof(PiQLds), as_stream(stream), m,
+                               sidecars_first<1>(last ? sc : none), rd);
         else
-            hipLaunchKernelGGL(k_pi_sample_q<ASAC_MAX_SIDECARS>, grid, dim3(kPiQThreads), sizeof(PiQLds), as_stream(stream), m,
-                               last ? sc : none);
+            hipLaunchKernelGGL((k_pi_sample_q<ASAC_MAX_SIDECARS, CR>), grid, dim3(kPiQThreads), sizeof(PiQLds), as_stream(stream), m,
+                               last ? sc : none, rd);
     }
-    return finish_launch("asac_policy_sample_q_forward");
+    return finish_launch(where);
+}
+
+extern "C" {
+
+int asac_policy_sample_q_forward(const asac_pi_q_job_t* job, const asac_mlp_job_t* extra_jobs, int n_extra,
+                                 const asac_sidecar_t* sidecars_host, int n_sidecars, void* stream) {
+    return policy_sample_q_forward<false>("asac_policy_sample_q_forward", job, extra_jobs, n_extra, sidecars_host, n_sidecars,
+                                          stream, CriticRiderIn<false>{}, 0);
+}
+
+int asac_policy_sample_q_forward_saving_ok(const asac_pi_q_job_t* job, const asac_mlp_job_t* extra_jobs, int n_extra,
+                                           const asac_sidecar_t* sidecars_host, int n_sidecars,
+                                           const asac_mlp_job_t* online_job, const float* save) {
+    if (!job || !online_job || !save || (reinterpret_cast<uintptr_t>(save) & 15)) return 0;
+    if (!pi_q_job_ok(*job) || !pi_q_extras_ok(*job, extra_jobs, n_extra) || n_extra < 1) return 0;
+    // the online critics on the stored pair: the rows of extra job 0 (the target critics), a scalar-head stock network
+    const asac_mlp_job_t &o = *online_job, &t = extra_jobs[0];
+    if (!o.desc || !desc_ok(*o.desc) || o.E < 1 || o.N <= 0 || !o.x0 || !o.x1 || o.x0_window_T != 0 || t.x0_window_T != 0) return 0;
+    if (!stock3(*o.desc, o.params, o.member_stride) || !scalar_head(*o.desc) || o.desc->in1 <= 0) return 0;
+    if (o.N != t.N || o.x0 != t.x0 || o.x1 != t.x1 || o.x0_row_stride != t.x0_row_stride || o.x1_row_stride != t.x1_row_stride ||
+        o.x0_member_stride != 0 || o.x1_member_stride != 0 || t.x0_member_stride != 0 || t.x1_member_stride != 0 ||
+        o.desc->in0 != t.desc->in0 || o.desc->in1 != t.desc->in1)
+        return 0;
+    if (!job_fits32(o) || !fits32(o.member_stride * o.E)) return 0;
+    if (job->ring.ids && job->ring.x_j0 < 0) return 0;       // (ring rows: the stored pair comes through the ring too)
+    // the tiles are the sixteen-wave Q-loss backward's: 16 rows
+    if (mlp_tile_rows(o.N, o.E) != 16) return 0;
+    SidecarsDev sc{};            // (the launch itself must accept its sidecars; their workgroups are not counted below)
+    if (sidecars_prepare(sidecars_host, n_sidecars, sc, job->ring.ids != nullptr)) return 0;
+    // One workgroup per CU (the launch's LDS), dispatched in block order: the fused job's, the extra jobs' and the rider's
+    // workgroups must all be resident in the first round, or the rider would wait for a CU and land on the chain.  The
+    // sidecars' workgroups come behind them in the grid and are not counted: they are short, and where the grid exceeds
+    // the CUs it is their tail that takes the CUs the first of them free (the headline launch has 160 + 32 + 76 = 268
+    // workgroups on 256 CUs without any rider).
+    const int64_t front = (int64_t)pi_q_front_blocks(*job, extra_jobs, n_extra) + (o.N + 15) / 16 * o.E;
+    return front <= device_cu_count() ? 1 : 0;
+}
+
+int asac_policy_sample_q_forward_saving(const asac_pi_q_job_t* job, const asac_mlp_job_t* extra_jobs, int n_extra,
+                                        const asac_sidecar_t* sidecars_host, int n_sidecars, const asac_mlp_job_t* online_job,
+                                        float* save, void* stream) {
+    if (!asac_policy_sample_q_forward_saving_ok(job, extra_jobs, n_extra, sidecars_host, n_sidecars, online_job, save))
+        return bad_arg("asac_policy_sample_q_forward_saving");
+    const int rider_blocks = (int)((online_job->N + 15) / 16) * online_job->E;
+    const CriticRiderIn<true> rd{stock_job_arg(*online_job), save, rider_blocks, online_job->E};
+    return policy_sample_q_forward<true>("asac_policy_sample_q_forward_saving", job, extra_jobs, n_extra, sidecars_host,
+                                         n_sidecars, stream, rd, rider_blocks);
 }
 
 int asac_mlp_backward_qloss_return_ok(const asac_mlp_job_t* job, const asac_vtrace_args_t* ret) {
@@ -3422,7 +3731,7 @@ int asac_mlp_backward_qloss_return_rider_ok(const asac_mlp_job_t* job, const asa
 static int backward_qloss_return(const char* where, const asac_mlp_job_t* job, const float* target_q,
                                  const asac_vtrace_args_t* ret, const float* weights, float clip_eps, float* loss_out,
                                  float* grad_x0, float* grad_params, float* workspace, int reduce_mode,
-                                 const asac_mlp_job_t* pi_job, float* save, void* stream) {
+                                 const asac_mlp_job_t* pi_job, float* save, void* stream, const float* saved = nullptr) {
     auto refuse = [&](const char* why) { return bad_arg((std::string(where) + why).c_str()); };
     if (!bwd_job_ok(job) || !target_q || !ret || !grad_params || !workspace || clip_eps <= 0.f) return refuse("");
     if (!scalar_head(*job->desc)) return refuse(": not a scalar-head network");
@@ -3437,11 +3746,15 @@ static int backward_qloss_return(const char* where, const asac_mlp_job_t* job, c
     a.clip_eps = clip_eps;
     a.gx0 = grad_x0;
     RetIn<true> rv{*ret, vtrace_scan_lanes(ret->B, ret->n)};
+    const LoadedIn<true> ld{saved};
+    const LoadedIn<true>* loaded = saved ? &ld : nullptr;      // (the loaded entry points have asked their `_ok`)
     if (pi_job) {
         RiderIn<true> rd{stock_job_arg(pi_rows(*pi_job)), save};
-        return mlp_backward_common(where, *job, a, grad_params, workspace, reduce_mode, loss_out, as_stream(stream), &rv, &rd);
+        return mlp_backward_common(where, *job, a, grad_params, workspace, reduce_mode, loss_out, as_stream(stream), &rv, &rd,
+                                   loaded);
     }
-    return mlp_backward_common(where, *job, a, grad_params, workspace, reduce_mode, loss_out, as_stream(stream), &rv);
+    return mlp_backward_common(where, *job, a, grad_params, workspace, reduce_mode, loss_out, as_stream(stream), &rv, nullptr,
+                               loaded);
 }
 
 int asac_mlp_backward_qloss_return(const asac_mlp_job_t* job, const float* target_q, const asac_vtrace_args_t* ret,
@@ -3459,6 +3772,44 @@ int asac_mlp_backward_qloss_return_rider(const asac_mlp_job_t* job, const float*
         return bad_arg("asac_mlp_backward_qloss_return_rider: the policy job");
     return backward_qloss_return("asac_mlp_backward_qloss_return_rider", job, target_q, ret, weights, clip_eps, loss_out,
                                  grad_x0, grad_params, workspace, reduce_mode, pi_job, save, stream);
+}
+
+int64_t asac_critic_forward_save_floats(int64_t N, int E) {
+    return N > 0 && E > 0 ? (N + 15) / 16 * E * kSavedCriticFloats : 0;
+}
+
+int asac_mlp_backward_qloss_return_loaded_ok(const asac_mlp_job_t* job, const asac_vtrace_args_t* ret, const float* saved) {
+    if (!saved || (reinterpret_cast<uintptr_t>(saved) & 15) || !asac_mlp_backward_qloss_return_ok(job, ret)) return 0;
+    // the saved tiles are the sixteen-wave kernel's 16-row tiles, one per (tile, member)
+    return mlp_tile_rows(job->N, job->E) == 16 && ASAC_BWD_WAVES == 16 ? 1 : 0;
+}
+
+int asac_mlp_backward_qloss_return_loaded(const asac_mlp_job_t* job, const float* target_q, const asac_vtrace_args_t* ret,
+                                          const float* weights, float clip_eps, float* loss_out, float* grad_params,
+                                          float* workspace, int reduce_mode, const float* saved, void* stream) {
+    if (!asac_mlp_backward_qloss_return_loaded_ok(job, ret, saved))
+        return bad_arg("asac_mlp_backward_qloss_return_loaded: the saved forward");
+    return backward_qloss_return("asac_mlp_backward_qloss_return_loaded", job, target_q, ret, weights, clip_eps, loss_out,
+                                 nullptr, grad_params, workspace, reduce_mode, nullptr, nullptr, stream, saved);
+}
+
+int asac_mlp_backward_qloss_return_rider_loaded_ok(const asac_mlp_job_t* job, const asac_vtrace_args_t* ret,
+                                                   const asac_mlp_job_t* pi_job, const float* save, const float* saved) {
+    return asac_mlp_backward_qloss_return_rider_ok(job, ret, pi_job, save) &&
+                   asac_mlp_backward_qloss_return_loaded_ok(job, ret, saved)
+               ? 1
+               : 0;
+}
+
+int asac_mlp_backward_qloss_return_rider_loaded(const asac_mlp_job_t* job, const float* target_q,
+                                                const asac_vtrace_args_t* ret, const float* weights, float clip_eps,
+                                                float* loss_out, float* grad_params, float* workspace, int reduce_mode,
+                                                const asac_mlp_job_t* pi_job, float* save, const float* saved,
+                                                void* stream) {
+    if (!asac_mlp_backward_qloss_return_rider_loaded_ok(job, ret, pi_job, save, saved))
+        return bad_arg("asac_mlp_backward_qloss_return_rider_loaded: the policy job or the saved forward");
+    return backward_qloss_return("asac_mlp_backward_qloss_return_rider_loaded", job, target_q, ret, weights, clip_eps,
+                                 loss_out, nullptr, grad_params, workspace, reduce_mode, pi_job, save, stream, saved);
 }
 
 int asac_mlp_backward_qloss(const asac_mlp_job_t* job, const float* target_q, const float* y, const float* weights,

@@ -361,6 +361,20 @@ _SIGNATURES = {
     'asac_mlp_backward_qloss_return_rider': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.POINTER(VtraceArgs), C.c_void_p,
                                                        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                        C.POINTER(MlpJob), C.c_void_p, C.c_void_p]),
+    'asac_mlp_backward_qloss_return_loaded_ok': (C.c_int, [C.POINTER(MlpJob), C.POINTER(VtraceArgs), C.c_void_p]),
+    'asac_mlp_backward_qloss_return_loaded': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.POINTER(VtraceArgs), C.c_void_p,
+                                                        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                        C.c_void_p]),
+    'asac_mlp_backward_qloss_return_rider_loaded_ok': (C.c_int, [C.POINTER(MlpJob), C.POINTER(VtraceArgs), C.POINTER(MlpJob),
+                                                                 C.c_void_p, C.c_void_p]),
+    'asac_mlp_backward_qloss_return_rider_loaded': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.POINTER(VtraceArgs), C.c_void_p,
+                                                              C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                              C.POINTER(MlpJob), C.c_void_p, C.c_void_p, C.c_void_p]),
+    'asac_critic_forward_save_floats': (C.c_int64, [C.c_int64, C.c_int]),
+    'asac_policy_sample_q_forward_saving_ok': (C.c_int, [C.POINTER(PiQJob), C.POINTER(MlpJob), C.c_int, C.POINTER(Sidecar),
+                                                         C.c_int, C.POINTER(MlpJob), C.c_void_p]),
+    'asac_policy_sample_q_forward_saving': (C.c_int, [C.POINTER(PiQJob), C.POINTER(MlpJob), C.c_int, C.POINTER(Sidecar),
+                                                      C.c_int, C.POINTER(MlpJob), C.c_void_p, C.c_void_p]),
     'asac_policy_step_fused_loaded_ok': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.POINTER(MlpDesc), C.c_void_p,
                                                    C.c_int64, C.c_int64, C.c_void_p]),
     'asac_policy_step_fused_loaded': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.POINTER(MlpDesc), C.c_void_p,
@@ -1414,6 +1428,44 @@ def policy_sample_q_forward(job: PiQJob, extra_jobs=(), sidecars=None):
            'asac_policy_sample_q_forward')
 
 
+def critic_forward_save_floats(N: int, E: int) -> int:
+    """floats of the buffer the critic-forward rider saves an [E][N] forward in (`policy_sample_q_forward_saving`)"""
+    return int(load().asac_critic_forward_save_floats(int(N), int(E)))
+
+
+def policy_sample_q_forward_saving_ok(job: PiQJob, extra_jobs, sidecars, online_job: MlpJob, save) -> bool:
+    """may `policy_sample_q_forward(job, extra_jobs, sidecars)` also carry the online critics' forward `online_job` on the
+    rows of `extra_jobs[0]` (saved in `save`) as a rider?  (Among the conditions: the workgroups in front of the sidecars' —
+    the fused job's, the extra jobs', the rider's — fit the device's CUs.)"""
+    extra_jobs = list(extra_jobs)
+    arr = (MlpJob * len(extra_jobs))(*extra_jobs) if extra_jobs else None
+    sc, n_sc = _sidecar_array(sidecars)
+    return bool(load().asac_policy_sample_q_forward_saving_ok(C.byref(job), arr, len(extra_jobs), sc, n_sc,
+                                                              C.byref(online_job) if online_job is not None else None,
+                                                              _p(save)))
+
+
+def _policy_sample_q_forward_saving(job: PiQJob, extra_jobs, sidecars, online_job: MlpJob, save):
+    """`policy_sample_q_forward` with the online critics' forward `online_job` (on the rows of `extra_jobs[0]`) riding on
+    further workgroups of the launch: `save` (float32, `critic_forward_save_floats(N, E)`) receives what
+    `mlp_backward_qloss_return_loaded` reads.  The launch's own outputs are `policy_sample_q_forward`'s, bit for bit."""
+    global _last_work
+    _last_work = (mlp_flops(job.pi.desc.contents, 1, job.pi.N) + mlp_flops(job.q.desc.contents, job.q.E, job.q.N)
+                  + sum(mlp_flops(j.desc.contents, j.E, j.N) for j in extra_jobs) + _pass_flops(online_job))
+    extra_jobs = list(extra_jobs)
+    assert 1 <= len(extra_jobs) <= MLP_MAX_JOBS
+    assert save.dtype == torch.float32 and save.is_contiguous()
+    assert save.numel() >= critic_forward_save_floats(online_job.N, online_job.E)
+    arr = (MlpJob * len(extra_jobs))(*extra_jobs)
+    sc, n_sc = _sidecar_array(sidecars)
+    _check(load().asac_policy_sample_q_forward_saving(C.byref(job), arr, len(extra_jobs), sc, n_sc, C.byref(online_job),
+                                                      _p(save), _stream()), 'asac_policy_sample_q_forward_saving')
+
+
+# (one launch of the step under the name it has without the rider: the kernel tables key on it)
+policy_sample_q_forward_saving = _profiled(_policy_sample_q_forward_saving, 'asac_policy_sample_q_forward')
+
+
 def mlp_backward_workspace(member_stride, E, N) -> int:
     return int(load().asac_mlp_backward_workspace(member_stride, E, N))
 
@@ -1494,6 +1546,40 @@ def _mlp_backward_qloss_return_rider(job: MlpJob, target_q, ret: VtraceArgs, wei
 
 # (one launch of the step under the name it has without the rider: the kernel tables key on it)
 mlp_backward_qloss_return_rider = _profiled(_mlp_backward_qloss_return_rider, 'asac_mlp_backward_qloss_return')
+
+
+def mlp_backward_qloss_return_loaded_ok(job: MlpJob, ret: VtraceArgs, saved, pi_job=None, save=None) -> bool:
+    """may the Q-loss backward load the critics' forward from `saved` (`policy_sample_q_forward_saving`)?  With `pi_job`:
+    ... while carrying the policy-forward rider (`mlp_backward_qloss_return_rider_ok`)"""
+    if pi_job is None:
+        return bool(load().asac_mlp_backward_qloss_return_loaded_ok(C.byref(job), C.byref(ret), _p(saved)))
+    return bool(load().asac_mlp_backward_qloss_return_rider_loaded_ok(C.byref(job), C.byref(ret), C.byref(pi_job), _p(save),
+                                                                      _p(saved)))
+
+
+def _mlp_backward_qloss_return_loaded(job: MlpJob, target_q, ret: VtraceArgs, weights, clip_eps, loss_out, grad_params,
+                                      workspace, reduce_mode, saved, pi_job=None, save=None):
+    """`mlp_backward_qloss_return` (with `pi_job` / `save`: `mlp_backward_qloss_return_rider`) LOADING the critics' forward
+    on the job's rows from `saved` instead of recomputing it: same slabs, loss and y, bit for bit.  No input gradient."""
+    global _last_work
+    _last_work = _pass_flops(job, backward=True) + (_pass_flops(pi_job) if pi_job is not None else 0)
+    E, N = job.E, job.N
+    assert target_q.is_contiguous() and target_q.numel() == E * N
+    assert saved.dtype == torch.float32 and saved.is_contiguous() and saved.numel() >= critic_forward_save_floats(N, E)
+    if pi_job is None:
+        _check(load().asac_mlp_backward_qloss_return_loaded(C.byref(job), _p(target_q), C.byref(ret), _p(weights),
+                                                            float(clip_eps), _p(loss_out), _p(grad_params), _p(workspace),
+                                                            int(reduce_mode), _p(saved), _stream()),
+               'asac_mlp_backward_qloss_return_loaded')
+        return
+    assert save.dtype == torch.float32 and save.is_contiguous() and save.numel() >= policy_forward_save_floats(pi_job.N)
+    _check(load().asac_mlp_backward_qloss_return_rider_loaded(C.byref(job), _p(target_q), C.byref(ret), _p(weights),
+                                                              float(clip_eps), _p(loss_out), _p(grad_params), _p(workspace),
+                                                              int(reduce_mode), C.byref(pi_job), _p(save), _p(saved),
+                                                              _stream()), 'asac_mlp_backward_qloss_return_rider_loaded')
+
+
+mlp_backward_qloss_return_loaded = _profiled(_mlp_backward_qloss_return_loaded, 'asac_mlp_backward_qloss_return')
 
 
 @_profiled

@@ -625,6 +625,27 @@ int asac_policy_sample_q_forward_jobs_ok(const asac_pi_q_job_t* job, const asac_
 int asac_policy_sample_q_forward(const asac_pi_q_job_t* job, const asac_mlp_job_t* extra_jobs, int n_extra,
                                  const asac_sidecar_t* sidecars_host, int n_sidecars, void* stream);
 
+/* asac_policy_sample_q_forward carrying the CRITIC-FORWARD RIDER: further four-wave workgroups of the same launch (a block
+ * range behind the extra jobs and in front of the sidecars, one per 16-row tile and member) run the ONLINE critics'
+ * forward `online_job` (stock scalar-head ensemble, E members) on the stored pair — the rows of extra job 0, read from
+ * the static batch or, with ring-addressed rows, through the ring description extra job 0 uses — and save per (tile,
+ * member), all 16 rows (rows >= N evaluated on zeros), what the Q-loss backward's forward recompute produces, bit for bit:
+ *   save [tiles][E][6160] floats = x_1..x_3 [3][16][64] | gelu'(z_l) [3][4 waves][64 lanes][4] (the MFMA C fragment each
+ *   lane holds) | raw q [16] (head bias added);  asac_critic_forward_save_floats(N, E) floats, 16-byte aligned.
+ * asac_mlp_backward_qloss_return_loaded reads it.  The launch's own outputs are asac_policy_sample_q_forward's, bit for
+ * bit; the rider reads nothing this launch writes.  `_ok`: what asac_policy_sample_q_forward accepts (sidecars included),
+ * n_extra >= 1, an online job on extra job 0's rows whose backward runs 16-row tiles, a save buffer, and no more workgroups
+ * in front of the sidecars' (the fused job's, the extra jobs', the rider's) than the device has CUs: the launch holds one
+ * workgroup per CU and dispatches in block order, so beyond that the rider would wait for a second round.  The sidecars'
+ * own workgroups follow in the grid and are not counted. */
+int64_t asac_critic_forward_save_floats(int64_t N, int E);
+int asac_policy_sample_q_forward_saving_ok(const asac_pi_q_job_t* job, const asac_mlp_job_t* extra_jobs, int n_extra,
+                                           const asac_sidecar_t* sidecars_host, int n_sidecars,
+                                           const asac_mlp_job_t* online_job, const float* save);
+int asac_policy_sample_q_forward_saving(const asac_pi_q_job_t* job, const asac_mlp_job_t* extra_jobs, int n_extra,
+                                        const asac_sidecar_t* sidecars_host, int n_sidecars, const asac_mlp_job_t* online_job,
+                                        float* save, void* stream);
+
 #define ASAC_MLP_REDUCE_OVERWRITE 0
 #define ASAC_MLP_REDUCE_ACCUMULATE 1
 #define ASAC_MLP_REDUCE_DEFER 2
@@ -688,6 +709,24 @@ int asac_mlp_backward_qloss_return_rider(const asac_mlp_job_t* job, const float*
                                          const float* weights, float clip_eps, float* loss_out, float* grad_x0,
                                          float* grad_params, float* workspace, int reduce_mode, const asac_mlp_job_t* pi_job,
                                          float* save, void* stream);
+
+/* asac_mlp_backward_qloss_return / _rider LOADING the critics' forward instead of recomputing it: `saved` is what
+ * asac_policy_sample_q_forward_saving wrote for the SAME parameters and the same rows (x0 | x1) of `job` (the caller's
+ * responsibility: neither may have changed in between).  The tile's x_1..x_3, gelu' fragments and raw q are requested
+ * with the weights; the launch then computes what the plain form computes, bit for bit — slabs, loss, y_out.  No input
+ * gradient (no grad_x0: the first layer's weights, which only that product reads, are not even fetched).
+ * `_ok`: the plain form's `_ok`, 16-row tiles and a 16-byte aligned `saved`. */
+int asac_mlp_backward_qloss_return_loaded_ok(const asac_mlp_job_t* job, const asac_vtrace_args_t* ret, const float* saved);
+int asac_mlp_backward_qloss_return_loaded(const asac_mlp_job_t* job, const float* target_q, const asac_vtrace_args_t* ret,
+                                          const float* weights, float clip_eps, float* loss_out, float* grad_params,
+                                          float* workspace, int reduce_mode, const float* saved, void* stream);
+int asac_mlp_backward_qloss_return_rider_loaded_ok(const asac_mlp_job_t* job, const asac_vtrace_args_t* ret,
+                                                   const asac_mlp_job_t* pi_job, const float* save, const float* saved);
+int asac_mlp_backward_qloss_return_rider_loaded(const asac_mlp_job_t* job, const float* target_q,
+                                                const asac_vtrace_args_t* ret, const float* weights, float clip_eps,
+                                                float* loss_out, float* grad_params, float* workspace, int reduce_mode,
+                                                const asac_mlp_job_t* pi_job, float* save, const float* saved,
+                                                void* stream);
 
 /* The policy step's Q backward (sac_base.py:1896-1903): the gradient of mean_b(-min_{e in subset} q_e)
  * w.r.t. the ensemble outputs is formed on chip from the value table q_table [E][N] the preceding

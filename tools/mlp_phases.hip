@@ -5,6 +5,10 @@
 // rows; its side waves (threads 256, 320, 384) stamp the end of their two steps.  The one-launch policy step is stamped
 // three times: with the action given, with the action sampled inside the launch, and with the action given and the
 // policy's forward loaded from a saved tile (the headline step's form; the saved values are zeros here: timing only).
+// The Q-loss backward is also stamped in the form that makes its own n-step return (n = 4, the headline step's launch) and
+// in that form LOADING the critics' forward (no stamps 20..24: the recompute is not in that instantiation; the row between
+// stamps 1 and 2 is the return's scan and the fragment requests).  The forward is stamped again with the stored pair's
+// extra job, without and with the critic-forward rider's workgroups beside the chain (workgroup 0 is a chain workgroup).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Iinclude -Iadvanced-soft-actor-critic_amd/csrc \
 //         tools/mlp_phases.hip -o tools/mlp_phases
 #define ASAC_MLP_STAMPS 1
@@ -54,14 +58,36 @@ int main() {
     jq.desc = &dq, jq.params = params, jq.member_stride = stride, jq.E = E, jq.N = N;
     jq.x0 = x0, jq.x0_row_stride = S, jq.x1 = x1, jq.x1_row_stride = A;
     jp = jq, jp.desc = &dp, jp.E = 1, jp.x1 = nullptr, jp.x1_row_stride = 0;
-    for (int mode = 0; mode < 3; ++mode) {
+    // the return target of the two `_return` modes: n = 4 steps, no importance ratios (zeros: timing only)
+    const int n_ret = 4;
+    float *rq, *rlogp, *rrew, *rratio;
+    uint8_t* rmask;
+    hipMalloc(&rq, E * N * (n_ret + 1) * 4); hipMemset(rq, 0, E * N * (n_ret + 1) * 4);
+    hipMalloc(&rlogp, N * (n_ret + 1) * 4); hipMemset(rlogp, 0, N * (n_ret + 1) * 4);
+    hipMalloc(&rrew, N * n_ret * 4); hipMemset(rrew, 0, N * n_ret * 4);
+    hipMalloc(&rratio, n_ret * 4); hipMemset(rratio, 0, n_ret * 4);
+    hipMalloc(&rmask, N * n_ret); hipMemset(rmask, 0, N * n_ret);
+    asac_vtrace_args_t ret{};
+    ret.q = rq, ret.q_stride_e = (int64_t)N * (n_ret + 1), ret.q_stride_b = n_ret + 1, ret.q_stride_t = 1, ret.E_sample = E;
+    ret.logp = rlogp, ret.log_alpha = la, ret.reward = rrew, ret.reward_stride = n_ret;
+    ret.done = rmask, ret.last_mask = rmask, ret.padding_mask = rmask, ret.mask_stride = n_ret;
+    ret.gamma_ratio = rratio, ret.lambda_ratio = rratio, ret.gamma = 0.99f, ret.v_rho = 1.f, ret.v_c = 1.f;
+    ret.B = N, ret.n = n_ret, ret.y_out = y;
+    float* csaved = nullptr;
+    hipMalloc(&csaved, asac_critic_forward_save_floats(N, E) * 4); hipMemset(csaved, 0, asac_critic_forward_save_floats(N, E) * 4);
+    for (int mode = 0; mode < 5; ++mode) {
         double acc[24] = {0};
         const int reps = 200;
+        int bad = 0;
         for (int r = 0; r < reps; ++r) {
             if (mode == 0)
                 asac_mlp_backward_qloss(&jq, tq, y, nullptr, 0.2f, loss, nullptr, grad, ws, ASAC_MLP_REDUCE_DEFER, nullptr);
             else if (mode == 1)
                 asac_mlp_backward_policy_q(&jq, qt, nullptr, E, g1, nullptr);
+            else if (mode == 3)
+                bad |= asac_mlp_backward_qloss_return(&jq, tq, &ret, nullptr, 0.2f, loss, nullptr, grad, ws, ASAC_MLP_REDUCE_DEFER, nullptr);
+            else if (mode == 4)
+                bad |= asac_mlp_backward_qloss_return_loaded(&jq, tq, &ret, nullptr, 0.2f, loss, grad, ws, ASAC_MLP_REDUCE_DEFER, csaved, nullptr);
             else
                 asac_mlp_backward_policy_sample(&jp, eps, ga, E, la, grad, ws, ASAC_MLP_REDUCE_DEFER, nullptr);
             hipDeviceSynchronize();
@@ -74,12 +100,17 @@ int main() {
             acc[11] += (double)(st[17] - st[16]) / 100.0;
             acc[12] += (double)(st[18] - st[17]) / 100.0;
             acc[13] += (double)(st[6] - st[18]) / 100.0;
-            for (int i = 0; i < 4; ++i) acc[14 + i] += (double)(st[21 + i] - st[20 + i]) / 100.0;
+            if (mode != 4)
+                for (int i = 0; i < 4; ++i) acc[14 + i] += (double)(st[21 + i] - st[20 + i]) / 100.0;
         }
         static const char* names[] = {"", "staging", "recompute", "loss / head mode", "head grads + g", "reverse L3", "reverse L2",
                                       "reverse L1", "input grads / end"};
-        printf("%s: workgroup (0,0) total %.2f us\n", mode == 0 ? "backward_qloss" : mode == 1 ? "backward_policy_q" : "backward_policy_sample", acc[0] / reps);
-        for (int i = 1; i < 9; ++i) printf("   %-18s %6.2f us\n", names[i], acc[i] / reps);
+        printf("%s: workgroup (0,0) total %.2f us%s\n",
+               mode == 0 ? "backward_qloss" : mode == 1 ? "backward_policy_q" : mode == 2 ? "backward_policy_sample"
+               : mode == 3 ? "backward_qloss_return" : "backward_qloss_return_loaded", acc[0] / reps, bad ? "  [the launch was refused]" : "");
+        for (int i = 1; i < 9; ++i)
+            printf("   %-18s %6.2f us\n", mode == 4 && i == 2 ? "scan + fragment requests" : names[i], acc[i] / reps);
+        if (mode != 4)
         printf("   recompute layer 2 in detail: gemm %.2f, gelu %.2f, LDS write %.2f, barrier %.2f\n", acc[14] / reps, acc[15] / reps,
                acc[16] / reps, acc[17] / reps);
         if (mode != 1)
@@ -156,11 +187,25 @@ int main() {
         rjob.ring.j0 = 0; rjob.ring.x_j0 = -1;
         rjob.ring.x0.src = obs_ring; rjob.ring.x0.row_bytes = S * 4; rjob.ring.x0.pad_mode = ASAC_PAD_KEEP;
         rjob.ring.action.src = act_ring; rjob.ring.action.row_bytes = A * 4; rjob.ring.action.pad_mode = ASAC_PAD_WORD;
-        for (int form = 0; form < 2; ++form) {
+        // forms 2..5: with the target critics on the stored pair as extra job 0 (ring rows: read through the ring, window row
+        // 0), without (2, 4) and with (3, 5) the critic-forward rider on 32 further workgroups
+        float* xq;
+        hipMalloc(&xq, E * N * 4);
+        asac_mlp_job_t jx = jq;
+        jx.out = xq;
+        asac_pi_q_job_t rjob_x = rjob;
+        rjob_x.ring.x_j0 = 0; rjob_x.ring.x_action_offset = 0;
+        for (int form = 0; form < 6; ++form) {
             double acc2[10] = {0}, side[6] = {0};
             int bad = 0;
+            const bool ringf = form == 1 || form >= 4;
             for (int r = 0; r < reps; ++r) {
-                bad |= asac_policy_sample_q_forward(form ? &rjob : &job, nullptr, 0, nullptr, 0, nullptr);
+                if (form < 2)
+                    bad |= asac_policy_sample_q_forward(form ? &rjob : &job, nullptr, 0, nullptr, 0, nullptr);
+                else if (form == 2 || form == 4)
+                    bad |= asac_policy_sample_q_forward(ringf ? &rjob_x : &job, &jx, 1, nullptr, 0, nullptr);
+                else
+                    bad |= asac_policy_sample_q_forward_saving(ringf ? &rjob_x : &job, &jx, 1, nullptr, 0, &jq, csaved, nullptr);
                 hipDeviceSynchronize();
                 unsigned long long st[32];
                 hipMemcpyFromSymbol(st, HIP_SYMBOL(asac::g_mlp_stamps), sizeof st);
@@ -173,7 +218,8 @@ int main() {
             // layer ends at the barrier that also waits for the side waves to retire)
             static const char* names2[] = {"", "staging", "policy forward", "policy head", "sampling", "actions -> tile",
                                            "critic forward", "critic head"};
-            printf("policy_sample_q_forward%s: workgroup 0 total %.2f us%s\n", form ? " (ring rows)" : "", acc2[0] / reps,
+            printf("policy_sample_q_forward%s%s: workgroup 0 total %.2f us%s\n", ringf ? " (ring rows)" : "",
+                   form < 2 ? "" : (form & 1) ? " + stored pair + critic-forward rider" : " + stored pair", acc2[0] / reps,
                    bad ? "  [the launch was refused]" : "");
             for (int i = 1; i <= 7; ++i) printf("   %-18s %6.2f us\n", names2[i], acc2[i] / reps);
             printf("   critic forward, first layer up to its barrier: %.2f us\n", acc2[8] / reps);

@@ -590,19 +590,32 @@ __device__ __forceinline__ void ring_tile_rows(const StageScalars& q, const Ring
     }
 }
 
-// FWD = false (a backward that loads its forward and forms no input gradient): nothing reads the first layer's weights or
-// the biases — they are not requested, and zeros take their places
+// Every word of the network is requested ONCE: the first layer's 64 x K0 matrix flat (slot u is word u * THREADS + t of
+// it, and only the slots it has are issued: one at the stock critics' K0 = 8, not one matrix row per wave instruction),
+// the NB bias vectors by the first 64 NB threads in one instruction, the head bias by the first kHeadPad threads.
+// FWD = false (a backward that loads its forward and forms no input gradient): nothing reads the first layer's weights,
+// the biases or the head bias — they are neither requested nor written, and their LDS words keep what they held
+template <int THREADS>
+__device__ __forceinline__ bool w0_slot(int u, int K0) { return u == 0 || u * THREADS < kMaxW * K0; }   // (uniform)
+// "this wave has the value": a register a load fills and only some waves store (see loads_landed) gets a consumer on
+// every wave, so that its wait is a counted one here and not a full vmcnt(0) wherever the register is next used
+__device__ __forceinline__ void staged_use(float v) { asm volatile("" ::"v"(v)); }
+
 template <int THREADS, int NB, bool FWD = true>
 __device__ __forceinline__ void net_fetch_fixed(const StageScalars& q, StagedNet<THREADS>& r) {
     constexpr int U = 4096 / THREADS;
+    static_assert(kMaxW * NB <= THREADS, "one bias word per thread");
     const rsrc_t rp = make_rsrc(q.P);
     const int K0 = q.in0 + q.in1;
+    if constexpr (FWD) {
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int i = threadIdx.x + u * THREADS;
-        const int rr = i >> 6, c = i & 63;
-        if constexpr (FWD) r.w[0][u] = __builtin_bit_cast(float, buf_ld(rp, c < K0 ? (unsigned)(q.w_off[0] + rr * K0 + c) * 4u : kOob));
-        else r.w[0][u] = 0.f;
+        for (int u = 0; u < U; ++u) {
+            r.w[0][u] = 0.f;
+            if (w0_slot<THREADS>(u, K0)) {
+                const int j = threadIdx.x + u * THREADS;
+                r.w[0][u] = __builtin_bit_cast(float, buf_ld(rp, j < kMaxW * K0 ? (unsigned)(q.w_off[0] + j) * 4u : kOob));
+            }
+        }
     }
 #pragma unroll
     for (int l = 1; l < NB; ++l) {
@@ -613,10 +626,17 @@ __device__ __forceinline__ void net_fetch_fixed(const StageScalars& q, StagedNet
             for (int k = 0; k < 4; ++k) r.w[l][4 * u + k] = __builtin_bit_cast(float, (int)t[k]);
         }
     }
+    if constexpr (FWD) {
+        const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        int boff = q.b_off[0];
+        ASAC_PIN(boff);      // (values, not addresses: a select between the struct's words becomes an indexed scratch load)
 #pragma unroll
-    for (int l = 0; l < NB; ++l) {
-        if constexpr (FWD) r.bias[l] = __builtin_bit_cast(float, buf_ld(rp, (unsigned)(q.b_off[l] + (threadIdx.x & 63)) * 4u));
-        else r.bias[l] = 0.f;
+        for (int l = 1; l < NB; ++l) {
+            int b = q.b_off[l];
+            ASAC_PIN(b);
+            boff = wv == l ? b : boff;
+        }
+        r.bias[0] = __builtin_bit_cast(float, buf_ld(rp, wv < NB ? (unsigned)(boff + (threadIdx.x & 63)) * 4u : kOob));
     }
     const int h0 = q.h0, h1 = q.h1;
 #pragma unroll
@@ -627,42 +647,63 @@ __device__ __forceinline__ void net_fetch_fixed(const StageScalars& q, StagedNet
         const int idx = second ? q.hw1 + (o - h0) * kMaxW + c : q.hw0 + o * kMaxW + c;
         r.head[u] = __builtin_bit_cast(float, buf_ld(rp, (first || second) ? (unsigned)idx * 4u : kOob));
     }
-    {
-        const int o = threadIdx.x & 15;
+    if constexpr (FWD) {
+        const int o = threadIdx.x;
         const bool first = o < h0, second = !first && o < h0 + h1;
         const int idx = second ? q.hb1 + o - h0 : q.hb0 + o;
-        r.head_bias = __builtin_bit_cast(float, buf_ld(rp, (first || second) ? (unsigned)idx * 4u : kOob));
+        r.head_bias = __builtin_bit_cast(float, buf_ld(rp, (o < kHeadPad && (first || second)) ? (unsigned)idx * 4u : kOob));
     }
 }
 
-template <int THREADS, int NB, typename LDS>
-__device__ __forceinline__ void net_put_fixed(const StagedNet<THREADS>& r, LDS& L) {
+// `q`: the scalars net_fetch_fixed had.  The first layer's tile: the columns >= K0 of every row
+// are zeroed by position, the words that came flat are scattered to (j / K0, j % K0) — disjoint words, no order between
+// the two.  j < 4096 and K0 <= 64: the quotient of (j + 0.5) / K0 lies at least 1/128 from an integer, far beyond what
+// the approximate reciprocal and the rounding of the product move it by — the truncation is floor(j / K0) exactly.
+template <int THREADS, int NB, bool FWD = true, typename LDS>
+__device__ __forceinline__ void net_put_fixed(const StageScalars& q, const StagedNet<THREADS>& r, LDS& L) {
     constexpr int U = 4096 / THREADS;
+    [[maybe_unused]] int K0 = q.in0 + q.in1;
+    ASAC_PIN(K0);        // (the slot conditions are formed again here, not carried from the fetch as lane masks)
+    if constexpr (FWD) {
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int i = threadIdx.x + u * THREADS;
-        L.w[0][(i >> 6) * kP + (i & 63)] = r.w[0][u];
+        for (int u = 0; u < U; ++u) {
+            const int i = threadIdx.x + u * THREADS;
+            if ((i & 63) >= K0) L.w[0][(i >> 6) * kP + (i & 63)] = 0.f;
+        }
+        const float inv = __builtin_amdgcn_rcpf((float)K0);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (w0_slot<THREADS>(u, K0)) {
+                const int j = threadIdx.x + u * THREADS;
+                const int row = (int)(((float)j + 0.5f) * inv);
+                if (j < kMaxW * K0) L.w[0][row * kP + (j - row * K0)] = r.w[0][u];
+                staged_use(r.w[0][u]);
+            }
+        }
     }
 #pragma unroll
     for (int l = 1; l < NB; ++l) {
 #pragma unroll
         for (int u = 0; u < U / 4; ++u) {
-            const int q = threadIdx.x + u * THREADS;   // float4 index: row q/16, col 4*(q%16)
-            float2* o2 = reinterpret_cast<float2*>(L.w[l] + (q >> 4) * kP + ((q & 15) << 2));
+            const int f = threadIdx.x + u * THREADS;   // float4 index: row f/16, col 4*(f%16)
+            float2* o2 = reinterpret_cast<float2*>(L.w[l] + (f >> 4) * kP + ((f & 15) << 2));
             o2[0] = make_float2(r.w[l][4 * u], r.w[l][4 * u + 1]);
             o2[1] = make_float2(r.w[l][4 * u + 2], r.w[l][4 * u + 3]);
         }
     }
-    if (threadIdx.x < kMaxW) {
-#pragma unroll
-        for (int l = 0; l < NB; ++l) L.bias[l][threadIdx.x] = r.bias[l];
+    if constexpr (FWD) {
+        if (threadIdx.x < kMaxW * NB) (&L.bias[0][0])[threadIdx.x] = r.bias[0];
+        staged_use(r.bias[0]);
     }
 #pragma unroll
     for (int u = 0; u < 1024 / THREADS; ++u) {
         const int i = threadIdx.x + u * THREADS;
         L.head[(i >> 6) * kP + (i & 63)] = r.head[u];
     }
-    if (threadIdx.x < kHeadPad) L.head_bias[threadIdx.x] = r.head_bias;
+    if constexpr (FWD) {
+        if (threadIdx.x < kHeadPad) L.head_bias[threadIdx.x] = r.head_bias;
+        staged_use(r.head_bias);
+    }
 }
 
 template <int TM>
@@ -721,7 +762,7 @@ __device__ __forceinline__ void mlp_fwd_tiles(const MlpFwdArgs& a, const int e, 
         net_fetch_fixed<THREADS, NB>(q, regs);
         if constexpr (RING) ring_tile_rows<THREADS, 4, true>(q, *ring, (int64_t)tile0 * TM, id_lo, in_lo);
         put_input_tile<THREADS>(in_lo, L.xs[0]);
-        net_put_fixed<THREADS, NB>(regs, L);
+        net_put_fixed<THREADS, NB>(q, regs, L);
     } else {
         float in_lo[4], in_hi[4];
         fetch_input_tile<THREADS, WINDOW>(a, e, (int64_t)tile0 * TM, in_lo);
@@ -1056,7 +1097,8 @@ constexpr size_t rider_karg_offset();
 // saved it on workgroups of its own (critic_forward_rider below: the recompute's statements on the same rows and
 // parameters, SavedCriticTile per (tile, member)).  The tile is requested with the weights: x_1..x_3 go straight into
 // L.x[1..3] and the raw q into the spare input tile L.x[kMaxB] (free: three blocks, no wide first layer) in front of the
-// staging barrier; the fragments are requested by waves 0..3 right behind that barrier, into z[l].  The three recompute
+// staging barrier; the fragments park in L.w[0] (no first layer is staged) and are read there by waves 0..3 at the
+// reverse step that uses them: no wave waits for memory behind the staging barrier.  The three recompute
 // layers, their barriers and the head product are not in this instantiation; everything from clipped_q_loss_row on is
 // the text of the others.  Of the invariants above: the saved tile is another LAUNCH's output, and `loads_landed()` at
 // the staging barrier covers the loads issued in front of it.  ONE LDS hand-over has no workgroup barrier here: the
@@ -1064,7 +1106,7 @@ constexpr size_t rider_karg_offset();
 // instantiations lies three recompute barriers on.  Writer and reader are both wave 0 (TM = 16: one row tile, the head
 // wave is wave 0), LDS serves a wave in order, and a wave-level fence stands between them (below).  The fourth kernel
 // argument exists in this form alone.  It forms no input gradient (its entry points take none), so the first layer's weights — read by that
-// dX alone — and the biases are not fetched (net_fetch_fixed<.., false>).
+// dX alone — the biases and the head bias are neither fetched nor written to LDS (net_fetch_fixed / net_put_fixed<.., false>).
 struct SavedCriticTile {
     float x[3][16 * kMaxW];                  // x_1..x_3, dense rows
     f32x4 zp[3][4 * 64];                     // gelu'(z_l): [layer][wave 0-3][lane], the MFMA C fragment of that lane
@@ -1151,13 +1193,18 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
             }
         }
         // LOADED: the saved forward of the tile, requested with the weights
-        [[maybe_unused]] float sv_x[3], sv_q;
+        // The fragments (12 KB, lane-linear: a flat copy) come with it and park in L.w[0] — this form stages no first layer
+        // (FWD = false), so the tile is free: three floats per thread.
+        [[maybe_unused]] float sv_x[3], sv_z[3], sv_q;
         if constexpr (LOADED) {
             static_assert(!LOADED || THREADS == 16 * kMaxW, "one float of x_l per thread");
+            static_assert(!LOADED || sizeof(SavedCriticTile::zp) <= sizeof(L.w[0]), "the fragments park in the first layer's tile");
             const SavedCriticTile& sv = *reinterpret_cast<const SavedCriticTile*>(
                 ld.saved + ((int64_t)blockIdx.x * gridDim.y + e) * kSavedCriticFloats);
 #pragma unroll
             for (int l = 0; l < 3; ++l) sv_x[l] = sv.x[l][threadIdx.x];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) sv_z[j] = reinterpret_cast<const float*>(&sv.zp[0][0])[threadIdx.x + j * THREADS];
             sv_q = sv.q[threadIdx.x & 15];          // (every thread loads; the first sixteen park it: L.x[kMaxB], the wide
                                                     // first layer's spare tile, is free on the fixed-shape path)
         }
@@ -1176,10 +1223,12 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
                 log_alpha = *v.log_alpha;
             }
             put_input_tile<THREADS, SLOTS>(in_lo, L.x[0]);
-            net_put_fixed<THREADS, NB>(regs, L);
+            net_put_fixed<THREADS, NB, !LOADED>(q, regs, L);
             if constexpr (LOADED) {
 #pragma unroll
                 for (int l = 0; l < 3; ++l) L.x[l + 1][(threadIdx.x >> 6) * kP + (threadIdx.x & 63)] = sv_x[l];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) L.w[0][threadIdx.x + j * THREADS] = sv_z[j];
                 if (threadIdx.x < 16) x_hi[threadIdx.x] = sv_q;
             }
             if (have) {
@@ -1191,7 +1240,7 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
             }
         } else {
             put_input_tile<THREADS, SLOTS>(in_lo, L.x[0]);
-            net_put_fixed<THREADS, NB>(regs, L);
+            net_put_fixed<THREADS, NB, !LOADED>(q, regs, L);
         }
         if (r < TM) L.delta[r * kP + c] = gin;
     } else {
@@ -1237,18 +1286,10 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
     }
 
     // ---- forward recompute ----------------------------------------------------------------------------
-    // (LOADED: x_1..x_3 arrived with the staging; the fragments are requested here, once the staged weights have left
-    // the registers — their first reader is the third layer's reverse step, the loss phase and the head gradients away;
-    // the last hidden layer is 64 wide)
+    // (LOADED: x_1..x_3 and the fragments arrived with the staging; the last hidden layer is 64 wide)
     int K = K0;
     if constexpr (LOADED) {
         K = kMaxW;
-        if (comp) {
-            const SavedCriticTile& sv = *reinterpret_cast<const SavedCriticTile*>(
-                ld.saved + ((int64_t)blockIdx.x * gridDim.y + e) * kSavedCriticFloats);
-#pragma unroll
-            for (int l = 0; l < 3; ++l) z[l] = sv.zp[l][threadIdx.x];
-        }
     } else {
 #pragma unroll
     for (int l = 0; l < kMaxB; ++l) {
@@ -1448,10 +1489,13 @@ __global__ __launch_bounds__(W8 ? 64 * W8 : TM * 16) void k_mlp_bwd(const MlpArg
             if constexpr (W8 != 0) dtile = dtile == spare ? L.delta : spare;
             else __syncthreads();   // readers of the previous delta tile are done
             if (comp) {
+                f32x4 zl;       // gelu'(pre-activation); LOADED: this lane's parked fragment, read where it is used
+                if constexpr (LOADED) zl = reinterpret_cast<const f32x4*>(L.w[0])[l * 256 + threadIdx.x];
+                else zl = z[l];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = rt * 16 + 4 * (lane >> 4) + r;
-                    dtile[row * kP + col] = col < W ? g[r] * z[l][r] : 0.f;     // z holds gelu'(pre-activation)
+                    dtile[row * kP + col] = col < W ? g[r] * zl[r] : 0.f;
                 }
             }
             __syncthreads();
@@ -1622,7 +1666,9 @@ __device__ __forceinline__ void ps_put_tile(const float (&v)[kPsSlots], float* x
 // PsLds (PsParked: outside the critics' overlay, no registers across the critic phase) in front of the staging barrier,
 // and read from there by the sampling backward, the weight-gradient tiles and the reverse layers.  The invariants above
 // hold: the saved tile is another LAUNCH's output, every parked word is written in front of the first barrier, and
-// `loads_landed()` stays where the policy's weights leave the registers.
+// `loads_landed()` stays where the policy's weights leave the registers.  With the forward loaded nothing reads the
+// policy's first layer (layer 0 forms no dX), its biases or its head bias: they are neither fetched nor written to LDS
+// (net_fetch_fixed / net_put_fixed<.., false>), and the "policy -> LDS" phase stores the two 64 x 64 layers and the head.
 template <bool OFFLINE, bool LOADED = false>
 __global__ __launch_bounds__(kPsThreads) void k_policy_step(
     const std::conditional_t<LOADED, PolicyStepArgsLoaded, PolicyStepArgs> a_by_value) {
@@ -1666,7 +1712,7 @@ __global__ __launch_bounds__(kPsThreads) void k_policy_step(
         sv_z = (&sv.zp[0][0])[threadIdx.x < 768 ? threadIdx.x : 767];
         sv_h = sv.head[threadIdx.x & 255];
     }
-    net_fetch_fixed<kPsThreads, 3>(sp, rp);
+    net_fetch_fixed<kPsThreads, 3, !LOADED>(sp, rp);
     float ev = 0.f, gl = 0.f;       // the sampling backward's per-(row, action dim) inputs
     {
         const int lrow = threadIdx.x / (A > 0 ? A : 1), d = threadIdx.x - lrow * A;
@@ -1680,7 +1726,7 @@ __global__ __launch_bounds__(kPsThreads) void k_policy_step(
     }
     if (sample_here) {
         // ---- the policy on the tile, once, for the action: weights -> LDS (they return from the registers later) ------
-        net_put_fixed<kPsThreads, 3>(rp, P);
+        net_put_fixed<kPsThreads, 3>(sp, rp, P);
         ps_put_tile(in_pi, P.x[0]);
         __syncthreads();
 #pragma unroll
@@ -1736,8 +1782,8 @@ __global__ __launch_bounds__(kPsThreads) void k_policy_step(
         ps_put_tile(in_q, L.q[0].xs[0]);
         ps_put_tile(in_q, L.q[1].xs[0]);
     }
-    net_put_fixed<kPsThreads, 3>(r0, L.q[0]);
-    net_put_fixed<kPsThreads, 3>(r1, L.q[1]);
+    net_put_fixed<kPsThreads, 3>(s0, r0, L.q[0]);
+    net_put_fixed<kPsThreads, 3>(s1, r1, L.q[1]);
     if constexpr (LOADED) {
 #pragma unroll
         for (int l = 0; l < 3; ++l) K.x[l][(threadIdx.x >> 6) * kP + (threadIdx.x & 63)] = sv_x[l];
@@ -1842,7 +1888,7 @@ __global__ __launch_bounds__(kPsThreads) void k_policy_step(
     MLP_STAMP(5);
 
     // ---- the policy takes over: parameters registers -> LDS, forward recompute ------------------------------------
-    net_put_fixed<kPsThreads, 3>(rp, P);
+    net_put_fixed<kPsThreads, 3, !LOADED>(sp, rp, P);
     ps_put_tile(in_pi, P.x[0]);
     // (LOADED: the raw head tile comes from the parked copy, and no forward follows)
     if (threadIdx.x < kPsRows * kHeadPad)
@@ -2118,7 +2164,7 @@ __device__ __forceinline__ void policy_forward_rider(const ASAC_KARG RiderIn<tru
     ps_fetch_tile(sp, row0, in_pi);
     StagedNet<kPsThreads> rp;
     net_fetch_fixed<kPsThreads, 3>(sp, rp);
-    net_put_fixed<kPsThreads, 3>(rp, P);
+    net_put_fixed<kPsThreads, 3>(sp, rp, P);
     ps_put_tile(in_pi, P.x[0]);
     __syncthreads();
 #pragma unroll
@@ -2217,7 +2263,7 @@ __device__ __forceinline__ void critic_forward_rider(const ASAC_KARG CriticRider
     net_fetch_fixed<THREADS, 3>(sq, regs);
     if constexpr (RING) ring_tile_rows<THREADS, 4, true>(sq, R, row0, id_lo, in_lo);
     put_input_tile<THREADS>(in_lo, L.x[0]);
-    net_put_fixed<THREADS, 3>(regs, L);
+    net_put_fixed<THREADS, 3>(sq, regs, L);
     __syncthreads();
     const int rt = 0, ct = wave;
     const int col = ct * 16 + (lane & 15);
@@ -2313,7 +2359,7 @@ __device__ __forceinline__ void pi_q_tiles(const ASAC_KARG PiQLaunch& a, PiQLds&
     net_fetch_fixed<THREADS, 3>(sq, rq);
     if constexpr (RING) ring_tile_rows<THREADS, SLOTS, false>(sp, R, (int64_t)group * 16, id_lo, in_lo);
     put_input_tile<THREADS, SLOTS>(in_lo, L.xs[0]);
-    net_put_fixed<THREADS, 3>(rp, L);
+    net_put_fixed<THREADS, 3>(sp, rp, L);
     // (looping workgroups: critic e's weights stay in registers until the policy has run and are written beside the
     // sampling phase; the barrier below waits for them all the same — its fence drains vmcnt)
     PiQCritic C{L.qw, L.qhead, L.qbias, L.qhead_bias};
@@ -2335,7 +2381,7 @@ __device__ __forceinline__ void pi_q_tiles(const ASAC_KARG PiQLaunch& a, PiQLds&
     //       side output's operand that is still travelling.
     constexpr bool single = SINGLE;
     float av_pre[2] = {0.f, 0.f}, ev2_pre[2] = {0.f, 0.f};
-    if (single) net_put_fixed<THREADS, 3>(rq, C);
+    if (single) net_put_fixed<THREADS, 3>(sq, rq, C);
 
     for (int tile = group; tile < n_tiles; tile += a.tile_groups) {
         const int row0 = tile * 16;
@@ -2611,7 +2657,7 @@ __device__ __forceinline__ void pi_q_tiles(const ASAC_KARG PiQLaunch& a, PiQLds&
             }
             if (job == 0 && lane < 16 && row0 + lane >= N)
                 for (int d = 0; d < A; ++d) L.act[lane * kHeadPad + d] = 0.f;
-            if (tile == group) net_put_fixed<THREADS, 3>(rq, C);
+            if (tile == group) net_put_fixed<THREADS, 3>(sq, rq, C);
             put_input_tile<THREADS, SLOTS>(in_lo, L.xs[0]);         // the states again (columns >= S are zero)
             __syncthreads();
             MLP_STAMP(4);

@@ -7,7 +7,7 @@
 // policy's forward loaded from a saved tile (the headline step's form; the saved values are zeros here: timing only).
 // The Q-loss backward is also stamped in the form that makes its own n-step return (n = 4, the headline step's launch) and
 // in that form LOADING the critics' forward (no stamps 20..24: the recompute is not in that instantiation; the row between
-// stamps 1 and 2 is the return's scan and the fragment requests).  The forward is stamped again with the stored pair's
+// stamps 1 and 2 is the return's scan).  The forward is stamped again with the stored pair's
 // extra job, without and with the critic-forward rider's workgroups beside the chain (workgroup 0 is a chain workgroup).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Iinclude -Iadvanced-soft-actor-critic_amd/csrc \
 //         tools/mlp_phases.hip -o tools/mlp_phases
@@ -109,7 +109,7 @@ int main() {
                mode == 0 ? "backward_qloss" : mode == 1 ? "backward_policy_q" : mode == 2 ? "backward_policy_sample"
                : mode == 3 ? "backward_qloss_return" : "backward_qloss_return_loaded", acc[0] / reps, bad ? "  [the launch was refused]" : "");
         for (int i = 1; i < 9; ++i)
-            printf("   %-18s %6.2f us\n", mode == 4 && i == 2 ? "scan + fragment requests" : names[i], acc[i] / reps);
+            printf("   %-18s %6.2f us\n", mode == 4 && i == 2 ? "return scan" : names[i], acc[i] / reps);
         if (mode != 4)
         printf("   recompute layer 2 in detail: gemm %.2f, gelu %.2f, LDS write %.2f, barrier %.2f\n", acc[14] / reps, acc[15] / reps,
                acc[16] / reps, acc[17] / reps);

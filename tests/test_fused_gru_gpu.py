@@ -267,9 +267,11 @@ def test_autograd_route_of_backward_from_position():
     assert all(torch.equal(a, b) for a, b in zip(*grads))
 
 
-def test_adam_epilogue_of_the_gradient_reduction_equals_a_separate_adam_launch():
+@pytest.mark.parametrize('steps_done', [6, 10 ** 6 - 1])
+def test_adam_epilogue_of_the_gradient_reduction_equals_a_separate_adam_launch(steps_done):
     """`asac_gru_backward_at(..., adam)`: the launch that finishes the cell parameters' gradients steps them —
-    parameters, moments and gradients bit-equal to the same launch followed by `asac_adam_step` over the flat buffers."""
+    parameters, moments and gradients bit-equal to the same launch followed by `asac_adam_step` over the flat buffers, early
+    and late in training (the bias corrections' powers take twenty rounds at 10^6 steps)."""
     from asac_amd import native
     I, H, layers, B, L, position = 8, 8, 2, 96, 21, 9
     _, dev = _layers(I, H, layers)
@@ -279,7 +281,7 @@ def test_adam_epilogue_of_the_gradient_reduction_equals_a_separate_adam_launch()
     desc = native.gru_desc(I, H, layers)
     n = native.gru_param_count(desc)
     cells = [[getattr(c, k).detach() for k in ('weight_ih_l0', 'weight_hh_l0', 'bias_ih_l0', 'bias_hh_l0')] for c in dev._grus]
-    steps = torch.full((1,), 6, dtype=torch.int64, device='cuda')
+    steps = torch.full((1,), steps_done, dtype=torch.int64, device='cuda')
     results = []
     for fused in (True, False):
         flat, grad = torch.zeros(n + 5, device='cuda'), torch.full((n + 5,), 0.25, device='cuda')
@@ -308,4 +310,4 @@ def test_adam_epilogue_of_the_gradient_reduction_equals_a_separate_adam_launch()
     for name, a, b in zip(('param', 'grad', 'exp_avg', 'exp_avg_sq'), *results):
         assert torch.equal(a[3:3 + n], b[3:3 + n]), name
         assert torch.equal(a[:3], b[:3]) and torch.equal(a[3 + n:], b[3 + n:]), name
-    assert int(steps.item()) == 6 and not torch.equal(results[0][0][3:3 + n], torch.cat([t.reshape(-1) for c in cells for t in c]))
+    assert int(steps.item()) == steps_done and not torch.equal(results[0][0][3:3 + n], torch.cat([t.reshape(-1) for c in cells for t in c]))

@@ -73,8 +73,10 @@ def test_q_ensemble_forward_backward(N, S):     # 12345 rows: workgroups loop ov
 
 @pytest.mark.parametrize('N,weighted', [(256, True), (100, False), (33, True)])
 def test_q_loss_backward_and_adam_from_partials(N, weighted):
-    """`asac_mlp_backward_qloss` (+ `asac_adam_step_partials`) against the chain it folds: module forward,
-    clipped double-Q loss (autograd), backward, torch.optim.Adam."""
+    """`asac_mlp_backward_qloss` against the chain it folds (module forward, clipped double-Q loss by autograd, backward),
+    and the deferred reduction folded into `asac_adam_step_partials` against the project's own separate launches: reduce in
+    the backward, then `FlatAdam.step` (`asac_adam_step`) — parameters and both moments bit for bit.  (Adam itself against
+    torch.optim.Adam: tests/test_adam_float64_gpu.py.)"""
     from asac_amd import native
     from algorithm.fused import FlatAdam
     E, S, A, clip = 3, 6, 2, 0.2
@@ -104,7 +106,7 @@ def test_q_loss_backward_and_adam_from_partials(N, weighted):
     m, v = torch.zeros_like(group.flat), torch.zeros_like(group.flat)
     opt = FlatAdam(group, [f'm{i}' for i in range(E)], 1e-3, steps, m, v)
     opt.step()
-    want, want_m = group.flat.clone(), m.clone()
+    want, want_m, want_v = group.flat.clone(), m.clone(), v.clone()
     group.flat.copy_(flat0)
     m.zero_(); v.zero_(); group.grad.zero_(); loss.zero_()
     mlp.accumulate = False
@@ -113,7 +115,8 @@ def test_q_loss_backward_and_adam_from_partials(N, weighted):
     mlp.adam_partials(opt, loss_out=loss)
     np.testing.assert_allclose(loss.cpu().numpy(), ref_loss.cpu().numpy(), rtol=2e-5, atol=1e-6)
     np.testing.assert_allclose(group.grad.cpu().numpy(), ref_gp.cpu().numpy(), rtol=2e-4, atol=2e-6)
-    assert torch.equal(group.flat, want) and torch.equal(m, want_m)
+    assert torch.equal(group.flat, want) and torch.equal(m, want_m) and torch.equal(v, want_v)
+    assert torch.count_nonzero(want_v) > 0
 
 
 @pytest.mark.parametrize('B,n,E,Es,use_is', [(256, 4, 2, 2, True), (100, 1, 3, 2, True), (33, 7, 2, 2, False),

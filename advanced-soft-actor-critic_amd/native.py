@@ -1,4 +1,5 @@
-"""ctypes binding of `libasac_hip.so` (C ABI: `include/asac_hip.h`).
+"""ctypes binding of `libasac_hip.so` (C ABI: `include/asac_hip.h`).  The signatures, the structs and the `ASAC_*` constants
+are not restated here: `abi.py` reads them from the header, and this module names the structs and wraps the entry points.
 
 There is NO fallback: if the library is missing or a launch fails this module raises.  torch must
 be imported before the library is loaded so that both bind to the same `libamdhip64.so.7` (the HIP
@@ -11,31 +12,81 @@ from pathlib import Path
 
 import torch  # noqa: F401  (must precede the dlopen below, see module docstring)
 
+from . import abi as _abi
+from .abi import AsacNativeError  # noqa: F401  (every failure of this binding raises it)
+
 PKG_DIR = Path(__file__).resolve().parent
 import os as _os
 
 LIB_PATH = Path(_os.environ.get('ASAC_HIP_LIB', PKG_DIR / 'lib' / 'libasac_hip.so'))   # env override: debugging builds
-ABI_VERSION = 91
-
-MAX_GATHER_KEYS = 16
-PAD_KEEP, PAD_WORD, PAD_BYTE, PAD_ROW, PAD_EMIT_MASK = 0, 1, 2, 3, 4
-CVT_NONE, CVT_U8_TO_F32_UNIT, CVT_BOOL_TO_F32 = 0, 1, 2
 
 
-class AsacNativeError(RuntimeError):
-    pass
+def _defined(*names):
+    """the header's integer constants `ASAC_<name>` (a `#define` or an enumerator)"""
+    values = tuple(_abi.defines['ASAC_' + n] for n in names)
+    return values if len(values) > 1 else values[0]
 
 
-class GatherKey(C.Structure):
-    _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('pad_row', C.c_void_p),
-                ('row_bytes', C.c_int32), ('pad_mode', C.c_int32), ('pad_word', C.c_uint32),
-                ('convert', C.c_int32), ('dst_row_pitch', C.c_int32), ('derive', C.c_int32)]
+ABI_VERSION = _defined('ABI_VERSION')
 
+MAX_GATHER_KEYS = _defined('MAX_GATHER_KEYS')
+PAD_KEEP, PAD_WORD, PAD_BYTE, PAD_ROW, PAD_EMIT_MASK = _defined('PAD_KEEP', 'PAD_WORD', 'PAD_BYTE', 'PAD_ROW', 'PAD_EMIT_MASK')
+CVT_NONE, CVT_U8_TO_F32_UNIT, CVT_BOOL_TO_F32 = _defined('CVT_NONE', 'CVT_U8_TO_F32_UNIT', 'CVT_BOOL_TO_F32')
+ROW_ITEM, ROW_SLOT, ROW_SLOT_ROW, ROW_BROADCAST = _defined('ROW_ITEM', 'ROW_SLOT', 'ROW_SLOT_ROW', 'ROW_BROADCAST')
+DERIVE_NONE, DERIVE_PREVIOUS, DERIVE_HOLD_LAST, DERIVE_HOLD_LAST_NEXT = _defined(
+    'DERIVE_NONE', 'DERIVE_PREVIOUS', 'DERIVE_HOLD_LAST', 'DERIVE_HOLD_LAST_NEXT')
+DISCRETE_MAX_WIDTH, DISCRETE_MAX_BRANCHES, DISCRETE_MAX_MEMBERS, DISCRETE_MAX_STEPS, DISCRETE_MAX_ROWS = _defined(
+    'DISCRETE_MAX_WIDTH', 'DISCRETE_MAX_BRANCHES', 'DISCRETE_MAX_MEMBERS', 'DISCRETE_MAX_STEPS', 'DISCRETE_MAX_ROWS')
+ACT_MAX_CONT = _defined('ACT_MAX_CONT')
+MLP_MAX_JOBS = _defined('MLP_MAX_JOBS')
+SIDECAR_ALPHA_ADAM, SIDECAR_SCATTER_ELECT, SIDECAR_SCATTER_WRITE, SIDECAR_WINDOW_GATHER, SIDECAR_WINDOW_GATHER_W = _defined(
+    'SIDECAR_ALPHA_ADAM', 'SIDECAR_SCATTER_ELECT', 'SIDECAR_SCATTER_WRITE', 'SIDECAR_WINDOW_GATHER', 'SIDECAR_WINDOW_GATHER_W')
+MAX_SIDECARS = _defined('MAX_SIDECARS')
+SQUASH_MAX_JOBS = _defined('SQUASH_MAX_JOBS')
+GRU_MAX_LAYERS, GRU_MAX_DIM = _defined('GRU_MAX_LAYERS', 'GRU_MAX_DIM')
+# the policy forward's sampling epilogue (`mlp_forward_multi_sampled`) instead of a `squash_multi` launch behind it;
+# ASAC_SAMPLE_EPILOGUE=0: the chain (A/B runs)
+SAMPLE_EPILOGUE = _os.environ.get('ASAC_SAMPLE_EPILOGUE', '1') != '0'
 
-class AdamEpilogue(C.Structure):
-    _fields_ = [('param_base', C.c_void_p), ('grad_base', C.c_void_p), ('exp_avg_base', C.c_void_p),
-                ('exp_avg_sq_base', C.c_void_p), ('lr', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float),
-                ('eps', C.c_float), ('steps_done', C.c_void_p)]
+# The structs of the header, one line each; fields, in the header's order, and layouts are `abi.ctypes_struct`'s
+# (tests/test_abi_host.py holds every size and offset to the host C compiler's).  A new struct of the header needs its
+# line here: `abi.signatures` refuses a header struct that has none.
+GatherKey = _abi.ctypes_struct('asac_gather_key_t')
+RowMove = _abi.ctypes_struct('asac_row_move_t')
+Sidecar = _abi.ctypes_struct('asac_sidecar_t')
+SquashJob = _abi.ctypes_struct('asac_squash_job_t')
+VtraceArgs = _abi.ctypes_struct('asac_vtrace_args_t')
+MlpDesc = _abi.ctypes_struct('asac_mlp_desc_t')
+MlpJob = _abi.ctypes_struct('asac_mlp_job_t')
+SampleEpilogue = _abi.ctypes_struct('asac_mlp_sample_epilogue_t')
+RingKey = _abi.ctypes_struct('asac_ring_key_t')
+RingRows = _abi.ctypes_struct('asac_ring_rows_t')
+PiQJob = _abi.ctypes_struct('asac_pi_q_job_t')
+GruDesc = _abi.ctypes_struct('asac_gru_desc_t')
+AdamEpilogue = _abi.ctypes_struct('asac_adam_epilogue_t')
+Conv2Desc = _abi.ctypes_struct('asac_conv2_desc_t')
+Conv1Desc = _abi.ctypes_struct('asac_conv1_desc_t')
+ObsDecoderParams = _abi.ctypes_struct('asac_obs_decoder_params_t')
+PartialSum = _abi.ctypes_struct('asac_partial_sum_t')
+BatchPutKey = _abi.ctypes_struct('asac_batch_put_key_t')
+BatchGatherKey = _abi.ctypes_struct('asac_batch_gather_key_t')
+Branches = _abi.ctypes_struct('asac_branches_t')
+Members = _abi.ctypes_struct('asac_members_t')
+DiscreteReturn = _abi.ctypes_struct('asac_discrete_return_t')
+DqnJob = _abi.ctypes_struct('asac_dqn_job_t')
+RndDesc = _abi.ctypes_struct('asac_rnd_desc_t')
+RndStack = _abi.ctypes_struct('asac_rnd_stack_t')
+RndGrads = _abi.ctypes_struct('asac_rnd_grads_t')
+ActJob = _abi.ctypes_struct('asac_act_job_t')
+ImageOp = _abi.ctypes_struct('asac_image_op_t')
+ImageWarpOp = _abi.ctypes_struct('asac_image_warp_op_t')
+WhitenJob = _abi.ctypes_struct('asac_whiten_job_t')
+NormalizerJob = _abi.ctypes_struct('asac_normalizer_job_t')
+_PtrArray = C.c_void_p * GRU_MAX_LAYERS
+
+# every entry point of the header: {name: (restype, [argtypes])} by the typing rule of abi.py
+_SIGNATURES = _abi.signatures([v for v in list(globals().values()) if isinstance(v, type) and issubclass(v, C.Structure)])
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 
 def adam_epilogue(param_flat, grad_flat, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, steps_done) -> AdamEpilogue:
@@ -50,676 +101,6 @@ def adam_epilogue(param_flat, grad_flat, exp_avg, exp_avg_sq, lr, beta1, beta2, 
     ep._span = (grad_flat.data_ptr(), grad_flat.data_ptr() + 4 * grad_flat.numel())
     return ep
 
-
-ROW_ITEM, ROW_SLOT, ROW_SLOT_ROW, ROW_BROADCAST = 0, 1, 2, 3
-DERIVE_NONE, DERIVE_PREVIOUS, DERIVE_HOLD_LAST, DERIVE_HOLD_LAST_NEXT = 0, 1, 2, 3
-
-
-class RowMove(C.Structure):
-    _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p),
-                ('src_stride0', C.c_int64), ('src_stride1', C.c_int64),
-                ('dst_stride0', C.c_int64), ('dst_stride1', C.c_int64),
-                ('row_bytes', C.c_int32), ('src_mode', C.c_int32), ('dst_mode', C.c_int32),
-                ('src_row_offset', C.c_int32), ('pad_word', C.c_uint32), ('reserved_', C.c_int32)]
-
-
-class BatchPutKey(C.Structure):
-    _fields_ = [('src', C.c_void_p), ('pool', C.c_void_p), ('pad_row', C.c_void_p), ('src_stride', C.c_int64),
-                ('row_bytes', C.c_int32), ('pad_mode', C.c_int32), ('pad_word', C.c_uint32), ('reserved_', C.c_int32)]
-
-
-class BatchGatherKey(C.Structure):
-    _fields_ = [('pool', C.c_void_p), ('dst', C.c_void_p), ('row_bytes', C.c_int32), ('convert', C.c_int32)]
-
-
-class VtraceArgs(C.Structure):
-    _fields_ = [
-        ('q', C.c_void_p), ('q_stride_e', C.c_int64), ('q_stride_b', C.c_int64), ('q_stride_t', C.c_int64),
-        ('subset_n', C.c_void_p), ('subset_next', C.c_void_p), ('E_sample', C.c_int32),
-        ('logp', C.c_void_p), ('log_alpha', C.c_void_p),
-        ('reward', C.c_void_p), ('reward_stride', C.c_int64),
-        ('done', C.c_void_p), ('last_mask', C.c_void_p), ('padding_mask', C.c_void_p), ('mask_stride', C.c_int64),
-        ('mu_prob', C.c_void_p), ('mu_stride_b', C.c_int64), ('mu_stride_t', C.c_int64), ('mu_offset', C.c_int32),
-        ('pi_prob', C.c_void_p), ('pi_stride_b', C.c_int64), ('pi_stride_t', C.c_int64), ('A', C.c_int32),
-        ('gamma_ratio', C.c_void_p), ('lambda_ratio', C.c_void_p),
-        ('gamma', C.c_float), ('v_rho', C.c_float), ('v_c', C.c_float),
-        ('use_n_step_is', C.c_int32), ('B', C.c_int32), ('n', C.c_int32),
-        ('q_online', C.c_void_p), ('E_online', C.c_int32),
-        ('td_error_out', C.c_void_p), ('y_out', C.c_void_p)]
-
-
-DISCRETE_MAX_WIDTH, DISCRETE_MAX_BRANCHES, DISCRETE_MAX_MEMBERS, DISCRETE_MAX_STEPS, DISCRETE_MAX_ROWS = 64, 8, 8, 64, 1024
-
-
-class Branches(C.Structure):
-    """asac_branches_t: the sizes of the discrete action branches (K of them, D entries in all)"""
-    _fields_ = [('K', C.c_int32), ('D', C.c_int32), ('size', C.c_int32 * DISCRETE_MAX_BRANCHES)]
-
-
-class Members(C.Structure):
-    """asac_members_t: the ensemble members' head outputs, separate tensors of one shape, as a pointer table"""
-    _fields_ = [('base', C.c_void_p * DISCRETE_MAX_MEMBERS), ('stride_b', C.c_int64), ('stride_t', C.c_int64),
-                ('E', C.c_int32), ('reserved_', C.c_int32)]
-
-
-class DiscreteReturn(C.Structure):
-    _fields_ = [('branches', Branches), ('q_target', Members), ('q_online', Members),
-                ('logits', C.c_void_p), ('logits_stride_b', C.c_int64), ('logits_stride_t', C.c_int64),
-                ('action', C.c_void_p), ('action_stride_b', C.c_int64), ('action_stride_t', C.c_int64)]
-
-
-class DqnJob(C.Structure):
-    """asac_dqn_job_t: the DQN-like target's tables (eval [B, n, D], target [B, n+1, D]), the online heads and the stored
-    action at the step's state"""
-    _fields_ = [('branches', Branches), ('q_eval', Members), ('q_target', Members), ('q_online', Members),
-                ('action', C.c_void_p), ('action_stride', C.c_int64)]
-
-
-ACT_MAX_CONT = 8
-
-
-class ActJob(C.Structure):
-    """asac_act_job_t: the policy's head outputs, the caller's draws and the outputs of the acting launch (csrc/act.hip)"""
-    _fields_ = [('branches', Branches), ('logits', C.c_void_p), ('logits_stride', C.c_int64),
-                ('loc', C.c_void_p), ('scale', C.c_void_p), ('ls_row_stride', C.c_int64),
-                ('A', C.c_int32), ('head_raw', C.c_int32),
-                ('u', C.c_void_p), ('u_stride', C.c_int64), ('eps', C.c_void_p), ('eps_stride', C.c_int64),
-                ('deterministic', C.c_int32), ('use_noise', C.c_int32), ('noise_lo', C.c_float), ('noise_hi', C.c_float),
-                ('action_out', C.c_void_p), ('action_stride', C.c_int64), ('prob_out', C.c_void_p), ('prob_stride', C.c_int64),
-                ('B', C.c_int32), ('reserved_', C.c_int32)]
-
-
-class RndDesc(C.Structure):
-    """asac_rnd_desc_t: state and action widths of an RND stack (in = S + A -> 64 -> 64) and its blocks' residual flags"""
-    _fields_ = [('S', C.c_int32), ('A', C.c_int32), ('residual', C.c_int32 * 2)]
-
-
-class RndStack(C.Structure):
-    """asac_rnd_stack_t: the four parameter pointers of one RND stack"""
-    _fields_ = [('w1', C.c_void_p), ('b1', C.c_void_p), ('w2', C.c_void_p), ('b2', C.c_void_p)]
-
-
-class MlpDesc(C.Structure):
-    _fields_ = [('in0', C.c_int32), ('in1', C.c_int32), ('n_blocks', C.c_int32),
-                ('width', C.c_int32 * 4), ('residual', C.c_int32 * 4), ('head_cols', C.c_int32 * 2),
-                ('w_off', C.c_int64 * 4), ('b_off', C.c_int64 * 4),
-                ('head_w_off', C.c_int64 * 2), ('head_b_off', C.c_int64 * 2),
-                ('head_transform', C.c_int32), ('reserved_', C.c_int32)]
-
-
-class MlpJob(C.Structure):
-    _fields_ = [('desc', C.POINTER(MlpDesc)), ('params', C.c_void_p), ('member_stride', C.c_int64),
-                ('x0', C.c_void_p), ('x0_row_stride', C.c_int64), ('x0_member_stride', C.c_int64),
-                ('x1', C.c_void_p), ('x1_row_stride', C.c_int64), ('x1_member_stride', C.c_int64),
-                ('N', C.c_int64), ('out', C.c_void_p), ('E', C.c_int32), ('x0_window_T', C.c_int32),
-                ('x0_sample_stride', C.c_int64)]
-
-
-MLP_MAX_JOBS = 2
-# the policy forward's sampling epilogue (`mlp_forward_multi_sampled`) instead of a `squash_multi` launch behind it;
-# ASAC_SAMPLE_EPILOGUE=0: the chain (A/B runs)
-SAMPLE_EPILOGUE = _os.environ.get('ASAC_SAMPLE_EPILOGUE', '1') != '0'
-
-
-class Sidecar(C.Structure):
-    """asac_sidecar_t: a small off-critical-path job that rides as extra workgroups of a hosting launch"""
-    _fields_ = [('kind', C.c_int32),
-                ('logp', C.c_void_p), ('B', C.c_int32), ('target', C.c_float), ('slot', C.c_int32),
-                ('param', C.c_void_p), ('grad', C.c_void_p), ('exp_avg', C.c_void_p), ('exp_avg_sq', C.c_void_p),
-                ('n', C.c_int32), ('lr', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float),
-                ('steps_done', C.c_void_p), ('advance_counter', C.c_int32),
-                ('ring', C.c_void_p), ('row_bytes', C.c_int32), ('capacity', C.c_int32), ('ids', C.c_void_p),
-                ('batch', C.c_int32), ('first_off', C.c_int32), ('count', C.c_int32), ('slot_ids', C.c_void_p),
-                ('padding_mask', C.c_void_p), ('mask_sample_stride', C.c_int32), ('rows', C.c_void_p),
-                ('rows_sample_stride_bytes', C.c_int64), ('rows_row_stride_bytes', C.c_int64), ('winner', C.c_void_p),
-                ('gather_plan', C.c_void_p), ('gather_blocks', C.c_int32)]
-
-
-SIDECAR_ALPHA_ADAM, SIDECAR_SCATTER_ELECT, SIDECAR_SCATTER_WRITE, SIDECAR_WINDOW_GATHER, MAX_SIDECARS = 1, 2, 3, 4, 4
-SIDECAR_WINDOW_GATHER_W = 5
-
-
-class SquashJob(C.Structure):
-    _fields_ = [('loc', C.c_void_p), ('scale', C.c_void_p), ('ls_row_stride', C.c_int64), ('eps', C.c_void_p),
-                ('rows', C.c_int64), ('A', C.c_int32), ('T', C.c_int32), ('a_tanh_out', C.c_void_p),
-                ('logp_out', C.c_void_p), ('x_out', C.c_void_p), ('action', C.c_void_p),
-                ('action_stride_b', C.c_int64), ('action_stride_t', C.c_int64), ('prob_out', C.c_void_p),
-                ('prob_stride_b', C.c_int64), ('prob_stride_t', C.c_int64), ('action_offset', C.c_int32),
-                ('prob_offset', C.c_int32)]
-
-
-SQUASH_MAX_JOBS = 4
-
-
-class RingKey(C.Structure):
-    """asac_ring_key_t: a float32 key of the replay ring as a ring-addressed launch reads it"""
-    _fields_ = [('src', C.c_void_p), ('pad_row', C.c_void_p), ('row_bytes', C.c_int32), ('pad_mode', C.c_int32),
-                ('pad_word', C.c_uint32), ('reserved_', C.c_int32)]
-
-
-class RingRows(C.Structure):
-    """asac_ring_rows_t: `policy_sample_q_forward` takes its rows from the replay ring (ids None: off)"""
-    _fields_ = [('ids', C.c_void_p), ('index_ring', C.c_void_p), ('capacity', C.c_int32), ('prev_n', C.c_int32),
-                ('L', C.c_int32), ('j0', C.c_int32), ('x_j0', C.c_int32), ('x_action_offset', C.c_int32),
-                ('x0', RingKey), ('action', RingKey)]
-
-
-class PiQJob(C.Structure):
-    """asac_pi_q_job_t: policy forward -> sampling -> critics forward over the same rows"""
-    _fields_ = [('pi', MlpJob), ('sample', SquashJob), ('eps2', C.c_void_p), ('t2', C.c_int32), ('reserved_', C.c_int32),
-                ('a2_out', C.c_void_p), ('logp2_out', C.c_void_p), ('q', MlpJob), ('ring', RingRows)]
-
-
-class SampleEpilogue(C.Structure):
-    """asac_mlp_sample_epilogue_t: asac_squash_multi's jobs as the epilogue of a policy job of `mlp_forward_multi_sampled`"""
-    _fields_ = [('sample', SquashJob), ('eps2', C.c_void_p), ('t2', C.c_int32), ('reserved_', C.c_int32),
-                ('a2_out', C.c_void_p), ('logp2_out', C.c_void_p)]
-
-
-class PartialSum(C.Structure):
-    """asac_partial_sum_t: one fixed-order sum of per-workgroup partials (`sum_partials_multi`)"""
-    _fields_ = [('partial', C.c_void_p), ('out', C.c_void_p), ('slab_stride', C.c_int64), ('n', C.c_int64),
-                ('slabs', C.c_int32), ('slices', C.c_int32), ('accumulate', C.c_int32), ('pad_', C.c_int32)]
-
-
-class GruDesc(C.Structure):
-    _fields_ = [('input', C.c_int32), ('hidden', C.c_int32), ('hidden_pow2', C.c_int32), ('layers', C.c_int32)]
-
-
-class Conv2Desc(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ('channels', 'height', 'width', 'out1', 'kernel1', 'stride1',
-                                         'out2', 'kernel2', 'stride2')]
-
-
-class Conv1Desc(C.Structure):
-    """`asac_conv1_desc_t`: the ray encoder's Conv1d LeakyReLU Conv1d LeakyReLU stack (csrc/conv1d.hip)"""
-    _fields_ = [(n, C.c_int32) for n in ('length', 'channels', 'out1', 'kernel1', 'stride1',
-                                         'out2', 'kernel2', 'stride2')] + [('negative_slope', C.c_float)]
-
-
-GRU_MAX_LAYERS, GRU_MAX_DIM = 2, 16
-_PtrArray = C.c_void_p * GRU_MAX_LAYERS
-
-class ObsDecoderParams(C.Structure):
-    """`asac_obs_decoder_params_t`: the ten parameter tensors of the observation decoder (or their gradients)"""
-    _fields_ = [(n, C.c_void_p) for n in ('dense1_w', 'dense1_b', 'dense2_w', 'dense2_b', 'ct1_w', 'ct1_b', 'ct2_w',
-                                          'ct2_b', 'ct3_w', 'ct3_b')]
-
-
-class ImageOp(C.Structure):
-    """asac_image_op_t: one member of an `image_augment` table"""
-    _fields_ = [('kind', C.c_int32), ('kx', C.c_int32), ('ky', C.c_int32), ('crop_h', C.c_int32), ('crop_w', C.c_int32),
-                ('top', C.c_int32), ('left', C.c_int32), ('lo', C.c_float), ('hi', C.c_float), ('a', C.c_float),
-                ('b', C.c_float), ('c', C.c_float)]
-
-
-class ImageWarpOp(C.Structure):
-    """asac_image_warp_op_t: one member of a `warp_image` table"""
-    _fields_ = [('kind', C.c_int32), ('k0', C.c_int32), ('k1', C.c_int32), ('scale_lo', C.c_float), ('scale_hi', C.c_float),
-                ('ratio_lo', C.c_float), ('ratio_hi', C.c_float), ('alpha0', C.c_float), ('alpha1', C.c_float),
-                ('sigma0', C.c_float), ('sigma1', C.c_float)]
-
-
-class WhitenJob(C.Structure):
-    """asac_whiten_job_t: one observation of an `obs_whiten` launch (pitches in elements, 0: dense)"""
-    _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('mean', C.c_void_p), ('variance', C.c_void_p), ('D', C.c_int64),
-                ('rows', C.c_int64), ('src_row_pitch', C.c_int64), ('dst_row_pitch', C.c_int64)]
-
-
-class NormalizerJob(C.Structure):
-    """asac_normalizer_job_t: one observation of a `normalizer_update` launch"""
-    _fields_ = [('x', C.c_void_p), ('mean', C.c_void_p), ('variance', C.c_void_p), ('D', C.c_int64),
-                ('x_row_pitch', C.c_int64), ('dtype', C.c_int32), ('reserved_', C.c_int32)]
-
-
-_SIGNATURES = {
-    'asac_version': (C.c_int, []),
-    'asac_last_error': (C.c_char_p, []),
-    'asac_set_launch_repeat': (C.c_int, [C.c_int]),
-    'asac_sumtree_sample': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p]),
-    'asac_per_is_weights': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
-                                      C.c_void_p, C.c_void_p]),
-    'asac_sumtree_update': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
-                                      C.c_void_p]),
-    'asac_per_add': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_float,
-                               C.c_void_p, C.c_void_p]),
-    'asac_sumtree_leaf_max': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    'asac_sumtree_check': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    'asac_gelu_eval': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    'asac_sumtree_plan_top': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_sumtree_descend_owned': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_per_is_weights_slice': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double,
-                                            C.c_void_p, C.c_void_p]),
-    'asac_window_gather_pad': (C.c_int, [C.POINTER(GatherKey), C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                         C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    'asac_window_gather_plan_bytes': (C.c_int64, []),
-    'asac_window_gather_plan': (C.c_int, [C.POINTER(GatherKey), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                          C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
-    'asac_window_gather_plan_w': (C.c_int, [C.POINTER(GatherKey), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
-    'asac_sumtree_descend': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p]),
-    'asac_gather_rows': (C.c_int, [C.POINTER(GatherKey), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    'asac_rows_move': (C.c_int, [C.POINTER(RowMove), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                 C.c_void_p]),
-    'asac_batch_put': (C.c_int, [C.POINTER(BatchPutKey), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                 C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
-                                 C.c_void_p, C.c_int32, C.c_void_p]),
-    'asac_batch_pop_gather': (C.c_int, [C.POINTER(BatchGatherKey), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                        C.c_int, C.c_int, C.c_void_p]),
-    'asac_window_aux': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
-                                  C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    'asac_scatter_rows_if_id_match': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                                C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                                C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
-    'asac_squash_sample_fwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int,
-                                         C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int,
-                                         C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
-    'asac_squash_sample_bwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
-                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
-                                         C.c_void_p, C.c_int64, C.c_void_p]),
-    'asac_squash_multi': (C.c_int, [C.POINTER(SquashJob), C.c_int, C.POINTER(Sidecar), C.c_int, C.c_void_p]),
-    'asac_squash_prob': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int64,
-                                   C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
-                                   C.c_void_p]),
-    'asac_vtrace_return_min': (C.c_int, [C.POINTER(VtraceArgs), C.c_void_p]),
-    'asac_vtrace_return_min_sc': (C.c_int, [C.POINTER(VtraceArgs), C.POINTER(Sidecar), C.c_int, C.POINTER(Sidecar),
-                                            C.c_void_p]),
-    'asac_td_update': (C.c_int, [C.POINTER(VtraceArgs), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
-                                 C.c_float, C.c_void_p, C.c_void_p, C.POINTER(Sidecar), C.c_int, C.POINTER(Sidecar),
-                                 C.c_void_p]),
-    'asac_sumtree_update_sc': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
-                                         C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Sidecar), C.c_int,
-                                         C.c_void_p]),
-    'asac_vtrace_return_direct': (C.c_int, [C.POINTER(VtraceArgs), C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p]),
-    'asac_q_loss_fwd_bwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                      C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_mlp_forward': (C.c_int, [C.POINTER(MlpJob), C.c_void_p]),
-    'asac_mlp_forward_multi': (C.c_int, [C.POINTER(MlpJob), C.c_int, C.POINTER(Sidecar), C.c_int, C.c_void_p]),
-    'asac_mlp_forward_multi_sampled_ok': (C.c_int, [C.POINTER(MlpJob), C.c_int, C.POINTER(SampleEpilogue)]),
-    'asac_mlp_forward_multi_sampled': (C.c_int, [C.POINTER(MlpJob), C.c_int, C.POINTER(SampleEpilogue), C.POINTER(Sidecar),
-                                                 C.c_int, C.c_void_p]),
-    'asac_mlp_backward_workspace': (C.c_int64, [C.c_int64, C.c_int, C.c_int64]),
-    'asac_mlp_backward_tiles': (C.c_int64, [C.c_int64, C.c_int]),
-    'asac_mlp_backward': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                    C.c_void_p]),
-    'asac_mlp_backward_qloss': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    'asac_mlp_backward_qloss_return_ok': (C.c_int, [C.POINTER(MlpJob), C.POINTER(VtraceArgs)]),
-    'asac_mlp_backward_qloss_return': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.POINTER(VtraceArgs), C.c_void_p, C.c_float,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    'asac_policy_forward_save_floats': (C.c_int64, [C.c_int64]),
-    'asac_mlp_backward_qloss_return_rider_ok': (C.c_int, [C.POINTER(MlpJob), C.POINTER(VtraceArgs), C.POINTER(MlpJob),
-                                                          C.c_void_p]),
-    'asac_mlp_backward_qloss_return_rider': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.POINTER(VtraceArgs), C.c_void_p,
-                                                       C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                                       C.POINTER(MlpJob), C.c_void_p, C.c_void_p]),
-    'asac_mlp_backward_qloss_return_loaded_ok': (C.c_int, [C.POINTER(MlpJob), C.POINTER(VtraceArgs), C.c_void_p]),
-    'asac_mlp_backward_qloss_return_loaded': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.POINTER(VtraceArgs), C.c_void_p,
-                                                        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                                        C.c_void_p]),
-    'asac_mlp_backward_qloss_return_rider_loaded_ok': (C.c_int, [C.POINTER(MlpJob), C.POINTER(VtraceArgs), C.POINTER(MlpJob),
-                                                                 C.c_void_p, C.c_void_p]),
-    'asac_mlp_backward_qloss_return_rider_loaded': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.POINTER(VtraceArgs), C.c_void_p,
-                                                              C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                                              C.POINTER(MlpJob), C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_critic_forward_save_floats': (C.c_int64, [C.c_int64, C.c_int]),
-    'asac_policy_sample_q_forward_saving_ok': (C.c_int, [C.POINTER(PiQJob), C.POINTER(MlpJob), C.c_int, C.POINTER(Sidecar),
-                                                         C.c_int, C.POINTER(MlpJob), C.c_void_p]),
-    'asac_policy_sample_q_forward_saving': (C.c_int, [C.POINTER(PiQJob), C.POINTER(MlpJob), C.c_int, C.POINTER(Sidecar),
-                                                      C.c_int, C.POINTER(MlpJob), C.c_void_p, C.c_void_p]),
-    'asac_policy_step_fused_loaded_ok': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.POINTER(MlpDesc), C.c_void_p,
-                                                   C.c_int64, C.c_int64, C.c_void_p]),
-    'asac_policy_step_fused_loaded': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.POINTER(MlpDesc), C.c_void_p,
-                                                C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.c_int, C.c_void_p]),
-    'asac_policy_step_fused_loaded_offline': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.POINTER(MlpDesc),
-                                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
-                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                                        C.c_void_p]),
-    'asac_mlp_backward_policy_q': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    'asac_mlp_backward_policy_sample': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    'asac_mlp_backward_policy_sample_offline': (C.c_int, [C.POINTER(MlpJob), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
-                                                          C.c_void_p]),
-    'asac_struct_size': (C.c_int64, [C.c_char_p]),
-    'asac_policy_sample_q_forward_ok': (C.c_int, [C.POINTER(PiQJob)]),
-    'asac_policy_sample_q_forward_jobs_ok': (C.c_int, [C.POINTER(PiQJob), C.POINTER(MlpJob), C.c_int]),
-    'asac_policy_sample_q_forward': (C.c_int, [C.POINTER(PiQJob), C.POINTER(MlpJob), C.c_int, C.POINTER(Sidecar), C.c_int,
-                                               C.c_void_p]),
-    'asac_policy_step_fused_ok': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.POINTER(MlpDesc), C.c_void_p,
-                                            C.c_int64, C.c_int64]),
-    'asac_policy_step_fused': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.POINTER(MlpDesc), C.c_void_p,
-                                         C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    'asac_policy_step_fused_offline': (C.c_int, [C.POINTER(MlpDesc), C.c_void_p, C.c_int64, C.POINTER(MlpDesc), C.c_void_p,
-                                                 C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    'asac_policy_offline_term': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
-                                           C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_mlp_param_extent': (C.c_int64, [C.POINTER(MlpDesc)]),
-    'asac_adam_step_partials': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
-                                          C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
-                                          C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
-    'asac_gauss_head_fwd': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_gauss_head_bwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
-                                      C.c_void_p]),
-    'asac_attention_supported': (C.c_int, [C.c_int, C.c_int, C.c_int]),
-    'asac_attention_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
-                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p]),
-    'asac_attention_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                          C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_attention_proj_workspace': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    'asac_attention_proj_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
-                                              C.c_void_p * 8, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
-                                              C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
-    'asac_attention_proj_backward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
-                                               C.c_void_p * 8, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                               C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
-                                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_int, C.c_void_p, C.c_void_p]),
-    'asac_linear_tanh_workspace': (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
-    'asac_linear_tanh_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
-                                           C.c_void_p, C.c_void_p]),
-    'asac_linear_tanh_backward': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
-                                            C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    'asac_linear_tanh_forward2': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
-                                            C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
-    'asac_linear_tanh_forward2w': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
-                                             C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
-    'asac_linear_tanh_backward2w': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
-                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                              C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                              C.c_void_p]),
-    'asac_linear_tanh_backward2': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    'asac_curiosity_bonus': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int,
-                                       C.c_int, C.c_int, C.c_float, C.c_void_p]),
-    'asac_masked_mse': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
-                                  C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_mse_mean_grad_workspace': (C.c_int64, []),
-    'asac_mse_mean_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_masked_mse_workspace': (C.c_int64, [C.c_int64]),
-    'asac_normal_nll_kl_workspace': (C.c_int64, [C.c_int64]),
-    'asac_normal_nll_kl': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
-                                     C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_normal_nll_kl_logstd': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_int64,
-                                            C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p]),
-    'asac_sum_partials_multi': (C.c_int, [C.c_int, C.POINTER(PartialSum), C.c_void_p]),
-    'asac_rows_wide_supported': (C.c_int, [C.c_int64, C.c_int, C.c_int]),
-    'asac_rows_wide_workspace': (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
-    'asac_rows_wide_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_rows_wide_backward_input': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int,
-                                                C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    'asac_rows_wide_backward_params': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p,
-                                                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    'asac_xty_supported': (C.c_int, [C.c_int64, C.c_int, C.c_int]),
-    'asac_xty_workspace': (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
-    'asac_xty': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
-                           C.c_int, C.c_void_p, C.c_void_p]),
-    'asac_xty_multi_workspace': (C.c_int64, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_xty_multi': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                 C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    'asac_conv2_tiles': (C.c_int, [C.POINTER(Conv2Desc)]),
-    'asac_conv2_z1_floats': (C.c_int64, [C.POINTER(Conv2Desc), C.c_int64]),
-    'asac_conv2_supported': (C.c_int, [C.POINTER(Conv2Desc)]),
-    'asac_conv2_group_frames': (C.c_int, [C.POINTER(Conv2Desc)]),
-    'asac_conv2_backward_windows': (C.c_int, [C.POINTER(Conv2Desc), C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                              C.c_void_p]),
-    'asac_conv2_backward_multi_max': (C.c_int, [C.POINTER(Conv2Desc)]),
-    'asac_conv2_backward_slabs': (C.c_int, [C.POINTER(Conv2Desc), C.c_int64, C.c_int]),
-    'asac_conv2_backward_multi': (C.c_int, [C.POINTER(Conv2Desc), C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int,
-                                            C.c_void_p, C.c_void_p]),
-    'asac_conv2_forward_windows': (C.c_int, [C.POINTER(Conv2Desc), C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p]),
-    'asac_conv2_param_count': (C.c_int64, [C.POINTER(Conv2Desc)]),
-    'asac_conv2_backward_workspace': (C.c_int64, [C.POINTER(Conv2Desc), C.c_int64]),
-    'asac_conv2_forward': (C.c_int, [C.POINTER(Conv2Desc), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_conv2_backward': (C.c_int, [C.POINTER(Conv2Desc), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    'asac_conv1_supported': (C.c_int, [C.POINTER(Conv1Desc)]),
-    'asac_conv1_param_count': (C.c_int64, [C.POINTER(Conv1Desc)]),
-    'asac_conv1_backward_workspace': (C.c_int64, [C.POINTER(Conv1Desc), C.c_int64]),
-    'asac_conv1_backward_slabs': (C.c_int, [C.POINTER(Conv1Desc), C.c_int64]),
-    'asac_conv1_forward': (C.c_int, [C.POINTER(Conv1Desc), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_conv1_backward': (C.c_int, [C.POINTER(Conv1Desc), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    'asac_gru_param_count': (C.c_int64, [C.POINTER(GruDesc)]),
-    'asac_gru_backward_workspace': (C.c_int64, [C.POINTER(GruDesc), C.c_int]),
-    'asac_gru_forward': (C.c_int, [C.POINTER(GruDesc), _PtrArray, _PtrArray, _PtrArray, _PtrArray, C.c_void_p,
-                                   C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
-                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_gru_forward_twin': (C.c_int, [C.POINTER(GruDesc), _PtrArray, _PtrArray, _PtrArray, _PtrArray, _PtrArray,
-                                        _PtrArray, _PtrArray, _PtrArray, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
-                                        C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_gru_backward': (C.c_int, [C.POINTER(GruDesc), _PtrArray, _PtrArray, _PtrArray, _PtrArray, C.c_void_p,
-                                    C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
-                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    'asac_gru_backward_at': (C.c_int, [C.POINTER(GruDesc), _PtrArray, _PtrArray, _PtrArray, _PtrArray, C.c_void_p,
-                                       C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_policy_loss_fwd_bwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_alpha_grad': (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
-    'asac_noise_fill': (C.c_int, [C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
-                                  C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    'asac_step_prologue': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int64, C.c_uint64,
-                                     C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
-                                     C.c_int, C.c_int, C.c_void_p]),
-    'asac_step_prologue_sample': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int64, C.c_uint64,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int,
-                                            C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_step_prologue_sample_partial': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int64, C.c_uint64,
-                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int,
-                                                    C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_window_gather_pad_w': (C.c_int, [C.POINTER(GatherKey), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
-                                           C.c_void_p]),
-    'asac_graph_launch': (C.c_int, [C.c_void_p, C.c_void_p]),
-    'asac_alpha_adam_step': (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
-                                       C.c_void_p, C.c_int, C.c_void_p]),
-    'asac_polyak': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
-    'asac_adam_step': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
-                                 C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
-    'asac_graph_replace_memset_nodes': (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    'asac_attention_mh_supported': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    'asac_attention_mh_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
-                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_attention_mh_proj_supported': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    'asac_attention_mh_proj_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                                 C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                 C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_attention_mh_block_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
-                                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
-                                                   C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_attention_mh_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
-                                             C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_attention_mh_dropout_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
-                                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint64,
-                                                    C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_attention_mh_dropout_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
-                                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint64,
-                                                     C.c_uint32, C.c_void_p, C.c_void_p]),
-    'asac_rows_proj_supported': (C.c_int, [C.c_int]),
-    'asac_rows_proj_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_rows_proj_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                          C.c_void_p]),
-    'asac_rows_resblock_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
-                                             C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_rows_resblock_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
-                                              C.c_void_p, C.c_void_p]),
-    'asac_rows_dense_proj_dropout_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                       C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint64, C.c_uint32,
-                                                       C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_rows_dense_proj_dropout_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                                        C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float,
-                                                        C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
-    'asac_rows_resblock_dropout_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
-                                                     C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint64, C.c_uint32,
-                                                     C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_rows_resblock_dropout_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
-                                                      C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint64, C.c_uint32,
-                                                      C.c_void_p, C.c_void_p]),
-    'asac_rows_gate_supported': (C.c_int, [C.c_int, C.c_int]),
-    'asac_rows_gate_forward': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
-                                         C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_rows_gate_backward': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
-                                          C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p]),
-    'asac_rope_supported': (C.c_int, [C.c_int, C.c_int]),
-    'asac_rope_forward': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                    C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
-                                    C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
-                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_rope_backward': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                     C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
-                                     C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
-                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_rows_proj_rope_forward': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
-                                              C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_rows_proj_rope_backward': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                               C.c_void_p, C.c_void_p]),
-    'asac_rows_affine_supported': (C.c_int, [C.c_int, C.c_int]),
-    'asac_rows_affine_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
-                                           C.c_void_p]),
-    'asac_rows_affine_gelu_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
-                                                C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_gru_wide_supported': (C.c_int, [C.c_int]),
-    'asac_gru_wide_forward_twin': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                             C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_gru_wide_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                        C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
-                                        C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_gru_wide_backward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p]),
-    'asac_cosine_gate_add': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
-                                       C.c_void_p]),
-    'asac_obs_decoder_packed_floats': (C.c_int64, []),
-    'asac_obs_decoder_saved_floats': (C.c_int64, [C.c_int64]),
-    'asac_obs_decoder_workspace_floats': (C.c_int64, [C.c_int64]),
-    'asac_obs_decoder_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(ObsDecoderParams),
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_obs_decoder_backward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.POINTER(ObsDecoderParams), C.c_int, C.c_void_p,
-                                            C.c_void_p]),
-    'asac_bc_loss_grad_workspace': (C.c_int64, []),
-    'asac_bc_loss_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int,
-                                    C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                    C.c_void_p]),
-    'asac_option_return': (C.c_int, [C.POINTER(VtraceArgs), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
-                                     C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
-    'asac_termination_loss_grad_workspace': (C.c_int64, []),
-    'asac_termination_loss_grad': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
-                                             C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_int, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_discrete_return': (C.c_int, [C.POINTER(VtraceArgs), C.POINTER(DiscreteReturn), C.c_void_p]),
-    'asac_option_discrete_return': (C.c_int, [C.POINTER(VtraceArgs), C.POINTER(DiscreteReturn), C.c_void_p, C.c_int64,
-                                              C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
-    'asac_discrete_q_loss_grad': (C.c_int, [C.POINTER(Branches), C.POINTER(Members), C.c_void_p, C.c_int64, C.c_void_p,
-                                            C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_discrete_policy_loss_grad': (C.c_int, [C.POINTER(Branches), C.c_void_p, C.c_int64, C.POINTER(Members), C.c_void_p,
-                                                 C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_int, C.c_void_p,
-                                                 C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_discrete_alpha_grad': (C.c_int, [C.POINTER(Branches), C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_hybrid_return': (C.c_int, [C.POINTER(VtraceArgs), C.POINTER(VtraceArgs), C.POINTER(DiscreteReturn), C.c_void_p,
-                                     C.c_void_p]),
-    'asac_hybrid_q_loss_grad': (C.c_int, [C.POINTER(Branches), C.POINTER(Members), C.c_void_p, C.c_int64, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                          C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_hybrid_policy_loss_grad': (C.c_int, [C.POINTER(Branches), C.c_void_p, C.c_int64, C.POINTER(Members), C.c_void_p,
-                                               C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
-                                               C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p]),
-    'asac_hybrid_alpha_grad': (C.c_int, [C.POINTER(Branches), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float,
-                                         C.c_int, C.c_void_p, C.c_void_p]),
-    'asac_dqn_return': (C.c_int, [C.POINTER(VtraceArgs), C.POINTER(DqnJob), C.c_void_p]),
-    'asac_dqn_q_loss_grad': (C.c_int, [C.POINTER(VtraceArgs), C.POINTER(DqnJob), C.c_void_p, C.c_int64, C.c_void_p,
-                                       C.c_void_p, C.c_void_p]),
-    'asac_dqn_act': (C.c_int, [C.POINTER(Branches), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p,
-                               C.c_int64, C.c_int, C.c_void_p]),
-    'asac_act_sizes_ok': (C.c_int, [C.POINTER(Branches), C.c_int]),
-    'asac_act_policy': (C.c_int, [C.POINTER(ActJob), C.c_void_p]),
-    'asac_rnd_supported': (C.c_int, [C.c_int, C.c_int, C.c_int]),
-    'asac_rnd_distill_workspace': (C.c_int64, [C.c_int64]),
-    'asac_rnd_distill': (C.c_int, [C.POINTER(RndDesc), C.POINTER(RndStack), C.POINTER(RndStack), C.c_void_p, C.c_int64,
-                                   C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
-                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                   C.c_void_p]),
-    'asac_rnd_pick': (C.c_int, [C.POINTER(RndDesc), C.POINTER(RndStack), C.POINTER(RndStack), C.c_void_p, C.c_int64,
-                                C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_drnd_supported': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    'asac_drnd_distill_workspace': (C.c_int64, [C.c_int64]),
-    'asac_drnd_distill': (C.c_int, [C.POINTER(Branches), C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
-                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_void_p]),
-    'asac_drnd_param_grads_workspace': (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
-    'asac_drnd_param_grads': (C.c_int, [C.POINTER(Branches), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_drnd_pick': (C.c_int, [C.POINTER(Branches), C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
-                                 C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_siamese_atc_workspace_floats': (C.c_int64, [C.c_int64, C.c_int]),
-    'asac_siamese_atc_loss_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_siamese_byol_loss_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_void_p]),
-    'asac_image_augment': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                     C.POINTER(ImageOp), C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'asac_image_warp': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                  C.POINTER(ImageWarpOp), C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_void_p, C.c_void_p]),
-    'asac_normalizer_row_lanes': (C.c_int, []),
-    'asac_obs_whiten': (C.c_int, [C.POINTER(WhitenJob), C.c_int, C.c_void_p, C.c_void_p]),
-    'asac_normalizer_update': (C.c_int, [C.POINTER(NormalizerJob), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-}
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 _lib = None
 
@@ -1475,7 +856,8 @@ def mlp_backward_tiles(N, E) -> int:
     return int(load().asac_mlp_backward_tiles(N, E))
 
 
-MLP_REDUCE_OVERWRITE, MLP_REDUCE_ACCUMULATE, MLP_REDUCE_DEFER = 0, 1, 2
+MLP_REDUCE_OVERWRITE, MLP_REDUCE_ACCUMULATE, MLP_REDUCE_DEFER = _defined(
+    'MLP_REDUCE_OVERWRITE', 'MLP_REDUCE_ACCUMULATE', 'MLP_REDUCE_DEFER')
 
 
 def mlp_param_extent(desc) -> int:
@@ -1857,9 +1239,10 @@ def attention_proj_backward(xq, xk, params, weights, grad_out, grad_weights, gra
                                                _p(workspace), _stream()), 'asac_attention_proj_backward')
 
 
-ATTN_SUM_DEFER = CONV_SUM_DEFER = SUM_DEFER = 2      # `accumulate` of attention_proj_backward / conv2_backward*: the partials
-                                                     # stay in the workspace (for `sum_partials_multi`)
-SUM_PARTIALS_MAX_JOBS = 16
+# `accumulate` of attention_proj_backward / conv2_backward*: the partials stay in the workspace (for `sum_partials_multi`)
+ATTN_SUM_DEFER, CONV_SUM_DEFER = _defined('ATTN_SUM_DEFER', 'CONV_SUM_DEFER')
+SUM_DEFER = ATTN_SUM_DEFER
+SUM_PARTIALS_MAX_JOBS = _defined('SUM_PARTIALS_MAX_JOBS')
 
 
 def attention_proj_partials(workspace, E: int, output_block: bool):
@@ -1883,7 +1266,7 @@ def sum_partials_multi(jobs):
     _check(load().asac_sum_partials_multi(len(jobs), arr, _stream()), 'asac_sum_partials_multi')
 
 
-LINEAR_TANH_MAX_IN, LINEAR_TANH_MAX_OUT = 64, 16
+LINEAR_TANH_MAX_IN, LINEAR_TANH_MAX_OUT = _defined('LINEAR_TANH_MAX_IN', 'LINEAR_TANH_MAX_OUT')
 
 
 def _rows2(x):
@@ -1916,7 +1299,7 @@ def linear_tanh_backward(x, weight, y, grad_y, grad_x, grad_params, accumulate, 
                                             _p(workspace), _stream()), 'asac_linear_tanh_backward')
 
 
-MASKED_MSE_MAX = 1 << 20
+MASKED_MSE_MAX = _defined('MASKED_MSE_MAX')
 _EXCHANGE_WS = {}
 
 
@@ -2613,7 +1996,7 @@ def obs_decoder_backward(state, packed, saved, frames, grad_frames, grad_state, 
                                             _p(workspace), _stream()), 'asac_obs_decoder_backward')
 
 
-GATE_MAX_LOSSES, GATE_MAX_N = 4, 1 << 20
+GATE_MAX_LOSSES, GATE_MAX_N = _defined('GATE_MAX_LOSSES', 'GATE_MAX_N')
 
 
 @_profiled
@@ -3251,7 +2634,7 @@ def xty_multi(jobs, accumulate=False):
 # ------------------------------------------------------------------------------------------------
 # behaviour cloning (csrc/imitation.hip)
 # ------------------------------------------------------------------------------------------------
-BC_MAX_ELEMENTS = 1 << 24
+BC_MAX_ELEMENTS = _defined('BC_MAX_ELEMENTS')
 
 
 def bc_loss_grad_workspace(device) -> torch.Tensor:
@@ -3289,8 +2672,8 @@ def bc_loss_grad(loc, scale, action, action_offset, t_valid, entropy_coef, loss_
 # ------------------------------------------------------------------------------------------------
 # the option-critic's per-option learner (csrc/option.hip)
 # ------------------------------------------------------------------------------------------------
-OPTION_MAX_OPTIONS = 1024
-TERMINATION_MAX_ROWS = 1 << 24
+OPTION_MAX_OPTIONS = _defined('OPTION_MAX_OPTIONS')
+TERMINATION_MAX_ROWS = _defined('TERMINATION_MAX_ROWS')
 
 
 @_profiled
@@ -3473,7 +2856,7 @@ def discrete_alpha_grad(br: Branches, logits, target, grad_slot, probs_out=None,
 # ------------------------------------------------------------------------------------------------
 # hybrid action spaces, policy-based SAC (csrc/hybrid.hip)
 # ------------------------------------------------------------------------------------------------
-MAX_ACTION = 64         # ASAC_MAX_ACTION
+MAX_ACTION = _defined('MAX_ACTION')
 
 
 def hybrid_sizes_ok(d_action_sizes, c_action_size: int, E: int, n: int, B: int) -> bool:
@@ -3684,7 +3067,7 @@ def act_policy(job: ActJob):
 # ------------------------------------------------------------------------------------------------
 # random network distillation, continuous actions (csrc/rnd.hip)
 # ------------------------------------------------------------------------------------------------
-RND_WIDTH, RND_MAX_IN, RND_MAX_SAMPLES, RND_MAX_ROWS = 64, 128, 64, 1 << 20
+RND_WIDTH, RND_MAX_IN, RND_MAX_SAMPLES, RND_MAX_ROWS = _defined('RND_WIDTH', 'RND_MAX_IN', 'RND_MAX_SAMPLES', 'RND_MAX_ROWS')
 
 
 def rnd_sizes_ok(S: int, A: int, k: int = 1, rows: int = 1) -> bool:
@@ -3773,7 +3156,7 @@ def rnd_pick(desc: RndDesc, predictor: RndStack, target: RndStack, state, loc, s
 # ------------------------------------------------------------------------------------------------
 # random network distillation, pure-discrete policy-based learner (csrc/drnd.hip)
 # ------------------------------------------------------------------------------------------------
-DRND_MAX_MEMBERS = 16
+DRND_MAX_MEMBERS = _defined('DRND_MAX_MEMBERS')
 
 
 def drnd_sizes_ok(S: int, d_action_sizes, k: int = 1, rows: int = 1) -> bool:
@@ -3801,6 +3184,11 @@ def drnd_table(members, device=None) -> torch.Tensor:
             raise AsacNativeError('drnd_table: a member is not a  S -> 64 -> 64  stack')
     dev = members[0][0].device if device is None else device
     return torch.tensor([[t.data_ptr() for t in m] for m in members], dtype=torch.int64).to(dev)
+
+
+def _table_p(table, struct):
+    """a `drnd_table` (or None) as the pointer to device `struct`s its entry points declare"""
+    return C.cast(_p(table), C.POINTER(struct))
 
 
 def _residual2(residual):
@@ -3847,9 +3235,9 @@ def drnd_distill(br: Branches, residual, predictors, targets, state, action, pad
     for tab in (predictors, targets):
         assert tab is None or (tab.is_cuda and tab.dtype == torch.int64 and tab.is_contiguous() and tab.shape == (D, 4))
     ws = workspace if workspace is not None else (drnd_distill_workspace(state.device, N) if 0 < N <= RND_MAX_ROWS else loss_out)
-    _check(load().asac_drnd_distill(C.byref(br), S, _residual2(residual), _p(predictors), _p(targets), ps, s_sb, s_st, pa, a_sb,
-                                    a_st, pm, m_sb, m_st, B, n, _p(sel), _p(x), _p(h1), _p(gz1), _p(gz2), _p(loss_out), _p(ws),
-                                    _stream()), 'asac_drnd_distill')
+    _check(load().asac_drnd_distill(C.byref(br), S, _residual2(residual), _table_p(predictors, RndStack),
+                                    _table_p(targets, RndStack), ps, s_sb, s_st, pa, a_sb, a_st, pm, m_sb, m_st, B, n, _p(sel),
+                                    _p(x), _p(h1), _p(gz1), _p(gz2), _p(loss_out), _p(ws), _stream()), 'asac_drnd_distill')
 
 
 @_profiled
@@ -3862,8 +3250,8 @@ def drnd_param_grads(br: Branches, S: int, sel, x, h1, gz1, gz2, grads, workspac
     assert sel.is_cuda and sel.dtype == torch.int32 and sel.is_contiguous()
     assert grads is None or (grads.is_cuda and grads.dtype == torch.int64 and grads.is_contiguous() and grads.shape == (D, 4))
     ws = workspace if workspace is not None else (drnd_param_grads_workspace(x.device, N, S, D) if 0 < N <= RND_MAX_ROWS else x)
-    _check(load().asac_drnd_param_grads(C.byref(br), int(S), _p(sel), _p(x), _p(h1), _p(gz1), _p(gz2), N, _p(grads), _p(ws),
-                                        _stream()), 'asac_drnd_param_grads')
+    _check(load().asac_drnd_param_grads(C.byref(br), int(S), _p(sel), _p(x), _p(h1), _p(gz1), _p(gz2), N,
+                                        _table_p(grads, RndGrads), _p(ws), _stream()), 'asac_drnd_param_grads')
 
 
 @_profiled
@@ -3888,16 +3276,18 @@ def drnd_pick(br: Branches, residual, predictors, targets, state, logits, u, act
         assert index_out.is_cuda and index_out.dtype == torch.int32 and index_out.is_contiguous() and index_out.numel() == batch
     for tab in (predictors, targets):
         assert tab is None or (tab.is_cuda and tab.dtype == torch.int64 and tab.is_contiguous() and tab.shape == (D, 4))
-    _check(load().asac_drnd_pick(C.byref(br), S, _residual2(residual), _p(predictors), _p(targets), _p(state), state.stride(0),
-                                 _p(logits), logits.stride(0), _p(u), k, batch, _p(action_out), _p(prob_out), _p(err_out),
-                                 _p(cand_out), _p(index_out), _stream()), 'asac_drnd_pick')
+    _check(load().asac_drnd_pick(C.byref(br), S, _residual2(residual), _table_p(predictors, RndStack),
+                                 _table_p(targets, RndStack), _p(state), state.stride(0), _p(logits), logits.stride(0), _p(u), k,
+                                 batch, _p(action_out), _p(prob_out), _p(err_out), _p(cand_out), _p(index_out), _stream()),
+           'asac_drnd_pick')
 
 
 # ------------------------------------------------------------------------------------------------
 # siamese representation losses (csrc/siamese.hip)
 # ------------------------------------------------------------------------------------------------
-SIAMESE_MAX_WIDTH, SIAMESE_MAX_BLOCK, SIAMESE_MAX_ROWS = 128, 64, 16384
-SIAMESE_BYOL_MAX_WIDTH, SIAMESE_BYOL_MAX_ROWS, SIAMESE_BYOL_WORKSPACE_FLOATS = 256, 1 << 20, 257
+SIAMESE_MAX_WIDTH, SIAMESE_MAX_BLOCK, SIAMESE_MAX_ROWS = _defined('SIAMESE_MAX_WIDTH', 'SIAMESE_MAX_BLOCK', 'SIAMESE_MAX_ROWS')
+SIAMESE_BYOL_MAX_WIDTH, SIAMESE_BYOL_MAX_ROWS, SIAMESE_BYOL_WORKSPACE_FLOATS = _defined(
+    'SIAMESE_BYOL_MAX_WIDTH', 'SIAMESE_BYOL_MAX_ROWS', 'SIAMESE_BYOL_WORKSPACE_FLOATS')
 
 
 def siamese_atc_workspace_floats(N: int, E: int) -> int:
@@ -3938,8 +3328,9 @@ def siamese_byol_loss_grad(pred, t_proj, pad, loss_out, g_pred, workspace):
 # ------------------------------------------------------------------------------------------------
 # image augmentations (csrc/image.hip)
 # ------------------------------------------------------------------------------------------------
-IMAGE_MAX_OPS, IMAGE_MAX_PLANE, IMAGE_MAX_KERNEL = 8, 9216, 31
-IMAGE_COPY, IMAGE_BLUR, IMAGE_BRIGHTNESS, IMAGE_CROP_RESIZE, IMAGE_SALT_PEPPER, IMAGE_UNIFORM_NOISE = range(6)
+IMAGE_MAX_OPS, IMAGE_MAX_PLANE, IMAGE_MAX_KERNEL = _defined('IMAGE_MAX_OPS', 'IMAGE_MAX_PLANE', 'IMAGE_MAX_KERNEL')
+IMAGE_COPY, IMAGE_BLUR, IMAGE_BRIGHTNESS, IMAGE_CROP_RESIZE, IMAGE_SALT_PEPPER, IMAGE_UNIFORM_NOISE = _defined(
+    'IMAGE_COPY', 'IMAGE_BLUR', 'IMAGE_BRIGHTNESS', 'IMAGE_CROP_RESIZE', 'IMAGE_SALT_PEPPER', 'IMAGE_UNIFORM_NOISE')
 IMAGE_STATE_WORDS = 2          # int64: the draw counter, the arrival word
 IMAGE_DRAWN = ('counter', 'choice', 'top', 'left', 'sigma', 'factor')     # the f64 record of a call's draws
 
@@ -3973,8 +3364,9 @@ def image_augment(x, y, ops, seed=0, instance=0, state=None, drawn=None):
 # ------------------------------------------------------------------------------------------------
 # image warps (csrc/image.hip): RandomResizedCrop / ElasticTransform with nearest sampling
 # ------------------------------------------------------------------------------------------------
-IMAGE_WARP_MAX_KERNEL = 63
-IMAGE_WARP_COPY, IMAGE_WARP_RESIZED_CROP, IMAGE_WARP_ELASTIC = range(3)
+IMAGE_WARP_MAX_KERNEL = _defined('IMAGE_WARP_MAX_KERNEL')
+IMAGE_WARP_COPY, IMAGE_WARP_RESIZED_CROP, IMAGE_WARP_ELASTIC = _defined(
+    'IMAGE_WARP_COPY', 'IMAGE_WARP_RESIZED_CROP', 'IMAGE_WARP_ELASTIC')
 IMAGE_WARP_DRAWN = ('counter', 'choice', 'top', 'left', 'height', 'width')     # the f64 record of a call's draws
 
 
@@ -4011,9 +3403,9 @@ warp_image = _profiled(warp_image, 'asac_image_warp')
 # ------------------------------------------------------------------------------------------------
 # observation normalization (csrc/normalize.hip): one-launch whitening, one-launch statistics update
 # ------------------------------------------------------------------------------------------------
-NORM_MAX_OBS = 8
-NORM_ROW_LANES = 64        # logical row lanes of the update's sums (ASAC_NORM_ROW_LANES): the tests' bound derives from it
-NORM_F32, NORM_U8 = 0, 1
+NORM_MAX_OBS = _defined('NORM_MAX_OBS')
+NORM_ROW_LANES = _defined('NORM_ROW_LANES')        # logical row lanes of the update's sums: the tests' bound derives from it
+NORM_F32, NORM_U8 = _defined('NORM_F32', 'NORM_U8')
 
 
 def whiten_jobs(specs):

@@ -54,21 +54,19 @@ def test_the_branch_is_asked_behind_the_four_earlier_ones():
 
 
 def test_header_binding_and_notes_name_both_entry_points():
-    from asac_amd import native
-    text = (ROOT / 'include' / 'asac_hip.h').read_text()
-    header = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = set(re.findall(r'\b(asac_act_[a-z0-9_]+)\s*\(', header))
+    from asac_amd import abi, native
+    declared = {name for name in abi.functions if name.startswith('asac_act_')}
     bound = {name for name in native.EXPORTED_SYMBOLS if name.startswith('asac_act_')}
     assert declared == bound == set(ENTRY_POINTS)
     notes = (ROOT / 'INTEGRATION.md').read_text()
     for name in ENTRY_POINTS:
         assert callable(getattr(native, name[len('asac_'):])) and f'| `{name}` |' in notes
-    assert int(re.search(r'#define ASAC_ABI_VERSION (\d+)', text).group(1)) == native.ABI_VERSION == 91
-    assert int(re.search(r'#define ASAC_ACT_MAX_CONT (\d+)', text).group(1)) == native.ACT_MAX_CONT == 8
+    assert abi.defines['ASAC_ABI_VERSION'] == native.ABI_VERSION == 91
+    assert abi.defines['ASAC_ACT_MAX_CONT'] == native.ACT_MAX_CONT == 8
     assert 'act.hip' in __import__('importlib').import_module('csrc.build').SOURCES
 
 
-C_TYPES = {'asac_branches_t': 'Branches', 'const float*': 'c_void_p', 'float*': 'c_void_p', 'int64_t': 'c_long',
+C_TYPES = {'asac_branches_t': 'asac_branches_t', 'const float*': 'c_void_p', 'float*': 'c_void_p', 'int64_t': 'c_long',
            'int32_t': 'c_int', 'float': 'c_float'}
 
 
@@ -86,7 +84,7 @@ def test_the_ctypes_mirror_has_the_headers_fields_in_order():
         fields += [(n.strip(), C_TYPES[ctype]) for n in names.split(',')]
     mirror = [(n, t.__name__) for n, t in native.ActJob._fields_]
     assert mirror == fields
-    assert fields[0] == ('branches', 'Branches') and fields[-2][0] == 'B'
+    assert fields[0] == ('branches', 'asac_branches_t') and native.ActJob._fields_[0][1] is native.Branches and fields[-2][0] == 'B'
 
 
 def test_sizes_ok_on_the_host_is_the_librarys_answer():

@@ -1,8 +1,6 @@
 """CPU: the draw contract of the attention-weight dropout (csrc/asac_dropout.h) as tests/attn_dropout_ref.py restates it —
 Philox4x32-10 against the published Random123 known-answer vectors, the threshold, the statistics and the independence of
 the restated mask — and the additive ABI of the two dropout entry points and the Python gate."""
-import re
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -10,8 +8,6 @@ import torch
 
 from tests import attn_dropout_ref as ref
 
-ROOT = Path(__file__).resolve().parent.parent
-HEADER = ROOT / 'include' / 'asac_hip.h'
 
 # Random123 (kat_vectors, philox4x32 with 10 rounds): counter, key -> output
 KAT = [
@@ -79,9 +75,9 @@ def test_mask_layout_does_not_depend_on_the_window():
 
 
 def _declared(name):
-    hdr = re.sub(r'/\*.*?\*/', '', HEADER.read_text(), flags=re.S)
-    m = re.search(r'\b' + name + r'\s*\(([^;{]*?)\)\s*;', hdr, re.S)
-    return None if m is None else [p_.strip() for p_ in m.group(1).split(',')]
+    """the header's parameters of `name` ((name, base type, pointer depth) each), None where it declares none such"""
+    from asac_amd import abi
+    return abi.functions[name][1] if name in abi.functions else None
 
 
 def test_abi_is_additive():
@@ -93,20 +89,20 @@ def test_abi_is_additive():
     assert fwd is not None and bwd is not None
     # the arguments of the plain entry points, then thr, scale, seed, instance, (state,) used, stream
     assert fwd[:len(plain_f) - 1] == plain_f[:-1] and bwd[:len(plain_b) - 1] == plain_b[:-1]
-    assert [a.split()[-1] for a in fwd[len(plain_f) - 1:]] == ['thr', 'scale', 'seed', 'instance', 'state', 'used', 'stream']
-    assert [a.split()[-1] for a in bwd[len(plain_b) - 1:]] == ['thr', 'scale', 'seed', 'instance', 'used', 'stream']
+    assert [a[0] for a in fwd[len(plain_f) - 1:]] == ['thr', 'scale', 'seed', 'instance', 'state', 'used', 'stream']
+    assert [a[0] for a in bwd[len(plain_b) - 1:]] == ['thr', 'scale', 'seed', 'instance', 'used', 'stream']
     for name, params in (('asac_attention_mh_dropout_forward', fwd), ('asac_attention_mh_dropout_backward', bwd)):
         assert hasattr(lib, name)
         res, args = native._SIGNATURES[name]
         assert res is C.c_int and len(args) == len(params)
-        for decl, ct in zip(params, args):      # every declared type travels as the ctypes type of its width
-            want = (C.c_void_p if '*' in decl else
+        for (pname, base, depth), ct in zip(params, args):      # every declared type travels as the ctypes type of its width
+            want = (C.c_void_p if depth else
                     {'int': C.c_int, 'int64_t': C.c_int64, 'uint32_t': C.c_uint32, 'uint64_t': C.c_uint64,
-                     'float': C.c_float}[decl.split()[0]])
-            assert ct is want, (name, decl, ct)
+                     'float': C.c_float}[base])
+            assert ct is want, (name, pname, ct)
     assert len(_declared('asac_attention_mh_forward')) == 19 and len(_declared('asac_attention_mh_backward')) == 19
-    m = re.search(r'#define ASAC_ABI_VERSION (\d+)', HEADER.read_text())
-    assert lib.asac_version() == int(m.group(1)) == native.ABI_VERSION == 91
+    from asac_amd import abi
+    assert lib.asac_version() == abi.defines['ASAC_ABI_VERSION'] == native.ABI_VERSION == 91
     assert callable(native.attention_mh_dropout_forward) and callable(native.attention_mh_dropout_backward)
 
 

@@ -4,7 +4,6 @@ predicates refuse.  Only `_ok` questions and refusals are asked of the library: 
 launch, so no GPU is needed.  (Without a device the forward's `_ok` reads a CU count of 0 and refuses every launch; what
 it accepts is asked on the GPU, `tests/test_critic_forward_rider_gpu.py`.)"""
 import ctypes as C
-import re
 from pathlib import Path
 
 import torch
@@ -21,16 +20,14 @@ SAVE = C.c_void_p(0x60000)
 
 
 def test_abi_version_is_unchanged_and_header_binding_and_notes_agree_on_the_exports():
-    text = (ROOT / 'include' / 'asac_hip.h').read_text()
-    assert native.ABI_VERSION == 91 and int(re.search(r'#define ASAC_ABI_VERSION (\d+)', text).group(1)) == 91
-    header = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
+    from asac_amd import abi
+    assert native.ABI_VERSION == 91 and abi.defines['ASAC_ABI_VERSION'] == 91
     notes = (ROOT / 'INTEGRATION.md').read_text()
     lib = native.load()
     for name in EXPORTS:
-        m = re.search(r'\b(?:int|int64_t)\s+' + name + r'\s*\(([^)]*)\)\s*;', header)
-        assert m, name
+        assert abi.functions[name][0] in ('int', 'int64_t'), name
         assert name in native.EXPORTED_SYMBOLS and getattr(lib, name) is not None
-        assert len(native._SIGNATURES[name][1]) == len([p for p in m.group(1).split(',') if p.strip()]), name
+        assert len(native._SIGNATURES[name][1]) == len(abi.functions[name][1]), name
         assert f'`{name}`' in notes, name
     # pure additions: the entry points they stand beside keep their signatures
     assert len(native._SIGNATURES['asac_policy_sample_q_forward'][1]) == 6

@@ -3,8 +3,6 @@ checks, the draw layout as tests/dense_dropout_ref.py restates it, the restateme
 the float32 CPU composition fed the restated masks against the cap the GPU tests hold the kernels to."""
 import copy
 import ctypes as C
-import re
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -12,17 +10,15 @@ import torch
 
 from tests import dense_dropout_ref as ref
 
-ROOT = Path(__file__).resolve().parent.parent
-HEADER = ROOT / 'include' / 'asac_hip.h'
 NEW = ('asac_rows_dense_proj_dropout_forward', 'asac_rows_dense_proj_dropout_backward',
        'asac_rows_resblock_dropout_forward', 'asac_rows_resblock_dropout_backward')
 SHAPES = [(3, 7, 7, 32), (3, 7, 1, 64), (5, 9, 4, 128), (1, 9, 9, 64), (70, 9, 3, 64), (3, 7, 2, 64)]      # (B, L, tail, E)
 
 
 def _declared(name):
-    hdr = re.sub(r'/\*.*?\*/', '', HEADER.read_text(), flags=re.S)
-    m = re.search(r'\b' + name + r'\s*\(([^;{]*?)\)\s*;', hdr, re.S)
-    return None if m is None else [p_.strip() for p_ in m.group(1).split(',')]
+    """the header's parameters of `name` ((name, base type, pointer depth) each), None where it declares none such"""
+    from asac_amd import abi
+    return abi.functions[name][1] if name in abi.functions else None
 
 
 def test_the_four_exports_exist_and_the_abi_number_is_unchanged():
@@ -33,16 +29,16 @@ def test_the_four_exports_exist_and_the_abi_number_is_unchanged():
         assert params is not None and hasattr(lib, name), name
         res, args = native._SIGNATURES[name]
         assert res is C.c_int and len(args) == len(params)
-        for decl, ct in zip(params, args):      # every declared type travels as the ctypes type of its width
-            want = (C.c_void_p if '*' in decl else
+        for (pname, base, depth), ct in zip(params, args):      # every declared type travels as the ctypes type of its width
+            want = (C.c_void_p if depth else
                     {'int': C.c_int, 'int64_t': C.c_int64, 'uint32_t': C.c_uint32, 'uint64_t': C.c_uint64,
-                     'float': C.c_float}[decl.split()[0]])
-            assert ct is want, (name, decl, ct)
-        tail = [a.split()[-1] for a in params[-7:]]
+                     'float': C.c_float}[base])
+            assert ct is want, (name, pname, ct)
+        tail = [a[0] for a in params[-7:]]
         want = ['thr', 'scale', 'seed', 'instance', 'state', 'used', 'stream']
         assert tail == want if name.endswith('forward') else tail[1:] == want[:4] + want[5:], (name, tail)
-    m = re.search(r'#define ASAC_ABI_VERSION (\d+)', HEADER.read_text())
-    assert lib.asac_version() == int(m.group(1)) == native.ABI_VERSION == 91
+    from asac_amd import abi
+    assert lib.asac_version() == abi.defines['ASAC_ABI_VERSION'] == native.ABI_VERSION == 91
     for name in NEW:
         assert callable(getattr(native, name[len('asac_'):]))
 

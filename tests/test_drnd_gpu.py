@@ -657,6 +657,7 @@ def test_entry_points_refuse_bad_arguments():
     c = dr.make_distill_case(B, n, S, sizes, seed=1)
     br, flags, pred, targ, keep = _tables(c)
     lib, s, bad, p = native.load(), native._stream(), 1, native._p      # 1: hipErrorInvalidValue
+    stacks, gstacks = (lambda t: native._table_p(t, native.RndStack)), (lambda t: native._table_p(t, native.RndGrads))
     N, K, D = B * n, br.K, br.D
     marker = lambda *shape: torch.full(shape, 7., device='cuda')      # noqa: E731
     x, h1, gz1, gz2, loss = marker(N, S), marker(N, K, 64), marker(N, K, 64), marker(N, K, 64), marker(1)
@@ -679,16 +680,16 @@ def test_entry_points_refuse_bad_arguments():
     ok_res = res(*map(int, flags))
 
     def distill(b=br, S_=S, r=ok_res, pr=pred, tg=targ, B_=B, h=h1, lo=loss, w=ws):
-        return lib.asac_drnd_distill(C.byref(b), S_, r, p(pr), p(tg), p(state), state.stride(0), state.stride(1), p(act),
+        return lib.asac_drnd_distill(C.byref(b), S_, r, stacks(pr), stacks(tg), p(state), state.stride(0), state.stride(1), p(act),
                                      act.stride(0), act.stride(1), p(pad), pad.stride(0), pad.stride(1), B_, n, p(sel), p(x), p(h),
                                      p(gz1), p(gz2), p(lo), p(w), s)
 
     def param_grads(b=br, S_=S, g_=grads, rows=N, h=h1, w=wg):
-        return lib.asac_drnd_param_grads(C.byref(b), S_, p(sel), p(x), p(h), p(gz1), p(gz2), rows, p(g_), p(w), s)
+        return lib.asac_drnd_param_grads(C.byref(b), S_, p(sel), p(x), p(h), p(gz1), p(gz2), rows, gstacks(g_), p(w), s)
 
     def pick(b=br, S_=S, r=ok_res, pr=pred, tg=targ, k_=k, batch=B, a=action, u_=u):
-        return lib.asac_drnd_pick(C.byref(b), S_, r, p(pr), p(tg), p(state[:, 0]), state.stride(0), p(logits), logits.stride(0),
-                                  p(u_), k_, batch, p(a), p(prob), p(err), None, None, s)
+        return lib.asac_drnd_pick(C.byref(b), S_, r, stacks(pr), stacks(tg), p(state[:, 0]), state.stride(0), p(logits),
+                                  logits.stride(0), p(u_), k_, batch, p(a), p(prob), p(err), None, None, s)
 
     wide, sum_off = native.branches((9, 8)), native.branches(sizes)
     sum_off.D = D + 1

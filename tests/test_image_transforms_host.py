@@ -2,7 +2,6 @@
 (tests/image_ref.py), the draw rules, the unsupported arguments, what `_native_ops` reduces to a launch, and the surface of
 `asac_image_augment` (header, binding, wrapper, INTEGRATION.md, the host refusals)."""
 import ctypes
-import re
 from pathlib import Path
 
 import numpy as np
@@ -226,24 +225,12 @@ def test_cpu_tensors_take_the_module_code_and_transform_wraps_unchanged():
 
 
 # ---------------------------------------------------------------------------------------------- surface
-def _header():
-    return (ROOT / 'include' / 'asac_hip.h').read_text()
-
-
-def _header_params(name):
-    hdr = re.sub(r'/\*.*?\*/', '', _header(), flags=re.S)
-    got = re.search(r'\b' + name + r'\s*\(([^;{]*?)\)\s*;', hdr, re.S)
-    assert got, f'{name} is not declared in include/asac_hip.h'
-    return [p for p in got.group(1).split(',') if p.strip()]
-
-
 def test_entry_point_is_declared_bound_wrapped_and_documented():
     import inspect
-    from asac_amd import native
-    hdr = _header()
-    assert native.ABI_VERSION == 91 and int(re.search(r'#define ASAC_ABI_VERSION (\d+)', hdr).group(1)) == 91
+    from asac_amd import abi, native
+    assert native.ABI_VERSION == 91 and abi.defines['ASAC_ABI_VERSION'] == 91
     assert 'asac_image_augment' in native.EXPORTED_SYMBOLS
-    assert len(native._SIGNATURES['asac_image_augment'][1]) == len(_header_params('asac_image_augment')) == 15
+    assert len(native._SIGNATURES['asac_image_augment'][1]) == len(abi.functions['asac_image_augment'][1]) == 15
     assert native.image_augment.__name__ == 'image_augment'
     assert [n for n, _ in inspect.getmembers(native) if n.startswith('image_') and callable(getattr(native, n))] == \
         ['image_augment', 'image_ops']
@@ -252,12 +239,11 @@ def test_entry_point_is_declared_bound_wrapped_and_documented():
                          ('ASAC_IMAGE_BLUR', native.IMAGE_BLUR), ('ASAC_IMAGE_BRIGHTNESS', native.IMAGE_BRIGHTNESS),
                          ('ASAC_IMAGE_CROP_RESIZE', native.IMAGE_CROP_RESIZE), ('ASAC_IMAGE_SALT_PEPPER', native.IMAGE_SALT_PEPPER),
                          ('ASAC_IMAGE_UNIFORM_NOISE', native.IMAGE_UNIFORM_NOISE)):
-        assert int(re.search(r'#define ' + macro + r' (\d+)', hdr).group(1)) == value, macro
+        assert abi.defines[macro] == value, macro
     # 84 x 84 and 30 x 30 fit, and two workgroups (two planes each, plus the taps) fit a CU's 160 KiB
     assert 84 * 84 <= native.IMAGE_MAX_PLANE and 2 * (2 * native.IMAGE_MAX_PLANE + 68) * 4 <= 160 * 1024
     # the descriptor: as many fields, in the header's order
-    body = re.search(r'typedef struct \{([^}]*)\} asac_image_op_t;', re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)).group(1)
-    fields = [n.strip() for decl in body.split(';') if decl.strip() for n in decl.strip().split(None, 1)[1].split(',')]
+    fields = [field for field, *_ in abi.structs['asac_image_op_t']]
     assert fields == [n for n, _ in native.ImageOp._fields_] and ctypes.sizeof(native.ImageOp) == 4 * len(fields)
     assert 'asac_image_augment' in (ROOT / 'INTEGRATION.md').read_text()
     assert "'image.hip'" in (ROOT / 'advanced-soft-actor-critic_amd' / 'csrc' / 'build.py').read_text()

@@ -4,8 +4,6 @@ port of the reference's `ugv_parking` augmentation block, what `_native_ops` red
 surface of `asac_image_warp` (header, binding, the host refusals)."""
 import ctypes
 import math
-import re
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -16,7 +14,6 @@ from algorithm.utils import image_transforms as T
 from algorithm.utils.image_transforms import InterpolationMode
 import algorithm.nn_models as m
 
-ROOT = Path(__file__).resolve().parent.parent
 NEAREST, BILINEAR = InterpolationMode.NEAREST, InterpolationMode.BILINEAR
 
 
@@ -215,22 +212,18 @@ def test_arguments():
 
 # ---------------------------------------------------------------------------------------------- surface
 def test_surface():
-    from asac_amd import native
-    hdr = (ROOT / 'include' / 'asac_hip.h').read_text()
-    bare = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-    assert native.ABI_VERSION == 91 and int(re.search(r'#define ASAC_ABI_VERSION (\d+)', hdr).group(1)) == 91
-    params = re.search(r'\basac_image_warp\s*\(([^;{]*?)\)\s*;', bare, re.S)
-    assert params, 'asac_image_warp is not declared in include/asac_hip.h'
-    assert len(native._SIGNATURES['asac_image_warp'][1]) == len(params.group(1).split(',')) == 17
+    from asac_amd import abi, native
+    assert native.ABI_VERSION == 91 and abi.defines['ASAC_ABI_VERSION'] == 91
+    assert 'asac_image_warp' in abi.functions, 'asac_image_warp is not declared in include/asac_hip.h'
+    assert len(native._SIGNATURES['asac_image_warp'][1]) == len(abi.functions['asac_image_warp'][1]) == 17
     assert 'asac_image_warp' in native.EXPORTED_SYMBOLS
     for name, value in (('ASAC_IMAGE_WARP_MAX_KERNEL', native.IMAGE_WARP_MAX_KERNEL), ('ASAC_IMAGE_WARP_COPY', native.IMAGE_WARP_COPY),
                         ('ASAC_IMAGE_WARP_RESIZED_CROP', native.IMAGE_WARP_RESIZED_CROP),
                         ('ASAC_IMAGE_WARP_ELASTIC', native.IMAGE_WARP_ELASTIC)):
-        assert int(re.search(rf'#define {name} (\d+)', hdr).group(1)) == value, name
+        assert abi.defines[name] == value, name
     assert native.IMAGE_WARP_MAX_KERNEL == 63
     assert native.IMAGE_WARP_DRAWN == ('counter', 'choice', 'top', 'left', 'height', 'width')
-    body = re.search(r'typedef struct \{([^}]*)\} asac_image_warp_op_t;', bare).group(1)
-    fields = [n.strip() for decl in body.split(';') if decl.strip() for n in decl.strip().split(None, 1)[1].split(',')]
+    fields = [field for field, *_ in abi.structs['asac_image_warp_op_t']]
     assert fields == [n for n, _ in native.ImageWarpOp._fields_] and ctypes.sizeof(native.ImageWarpOp) == 4 * len(fields)
     # the existing entry point keeps its bits
     assert native.IMAGE_DRAWN == ('counter', 'choice', 'top', 'left', 'sigma', 'factor') and native.IMAGE_MAX_KERNEL == 31

@@ -3,13 +3,10 @@ entry points and their binding, the dispatch predicate, and the owner on CPU ten
 and the eager update.  (The learner has no CPU path: its checkpoint layout with the switch on and off is compared in
 tests/test_normalized_step_gpu.py.)"""
 import ctypes
-import re
-from pathlib import Path
 
 import pytest
 import torch
 
-ROOT = Path(__file__).resolve().parent.parent
 SYMBOLS = ['asac_obs_whiten', 'asac_normalizer_update', 'asac_normalizer_row_lanes']
 
 TAKEN = dict(enabled=True, use_normalization=True, plain_learner=True, data_parallel=False, float32_on_device=True)
@@ -27,17 +24,15 @@ def test_library_exports_the_entry_points():
 
 
 def test_binding_lists_the_header_argument_counts():
-    from asac_amd import native
-    hdr = re.sub(r'/\*.*?\*/', '', (ROOT / 'include' / 'asac_hip.h').read_text(), flags=re.S)
+    from asac_amd import abi, native
     for name in SYMBOLS:
-        m = re.search(r'\b' + name + r'\s*\(([^;{]*?)\)\s*;', hdr, re.S)
-        assert m, f'{name} is not declared'
-        params = [p_ for p_ in m.group(1).split(',') if p_.strip() and p_.strip() != 'void']
+        assert name in abi.functions, f'{name} is not declared'
+        params = abi.functions[name][1]
         assert name in native._SIGNATURES and len(native._SIGNATURES[name][1]) == len(params), name
     for wrapper in ('whiten_jobs', 'obs_whiten', 'normalizer_update'):
         assert callable(getattr(native, wrapper)), wrapper
-    assert re.search(r'#define ASAC_NORM_MAX_OBS (\d+)', hdr).group(1) == str(native.NORM_MAX_OBS) == '8'
-    assert re.search(r'#define ASAC_NORM_ROW_LANES (\d+)', hdr).group(1) == str(native.NORM_ROW_LANES)
+    assert abi.defines['ASAC_NORM_MAX_OBS'] == native.NORM_MAX_OBS == 8
+    assert abi.defines['ASAC_NORM_ROW_LANES'] == native.NORM_ROW_LANES
     assert native.ABI_VERSION == 91, 'pure additions: the ABI version stays'
 
 

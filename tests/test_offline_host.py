@@ -1,7 +1,6 @@
 """CPU: the host side of the offline loss on the native continuous path (`hip_config['fused_offline']`): the dispatch
 predicate, the three entry points' bookkeeping, what the Python wrappers refuse before a launch, and the float64
 restatement the GPU tests compare the kernels with (tests/offline_ref.py)."""
-import re
 from pathlib import Path
 
 import numpy as np
@@ -45,21 +44,18 @@ def test_the_switch_is_on_by_default_and_gates_the_stock_path():
 
 
 def test_header_binding_and_notes_name_the_three_entry_points():
-    from asac_amd import native
-    text = (ROOT / 'include' / 'asac_hip.h').read_text()
-    header = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
+    from asac_amd import abi, native
     notes = (ROOT / 'INTEGRATION.md').read_text()
     for name in ENTRY_POINTS:
-        assert re.search(r'\bint\s+' + name + r'\s*\(', header), name
+        assert abi.functions[name][0] == 'int', name
         assert name in native.EXPORTED_SYMBOLS
         assert f'| `{name}` |' in notes
         # the binding's argument count is the header's
-        params = re.search(r'\bint\s+' + name + r'\s*\(([^)]*)\)', header).group(1)
-        assert len(native._SIGNATURES[name][1]) == len([p for p in params.split(',') if p.strip()]), name
+        assert len(native._SIGNATURES[name][1]) == len(abi.functions[name][1]), name
     for wrapper in ('mlp_backward_policy_sample', 'mlp_backward_policy_sample_offline', 'policy_step_fused',
                     'policy_step_fused_offline', 'policy_offline_term'):
         assert callable(getattr(native, wrapper))
-    assert int(re.search(r'#define ASAC_ABI_VERSION (\d+)', text).group(1)) == native.ABI_VERSION
+    assert abi.defines['ASAC_ABI_VERSION'] == native.ABI_VERSION
     # the old entry points keep their signatures: the `_offline` ones are the old ones plus (off_action, off_row_stride)
     for old in ('asac_mlp_backward_policy_sample', 'asac_policy_step_fused'):
         assert len(native._SIGNATURES[old + '_offline'][1]) == len(native._SIGNATURES[old][1]) + 2

@@ -1,6 +1,5 @@
 """CPU: the host side of the pure-discrete option on the native path (`hip_config['fused_option_discrete']`): which
 configurations `fused_option_discrete_applies` takes, and that the entry point is declared, bound and wrapped."""
-import re
 from pathlib import Path
 
 import pytest
@@ -52,12 +51,9 @@ def test_the_plain_learner_s_switches_stay_off_for_an_option():
 
 
 def test_header_binding_and_wrapper_name_the_entry_point():
-    from asac_amd import native
-    text = (ROOT / 'include' / 'asac_hip.h').read_text()
-    header = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    m = re.search(r'\basac_option_discrete_return\s*\(([^;{]*?)\)\s*;', header, re.S)
-    assert m, 'asac_option_discrete_return is not declared'
-    assert len(m.group(1).split(',')) == len(native._SIGNATURES['asac_option_discrete_return'][1]) == 11
+    from asac_amd import abi, native
+    assert 'asac_option_discrete_return' in abi.functions, 'asac_option_discrete_return is not declared'
+    assert len(abi.functions['asac_option_discrete_return'][1]) == len(native._SIGNATURES['asac_option_discrete_return'][1]) == 11
     assert 'asac_option_discrete_return' in native.EXPORTED_SYMBOLS and callable(native.option_discrete_return)
-    assert int(re.search(r'#define ASAC_OPTION_MAX_OPTIONS (\d+)', text).group(1)) == native.OPTION_MAX_OPTIONS
+    assert abi.defines['ASAC_OPTION_MAX_OPTIONS'] == native.OPTION_MAX_OPTIONS
     assert 'asac_option_discrete_return' in (ROOT / 'INTEGRATION.md').read_text()

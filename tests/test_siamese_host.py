@@ -2,7 +2,6 @@
 csrc/siamese.hip): the predicate that decides when the learner takes them, and the three entry points named alike by the
 header, the binding, the wrappers and INTEGRATION.md."""
 import inspect
-import re
 from pathlib import Path
 
 import pytest
@@ -59,23 +58,15 @@ def test_fused_siamese_applies(over, want):
     assert _applies(**over) is want
 
 
-def _header_params(name):
-    hdr = re.sub(r'/\*.*?\*/', '', (ROOT / 'include' / 'asac_hip.h').read_text(), flags=re.S)
-    m = re.search(r'\b' + name + r'\s*\(([^;{]*?)\)\s*;', hdr, re.S)
-    assert m, f'{name} is not declared in include/asac_hip.h'
-    return [p for p in m.group(1).split(',') if p.strip()]
-
-
 def test_entry_points_are_declared_bound_and_wrapped_alike():
     import asac_amd  # noqa: F401
-    from asac_amd import native
+    from asac_amd import abi, native
     assert native.ABI_VERSION == 91          # pure additions
-    hdr = (ROOT / 'include' / 'asac_hip.h').read_text()
-    assert int(re.search(r'#define ASAC_ABI_VERSION (\d+)', hdr).group(1)) == 91
+    assert abi.defines['ASAC_ABI_VERSION'] == 91
     for name in ENTRY_POINTS:
         assert name in native.EXPORTED_SYMBOLS
-        assert len(native._SIGNATURES[name][1]) == len(_header_params(name)), name
-    assert len(_header_params('asac_siamese_atc_loss_grad')) == 12 and len(_header_params('asac_siamese_byol_loss_grad')) == 9
+        assert len(native._SIGNATURES[name][1]) == len(abi.functions[name][1]), name
+    assert len(abi.functions['asac_siamese_atc_loss_grad'][1]) == 12 and len(abi.functions['asac_siamese_byol_loss_grad'][1]) == 9
     # the wrappers carry the entry points' names (the launch profiler's keys are derived from them)
     assert native.siamese_atc_loss_grad.__name__ == 'siamese_atc_loss_grad'
     assert native.siamese_byol_loss_grad.__name__ == 'siamese_byol_loss_grad'
@@ -85,8 +76,8 @@ def test_entry_points_are_declared_bound_and_wrapped_alike():
                          ('ASAC_SIAMESE_MAX_ROWS', native.SIAMESE_MAX_ROWS),
                          ('ASAC_SIAMESE_BYOL_MAX_WIDTH', native.SIAMESE_BYOL_MAX_WIDTH),
                          ('ASAC_SIAMESE_BYOL_WORKSPACE_FLOATS', native.SIAMESE_BYOL_WORKSPACE_FLOATS)):
-        assert int(re.search(r'#define ' + macro + r' (\d+)', hdr).group(1)) == value, macro
-    assert '#define ASAC_SIAMESE_BYOL_MAX_ROWS (1 << 20)' in hdr and native.SIAMESE_BYOL_MAX_ROWS == 1 << 20
+        assert abi.defines[macro] == value, macro
+    assert abi.defines['ASAC_SIAMESE_BYOL_MAX_ROWS'] == native.SIAMESE_BYOL_MAX_ROWS == 1 << 20
 
 
 def test_profiler_names_and_documents():

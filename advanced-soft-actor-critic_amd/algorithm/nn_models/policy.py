@@ -129,14 +129,22 @@ class ModelPolicy(ModelBasePolicy):
     def d_head_raw(self, state):
         """the discrete branches' head outputs, concatenated [.., D]: logits before `OneHotCategorical` normalises them;
         the fused discrete kernels (`native.discrete_*`) form the branch softmax themselves."""
-        h = self.dense(state)
-        return torch.cat([head(h) for head in self.d_dense_list], dim=-1)
+        return self._d_logits(self.dense(state))
+
+    def _d_logits(self, h):
+        """the branch stacks on the trunk's output, concatenated: one launch per pass where the learner attached a bank
+        (`fused_heads.attach`), else stack by stack"""
+        from algorithm.fused_heads import d_heads      # lazy: avoids an import cycle
+        logits = d_heads(self, h)
+        if logits is None:
+            logits = torch.cat([head(h) for head in self.d_dense_list], dim=-1)
+        return logits
 
     def heads_raw(self, state):
         """(`d_head_raw`, *`c_head_raw`) with the trunk evaluated once; None for a part the action space does not have.
         The acting kernel (`native.act_policy`) forms the branch softmax and the bounding itself."""
         h = self.dense(state)
-        logits = torch.cat([head(h) for head in self.d_dense_list], dim=-1) if self.d_action_sizes else None
+        logits = self._d_logits(h) if self.d_action_sizes else None
         if not self.c_action_size:
             return logits, None, None
         z = self.c_dense(h)
@@ -146,9 +154,12 @@ class ModelPolicy(ModelBasePolicy):
         h = self.dense(state)
         d_policy = c_policy = None
         if self.d_action_sizes:
+            from algorithm.fused_heads import d_heads      # lazy: avoids an import cycle
+            logits = d_heads(self, h)
+            parts = logits.split(list(self.d_action_sizes), dim=-1) if logits is not None else [
+                head(h) for head in self.d_dense_list]
             d_policy = JointOneHotCategorical([
-                torch.distributions.OneHotCategorical(logits=head(h), validate_args=False)
-                for head in self.d_dense_list])
+                torch.distributions.OneHotCategorical(logits=z, validate_args=False) for z in parts])
         if self.c_action_size:
             z = self.c_dense(h)
             mean, logstd = self.mean_dense(z), self.logstd_dense(z)

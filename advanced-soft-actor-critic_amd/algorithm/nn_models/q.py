@@ -59,7 +59,10 @@ class ModelQ(ModelBaseQ):
         h = self.dense(state)
         d_qs = c_q = None
         if self.d_action_sizes:
-            d_qs = torch.cat([head(h) for head in self.d_dense_list], dim=-1)
+            from algorithm.fused_heads import d_heads      # lazy: avoids an import cycle
+            d_qs = d_heads(self, h)      # the branch stacks as one launch per pass, where the learner attached a bank
+            if d_qs is None:
+                d_qs = torch.cat([head(h) for head in self.d_dense_list], dim=-1)
         if self.c_action_size:
             joint = torch.cat([self.c_state_dense(h), self.c_action_dense(c_action)], dim=-1)
             c_q = self.c_dense(joint)

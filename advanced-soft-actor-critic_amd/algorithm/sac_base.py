@@ -399,6 +399,10 @@ class SAC_Base(AuxHeadsMixin):
         # is held to the recorded tolerances of the `aux_norm` golden case, and another summation order in the statistics
         # cannot promise to stay inside them
         self._fused_normalizer = bool(hip_config.get('fused_normalizer', False))
+        # asac_head_bank_* (the discrete branch stacks of the stock critics and policy as one launch per pass,
+        # algorithm/fused_heads.py).  Off by default: the discrete, DQN-like, hybrid and option steps are held to tolerances
+        # recorded on the module path, and another summation order cannot promise to stay inside them
+        self._fused_discrete_nets = bool(hip_config.get('fused_discrete_nets', False))
         self.normalizer = None
         self._siamese_ws = {}            # (N, E) / ('byol', encoder index) -> the launch's zeroed exchange words
         self._fused_rpm_loss = bool(hip_config.get('fused_rpm_loss', True))
@@ -627,6 +631,7 @@ class SAC_Base(AuxHeadsMixin):
             if dp is not None:
                 self._fpi = StockMLP(dp, self._params.flat, self._params.grad, seg['policy'][0],
                                      seg['policy'][1] - seg['policy'][0], 1, dev, list(self.model_policy.parameters()))
+        self._attach_head_banks()
         self._wide_critics = self._fq is not None and self._fq.wide
         if self._wide_critics:
             # critics whose first layer is wider than 64 inputs (64-wide state + action): one launch per network pass — the
@@ -1323,6 +1328,41 @@ class SAC_Base(AuxHeadsMixin):
             float32_on_device=self._params.flat.dtype == torch.float32 and self._params.flat.is_cuda,
             ensemble_q_num=self.ensemble_q_num, n_step=self.n_step, batch_size=B)
 
+    def _attach_head_banks(self):
+        """`hip_config['fused_discrete_nets']`: every stock critic (online and target) and the stock policy whose `dense` trunk
+        is the identity gets the bank of its `d_dense_list` (`fused_heads.attach`: its `forward` then issues one launch per
+        pass for the branch stacks); the E online critics' and the E target critics' stacks also form one bank each
+        (`_d_q_heads`).  A network with its own `forward`, a trunk, a live dropout, another activation or a width the kernel
+        refuses keeps its module code."""
+        from . import fused_heads
+        from .fused_mlp import _is_identity
+        self._q_bank = self._tq_bank = None
+        if not (self._fused_discrete_nets and self.d_action_sizes):
+            return
+        qs, tqs = self.model_q_list, self.model_target_q_list
+        stock_q = [type(q).forward is ModelQ.forward and _is_identity(q.dense) for q in qs + tqs]
+        attached = [ok and fused_heads.attach(q) for q, ok in zip(qs + tqs, stock_q)]
+        pi = self.model_policy
+        stock_pi = (all(getattr(type(pi), f) is getattr(ModelPolicy, f) for f in ('forward', 'd_head_raw', 'heads_raw'))
+                    and _is_identity(pi.dense))
+        pi_attached = stock_pi and fused_heads.attach(pi)
+        if all(attached) and not self.c_action_size:
+            for name, nets in (('_q_bank', qs), ('_tq_bank', tqs)):
+                shape = fused_heads.describe_head_bank([q.d_dense_list for q in nets])
+                if shape is not None:
+                    setattr(self, name, fused_heads.HeadBank(shape))
+        self._logger.info(f'head banks: critics={sum(attached)}/{len(attached)} policy={bool(pi_attached)} '
+                          f'ensemble={self._q_bank is not None}')
+
+    def _d_q_heads(self, target: bool, state, obs_list, c_action=None):
+        """the discrete head outputs of the E online (or target) critics of a pure-discrete learner on `state` -> a list of
+        E [.., D] tensors: views of one [E, .., D] launch output where the ensemble forms a bank, else the loop over the
+        critics (`c_action`: what that loop hands a critic for the continuous action it does not have)"""
+        bank = self._tq_bank if target else self._q_bank
+        if bank is not None:
+            return list(bank(state).unbind(0))
+        return [q(state, c_action, obs_list)[0] for q in (self.model_target_q_list if target else self.model_q_list)]
+
     def _hybrid_fused(self, B: int) -> bool:
         """the step's arithmetic on a hybrid action space runs on the `asac_hybrid_*` launches (`fused_hybrid_applies`), B
         rows a batch.  `plain_gaussian`: known without a forward pass for the stock policy's `forward` only (a `Normal`
@@ -1420,11 +1460,11 @@ class SAC_Base(AuxHeadsMixin):
         head outputs [B, D] at the step's state (detached)."""
         E = self.ensemble_q_num
         no_c = torch.zeros(0, device=self.device)
-        target = [q(nx_states, no_c, nx_obses_list)[0] for q in self.model_target_q_list]
+        target = self._d_q_heads(True, nx_states, nx_obses_list, no_c)
         sub_next, sub_eval = self._subsets[subset_prefix + '_dnext'], self._subsets[subset_prefix + '_dn']
         self.noise.subset_(sub_next, E)
         next_obs = [o[:, 1:] for o in nx_obses_list]
-        eval_next = [q(nx_states[:, 1:], no_c, next_obs)[0] for q in self.model_q_list]
+        eval_next = self._d_q_heads(False, nx_states[:, 1:], next_obs, no_c)
         self.noise.subset_(sub_eval, E)
         args = self._vtrace_args(n_rewards, n_dones, n_last_masks, n_padding_masks, y_out)
         args.subset_n, args.subset_next, args.E_sample = sub_eval.data_ptr(), sub_next.data_ptr(), self.ensemble_q_sample
@@ -1583,7 +1623,9 @@ class SAC_Base(AuxHeadsMixin):
         d_y = c_y = ret = None
         E = self.ensemble_q_num
         nx_qs = None
-        if self.d_action_sizes:
+        if self.d_action_sizes and not self.c_action_size:
+            nx_qs = [(h, None) for h in self._d_q_heads(True, nx_states, nx_obses_list, a_tanh)]
+        elif self.d_action_sizes:
             nx_qs = [q(nx_states, a_tanh, nx_obses_list) for q in self.model_target_q_list]
 
         if self.d_action_sizes and self.discrete_dqn_like:   # 1363-1382: double-DQN target, no policy
@@ -1592,7 +1634,10 @@ class SAC_Base(AuxHeadsMixin):
             target_next = torch.stack([q[0][:, 1:] for q in nx_qs]).index_select(0, sub_next.long())
             next_c = a_tanh[:, 1:] if self.c_action_size else a_tanh
             next_obs = [o[:, 1:] for o in nx_obses_list]
-            eval_next = torch.stack([q(nx_states[:, 1:], next_c, next_obs)[0] for q in self.model_q_list])
+            if self.c_action_size:
+                eval_next = torch.stack([q(nx_states[:, 1:], next_c, next_obs)[0] for q in self.model_q_list])
+            else:
+                eval_next = torch.stack(self._d_q_heads(False, nx_states[:, 1:], next_obs, next_c))
             self.noise.subset_(sub_eval, E)
             d_y = self.get_dqn_like_d_y(n_last_masks, n_padding_masks, n_rewards, n_dones,
                                         eval_next.index_select(0, sub_eval.long()), target_next)
@@ -1927,9 +1972,11 @@ class SAC_Base(AuxHeadsMixin):
                 return
             return self._finish_rep_q(None, None)
         q_list = None
-        if self.d_action_sizes:
+        if self.d_action_sizes and not self.c_action_size:
+            q_list, c_q = [(h, None) for h in self._d_q_heads(False, state, obs_list, c_action)], None
+        elif self.d_action_sizes:
             q_list = [q(state, c_action, obs_list) for q in self.model_q_list]
-            c_q = torch.stack([q[1] for q in q_list]).squeeze(-1) if self.c_action_size else None
+            c_q = torch.stack([q[1] for q in q_list]).squeeze(-1)
         else:
             c_q = self._c_q_values(False, state, c_action, obs_list, select=state_base)   # [E, B]
         if self.d_action_sizes and aux is None and self._dqn_fused(state.shape[0]):
@@ -2168,7 +2215,7 @@ class SAC_Base(AuxHeadsMixin):
             # launch; back-propagation starts at the logits
             logits = self._discrete_logits(state, obs_list)
             with torch.no_grad():
-                d_qs = [q(state, action[..., dsum:], obs_list)[0] for q in self.model_q_list]
+                d_qs = self._d_q_heads(False, state, obs_list, action[..., dsum:])
             sub = self._subsets['pi_d']
             self.noise.subset_(sub, E)
             _, grad_logits = self._discrete_grad_buffers(state.shape[0])
@@ -2220,7 +2267,10 @@ class SAC_Base(AuxHeadsMixin):
         if self.d_action_sizes and not self.discrete_dqn_like:
             probs = d_policy.probs
             c_action = action[..., dsum:]
-            d_qs = torch.stack([q(state, c_action, obs_list)[0] for q in self.model_q_list])
+            if self.c_action_size:
+                d_qs = torch.stack([q(state, c_action, obs_list)[0] for q in self.model_q_list])
+            else:
+                d_qs = torch.stack(self._d_q_heads(False, state, obs_list, c_action))
             sub = self._subsets['pi_d']
             self.noise.subset_(sub, E)
             mean_q = d_qs.index_select(0, sub.long()).mean(0)
@@ -2443,7 +2493,7 @@ class SAC_Base(AuxHeadsMixin):
         if c_q is None and self._discrete_fused(state.shape[0]):
             # pure-discrete: the return's launch writes mean_e |(1/K) sum_j a_j q_e - y| itself
             assert not sidecars and pending_alpha is None and td_update is None
-            heads = [q(state, c_action, obs_list)[0] for q in self.model_q_list]
+            heads = self._d_q_heads(False, state, obs_list, c_action)
             self._get_y(n_last_masks, n_padding_masks, nx_obses_list, nx_target_states, nx_actions, n_rewards, n_dones,
                         n_mu_probs, eps_buf=self._eps_td, subset_prefix='td', y_out=self._y_td_buf, td_out=self._td_error,
                         d_q_online=heads)
@@ -2460,7 +2510,7 @@ class SAC_Base(AuxHeadsMixin):
         if c_q is None and self._dqn_fused(state.shape[0]):
             # DQN-like: the return's launch writes mean_e |(1/K) sum_j a_j q_e - y| itself
             assert not sidecars and pending_alpha is None and td_update is None
-            heads = [q(state, c_action, obs_list)[0] for q in self.model_q_list]
+            heads = self._d_q_heads(False, state, obs_list, c_action)
             ret = self._dqn_target_job(n_last_masks, n_padding_masks, nx_obses_list, nx_target_states, nx_actions,
                                        n_rewards, n_dones, subset_prefix='td', y_out=self._y_td_buf, q_online=heads,
                                        td_out=self._td_error)
@@ -2470,9 +2520,11 @@ class SAC_Base(AuxHeadsMixin):
         q_list = None
         if c_q is not None:
             pass                  # [E, B] online Q of (s0, a0), already computed by the caller
+        elif self.d_action_sizes and not self.c_action_size:
+            q_list = [(h, None) for h in self._d_q_heads(False, state, obs_list, c_action)]
         elif self.d_action_sizes:
             q_list = [q(state, c_action, obs_list) for q in self.model_q_list]
-            c_q = torch.stack([q[1] for q in q_list]).squeeze(-1).contiguous() if self.c_action_size else None
+            c_q = torch.stack([q[1] for q in q_list]).squeeze(-1).contiguous()
         else:
             c_q = self._c_q_values(False, state, c_action, obs_list).contiguous()
         fused_td = bool(self.c_action_size) and not self.d_action_sizes

@@ -82,6 +82,7 @@ ImageOp = _abi.ctypes_struct('asac_image_op_t')
 ImageWarpOp = _abi.ctypes_struct('asac_image_warp_op_t')
 WhitenJob = _abi.ctypes_struct('asac_whiten_job_t')
 NormalizerJob = _abi.ctypes_struct('asac_normalizer_job_t')
+HeadBankDesc = _abi.ctypes_struct('asac_head_bank_t')
 _PtrArray = C.c_void_p * GRU_MAX_LAYERS
 
 # every entry point of the header: {name: (restype, [argtypes])} by the typing rule of abi.py
@@ -3470,3 +3471,93 @@ def normalizer_update(jobs, T, step, counter):
     assert step.is_cuda and step.dtype == torch.int32 and counter.is_cuda and counter.dtype == torch.int32
     _check(load().asac_normalizer_update(jobs, len(jobs), int(T), _p(step), _p(counter), _stream()),
            'asac_normalizer_update')
+
+
+# ------------------------------------------------------------------------------------------------
+# head banks: the discrete branch stacks of an ensemble or a policy, one launch per pass (csrc/head_bank.hip)
+# ------------------------------------------------------------------------------------------------
+HEAD_BANK_MAX_DEPTH, HEAD_BANK_MAX_ROWS = _defined('HEAD_BANK_MAX_DEPTH', 'HEAD_BANK_MAX_ROWS')
+
+
+def head_bank_supported(S: int, W: int, depth: int, sizes, G: int) -> bool:
+    """the limits of the `head_bank_*` entry points (include/asac_hip.h)"""
+    sizes = [int(s) for s in sizes]
+    return (len(sizes) > 0 and all(s > 0 for s in sizes)
+            and bool(load().asac_head_bank_supported(int(S), int(W), int(depth), len(sizes), sum(sizes), int(G))))
+
+
+def head_bank_desc(S: int, W: int, residual, sizes, G: int) -> HeadBankDesc:
+    d = HeadBankDesc()
+    d.S, d.W, d.depth, d.G = int(S), int(W), len(residual), int(G)
+    for l, r in enumerate(list(residual)[:HEAD_BANK_MAX_DEPTH]):      # (a deeper stack is refused by the entry point: depth)
+        d.residual[l] = int(bool(r))
+    d.branches = branches(sizes)
+    return d
+
+
+def head_bank_table(stacks, device=None) -> torch.Tensor:
+    """the stacks' tensors ((w_0, b_0, .., head w, head b) each, group-major: parameters, or gradient views) -> the DEVICE table
+    of the `head_bank_*` launches, int64 [M, 2 (depth + 1)].  Every tensor is a contiguous float32 device tensor (any float
+    alignment); the tensors must stay alive and keep their addresses as long as the table is used."""
+    stacks = [tuple(s) for s in stacks]
+    for s in stacks:
+        if len(s) != len(stacks[0]) or len(s) % 2:
+            raise AsacNativeError('head_bank_table: stacks of unequal depth')
+        for t in s:
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise AsacNativeError('head_bank_table: a tensor is not a contiguous float32 device tensor')
+    dev = stacks[0][0].device if device is None else device
+    return torch.tensor([[t.data_ptr() for t in s] for s in stacks], dtype=torch.int64).to(dev)
+
+
+def _head_bank_rows(x, S):
+    """x [.., S] (dense) or a [samples, T, S] window view with a dense last dim -> (pointer, sample stride, step stride,
+    samples, steps)"""
+    assert x.is_cuda and x.dtype == torch.float32 and x.shape[-1] == S and (x.stride(-1) == 1 or S == 1)
+    if x.dim() == 3 and not x.is_contiguous():
+        return _p(x), x.stride(0), x.stride(1), x.shape[0], x.shape[1]
+    assert x.is_contiguous(), 'head bank rows: dense rows, or a [samples, T, S] window view'
+    return _p(x), S, S, x.numel() // S, 1
+
+
+def _head_bank_table_ok(table, desc):
+    return (table.is_cuda and table.dtype == torch.int64 and table.is_contiguous()
+            and tuple(table.shape) == (desc.G * desc.branches.K, 2 * (desc.depth + 1)))
+
+
+def head_bank_backward_workspace(device, rows: int, desc: HeadBankDesc) -> torch.Tensor:
+    """a zeroed workspace of `head_bank_backward` over `rows` rows (records, partial sums, arrival counters); every launch
+    leaves it ready for the next.  One per bank: two banks' launches must not meet in one workspace"""
+    words = int(load().asac_head_bank_backward_workspace(int(rows), desc.S, desc.W, desc.depth, desc.branches.D,
+                                                         desc.G * desc.branches.K))
+    if words < 0:
+        raise AsacNativeError(f'head_bank_backward_workspace: {rows} rows, or a bank outside the limits')
+    return torch.zeros(words, dtype=torch.float32, device=device)
+
+
+@_profiled
+def head_bank_forward(desc: HeadBankDesc, params, x, out):
+    """out [G, N, D] (contiguous) <- every stack of the bank on the rows of x: one launch"""
+    px, ss, st, samples, steps = _head_bank_rows(x, desc.S)
+    assert _head_bank_table_ok(params, desc)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+    assert out.numel() == desc.G * samples * steps * desc.branches.D
+    _check(load().asac_head_bank_forward(C.byref(desc), _p(params), px, ss, st, samples, steps, _p(out), _stream()),
+           'asac_head_bank_forward')
+
+
+@_profiled
+def head_bank_backward(desc: HeadBankDesc, params, grads, x, grad_out, grad_x=None, accumulate=False, workspace=None):
+    """grad_out [G, N, D] (contiguous) -> the views of the `grads` table written or (accumulate) added to, and, if given,
+    grad_x [N, S] written: the chain launch and (with `grads`) the product launch"""
+    px, ss, st, samples, steps = _head_bank_rows(x, desc.S)
+    N = samples * steps
+    assert _head_bank_table_ok(params, desc) and (grads is None or _head_bank_table_ok(grads, desc))
+    assert grad_out.is_cuda and grad_out.dtype == torch.float32 and grad_out.is_contiguous()
+    assert grad_out.numel() == desc.G * N * desc.branches.D
+    assert grad_x is None or (grad_x.is_cuda and grad_x.dtype == torch.float32 and grad_x.is_contiguous()
+                              and grad_x.numel() == N * desc.S)
+    ws = workspace if workspace is not None else (
+        head_bank_backward_workspace(x.device, N, desc) if 0 < N <= HEAD_BANK_MAX_ROWS else grad_out)
+    _check(load().asac_head_bank_backward(C.byref(desc), _p(params), _p(grads), px, ss, st, samples, steps, _p(grad_out),
+                                          _p(grad_x), int(bool(accumulate)), _p(ws), _stream()), 'asac_head_bank_backward')

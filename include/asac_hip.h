@@ -2075,6 +2075,62 @@ int asac_drnd_pick(const asac_branches_t* branches, int S, const int32_t* residu
                    int32_t* cand_out, int32_t* index_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Head banks: the discrete-action branch stacks of a critic ensemble or of a policy (csrc/head_bank.hip; nn_models
+ * ModelQ.d_dense_list / ModelPolicy.d_dense_list).  A bank is G groups of K stacks, M = G K in all, every one reading the
+ * same rows x [N][S].  Stack (g, k) is LinearLayers(S, W, depth, size_k): depth ResBlocks
+ *   z_l = W_l h_l + b_l,  h_{l+1} = gelu(z_l) + residual[l] h_l        (h_0 = x; erf-form GELU on the library's erff)
+ * and the output Linear(W, size_k).  depth, W, residual and the branch sizes belong to the bank; only the parameters differ.
+ * Limits (asac_head_bank_supported): W <= ASAC_HEAD_BANK_MAX_WIDTH (tiles of 64 or 128 features; a narrower stack runs on
+ * zero-padded tiles: a padded feature is gelu(0) = 0 and carries no cotangent), S <= ASAC_HEAD_BANK_MAX_IN, 1 <= depth <=
+ * ASAC_HEAD_BANK_MAX_DEPTH, K <= ASAC_DISCRETE_MAX_BRANCHES, D = sum size_k <= ASAC_DISCRETE_MAX_WIDTH, G <=
+ * ASAC_HEAD_BANK_MAX_GROUPS, M <= ASAC_HEAD_BANK_MAX_STACKS, N <= ASAC_HEAD_BANK_MAX_ROWS; residual[0] only where S == W.
+ * params: a DEVICE table of M records of 2 (depth + 1) pointers, stack m = g K + k:  w_0, b_0, .., w_{depth-1}, b_{depth-1},
+ * head w, head b  (nn.Linear layout, out x in).  The pointers need float alignment only: the stacks of one network lie back
+ * to back in a flat buffer, and every load of a parameter and store of a gradient is one dword.  grads: the same table of
+ * the gradient views.  Row r of N = samples * steps reads x + (r / steps) x_stride_sample + (r % steps) x_stride_step (in
+ * floats; the S features dense): a [samples][steps][S] window is read in place.
+ * A workgroup owns (tile of 16 rows, stack); the activations stay in LDS, one layer's weights are staged at a time, the
+ * products are __builtin_amdgcn_mfma_f32_16x16x4f32.  Nothing allocates or synchronises; no float atomics: equal inputs
+ * give equal bits.  Bad arguments (a null required pointer, a size outside the limits, residual[0] at S != W, a branch
+ * table that does not add up) return hipErrorInvalidValue without a launch; N == 0 launches nothing.
+ * ------------------------------------------------------------------------------------------- */
+#define ASAC_HEAD_BANK_MAX_DEPTH 3
+#define ASAC_HEAD_BANK_MAX_WIDTH 128
+#define ASAC_HEAD_BANK_MAX_IN 128
+#define ASAC_HEAD_BANK_MAX_GROUPS 8
+#define ASAC_HEAD_BANK_MAX_STACKS 64
+#define ASAC_HEAD_BANK_MAX_ROWS (1 << 20)
+typedef struct {
+    int32_t S, W, depth, G;
+    int32_t residual[ASAC_HEAD_BANK_MAX_DEPTH];
+    int32_t reserved_;
+    asac_branches_t branches;
+} asac_head_bank_t;
+
+int asac_head_bank_supported(int S, int W, int depth, int K, int D, int G);
+
+/* out [G][N][D] (dense): out[g][r][off_k .. off_k + size_k) <- stack (g, k) on row r, off_k the branch's first column —
+ * each group's branches arrive concatenated.  ONE launch, grid (row tiles, M). */
+int asac_head_bank_forward(const asac_head_bank_t* bank, const float* const* params, const float* x, int64_t x_stride_sample,
+                           int64_t x_stride_step, int64_t samples, int steps, float* out, void* stream);
+
+/* The gradients for grad_out [G][N][D] (dense), TWO launches; nothing is kept from the forward: it is redone on chip.
+ *   launch 1, grid (row tiles, M): the forward, then the chain  gz_l = gh_{l+1} gelu'(z_l),  gh_l = gz_l W_l + residual[l]
+ *     gh_{l+1}  back from the head; the layers' inputs and cotangents go to records in the workspace.  With grad_x non-NULL
+ *     ([N][S] dense, every element written) each stack's gh_0 is published and the tile's last arriver adds the M of them
+ *     in ascending stack order (csrc/asac_ordered_finish.h).
+ *   launch 2, grid (blocks of 16 outputs, depth + 1 layers, M): dW = sum_r gz[r]^T h[r], db = sum_r gz[r] on the matrix
+ *     pipe (float64 MFMA on the float32 records, rounded once), rows in ascending order inside one workgroup: no
+ *     cross-workgroup sum.  Every element of every view of the grads
+ *     table is written (accumulate == 0) or added to (accumulate != 0).  grads == NULL: launch 1 only (grad_x required).
+ * workspace: asac_head_bank_backward_workspace(N, S, W, depth, D, M) floats (-1 outside the limits), 16-byte aligned, zero
+ * before its first use; every launch leaves its counters zero. */
+int64_t asac_head_bank_backward_workspace(int64_t n_rows, int S, int W, int depth, int D, int M);
+int asac_head_bank_backward(const asac_head_bank_t* bank, const float* const* params, float* const* grads, const float* x,
+                            int64_t x_stride_sample, int64_t x_stride_step, int64_t samples, int steps, const float* grad_out,
+                            float* grad_x, int accumulate, float* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Acting of a policy-based learner on the policy's head outputs (csrc/act.hip; sac_base.py _choose_action 931-966 and
  * _random_action 858-880, operators.py squash_correction_prob 17-19): discrete branches, continuous actions or both, sampled
  * or deterministic, with or without action_noise, as ONE launch.  One lane per row, workgroups of 64 rows, no exchange

@@ -7,12 +7,15 @@
           profiler.  With the flag off the step runs exactly the code of the commit before the discrete kernels, so this is
           the A/B against it without a second checkout; bench.py has no discrete configuration.
 
-    python tools/discrete_bench.py [--steps 600] [--fill 16384] [--dqn-like | --hybrid]
+    python tools/discrete_bench.py [--steps 600] [--fill 16384] [--dqn-like | --hybrid] [--nets]
 
 `--dqn-like`: the same A/B with `discrete_dqn_like=True` (critics only, double-DQN target; csrc/dqn.hip,
 `hip_config['fused_dqn']`), and — acting is not part of the step's figure — the device kernels of ONE `choose_action` call in
 train mode with the flag off and on, from torch's profiler.
 
+`--nets`: the A/B of `hip_config['fused_discrete_nets']` (default off: the `eager` column is what a default learner runs) —
+the branch stacks of the critics and the policy as head banks (csrc/head_bank.hip), everything around them as by default;
+with `--dqn-like` on the DQN-like learner.
 `--hybrid`: the same A/B on a hybrid action space, `d_action_sizes=[3, 2]` and `c_action_size=2` (csrc/hybrid.hip,
 `hip_config['fused_hybrid']`, default off: the `eager` column is what a default learner runs).
 
@@ -47,7 +50,7 @@ def count_kernels(fn):
 C_ACTION_SIZE_HYBRID = 2
 
 
-def step_row(steps, fill, dqn_like=False, hybrid=False):
+def step_row(steps, fill, dqn_like=False, hybrid=False, nets=False):
     import bench
     from asac_amd import native
     from algorithm.sac_base import SAC_Base
@@ -62,6 +65,8 @@ def step_row(steps, fill, dqn_like=False, hybrid=False):
     flag, prefix = ('fused_dqn', 'asac_dqn_') if dqn_like else ('fused_discrete', 'asac_discrete_')
     if hybrid:
         flag, prefix = 'fused_hybrid', 'asac_hybrid_'
+    if nets:       # the networks themselves: everything else as the default learner runs it
+        flag, prefix = 'fused_discrete_nets', 'asac_head_bank_'
 
     def learner(fused, use_graph):
         torch.manual_seed(0)
@@ -75,7 +80,7 @@ def step_row(steps, fill, dqn_like=False, hybrid=False):
         return agent
 
     agents = {}
-    row = {'mode': 'step', 'dqn_like': dqn_like, 'd_action_sizes': D_ACTION_SIZES, 'c_action_size': c_size,
+    row = {'mode': 'step', 'nets': nets, 'dqn_like': dqn_like, 'd_action_sizes': D_ACTION_SIZES, 'c_action_size': c_size,
            'batch': cfg['batch_size'],
            'n_step': cfg['n_step'], 'steps': steps, 'rounds': ROUNDS}
     for fused in (False, True):
@@ -127,11 +132,13 @@ def main():
     ap.add_argument('--fill', type=int, default=16384, help='rows put into the replay before the first step')
     ap.add_argument('--dqn-like', action='store_true', help='discrete_dqn_like=True: the A/B of hip_config[\'fused_dqn\']')
     ap.add_argument('--hybrid', action='store_true', help='c_action_size=2 beside the branches: the A/B of hip_config[\'fused_hybrid\']')
+    ap.add_argument('--nets', action='store_true', help='the A/B of hip_config[\'fused_discrete_nets\'] (the branch stacks as head banks); '
+                                                         'with --dqn-like on the DQN-like learner')
     args = ap.parse_args()
-    assert not (args.dqn_like and args.hybrid), 'one A/B at a time'
+    assert not (args.dqn_like and args.hybrid) and not (args.nets and args.hybrid), 'one A/B at a time'
     assert torch.cuda.is_available(), 'needs the GPU: nothing is measured without one'
     import asac_amd  # noqa: F401
-    print(json.dumps(step_row(args.steps, args.fill, args.dqn_like, args.hybrid)), flush=True)
+    print(json.dumps(step_row(args.steps, args.fill, args.dqn_like, args.hybrid, args.nets)), flush=True)
 
 
 if __name__ == '__main__':
